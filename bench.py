@@ -3,6 +3,8 @@
 T_out 1000 mel frames, r=5), bf16 MFMA operands, synthetic data, data-parallel over N GPUs.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+        [--dump-outputs DIR]    what the last timed step computed, as DIR/<name>.npy (dump_outputs)
+        [--full]                after the headline: phases, rooflines, the other legs and the CPU baseline (full_legs)
 
 Prints ONE JSON line on rank 0 (Measurement)."""
 import argparse
@@ -394,114 +396,9 @@ def e2e_bench(hp, model, args, device, modes=("hbm_cache", "hbm_cache_sync_loss"
     return out
 
 
-def launch_ranks(n):
-    """Start `n` ranks of this script under torch.distributed.run on this node and relay their output.  The driver's own
-    multi-GPU runs launch torch.distributed.run themselves; this is the same command line."""
-    import socket
-    import subprocess
-    with socket.socket() as sk:                 # a free rendezvous port
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    sys.stderr.write("[bench] starting %d ranks: %s\n" % (n, " ".join(cmd)))
-    sys.stderr.flush()
-    return subprocess.call(cmd, env=env)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)       # SURVEY 8d: 50 steps after 10 warm-up (2.2 s timed)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--t-in", type=int, default=160)
-    ap.add_argument("--t-out", type=int, default=1000)
-    ap.add_argument("--dtype", default="mixed", choices=["mixed", "bf16", "bf16x3", "fp32"],
-                    help="mixed (default): split-bf16 x3 on the mel path forward, bf16 elsewhere - meets the 1e-3 mel tolerance")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--phases", action="store_true", help="print a per-phase time table to stderr")
-    ap.add_argument("--train-only", action="store_true",
-                    help="skip the Griffin-Lim / synthesis / WaveNet legs (profiling passes of the headline workload)")
-    ap.add_argument("--e2e-steps", type=int, default=12,
-                    help="steps of the end-to-end leg (feeder thread + pinned H2D + per-step loss read-back); 0 = skip")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` on its own: start the N ranks as a CHILD process (never re-exec a process that may
-        # have touched the GPU) and relay rank 0's JSON line.  Nothing above has made a HIP call.
-        sys.exit(launch_ranks(args.gpus))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        sys.stderr.write("bench.py: --gpus %d but WORLD_SIZE=%d: launch with --nproc-per-node %d (or let bench.py start "
-                         "the ranks itself: run it without torch.distributed.run)\n" % (args.gpus, world, args.gpus))
-        sys.exit(2)
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    # NSPEECH_DIST_BACKEND=gloo lets the multi-rank flow be rehearsed with several ranks on ONE GPU (tests); the
-    # driver's runs use nccl = RCCL, one rank per GPU
-    backend = os.environ.get("NSPEECH_DIST_BACKEND", "nccl")
-    local = local % max(1, torch.cuda.device_count())
-    torch.cuda.set_device(local)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend)
-    hp = hparams_mod.load("taco2")
-    model = create_model("taco2", hp, device="cuda:%d" % local, dtype=args.dtype, seed=1234, world_size=world)
-    if world > 1:
-        from nspeech_amd import parallel
-        parallel.broadcast_parameters(model, 0)
-        model.reducer = parallel.make_reducer(model)
-    inputs, lengths, mel, lin = synthetic_batch(hp, args.batch, args.t_in, args.t_out, 1234 + rank)
-    model.add_optimizer(global_step=0)
-    model.initialize(inputs, lengths, None, mel, lin)
-
-    def one_step():
-        model.forward_train()
-        model.backward()          # hands each gradient bucket to RCCL as soon as it is final
-        model.apply_gradients()   # waits for the reductions, then clip + Adam on the summed gradients
-
-    for _ in range(args.warmup):
-        one_step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    t0 = time.perf_counter()
-    marks[0].record()
-    for i in range(args.steps):
-        one_step()
-        marks[i + 1].record()        # an event record does not synchronise: per-step times for the median
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-    if world > 1:
-        t = torch.tensor([dt], device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    loss = model.read_losses()
-    # who took part: every rank reports its device, rank 0 checks the count against --gpus
-    seen, devices = world, [torch.cuda.get_device_name(local)]
-    if world > 1:
-        seen = dist.get_world_size()
-        names = [None] * world
-        dist.all_gather_object(names, "rank %d: cuda:%d %s" % (rank, local, torch.cuda.get_device_name(local)))
-        devices = names
-        if seen != args.gpus:
-            raise RuntimeError("bench.py: --gpus %d but the process group has %d ranks" % (args.gpus, seen))
-    ms = dt / args.steps * 1e3
-    frames = args.batch * args.t_out * world
-
+def full_legs(args, hp, model, one_step, res, rank, world, local):
+    """--full: everything the bench measures beyond the headline, run after the timed steps (and after
+    --dump-outputs).  `res` = rank 0's result line (None on the other ranks), extended in place."""
     # Two more steps outside the timed region, executed by EVERY rank (the step contains collectives):
     # one with per-phase events, one with an event pair around every large GEMM launch.
     # The phase pass runs every launch on ONE stream (the timed steps put the weight gradients on a second one): a
@@ -560,32 +457,21 @@ def main():
             "traffic": _prof.pmc_traffic("lstm_wide"),
             "traffic_note": "bytes per LAUNCH (= %d steps) at the L2's fabric side, %s" % (S, _prof.pmc_traffic_source()),
         }
-        res = {
-            "metric": "mel-frames/sec Tacotron-2 LJSpeech bs32 train step", "value": frames / (dt / args.steps),
-            "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "ms_per_step_median": median_ms, "value_at_median": args.batch * args.t_out * world / (median_ms * 1e-3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"mixed": "bf16", "bf16": "bf16", "bf16x3": "bf16", "fp32": "f32"}[args.dtype], "precision_mode": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": "Tacotron-2 train step (fwd+bwd+clip+Adam), batch %d/GPU, T_in %d, T_out %d, r=%d; "
-                                   "targets = spectrogram features of synthetic speech (SURVEY 8d)"
-                                   % (args.batch, args.t_in, args.t_out, hp.outputs_per_step),
-                       "global_batch": args.batch * world, "parallelism": "dp%d" % world, "loss": loss},
+        res.update({
             "roofline": gate_roof,
             "roofline_gemm_family": roof,
             "phases_ms": {k: round(v, 3) for k, v in pd.items()},
             "phases_note": "one extra step with every launch on one stream (sum = single-stream step); the timed steps "
                            "run the weight-gradient products on a second stream",
-        }
-        res["ranks_seen"] = seen
-        res["rank_devices"] = devices
+        })
         if world == 1 and not args.train_only:
             # the same step on targets with real dynamics: under the shipped min_level_db = +100 the
             # normalisation saturates and every target frame is the same vector; with -100 the features of the
             # same synthetic speech spread over [0, 1]
             res["real_dynamics"] = real_dynamics_bench(hp, model, args, one_step)
-            # the same step with hparams.deterministic_gradients (every sum of the backward pass in a fixed order)
-            model.deterministic = True
+            # the same step with the split-K slices meeting in fp32 atomics (hparams.deterministic_gradients false, the
+            # training default); the headline runs the fixed-order form
+            model.deterministic = False
             for _ in range(3):
                 one_step()
             torch.cuda.synchronize()
@@ -593,11 +479,11 @@ def main():
             for _ in range(10):
                 one_step()
             torch.cuda.synchronize()
-            dtd = (time.perf_counter() - t0) / 10
-            model.deterministic = False
-            res["deterministic_gradients"] = {"ms_per_step": dtd * 1e3, "value": args.batch * args.t_out / dtd,
-                                              "note": "bit-reproducible gradients (split-K partial tiles parked and added in "
-                                                      "slice order); the headline runs the default, fp32-atomic split-K"}
+            dta = (time.perf_counter() - t0) / 10
+            model.deterministic = True
+            res["atomic_split_k"] = {"ms_per_step": dta * 1e3, "value": args.batch * args.t_out / dta,
+                                     "note": "split-K partial tiles added with fp32 atomics (not bit-reproducible: the "
+                                             "training default); the headline parks them and adds them in slice order"}
             if args.e2e_steps > 0:
                 em = create_model("taco2", hp, device="cuda:%d" % local, dtype=args.dtype, seed=1234)
                 em.add_optimizer(global_step=0)
@@ -609,6 +495,180 @@ def main():
             res["taco1"] = taco1_bench(args, None)
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(hp, 1234)
+
+
+def _sample(t, limit, seed):
+    """A device tensor as a float32 host array: whole when it has at most `limit` elements, otherwise `limit` of its
+    elements (flattened order) at fixed positions - one per equal stratum, the offset inside it drawn from `seed` - so
+    that every run with the same arguments writes the same positions."""
+    flat = t.reshape(-1)
+    n = flat.numel()
+    if n <= limit:
+        return t.detach().float().cpu().numpy()
+    rng = np.random.default_rng(seed)
+    lo = (np.arange(limit, dtype=np.int64) * n) // limit
+    hi = (np.arange(1, limit + 1, dtype=np.int64) * n) // limit
+    idx = lo + (rng.random(limit) * (hi - lo)).astype(np.int64)
+    return flat.index_select(0, torch.from_numpy(idx).to(flat.device)).float().cpu().numpy()
+
+
+def dump_outputs(model, out_dir):
+    """What the last timed step handed its caller, as DIR/<name>.npy (float32; the loss scalars float64): the loss
+    terms, the forward outputs, and samples of the gradient and of the parameters Adam left behind.  At most 15 M
+    float32 elements in all (60 MB): outputs larger than their share are written as a fixed sample (_sample)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": np.array([model.loss, model.mel_loss, model.linear_loss, model.grad_norm], np.float64)}
+    for i, (name, t, limit) in enumerate((("mel_outputs", model.mel_outputs, 4000000),
+                                          ("decoder_outputs", model.decoder_outputs, 4000000),
+                                          ("linear_outputs", model.linear_outputs, 3000000),
+                                          ("alignments", model.alignments, 2000000),
+                                          ("gradients", model.flat_g, 1000000),
+                                          ("parameters", model.flat_p, 1000000))):
+        arrays[name] = _sample(t, limit, 1000 + i)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
+def launch_ranks(n):
+    """Start `n` ranks of this script under torch.distributed.run on this node and relay their output.  The driver's own
+    multi-GPU runs launch torch.distributed.run themselves; this is the same command line."""
+    import socket
+    import subprocess
+    with socket.socket() as sk:                 # a free rendezvous port
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
+           "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    sys.stderr.write("[bench] starting %d ranks: %s\n" % (n, " ".join(cmd)))
+    sys.stderr.flush()
+    return subprocess.call(cmd, env=env)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=50)       # SURVEY 8d: 50 steps after 10 warm-up (2.2 s timed)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--t-in", type=int, default=160)
+    ap.add_argument("--t-out", type=int, default=1000)
+    ap.add_argument("--dtype", default="mixed", choices=["mixed", "bf16", "bf16x3", "fp32"],
+                    help="mixed (default): split-bf16 x3 on the mel path forward, bf16 elsewhere - meets the 1e-3 mel tolerance")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures: phase table, roofline blocks, the "
+                         "real-dynamics / atomic split-K / end-to-end / Griffin-Lim / synthesis / WaveNet / Tacotron-1 "
+                         "legs and the CPU baseline.  Without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU legs")
+    ap.add_argument("--phases", action="store_true", help="(--full) print a per-phase time table to stderr")
+    ap.add_argument("--train-only", action="store_true",
+                    help="(--full) skip the Griffin-Lim / synthesis / WaveNet legs (profiling passes of the headline workload)")
+    ap.add_argument("--e2e-steps", type=int, default=12,
+                    help="(--full) steps of the end-to-end leg (feeder thread + pinned H2D + per-step loss read-back); 0 = skip")
+    args = ap.parse_args()
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # `python bench.py --gpus N` on its own: start the N ranks as a CHILD process (never re-exec a process that may
+        # have touched the GPU) and relay rank 0's JSON line.  Nothing above has made a HIP call.
+        sys.exit(launch_ranks(args.gpus))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        sys.stderr.write("bench.py: --gpus %d but WORLD_SIZE=%d: launch with --nproc-per-node %d (or let bench.py start "
+                         "the ranks itself: run it without torch.distributed.run)\n" % (args.gpus, world, args.gpus))
+        sys.exit(2)
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    # NSPEECH_DIST_BACKEND=gloo lets the multi-rank flow be rehearsed with several ranks on ONE GPU (tests); the
+    # driver's runs use nccl = RCCL, one rank per GPU
+    backend = os.environ.get("NSPEECH_DIST_BACKEND", "nccl")
+    local = local % max(1, torch.cuda.device_count())
+    torch.cuda.set_device(local)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        else:
+            dist.init_process_group(backend)
+    hp = hparams_mod.load("taco2")
+    model = create_model("taco2", hp, device="cuda:%d" % local, dtype=args.dtype, seed=1234, world_size=world)
+    # the timed steps add the k slices of every split-K product in a fixed order (hparams.deterministic_gradients): with
+    # the same arguments every run computes the same bits, which --dump-outputs relies on.  In the fp32-atomic form the
+    # rounding noise of one step grows through Adam to tens of per cent within 25 steps; --full times that form too.
+    model.deterministic = True
+    if world > 1:
+        from nspeech_amd import parallel
+        parallel.broadcast_parameters(model, 0)
+        model.reducer = parallel.make_reducer(model)
+    inputs, lengths, mel, lin = synthetic_batch(hp, args.batch, args.t_in, args.t_out, 1234 + rank)
+    model.add_optimizer(global_step=0)
+    model.initialize(inputs, lengths, None, mel, lin)
+
+    def one_step():
+        model.forward_train()
+        model.backward()          # hands each gradient bucket to RCCL as soon as it is final
+        model.apply_gradients()   # waits for the reductions, then clip + Adam on the summed gradients
+
+    for _ in range(args.warmup):
+        one_step()
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    t0 = time.perf_counter()
+    marks[0].record()
+    for i in range(args.steps):
+        one_step()
+        marks[i + 1].record()        # an event record does not synchronise: per-step times for the median
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+    if world > 1:
+        t = torch.tensor([dt], device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    loss = model.read_losses()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)      # before anything else runs a step
+    # who took part: every rank reports its device, rank 0 checks the count against --gpus
+    seen, devices = world, [torch.cuda.get_device_name(local)]
+    if world > 1:
+        seen = dist.get_world_size()
+        names = [None] * world
+        dist.all_gather_object(names, "rank %d: cuda:%d %s" % (rank, local, torch.cuda.get_device_name(local)))
+        devices = names
+        if seen != args.gpus:
+            raise RuntimeError("bench.py: --gpus %d but the process group has %d ranks" % (args.gpus, seen))
+    ms = dt / args.steps * 1e3
+    frames = args.batch * args.t_out * world
+
+    res = None
+    if rank == 0:
+        res = {
+            "metric": "mel-frames/sec Tacotron-2 LJSpeech bs32 train step", "value": frames / (dt / args.steps),
+            "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms, "ms_per_step_median": median_ms, "value_at_median": args.batch * args.t_out * world / (median_ms * 1e-3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"mixed": "bf16", "bf16": "bf16", "bf16x3": "bf16", "fp32": "f32"}[args.dtype], "precision_mode": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": "Tacotron-2 train step (fwd+bwd+clip+Adam), batch %d/GPU, T_in %d, T_out %d, r=%d; "
+                                   "targets = spectrogram features of synthetic speech (SURVEY 8d)"
+                                   % (args.batch, args.t_in, args.t_out, hp.outputs_per_step),
+                       "global_batch": args.batch * world, "parallelism": "dp%d" % world, "loss": loss,
+                       "deterministic_gradients": bool(model.deterministic)},
+            "ranks_seen": seen, "rank_devices": devices,
+        }
+    if args.full:
+        full_legs(args, hp, model, one_step, res, rank, world, local)
+    if rank == 0:
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

@@ -1,8 +1,8 @@
 """Summarises one rocprofv3 PMC pass with the matrix-core counters into per-kernel MFMA utilisation.
 
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv \\
-      -d gpurun_out/pmc_mfma -- python3 bench.py --no-cpu-baseline --train-only --steps 1 --warmup 0
-  python3 profiles/pmc_mfma.py gpurun_out/pmc_mfma profiles/r04_pmc_mfma.csv
+      -d pmc_mfma -- python3 bench.py --full --no-cpu-baseline --train-only --steps 1 --warmup 0
+  python3 profiles/pmc_mfma.py pmc_mfma profiles/r04_pmc_mfma.csv
 
 mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 256 CUs * 4 SIMDs): the fraction of the chip's SIMD-cycles,
 while the kernel ran, in which a SIMD's matrix pipe was busy (MI355X_MICROARCH.md: SQ_VALU_MFMA_BUSY_CYCLES counts cycles

@@ -1,9 +1,9 @@
 """Summarises two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs, as the MI355X guide prescribes) into
 per-kernel memory-side traffic per launch.
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --no-cpu-baseline --train-only --steps 1 --warmup 0
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --no-cpu-baseline --train-only --steps 1 --warmup 0
-  python profiles/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r02_pmc_traffic
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d pmc_fetch -- python3 bench.py --full --no-cpu-baseline --train-only --steps 1 --warmup 0
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d pmc_write -- python3 bench.py --full --no-cpu-baseline --train-only --steps 1 --warmup 0
+  python profiles/pmc_traffic.py pmc_fetch pmc_write profiles/r02_pmc_traffic
 
 Units and corrections (MI355X_MICROARCH.md, HBM section): both counters are in KiB-like units of 1 KB; on gfx950
 FETCH_SIZE reports half of the bytes of wide coalesced reads, so it is doubled; Infinity-Cache hits are counted

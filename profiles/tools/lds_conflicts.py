@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel LDS bank-conflict share from one rocprofv3 PMC pass:
-  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d gpurun_out/pmc_lds -- python3 bench.py --no-cpu-baseline --train-only --steps 1 --warmup 0
-  python profiles/tools/lds_conflicts.py gpurun_out/pmc_lds
+  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d pmc_lds -- python3 bench.py --full --no-cpu-baseline --train-only --steps 1 --warmup 0
+  python profiles/tools/lds_conflicts.py pmc_lds
 SQ_LDS_BANK_CONFLICT = extra LDS cycles, SQ_LDS_IDX_ACTIVE = all LDS-array cycles (MI355X_MICROARCH.md)."""
 import collections
 import csv

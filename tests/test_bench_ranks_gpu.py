@@ -14,12 +14,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_two_ranks_one_gpu(dev):
     """`python bench.py --gpus 2` on its own: bench.py starts the two ranks itself (as a child process, before any GPU
-    call) and rank 0's line reports what took part."""
+    call) and rank 0's line reports what took part; with --full every rank runs the instrumented steps as well."""
     env = dict(os.environ, NSPEECH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--t-out", "200", "--t-in", "40", "--no-cpu-baseline"]
+           "--batch", "8", "--t-out", "200", "--t-in", "40", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
