@@ -730,6 +730,41 @@ size_t ns_taco1_attn_cluster_work_bytes(const ns_taco1_attn_params* p);
 int ns_taco1_attn_cluster_fwd(const ns_taco1_attn_params* p, void* work, ns_stream_t stream);
 int ns_taco1_attn_cluster_bwd(const ns_taco1_attn_params* p, void* work, ns_stream_t stream);
 
+/* Tacotron-1 free-running synthesis loop (tacotron.py:80-86 with TacoTestHelper, helpers.py:7-38, rnn_wrappers.py:25-31)
+ * as ONE persistent launch.  Step s = 0 .. S-1:
+ *   p1 = relu(frame[s-1].W1[:M] + ctx[s-1].W1[M:] + b1)   (frame[-1] = 0, ctx[-1] = 0)   p2 = relu(p1.W2 + b2)
+ *   h_a = GRU_att([p2 | speaker projection | h_a])   align = softmax_t<length(v.tanh(keys[t] + h_a.Wq))   ctx = align.values
+ *   x1 = [h_a | ctx].W_proj + b_proj   h1 = GRU_1(x1, h1)   y1 = x1 + h1   h2 = GRU_2(y1, h2)   y2 = y1 + h2
+ *   frame[s] = last of the r frames of y2.W_out + b_out
+ * with GRUCell: [r | u] = sigmoid([x | h].Wg + bg), c = tanh([x | r*h].Wc + bc), h' = u*h + (1-u)*c.
+ * The attention part runs on the clusters of ns_taco1_attn_cluster_fwd (8 workgroups per utterance, weights of `att` in
+ * its dtype); 16 more workgroups keep W_proj and both decoder GRUs register-resident as fp32 (16 units each).  The frame
+ * feedback is folded: f1[s+1] = y2[s].wpf + bpf with wpf = W_out[:, last frame].W1[:M] ([D, D1]) and
+ * bpf = b_out[last frame].W1[:M] + b1, so the output projection leaves the loop: the caller forms
+ * y2.W_out + b_out over the whole history afterwards.
+ * att: as for ns_taco1_attn_cluster_fwd with S = decoder steps and pv = values.W1[M:]; f1 slot 1 must hold the <GO>
+ * frame's term (= b1), later slots are not read; xa carries the speaker projection in every slot when Dsp > 0.
+ * Writes att.align / p1 / xa / xc / hc[:, :, :A] / ru / cc / q (/ align_t) as the teacher-forced call does, and y2.
+ * Shapes: A = D1 = D = 256, D2 = 128, any E, T_in <= 256, N <= 2, any Dsp; 8 N + 16 workgroups must fit the device
+ * (one per CU).  The caller owns `work` (ns_taco1_decode_work_bytes()); the call re-initialises it.  work[0] (int) is
+ * the status word: non-zero after the call completes = an exchange timed out and the outputs are invalid (1-3: the
+ * attention's exchanges, 4: its frame-term poll, 5-10: the decoder workgroups' six exchanges). */
+typedef struct {
+  ns_taco1_attn_params att;
+  int D;
+  const void* values;                      /* (att.dtype) [N*Pi, E] attention memory (encoder outputs) */
+  const float* w_proj; const float* b_proj;   /* decoder/attention_projection kernel [(A+E), D], bias [D], fp32 */
+  const float* wg_1; const float* bg_1;    /* decoder/gru_1 gates kernel [2D, 2D], bias [2D] */
+  const float* wc_1; const float* bc_1;    /* decoder/gru_1 candidate kernel [2D, D], bias [D] */
+  const float* wg_2; const float* bg_2;    /* decoder/gru_2, same shapes */
+  const float* wc_2; const float* bc_2;
+  const float* wpf; const float* bpf;      /* folded feedback [D, D1], [D1] */
+  float* y2;                               /* fp32 [N, S+1, D] out: y2 of step s in slot s+1 */
+} ns_taco1_decode_params;
+int ns_taco1_decode_supported(const ns_taco1_decode_params* p);
+size_t ns_taco1_decode_work_bytes(const ns_taco1_decode_params* p);
+int ns_taco1_decode(const ns_taco1_decode_params* p, void* work, ns_stream_t stream);
+
 /* Free-running synthesis loop (tacotron2.py:78-83 with TacoTestHelper, helpers.py:7-38: the last predicted frame is
  * the next step's input) as ONE persistent launch: the attention-RNN clusters of ns_taco2_attn_cluster_fwd plus
  * workgroups that keep the two decoder LSTMs (tacotron2.py:67-70) register-resident as fp32, 12 units each, exchanging

@@ -52,12 +52,20 @@ constexpr int NQ = 4;                                    // column groups of the
 constexpr int PPT = NQ * K / CT;                         // (row, group) pairs per thread: 3
 constexpr int CPQ_C = UPW / NQ, CPQ_G = GC / NQ;         // columns per group: candidate 8, gates 16
 constexpr int W2H = CT / D1, W2K = D2 / W2H;             // dp1 product: 2 halves x 64
+// free-running synthesis: decoder workgroups (see "free-running synthesis" below)
+constexpr int DD = 256;                                  // decoder width D
+constexpr int DU = 16;                                   // decoder units per decoder workgroup
+constexpr int DNW = DD / DU;                             // decoder workgroups per launch: 16
+constexpr int DNR = 2;                                   // utterances per launch
 static_assert(NQ * K == PPT * CT && P2K == 64 && GKP + GKH == 48 && CKP + CKH == 24, "shape");
 
 struct TArgs {
   ns_taco1_attn_params p;
   u64* x1; u64* x2; u64* x3; u64* x4;       // fwd: [N][CG][X1N | X2N | X3N]; bwd: E1 [N][CG], E2 [N][CG][A], E3a / E3b [N][CG][K]
   int* status;
+  // free-running synthesis (taco1_decode_kernel): the next step's frame term arrives as nwd partial sums per column
+  // ([N][nwd][D1] granules, plus bpf), the alignment goes out as [N][Tia] granules
+  u64* f1x; u64* alx; const float* bpf; int nwd;
 };
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -116,10 +124,36 @@ __device__ __forceinline__ float dot_regs(const float (&w)[NK], const float* x) 
   return s0 + s1;
 }
 
+// The partial sums of one frame-term column from the nw decoder workgroups (stride D1), polled by its owner thread and
+// added in a fixed order.  Returns false on time-out / raised status.
+template <int NW>
+__device__ __forceinline__ bool poll_partials(const u64* src_, unsigned tag, float& out, int* status, int code) {
+  const NS_GLOBAL u64* src = (const NS_GLOBAL u64*)src_;
+  u64 v[NW];
+  unsigned spins = 0, clk0 = 0;
+  for (;;) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) v[j] = __hip_atomic_load(src + (size_t)j * D1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int j = 0; j < NW; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
+    if (ok) break;
+    if ((++spins & 1023u) == 0) {
+      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
+      if (ns_spin_timed_out(clk0)) { atomicExch(status, code); return false; }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NW; ++j) out += __uint_as_float((unsigned)v[j]);
+  return true;
+}
+
 // ===================================================================================== forward
-template <typename T>
-__global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
+// One workgroup of an utterance's cluster (bid = utterance * CG + member).  INFER = free-running synthesis: the frame
+// term of the next step is not hoisted (it depends on this step's output through the decoder GRUs) but polled from
+// a.f1x, and the alignment is published to a.alx for the decoder workgroups (attn_cluster.hip: attn_fwd_body<INFER>).
+template <typename T, bool INFER>
+__device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const int bid) {
   const ns_taco1_attn_params& p = a.p;
   float* xs = sm;                          // [K]      p2 | h(s-1)
   float* p1s = xs + K;                     // [D1]     prenet layer 1 of the current step
@@ -136,7 +170,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
   float* wq_s = pv_s + TSMAX * D1;         // [UPW][A]  W_query rows of the own units
 
   const int tid_ = threadIdx.x;
-  const int n = blockIdx.x / CG, g = blockIdx.x % CG;
+  const int n = bid / CG, g = bid % CG;
   const long S1 = p.S + 1;
   const int HC = A + p.E;
   // multi-speaker (rnn_wrappers.py:28-30): the GRU's input row is [p2 | speaker projection (Dsp) | h]; the projection is
@@ -219,7 +253,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
     asm volatile("" : "+v"(tid));           // opaque per iteration: addresses are recomputed in the loop, not hoisted as 64-bit pairs
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float f1n = 0.f;
-    if (tid < D1 && st + 1 < p.S) f1n = p.f1[(rowS + 1) * D1 + tid];
+    if (!INFER && tid < D1 && st + 1 < p.S) f1n = p.f1[(rowS + 1) * D1 + tid];
 
     // ---- (1) p2 = relu(p1 . W2 + b2): every workgroup computes all of it
     red[tid] = dot_regs<P2K>(w2r, p1s + (tid / D2) * P2K);
@@ -380,9 +414,16 @@ __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
       if (mine) {
         p.align[rowS * p.Tia + t] = v;
         if (p.align_t) stf((T*)p.align_t + rowS * p.Tia + t, v);
+        if (INFER) put_granule(a.alx + (size_t)n * p.Tia + t, tag, v);      // the decoder workgroups wait for it
       }
     }
     if (tid < D1) {
+      // free-running: the next frame term comes back through both decoder GRUs as one partial sum per decoder workgroup
+      // (tag = the consuming step + 1); the alignment above went out first - they cannot answer before they have it
+      if (INFER && st + 1 < p.S) {
+        f1n = a.bpf[tid];
+        if (!poll_partials<DNW>(a.f1x + (size_t)n * DNW * D1 + tid, tag + 1, f1n, a.status, 4)) sc[2] = 1.f;
+      }
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < CG; ++q) s = fmaf(scl[q], gath[q * X3N + tid], s);
@@ -391,7 +432,14 @@ __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
       if (st + 1 < p.S && tid / (D1 / CG) == g) stf((T*)p.p1 + (rowS + 1) * D1 + tid, v);
     }
     lds_barrier();
+    if (INFER && sc[2] != 0.f) return;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  attn_fwd_body<T, false>(a, sm, blockIdx.x);
 }
 
 // ===================================================================================== backward
@@ -729,6 +777,289 @@ static_assert(FWD_LDS <= 160 * 1024 && BWD_LDS <= 160 * 1024, "LDS");
 
 size_t fwd_granules(int N) { return (size_t)N * CG * (X1N + X2N + X3N); }
 size_t bwd_granules(int N) { return (size_t)N * CG * (1 + A + 2 * K); }
+
+// ===================================================================================== free-running synthesis
+// Synthesis (tacotron.py:80-86 with TacoTestHelper, helpers.py:7-38): the frame fed to step s+1 is the last frame
+// predicted at step s, so nothing can be hoisted out of the time loop and the launch-per-step form needs ~28 dependent
+// launches per decoder step.  Here the whole loop is ONE launch with two roles, selected by blockIdx:
+//   workgroups [0, 8N)        the attention clusters of attn_fwd_body<INFER> above
+//   the next DNW = 16         decoder workgroups, DU = 16 units of D = 256 each, for BOTH decoder GRUs and the
+//                             attention projection (N <= 2 utterances per workgroup)
+// A decoder workgroup keeps, as fp32 in registers, the columns of its own units: W_proj[h rows] (8 per thread), GRU_1 and
+// GRU_2 gates (2 x 32) and candidates (2 x 16), and the rows of the folded feedback wpf that its y2 units multiply (8):
+// 112 weights per thread, matrix-VECTOR products as exact fp32 FMAs.  The context never forms in the loop: the projected
+// memory PM = memory . W_proj[ctx rows] of the own 16 columns sits in LDS (built once per call), so x1 of the own units
+// = h_att . W_proj[h rows] + align . PM + b_proj.  Per step (granule exchanges, each 8 bytes {step tag, fp32}):
+//   attention:  h_att(s) -> x2 (its own exchange), align(s) -> alx, then waits for f1(s+1)
+//   D1: gather h_att(s), align(s); x1 of the own units                                          -> xa
+//   D2: gather x1; GRU_1 gates of the own units (h rows: h1(s-1), gathered a step before); r * h1 -> xb
+//   D3: gather r * h1; candidate, h1(s), y1 = x1 + h1 of the own units                           -> xc (y1 | h1)
+//   D4: gather y1 | h1; GRU_2 gates; r * h2                                                      -> xd
+//   D5: gather r * h2; candidate, h2(s), y2 = y1 + h2 (history); h2 -> xe; the own rows' share of the
+//       folded feedback f1(s+1) = y2(s) . wpf + bpf, wpf = W_out[:, last frame] . W_prenet1[frame rows]   -> f1x
+//       (the attention sums the 16 shares in a fixed order; the output projection leaves the loop: ONE product over
+//       the y2 history after the launch)
+//   D6: gather h2(s) for the next step's GRU_2 gates (off the critical path)
+// Layout choice: folding W_proj into GRU_1's input weights would save the xa hop but needs a second copy of GRU_1's x
+// rows (x1 itself is the residual) and changes the rounding of x1; with one unit range per workgroup for all three
+// layers every product stays a plain fp32 dot product of the reference's weights.  One buffer per exchange suffices:
+// a workgroup publishes exchange X of step s+1 only behind a chain that passes every reader of X of step s (xa..xe: the
+// gathers of the same step by every decoder workgroup; f1x / alx / x2: the attention's poll of f1(s+1) needs every
+// decoder workgroup's D1 of step s, and the decoder reads h_att(s+1) only after the attention has passed that poll).
+// LDS hand-over audit (decoder role): ha / als are written by the D1 gather and read by D1's products only; x1f by the
+// D2 gather, read through D3; rhf by the D2 (GRU_1) and D4 (GRU_2) gathers, each read by the next phase's products
+// only; yh1 by the D3 gather (its h1 half is read in D2 / D3 of the NEXT step, so the D3 gather sits behind a barrier
+// after D3's reduction); h2f by the D6 gather, read in D4 / D5 of the next step; red / rus / y2s are reduction
+// scratch, each rewritten only behind the barrier that follows its readers.  Status codes: 1-3 the attention's three
+// gathers, 4 its frame-term poll, 5-10 the decoder phases D1-D6.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, both dtypes): 229 VGPRs, 0 AGPRs, no scratch, 115 328 bytes of
+// dynamic LDS (the attention role's image; the decoder role needs 82 KB), one workgroup per CU.  Measured on one MI355X
+// (profiles/taco1_decode.txt): 300 steps at T_in = 160 in 5.22 ms (N = 1, 17.4 us per step) / 5.68 ms (N = 2).
+struct DArgs {
+  TArgs att;
+  const void* values;                     // (dtype) [N*Pi, E]
+  const float *wp, *bp, *wg1, *bg1, *wc1, *bc1, *wg2, *bg2, *wc2, *bc2, *wpf;
+  float* y2;                              // [N][S+1][DD]
+  u64 *xa, *xb, *xc, *xd, *xe;            // [N][DD]; xc [N][2 DD]
+};
+
+// PER granules per thread, all loads of a pass in flight together; at(i, src, dsti) maps item i to its granule and LDS
+// word.  Returns false on time-out / raised status (attn_cluster.hip: dec_gather).
+template <int PER, typename F>
+__device__ __forceinline__ bool map_gather(int total, unsigned tag, float* dst, int tid, int* status, int code, F at) {
+  const NS_GLOBAL u64* src[PER];
+  int di[PER];
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int i = tid + j * CT;
+    src[j] = nullptr; di[j] = 0;
+    if (i < total) { const u64* s_; at(i, s_, di[j]); src[j] = (const NS_GLOBAL u64*)s_; }
+  }
+  u64 v[PER];
+  unsigned spins = 0, clk0 = 0;
+  bool ok, good = true;
+  do {
+    ok = true;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) v[j] = src[j] ? __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((u64)tag << 32);
+#pragma unroll
+    for (int j = 0; j < PER; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
+    if (!ok && (++spins & 1023u) == 0) {
+      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { good = false; ok = true; }
+      else if (ns_spin_timed_out(clk0)) { atomicExch(status, code); good = false; ok = true; }
+    }
+  } while (!ok);
+#pragma unroll
+  for (int j = 0; j < PER; ++j) if (src[j]) dst[di[j]] = __uint_as_float((unsigned)v[j]);
+  return good;
+}
+
+template <typename T>
+__device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w) {
+  const ns_taco1_attn_params& p = d.att.p;
+  const int tid = threadIdx.x, N = p.N, Tia = p.Tia, u0 = w * DU;
+  const long S1 = p.S + 1;
+  int* status = d.att.status;
+  float* ha = sm;                          // [DNR][A]      h_att(s)
+  float* als = ha + DNR * A;               // [DNR][256]    align(s)
+  float* x1f = als + DNR * 256;            // [DNR][DD]     x1(s) of every unit
+  float* rhf = x1f + DNR * DD;             // [DNR][DD]     r * h(s-1) of every unit (GRU_1, then GRU_2)
+  float* yh1 = rhf + DNR * DD;             // [DNR][2 DD]   y1(s) | h1(s)
+  float* h2f = yh1 + DNR * 2 * DD;         // [DNR][DD]     h2(s-1)
+  float* red = h2f + DNR * DD;             // [DNR][CT]     partial sums over the k groups
+  float* rus = red + DNR * CT;             // [DNR][2 DU]   r | u of the own units
+  float* y2s = rus + DNR * 2 * DU;         // [DNR][DU]     y2 of the own units
+  float* flag = y2s + DNR * DU;            // [4]           [0] abort
+  float* PM = flag + 4;                    // [DNR][256][DU] projected memory of the own columns
+
+  // ---- resident weights: 16 columns x 32 k groups (c16, k16) or 32 columns x 16 k groups (c32, k32)
+  const int c16 = tid & 15, k16 = tid >> 4, c32 = tid & 31, k32 = tid >> 5;
+  const int gcol = c32 < DU ? u0 + c32 : DD + u0 + (c32 - DU);
+  float wpr[8], g1r[32], c1r[16], g2r[32], c2r[16], fpr[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) wpr[i] = d.wp[(long)(k16 * 8 + i) * DD + u0 + c16];
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    g1r[i] = d.wg1[(long)(k32 * 32 + i) * 2 * DD + gcol];
+    g2r[i] = d.wg2[(long)(k32 * 32 + i) * 2 * DD + gcol];
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    c1r[i] = d.wc1[(long)(k16 * 16 + i) * DD + u0 + c16];
+    c2r[i] = d.wc2[(long)(k16 * 16 + i) * DD + u0 + c16];
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) fpr[i] = d.wpf[(long)(u0 + (tid >> 8) * 8 + i) * D1 + (tid & 255)];
+  const float bpv = d.bp[u0 + c16], bc1v = d.bc1[u0 + c16], bc2v = d.bc2[u0 + c16];
+  const float bg1v = d.bg1[gcol], bg2v = d.bg2[gcol];
+  // ---- LDS images: PM = memory . W_proj[ctx rows] (own columns), zero states
+  {
+    const T* val = (const T*)d.values;
+    for (int o = tid; o < N * 256 * DU; o += CT) {
+      const int j = o % DU, t = (o / DU) % 256, n = o / (DU * 256);
+      float s = 0.f;
+      if (t < p.Ti) {
+        const T* vr = val + ((long)n * p.Pi + p.padl_i + t) * p.E;
+        const float* wc = d.wp + (long)A * DD + u0 + j;
+        for (int e = 0; e < p.E; ++e) s = fmaf(ldf(vr + e), wc[(long)e * DD], s);
+      }
+      PM[o] = s;
+    }
+    for (int i = tid; i < DNR * 2 * DD; i += CT) yh1[i] = 0.f;
+    for (int i = tid; i < DNR * DD; i += CT) h2f[i] = 0.f;
+    if (tid < 4) flag[tid] = 0.f;
+  }
+  __syncthreads();
+
+  for (int st = 0; st < p.S; ++st) {
+    const unsigned tag = (unsigned)(st + 1);
+    const long slot = st + 1;
+    // ---- D1: h_att(s), align(s) -> x1 of the own units
+    bool good = map_gather<(DNR * A + CT - 1) / CT>(N * A, tag, ha, tid, status, 5, [&](int i, const u64*& src, int& di) {
+      const int n = i / A, u = i % A;
+      src = d.att.x2 + ((size_t)n * CG + u / UPW) * X2N + A + u % UPW;
+      di = i;
+    });
+    good = map_gather<(DNR * 256 + CT - 1) / CT>(N * Tia, tag, als, tid, status, 5, [&](int i, const u64*& src, int& di) {
+      src = d.att.alx + i;
+      di = (i / Tia) * 256 + i % Tia;
+    }) && good;
+    if (!good) flag[0] = 1.f;
+    lds_barrier();
+    if (flag[0] != 0.f) return;
+    for (int n = 0; n < N; ++n) {
+      float s = dot_regs<8>(wpr, ha + n * A + k16 * 8);
+      for (int t = k16; t < Tia; t += 32) s = fmaf(als[n * 256 + t], PM[(n * 256 + t) * DU + c16], s);
+      red[n * CT + tid] = s;
+    }
+    lds_barrier();
+    if (tid < N * DU) {
+      const int n = tid / DU, j = tid % DU;
+      float s = bpv;
+#pragma unroll
+      for (int q = 0; q < 32; ++q) s += red[n * CT + q * DU + j];
+      put_granule(d.xa + (size_t)n * DD + u0 + j, tag, s);
+    }
+    // ---- D2: x1 of every unit -> GRU_1 gates of the own units, r * h1(s-1)
+    good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, x1f, tid, status, 6, [&](int i, const u64*& src, int& di) {
+      src = d.xa + i; di = i;
+    });
+    if (!good) flag[0] = 1.f;
+    lds_barrier();
+    if (flag[0] != 0.f) return;
+    for (int n = 0; n < N; ++n)
+      red[n * CT + tid] = dot_regs<32>(g1r, k32 < 8 ? x1f + n * DD + k32 * 32 : yh1 + n * 2 * DD + DD + (k32 - 8) * 32);
+    lds_barrier();
+    if (tid < N * 2 * DU) {
+      const int n = tid / (2 * DU), c = tid % (2 * DU);
+      float z = bg1v;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) z += red[n * CT + q * 2 * DU + c];
+      const float v = sigmoidf_(z);
+      rus[n * 2 * DU + c] = v;
+      if (c < DU) put_granule(d.xb + (size_t)n * DD + u0 + c, tag, v * yh1[n * 2 * DD + DD + u0 + c]);
+    }
+    // ---- D3: r * h1 of every unit -> candidate, h1(s), y1 = x1 + h1 of the own units
+    good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, rhf, tid, status, 7, [&](int i, const u64*& src, int& di) {
+      src = d.xb + i; di = i;
+    });
+    if (!good) flag[0] = 1.f;
+    lds_barrier();
+    if (flag[0] != 0.f) return;
+    for (int n = 0; n < N; ++n)
+      red[n * CT + tid] = dot_regs<16>(c1r, k16 < 16 ? x1f + n * DD + k16 * 16 : rhf + n * DD + (k16 - 16) * 16);
+    lds_barrier();
+    if (tid < N * DU) {
+      const int n = tid / DU, j = tid % DU;
+      float z = bc1v;
+#pragma unroll
+      for (int q = 0; q < 32; ++q) z += red[n * CT + q * DU + j];
+      const float c = tanhf_(z), u = rus[n * 2 * DU + DU + j];
+      const float h = u * yh1[n * 2 * DD + DD + u0 + j] + (1.f - u) * c;
+      put_granule(d.xc + (size_t)n * 2 * DD + u0 + j, tag, x1f[n * DD + u0 + j] + h);
+      put_granule(d.xc + (size_t)n * 2 * DD + DD + u0 + j, tag, h);
+    }
+    lds_barrier();                           // yh1's h1 half was read above; the gather below rewrites it
+    // ---- D4: y1 | h1 of every unit -> GRU_2 gates of the own units, r * h2(s-1)
+    good = map_gather<(DNR * 2 * DD + CT - 1) / CT>(N * 2 * DD, tag, yh1, tid, status, 8, [&](int i, const u64*& src, int& di) {
+      src = d.xc + i; di = i;
+    });
+    if (!good) flag[0] = 1.f;
+    lds_barrier();
+    if (flag[0] != 0.f) return;
+    for (int n = 0; n < N; ++n)
+      red[n * CT + tid] = dot_regs<32>(g2r, k32 < 8 ? yh1 + n * 2 * DD + k32 * 32 : h2f + n * DD + (k32 - 8) * 32);
+    lds_barrier();
+    if (tid < N * 2 * DU) {
+      const int n = tid / (2 * DU), c = tid % (2 * DU);
+      float z = bg2v;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) z += red[n * CT + q * 2 * DU + c];
+      const float v = sigmoidf_(z);
+      rus[n * 2 * DU + c] = v;
+      if (c < DU) put_granule(d.xd + (size_t)n * DD + u0 + c, tag, v * h2f[n * DD + u0 + c]);
+    }
+    // ---- D5: r * h2 of every unit -> candidate, h2(s), y2 = y1 + h2 of the own units; the feedback shares
+    good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, rhf, tid, status, 9, [&](int i, const u64*& src, int& di) {
+      src = d.xd + i; di = i;
+    });
+    if (!good) flag[0] = 1.f;
+    lds_barrier();
+    if (flag[0] != 0.f) return;
+    for (int n = 0; n < N; ++n)
+      red[n * CT + tid] = dot_regs<16>(c2r, k16 < 16 ? yh1 + n * 2 * DD + k16 * 16 : rhf + n * DD + (k16 - 16) * 16);
+    lds_barrier();
+    if (tid < N * DU) {
+      const int n = tid / DU, j = tid % DU;
+      float z = bc2v;
+#pragma unroll
+      for (int q = 0; q < 32; ++q) z += red[n * CT + q * DU + j];
+      const float c = tanhf_(z), u = rus[n * 2 * DU + DU + j];
+      const float h = u * h2f[n * DD + u0 + j] + (1.f - u) * c;
+      const float y = yh1[n * 2 * DD + u0 + j] + h;
+      y2s[n * DU + j] = y;
+      d.y2[((long)n * S1 + slot) * DD + u0 + j] = y;
+      if (st + 1 < p.S) put_granule(d.xe + (size_t)n * DD + u0 + j, tag, h);
+    }
+    lds_barrier();
+    if (st + 1 < p.S) {
+      // f1(s+1) share of the own rows: thread = (column tid & 255, rows 8 (tid >> 8) ..)
+      for (int n = 0; n < N; ++n) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s = fmaf(fpr[i], y2s[n * DU + (tid >> 8) * 8 + i], s);
+        red[n * CT + tid] = s;
+      }
+      lds_barrier();
+      if (tid < D1)
+        for (int n = 0; n < N; ++n)
+          put_granule(d.att.f1x + ((size_t)n * DNW + w) * D1 + tid, tag + 1, red[n * CT + tid] + red[n * CT + D1 + tid]);
+      // ---- D6: h2(s) of every unit for the next step
+      good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, h2f, tid, status, 10, [&](int i, const u64*& src, int& di) {
+        src = d.xe + i; di = i;
+      });
+      if (!good) flag[0] = 1.f;
+      lds_barrier();
+      if (flag[0] != 0.f) return;
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(CT) void taco1_decode_kernel(DArgs d) {
+  extern __shared__ __attribute__((aligned(16))) float sm_dec[];
+  const int na = d.att.p.N * CG;
+  if ((int)blockIdx.x < na) attn_fwd_body<T, true>(d.att, sm_dec, blockIdx.x);
+  else dec_role<T>(d, sm_dec, blockIdx.x - na);
+}
+
+constexpr size_t DEC_LDS = sizeof(float) * (DNR * A + DNR * 256 + DNR * DD * 2 + DNR * 2 * DD + DNR * DD + DNR * CT +
+                                            DNR * 2 * DU + DNR * DU + 4 + DNR * 256 * DU);
+constexpr size_t DECODE_LDS = DEC_LDS > FWD_LDS ? DEC_LDS : FWD_LDS;
+static_assert(DECODE_LDS <= 160 * 1024 && D1 == 256 && DD == 256, "LDS / shapes");
+size_t decode_granules(int N) {
+  return fwd_granules(N) + (size_t)N * DNW * D1 + (size_t)N * 256 + (size_t)N * DD * 6;
+}
 }  // namespace
 
 extern "C" int ns_taco1_attn_cluster_supported(const ns_taco1_attn_params* p) {
@@ -791,4 +1122,58 @@ extern "C" int ns_taco1_attn_cluster_fwd(const ns_taco1_attn_params* p, void* wo
 }
 extern "C" int ns_taco1_attn_cluster_bwd(const ns_taco1_attn_params* p, void* work, ns_stream_t s) {
   return taco1_run(p, work, (hipStream_t)s, 1);
+}
+
+// ------------------------------------------------------------------ free-running synthesis, C ABI
+extern "C" int ns_taco1_decode_supported(const ns_taco1_decode_params* q) {
+  if (!q) return 0;
+  const ns_taco1_attn_params* p = &q->att;
+  if (!ns_taco1_attn_cluster_supported(p)) return 0;
+  if (q->D != DD || p->N > DNR || p->Tia > 256 || p->E < 1) return 0;
+  if (!q->values || !q->w_proj || !q->b_proj || !q->wg_1 || !q->bg_1 || !q->wc_1 || !q->bc_1 || !q->wg_2 || !q->bg_2 ||
+      !q->wc_2 || !q->bc_2 || !q->wpf || !q->bpf || !q->y2)
+    return 0;
+  return p->N * CG + DNW <= ns_device_cus();     // every workgroup of the launch resident at once, one per CU
+}
+
+extern "C" size_t ns_taco1_decode_work_bytes(const ns_taco1_decode_params* q) {
+  if (!q) return 0;
+  return 256 + decode_granules(q->att.N) * sizeof(u64);
+}
+
+extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  NS_CHECK_ARG(q && work, "ns_taco1_decode: null");
+  NS_CHECK_ARG(ns_taco1_decode_supported(q), "ns_taco1_decode: unsupported shape (needs A = D1 = D = 256, D2 = 128, "
+               "T_in <= 256, N <= 2, 8 N + 16 workgroups resident) or a null operand");
+  const ns_taco1_attn_params* p = &q->att;
+  DArgs d = {};
+  d.att.p = *p;
+  d.att.status = (int*)work;
+  const size_t N = (size_t)p->N;
+  u64* x = (u64*)((char*)work + 256);
+  d.att.x1 = x; d.att.x2 = d.att.x1 + N * CG * X1N; d.att.x3 = d.att.x2 + N * CG * X2N; d.att.x4 = nullptr;
+  d.att.f1x = d.att.x3 + N * CG * X3N;
+  d.att.alx = d.att.f1x + N * DNW * D1;
+  d.att.bpf = q->bpf;
+  d.att.nwd = DNW;
+  d.xa = d.att.alx + N * 256;
+  d.xb = d.xa + N * DD; d.xc = d.xb + N * DD; d.xd = d.xc + 2 * N * DD; d.xe = d.xd + N * DD;
+  d.values = q->values;
+  d.wp = q->w_proj; d.bp = q->b_proj;
+  d.wg1 = q->wg_1; d.bg1 = q->bg_1; d.wc1 = q->wc_1; d.bc1 = q->bc_1;
+  d.wg2 = q->wg_2; d.bg2 = q->bg_2; d.wc2 = q->wc_2; d.bc2 = q->bc_2;
+  d.wpf = q->wpf; d.y2 = q->y2;
+  { const int zrc = ns_zero_async(work, (256 + decode_granules(p->N) * sizeof(u64) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)taco1_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)taco1_decode_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  const dim3 grid((unsigned)(p->N * CG + DNW)), block(CT);
+  if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_decode_kernel<bf16_t>, grid, block, DECODE_LDS, s, d);
+  else hipLaunchKernelGGL(taco1_decode_kernel<float>, grid, block, DECODE_LDS, s, d);
+  NS_CHECK_LAUNCH("ns_taco1_decode");
+  return NS_OK;
 }

@@ -665,6 +665,72 @@ class Tacotron(Tacotron2):
                           hp_sn=x_sn, out=(out, out_off), out_sn=out_sn, out2=(out2, out2_off) if out2 is not None else None,
                           out2_sn=out2_sn)
 
+    def _decode_persistent(self, N, Ti, Pi, Tia, S, enc, keys, spk_dec):
+        """The free-running decoder loop as ONE launch (ns_taco1_decode): attention clusters + register-resident
+        projection / decoder GRUs + folded frame feedback.  Returns (dec, al, S1) in the [N, S+1, X] slot layout, or
+        None when the shape is not covered (other widths, T_in > 256, more than two utterances)."""
+        import ctypes as C
+        from .. import _lib as L
+        hp = self._hparams
+        T_ = self.T
+        r, M = hp.outputs_per_step, hp.num_mels
+        A, D, E = hp.attention_dim, hp.decoder_dim, 256
+        S1 = S + 1
+        buf, o, W, fp = self._buf, self._o, self._W(T_), self.flat_p
+        Dsp = self.Dsp
+        XA = 128 + Dsp + A
+        w1, b1 = o("decoder/decoder_prenet/dense_1/kernel"), o("decoder/decoder_prenet/dense_1/bias")
+        # <GO> frame = zeros and no context yet: the frame term of step 0 is the prenet bias (only slot 1 is read)
+        f1 = buf("pd_f1", N * S1 * 256, torch.float32)
+        ops.copy3d(fp, f1, N, 1, 256, (0, 0), (S1 * 256, 0), src_off=b1, dst_off=256)
+        pv = buf("pd_pv", N * Pi * 256, T_)
+        ops.gemm(enc.buf, W, pv, N * Pi, 256, E, E, 256, 256, b_mode=1, b_off=w1 + M * 256)
+        xa = buf("pd_xa", N * S1 * XA, T_)
+        if Dsp:
+            ops.copy3d(spk_dec.buf, xa, N, S1, Dsp, (Dsp, 0), (S1 * XA, XA), dst_off=128)
+        al = buf("pd_al", N * S1 * Tia, torch.float32)
+        args = dict(dtype=ops.dt(xa), N=N, S=S, Ti=Ti, Pi=Pi, padl_i=self.padl, Tia=Tia, A=A, E=E, D1=256, D2=128,
+                    lengths=self.input_lengths, keys=keys, pv=pv, f1=f1,
+                    w2=(W, o("decoder/decoder_prenet/dense_2/kernel")), wg=(W, o("decoder/attention_gru/gates/kernel")),
+                    wc=(W, o("decoder/attention_gru/candidate/kernel")), wq=(W, o("decoder/attention/query_layer/kernel")),
+                    b2=(fp, o("decoder/decoder_prenet/dense_2/bias")), bg=(fp, o("decoder/attention_gru/gates/bias")),
+                    bc=(fp, o("decoder/attention_gru/candidate/bias")), v=(fp, o("decoder/attention/attention_v")),
+                    p1=buf("pd_p1", N * S1 * 256, T_), xa=xa, xc=buf("pd_xc", N * S1 * XA, T_),
+                    hc=buf("pd_hc", N * S1 * (A + E), T_), ru=buf("pd_ru", N * S1 * 2 * A, torch.float32),
+                    cc=buf("pd_cc", N * S1 * A, torch.float32), q=buf("pd_q", N * S1 * A, torch.float32), align=al, Dsp=Dsp)
+        q = L.struct("ns_taco1_decode_params")
+        q.att = ops._taco1_attn_params(args)
+        q.D = D
+        q.values = ops.ptr(enc.buf)
+        q.w_proj = ops.ptr(fp, o("decoder/attention_projection/kernel"))
+        q.b_proj = ops.ptr(fp, o("decoder/attention_projection/bias"))
+        for i in (1, 2):
+            for f, nm in (("wg", "gates/kernel"), ("bg", "gates/bias"), ("wc", "candidate/kernel"), ("bc", "candidate/bias")):
+                setattr(q, "%s_%d" % (f, i), ops.ptr(fp, o("decoder/gru_%d/%s" % (i, nm))))
+        # folded feedback (exact fp32): wpf = W_out[:, last frame] . W_prenet1[frame rows], bpf = b_out[last frame] . same + b1
+        wpf = buf("pd_wpf", D * 256, torch.float32)
+        bpf = buf("pd_bpf", 256, torch.float32)
+        kp, bp = o("decoder/output_projection/kernel"), o("decoder/output_projection/bias")
+        ops.gemm(fp, fp, wpf, D, 256, M, M * r, 256, 256, b_mode=1, a_off=kp + (r - 1) * M, b_off=w1, f32_passes=0)
+        ops.gemm(fp, fp, bpf, 1, 256, M, M * r, 256, 256, b_mode=1, a_off=bp + (r - 1) * M, b_off=w1, bias=fp,
+                 bias_off=b1, f32_passes=0)
+        q.wpf, q.bpf = ops.ptr(wpf), ops.ptr(bpf)
+        y2 = buf("pd_y2", N * S1 * D, torch.float32)
+        q.y2 = ops.ptr(y2)
+        lib = L.lib()
+        if not lib.ns_taco1_decode_supported(C.byref(q)):
+            return None
+        fn = lib.ns_taco1_decode_work_bytes
+        fn.restype = C.c_size_t
+        # a work buffer of its own: a status word shared with another persistent kernel could be cleared under a raised one
+        work = buf("t1_decode_work", (int(fn(C.byref(q))) + 3) // 4, torch.float32)
+        L.check(lib.ns_taco1_decode(C.byref(q), C.c_void_p(ops.ptr(work)), C.c_void_p(ops.stream())), "ns_taco1_decode")
+        self._status_words[("decode", "fwd")] = work
+        # the output projection over the whole y2 history (tacotron.py:76), off the loop's critical path
+        dec = buf("pd_dec", N * S1 * M * r, torch.float32)
+        ops.gemm(y2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=kp, bias=fp, bias_off=bp)
+        return dec, al, S1
+
     def forward_infer(self):
         """tacotron.py with linear_targets=None: TacoTestHelper feedback for max_iters steps (Q7),
         BatchNorm on moving statistics; sets mel_outputs, linear_outputs, alignments and audio."""
@@ -714,48 +780,58 @@ class Tacotron(Tacotron2):
         Tia = _round_up(Ti, 8)
         keys_t = buf("keys_t", N * A * Tia, torch.float32)
         ops.keys_transpose(keys, keys_t, N, Ti, Tia, Pi, self.padl, A)
-        XP, XA, HC, X1 = M + E, XI + A, A + E, 2 * D
-        xp = buf("i_xp", N * S1 * XP, T_); p1 = buf("i_p1", N * 256, T_)
-        xa = buf("i_xa", N * S1 * XA, T_); xc = buf("i_xc", N * max(XA, X1), T_)
-        hc = buf("i_hc", N * S1 * HC, T_)
-        g1 = buf("i_g1", N * S1 * X1, T_); g2 = buf("i_g2", N * S1 * X1, T_)     # [input | h_prev] rows of the GRUs
-        y1 = buf("i_y1", N * D, T_); y2 = buf("i_y2", N * D, T_); hh = buf("i_hh", N * D, T_)
-        ru = buf("i_ru", N * 2 * max(A, D), torch.float32); cc = buf("i_cc", N * max(A, D), torch.float32)
-        q = buf("i_q", N * A, torch.float32); al = buf("i_al", N * S1 * Tia, torch.float32)
-        er = buf("i_er", N * Tia, torch.float32); dec = buf("i_dec", N * S1 * M * r, torch.float32)
-        for b in (xp, xa, hc, g1, g2, al):
-            ops.zero(b)
-        if Dsp:
-            ops.copy3d(spk_dec.buf, xa, N, S1, Dsp, (Dsp, 0), (S1 * XA, XA), dst_off=128)
-        ov = o("decoder/attention/attention_v")
-        for s in range(S):
-            sl, nx = s + 1, s + 2
-            ops.gemm(xp, tsh["w1T_full"], p1, N, 256, XP, S1 * XP, XP, 256, a_off=sl * XP, bias=self.flat_p,
-                     bias_off=o("decoder/decoder_prenet/dense_1/bias"), act=ACT_RELU)
-            ops.gemm(p1, tsh["w2T"], xa, N, 128, 256, 256, 256, S1 * XA, c_off=sl * XA, bias=self.flat_p,
-                     bias_off=o("decoder/decoder_prenet/dense_2/bias"), act=ACT_RELU)
-            self._gru_step_infer(xa, sl * XA, S1 * XA, XA, tsh["att_gT"], tsh["att_cT"], o("decoder/attention_gru/gates/bias"),
-                                 o("decoder/attention_gru/candidate/bias"), xc, A, 0, hc, sl * HC, S1 * HC, xa,
-                                 nx * XA + XI, S1 * XA, ru, cc, N)
-            ops.gemm(hc, tsh["wqT"], q, N, A, A, S1 * HC, A, A, a_off=sl * HC)
-            ops.attention_step(hc, N, Ti, Pi, self.padl, Tia, A, E, self.KW, lengths, keys_t, enc.buf, (q, 0), A,
-                               (al, s * Tia), (al, sl * Tia), S1 * Tia, (hc, sl * HC + A), S1 * HC, (xp, nx * XP + M),
-                               S1 * XP, tsh["wcl"], (self.flat_p, ov), er)
-            # x1 = Dense([h_att | ctx]) -> residual GRU 1 -> residual GRU 2 -> r frames
-            ops.gemm(hc, tsh["wprojT"], g1, N, D, HC, S1 * HC, HC, S1 * X1, a_off=sl * HC, c_off=sl * X1, bias=self.flat_p,
-                     bias_off=o("decoder/attention_projection/bias"))
-            self._gru_step_infer(g1, sl * X1, S1 * X1, X1, tsh["gru_1_gTf"], tsh["gru_1_cTf"], o("decoder/gru_1/gates/bias"),
-                                 o("decoder/gru_1/candidate/bias"), xc, D, 0, hh, 0, D, g1, nx * X1 + D, S1 * X1, ru, cc, N)
-            ops.copy3d(g1, y1, N, 1, D, (S1 * X1, 0), (D, 0), src_off=sl * X1)
-            ops.copy3d(hh, y1, N, 1, D, (D, 0), (D, 0), accumulate=1)
-            ops.copy3d(y1, g2, N, 1, D, (D, 0), (S1 * X1, 0), dst_off=sl * X1)
-            self._gru_step_infer(g2, sl * X1, S1 * X1, X1, tsh["gru_2_gTf"], tsh["gru_2_cTf"], o("decoder/gru_2/gates/bias"),
-                                 o("decoder/gru_2/candidate/bias"), xc, D, 0, hh, 0, D, g2, nx * X1 + D, S1 * X1, ru, cc, N)
-            ops.copy3d(y1, y2, N, 1, D, (D, 0), (D, 0))
-            ops.copy3d(hh, y2, N, 1, D, (D, 0), (D, 0), accumulate=1)
-            ops.gemm(y2, tsh["woutT"], dec, N, M * r, D, D, D, S1 * M * r, c_off=sl * M * r, bias=self.flat_p,
-                     bias_off=o("decoder/output_projection/bias"))
-            ops.copy3d(dec, xp, N, 1, M, (S1 * M * r, 0), (S1 * XP, 0), src_off=sl * M * r + (r - 1) * M, dst_off=nx * XP)
+        # The whole free-running loop as ONE persistent launch (csrc/attn_gru.hip "free-running synthesis") where the shape
+        # allows; otherwise one decoder step = ~28 dependent launches from here.  last_paths["decode"] says which ran.
+        done = None
+        if getattr(self, "use_decode_kernel", True):
+            done = self._decode_persistent(N, Ti, Pi, Tia, S, enc, keys, spk_dec)
+        if done is not None:
+            self.last_paths["decode"] = "persistent"
+            dec, al, S1 = done
+        else:
+            self.last_paths["decode"] = "step"
+            XP, XA, HC, X1 = M + E, XI + A, A + E, 2 * D
+            xp = buf("i_xp", N * S1 * XP, T_); p1 = buf("i_p1", N * 256, T_)
+            xa = buf("i_xa", N * S1 * XA, T_); xc = buf("i_xc", N * max(XA, X1), T_)
+            hc = buf("i_hc", N * S1 * HC, T_)
+            g1 = buf("i_g1", N * S1 * X1, T_); g2 = buf("i_g2", N * S1 * X1, T_)     # [input | h_prev] rows of the GRUs
+            y1 = buf("i_y1", N * D, T_); y2 = buf("i_y2", N * D, T_); hh = buf("i_hh", N * D, T_)
+            ru = buf("i_ru", N * 2 * max(A, D), torch.float32); cc = buf("i_cc", N * max(A, D), torch.float32)
+            q = buf("i_q", N * A, torch.float32); al = buf("i_al", N * S1 * Tia, torch.float32)
+            er = buf("i_er", N * Tia, torch.float32); dec = buf("i_dec", N * S1 * M * r, torch.float32)
+            for b in (xp, xa, hc, g1, g2, al):
+                ops.zero(b)
+            if Dsp:
+                ops.copy3d(spk_dec.buf, xa, N, S1, Dsp, (Dsp, 0), (S1 * XA, XA), dst_off=128)
+            ov = o("decoder/attention/attention_v")
+            for s in range(S):
+                sl, nx = s + 1, s + 2
+                ops.gemm(xp, tsh["w1T_full"], p1, N, 256, XP, S1 * XP, XP, 256, a_off=sl * XP, bias=self.flat_p,
+                         bias_off=o("decoder/decoder_prenet/dense_1/bias"), act=ACT_RELU)
+                ops.gemm(p1, tsh["w2T"], xa, N, 128, 256, 256, 256, S1 * XA, c_off=sl * XA, bias=self.flat_p,
+                         bias_off=o("decoder/decoder_prenet/dense_2/bias"), act=ACT_RELU)
+                self._gru_step_infer(xa, sl * XA, S1 * XA, XA, tsh["att_gT"], tsh["att_cT"], o("decoder/attention_gru/gates/bias"),
+                                     o("decoder/attention_gru/candidate/bias"), xc, A, 0, hc, sl * HC, S1 * HC, xa,
+                                     nx * XA + XI, S1 * XA, ru, cc, N)
+                ops.gemm(hc, tsh["wqT"], q, N, A, A, S1 * HC, A, A, a_off=sl * HC)
+                ops.attention_step(hc, N, Ti, Pi, self.padl, Tia, A, E, self.KW, lengths, keys_t, enc.buf, (q, 0), A,
+                                   (al, s * Tia), (al, sl * Tia), S1 * Tia, (hc, sl * HC + A), S1 * HC, (xp, nx * XP + M),
+                                   S1 * XP, tsh["wcl"], (self.flat_p, ov), er)
+                # x1 = Dense([h_att | ctx]) -> residual GRU 1 -> residual GRU 2 -> r frames
+                ops.gemm(hc, tsh["wprojT"], g1, N, D, HC, S1 * HC, HC, S1 * X1, a_off=sl * HC, c_off=sl * X1, bias=self.flat_p,
+                         bias_off=o("decoder/attention_projection/bias"))
+                self._gru_step_infer(g1, sl * X1, S1 * X1, X1, tsh["gru_1_gTf"], tsh["gru_1_cTf"], o("decoder/gru_1/gates/bias"),
+                                     o("decoder/gru_1/candidate/bias"), xc, D, 0, hh, 0, D, g1, nx * X1 + D, S1 * X1, ru, cc, N)
+                ops.copy3d(g1, y1, N, 1, D, (S1 * X1, 0), (D, 0), src_off=sl * X1)
+                ops.copy3d(hh, y1, N, 1, D, (D, 0), (D, 0), accumulate=1)
+                ops.copy3d(y1, g2, N, 1, D, (D, 0), (S1 * X1, 0), dst_off=sl * X1)
+                self._gru_step_infer(g2, sl * X1, S1 * X1, X1, tsh["gru_2_gTf"], tsh["gru_2_cTf"], o("decoder/gru_2/gates/bias"),
+                                     o("decoder/gru_2/candidate/bias"), xc, D, 0, hh, 0, D, g2, nx * X1 + D, S1 * X1, ru, cc, N)
+                ops.copy3d(y1, y2, N, 1, D, (D, 0), (D, 0))
+                ops.copy3d(hh, y2, N, 1, D, (D, 0), (D, 0), accumulate=1)
+                ops.gemm(y2, tsh["woutT"], dec, N, M * r, D, D, D, S1 * M * r, c_off=sl * M * r, bias=self.flat_p,
+                         bias_off=o("decoder/output_projection/bias"))
+                ops.copy3d(dec, xp, N, 1, M, (S1 * M * r, 0), (S1 * XP, 0), src_off=sl * M * r + (r - 1) * M, dst_off=nx * XP)
         melp = Act(self, "mel_pad", N, Po, self.padl, To, M)
         ops.copy3d(dec, melp.buf, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
         post = self._cbhg("post", melp, None, "post_cbhg", hp.post_cbhg_banks, list(hp.post_cbhg_bank_sizes) + [M], False)
