@@ -364,7 +364,9 @@ int ns_lstm_seq2_bwd(const ns_lstm_seq_params* p0, const ns_lstm_seq_params* p1,
  * (+ the optional h_bf16 copy), c as fp32 and the saved gates as BF16 - the backward pass of that arrangement is the
  * bf16 call on wh = the bf16 weight copy.  ns_lstm_cluster_supported() says whether a pair of parameter blocks
  * qualifies.  work[0] (int) is a status word: non-zero after the call completes = an exchange timed out and the
- * outputs are invalid. */
+ * outputs are invalid.  For H <= 256 the launch picks the rows of a chain itself - 16, 8 or 4, the narrowest whose grid
+ * stays within half of the device's CUs; every form writes the same bits - and NS_CLUSTER_ROWS=16|8|4 in the
+ * environment, read per call, forces one; work[1] (int) reports a narrow form's rows (0 = 16). */
 int ns_lstm_cluster_supported(const ns_lstm_seq_params* fw, const ns_lstm_seq_params* bw, int backward);
 size_t ns_lstm_cluster_work_bytes(const ns_lstm_seq_params* p);
 int ns_lstm_cluster_fwd(const ns_lstm_seq_params* fw, const ns_lstm_seq_params* bw, void* work, ns_stream_t stream);

@@ -1,10 +1,16 @@
 // Persistent BiLSTM recurrence: ONE launch for the whole sequence instead of one per time step.
 //
-// A "chain" = (direction, group of 16 batch rows) is an independent recurrence.  It runs on a
+// A "chain" = (direction, group of batch rows) is an independent recurrence: 16 rows (the MFMA tile's other
+// dimension) in the single-role and interleaved kernels, 16, 8 or 4 in the role-split kernels (template parameter RPC,
+// picked per launch by cluster_rows(); the rows of the tile beyond RPC are padding that is never loaded, published or
+// stored).  Batch rows are independent, so every form writes the same bits; a narrow chain moves RPC / 16 of the bytes
+// per hop - the hop is what bounds a step - and the batch takes 16 / RPC times the workgroups: at batch 32, H 256 the
+// expand BiLSTM runs on 64 CUs instead of 16, forward 2.16 -> 1.59 ms, backward 2.16 -> 1.90 ms
+// (profiles/cluster_rows.txt).  It runs on a
 // cluster of CS = H/64 workgroups (one per CU); workgroup c owns hidden units [64c, 64c+64) and
 // keeps its slice of W_h^T - 64 units x 4 gates x H - in REGISTERS as MFMA B fragments for the
 // whole sequence (8 waves x 8 units, 64 VGPRs per lane), and the cell state in registers too.
-// Per step the only inter-workgroup traffic is the new h slice (16 rows x 64 units), exchanged
+// Per step the only inter-workgroup traffic is the new h slice (rows of the chain x 64 units), exchanged
 // through global memory as 8-byte {step tag, 2 x bf16} granules written and polled with relaxed
 // agent-scope atomics (sc1; no fences, data is its own flag), double-buffered by step parity.
 // Measured exchange cost: ~1.3 us per step for 4 workgroups (vs ~6-8 us per dependent launch).
@@ -418,20 +424,21 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
 // waves (own block: R = 1 in slot q-1 behind barrier(q-1), R = 2 behind barrier(q-1) of the slot after the producing
 // one) in front of barrier(q), read behind it, refilled behind barrier(q+1); xgs[(q+1)&1] is stored between
 // barrier(q-1) and barrier(q), read between barrier(q) and barrier(q+1); svs as before.
-template <int HB, int R>
+template <int HB, int R, int RPC>
 __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int H = HB * 64, KS = H / 32, CS = HB;
-  constexpr int GPD = XW * 64 * 2;                              // granules per source workgroup and slot: [wave][lane][2]
+  static_assert(RPC == 16 || ((RPC == 8 || RPC == 4) && R == 1), "rows per chain");
+  constexpr int GPD = XW * (4 * RPC) * 2;                       // granules per source workgroup and slot: [wave][g][row][2]
   bf16_t* hs = (bf16_t*)smem;                                   // [2][16][H] swizzled
   float* xgs = (float*)(smem + (size_t)2 * 16 * H * 2);         // [2][16][XG_LD]: row, gate * 64 + unit
-  // this slot's results for the saver wave: h bf16 [16][64], c f32 [16][64], gates bf16 [16][4][64]  (2 + 4 + 8 KB)
-  constexpr int SV_H = 16 * 64 * 2, SV_C = 16 * 64 * 4, SV_G = 16 * 4 * 64 * 2, SV_BYTES = SV_H + SV_C + SV_G;
+  // this slot's results for the saver wave: h bf16 [RPC][64], c f32 [RPC][64], gates bf16 [RPC][4][64]  (2 + 4 + 8 KB at 16 rows)
+  constexpr int SV_H = RPC * 64 * 2, SV_C = RPC * 64 * 4, SV_G = RPC * 4 * 64 * 2, SV_BYTES = SV_H + SV_C + SV_G;
   char* svs = (char*)(xgs + 2 * 16 * XG_LD);                    // [2][SV_BYTES]
   int* abortf = (int*)(svs + 2 * SV_BYTES);                     // [2]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nsets = ((a.N + 15) / 16 + R - 1) / R;
+  const int nsets = ((a.N + RPC - 1) / RPC + R - 1) / R;
   const int set = blockIdx.x / CS, wgc = blockIdx.x % CS;
   const int d = set / nsets, rg0 = (set % nsets) * R;           // this workgroup serves row groups rg0 .. rg0+R-1
   const int r16 = lane & 15, g = lane >> 4;
@@ -439,9 +446,17 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
   const int u0 = wgc * 64;
   const int T = a.T, Q = a.T * R;
   if (tid < 3) abortf[tid] = 0;
+  if (RPC < 16) {
+    // rows >= RPC of the operand images are padding of the MFMA's B operand: zeroed here, in front of every role's first
+    // barrier, and never written again
+    for (int i = tid; i < 2 * 16 * H / 8; i += FW_WAVES * 64) ((uint4*)hs)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
+  }
 
   if (wave < XW) {
-    // ================================================================ compute role: batch row r16, units wq .. wq + 3
+    // ================================================================ compute role: batch row r16, units wq .. wq + 3;
+    // lanes with r16 >= RPC are padding: they publish nothing, store nothing, and what they compute is never read
+    const bool live = RPC == 16 || r16 < RPC;
     const int wq = wave * 16 + g * 4;                  // first of the lane's 4 units inside the workgroup's 64
     bf16x8 bw[4][KS];                                  // A fragments: row (unit) wave * 16 + r16, k chunk g
     {
@@ -458,8 +473,8 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
     uint2 pend[R];                                     // R = 2: the own h block waits for the next slot's barrier
 #pragma unroll
     for (int rg = 0; rg < R; ++rg) {
-      const int n = (rg0 + rg) * 16 + r16;
-      len[rg] = (a.lengths && n < a.N) ? a.lengths[n] : T;
+      const int n = (rg0 + rg) * RPC + r16;
+      len[rg] = (a.lengths && live && n < a.N) ? a.lengths[n] : T;
       pend[rg] = make_uint2(0u, 0u);
 #pragma unroll
       for (int r = 0; r < 4; ++r) cst[rg][r] = 0.f;
@@ -512,17 +527,17 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         hp.x = pack_bf16(hv[0], hv[1]);
         hp.y = pack_bf16(hv[2], hv[3]);
         if (step + 1 < T) {
-          if (CS > 1) {
-            u64* nxt = xb0 + ((size_t)rg * 2 + ((step + 1) & 1)) * CS * GPD + (size_t)wgc * GPD + (wave * 64 + lane) * 2;
+          if (CS > 1 && live) {
+            u64* nxt = xb0 + ((size_t)rg * 2 + ((step + 1) & 1)) * CS * GPD + (size_t)wgc * GPD + (wave * 4 * RPC + g * RPC + r16) * 2;
             __hip_atomic_store(nxt, ((u64)(unsigned)(step + 1) << 32) | hp.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(nxt + 1, ((u64)(unsigned)(step + 1) << 32) | hp.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
-          if (R == 1) *(uint2*)(hs + (size_t)((q + 1) & 1) * 16 * H + swz_off(r16, u0 + wq, H)) = hp;
+          if (R == 1) { if (live) *(uint2*)(hs + (size_t)((q + 1) & 1) * 16 * H + swz_off(r16, u0 + wq, H)) = hp; }
           else pend[rg] = hp;
         }
         if (tr) a.trace[q * 8 + 2] = wall_clock64();
         // results for the backward pass / the consumers of h go to LDS; the saver wave writes them out
-        {
+        if (live) {
           char* sv = svs + (size_t)buf * SV_BYTES;
           *(uint2*)((bf16_t*)sv + r16 * 64 + wq) = hp;
           *(f32x4*)((float*)(sv + SV_H) + r16 * 64 + wq) = (f32x4){cst[rg][0], cst[rg][1], cst[rg][2], cst[rg][3]};
@@ -576,12 +591,12 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         bf16_t* dst = hs + (size_t)buf * 16 * H;
 #pragma unroll
         for (int j = 0; j < PPG; ++j) {
-          // granule li of source ws: wave (li / 128) % 4, lane' = (li / 2) % 64 -> row lane' % 16, units 4 (lane' / 16) + 2 (li % 2)
+          // granule li of source ws: wave (li / (8 RPC)) % 4, lane' = (li / 2) % (4 RPC) -> row lane' % RPC, units 4 (lane' / RPC) + 2 (li % 2)
           const int li = lane + 64 * (j0 + j), sx = li / GPD, lw = li % GPD;
           const int ws = sx < wgc ? sx : sx + 1;
-          const int lp = (lw >> 1) & 63;
-          const int k = ws * 64 + (lw >> 7) * 16 + (lp >> 4) * 4 + (lw & 1) * 2;
-          *(unsigned*)(dst + swz_off(lp & 15, k, H)) = (unsigned)v[j];
+          const int lp = (lw >> 1) % (4 * RPC);
+          const int k = ws * 64 + (lw / (8 * RPC)) * 16 + (lp / RPC) * 4 + (lw & 1) * 2;
+          *(unsigned*)(dst + swz_off(lp % RPC, k, H)) = (unsigned)v[j];
         }
       }
       wg_barrier();
@@ -591,26 +606,28 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
   } else if (wave == XW + 2) {
     // ================================================================ saver role (stores only)
     // Runs one slot behind the compute waves (slot q-1 is complete once barrier q has passed), so its store
-    // issue overlaps their next slot.  Per slot: h 128 chunks of 16 B, c 256, gates 512 -> 14 per lane.
+    // issue overlaps their next slot.  Per slot and row: h 8 chunks of 16 B, c 16, gates 32 -> 14 per lane at 16 rows.
+    constexpr int NH = RPC * 8, NC = RPC * 16, NG = RPC * 32, NJ = (NH + NC + NG + 63) / 64;
     auto save = [&](int q) {
       const int step = q / R, rg = q % R;
       const int t = d ? T - 1 - step : step;
-      const int n0 = (rg0 + rg) * 16;
+      const int n0 = (rg0 + rg) * RPC;
       const char* sv = svs + (size_t)(q & 1) * SV_BYTES;
 #pragma unroll
-      for (int j = 0; j < 14; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         const int idx = lane + 64 * j;
+        if ((NH + NC + NG) % 64 != 0 && idx >= NH + NC + NG) break;
         const f32x4 v = *(const f32x4*)(sv + idx * 16);
-        if (idx < 128) {
+        if (idx < NH) {
           const int row = idx >> 3, cc = idx & 7;
           if (n0 + row < a.N)
             *(f32x4*)(a.h[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)a.ld_h + (unsigned)(u0 + cc * 8))) = v;
-        } else if (idx < 384) {
-          const int jj = idx - 128, row = jj >> 4, cc = jj & 15;
+        } else if (idx < NH + NC) {
+          const int jj = idx - NH, row = jj >> 4, cc = jj & 15;
           if (n0 + row < a.N)
             *(f32x4*)(a.c[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)H + (unsigned)(u0 + cc * 4))) = v;
         } else {
-          const int jj = idx - 384, row = jj >> 5, gate = (jj >> 3) & 3, cc = jj & 7;
+          const int jj = idx - NH - NC, row = jj >> 5, gate = (jj >> 3) & 3, cc = jj & 7;
           if (n0 + row < a.N)
             *(f32x4*)(a.gates[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)(4 * H) + (unsigned)(gate * H + u0 + cc * 8))) = v;
         }
@@ -627,15 +644,15 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
   } else {
     // ================================================================ prefetcher role, one interval ahead:
     // xg of slot q + 1 is in LDS before barrier(q).  Stage row j, gate = lane / 16, 4 floats at (lane % 16) * 4
-    f32x4 pf[16];
+    f32x4 pf[RPC];
     const float* xg = a.xg[d];
     const int pgate = lane >> 4, pf4 = (lane & 15) * 4;
     auto pf_load = [&](int q) {
       const int step = q / R, rg = q % R;
       const int t = d ? T - 1 - step : step;
-      const int n0 = (rg0 + rg) * 16;
+      const int n0 = (rg0 + rg) * RPC;
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
+      for (int j = 0; j < RPC; ++j) {
         const int n = n0 + j;
         pf[j] = n < a.N ? *(const f32x4*)(xg + ((unsigned)(n * a.P + a.padl + t) * (unsigned)a.ld_xg + (unsigned)(pgate * H + u0 + pf4)))
                         : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -643,7 +660,7 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
     };
     auto pf_store = [&](int buf) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) *(f32x4*)(xgs + ((size_t)buf * 16 + j) * XG_LD + pgate * 64 + pf4) = pf[j];
+      for (int j = 0; j < RPC; ++j) *(f32x4*)(xgs + ((size_t)buf * 16 + j) * XG_LD + pgate * 64 + pf4) = pf[j];
     };
     pf_load(0);
     pf_store(0);
@@ -677,24 +694,25 @@ constexpr int X3W = 4, X3_POLL = 2, X3_UPW = 32;
 constexpr int X3_WAVES = X3W + X3_POLL + 2;          // compute, pollers, prefetcher, saver: 8 waves, two per SIMD
 constexpr int XG3_LD = 4 * X3_UPW + 4;
 
-template <int HB, int R>        // HB = H / 64
+template <int HB, int R, int RPC>        // HB = H / 64, RPC = batch rows per chain
 __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int H = HB * 64, KS = H / 32, GPC = 16 * H;          // granules per chain and step
+  static_assert(RPC == 16 || ((RPC == 8 || RPC == 4) && R == 1), "rows per chain");
+  constexpr int H = HB * 64, KS = H / 32, GPC = RPC * H;         // granules per chain and step
   constexpr int CS = H / X3_UPW;                                   // workgroups per chain
   constexpr int PPG = GPC / (X3_POLL * 64);                        // granules per poller lane (H / 8)
   static_assert(GPC % (X3_POLL * 64) == 0, "poller coverage");
   bf16_t* hsh = (bf16_t*)smem;                                    // [2][16][H] swizzled, high parts
   bf16_t* hsl = hsh + 2 * 16 * H;                                 // [2][16][H] low parts
   float* xgs = (float*)(hsl + 2 * 16 * H);                        // [2][16][XG3_LD]: row, gate * 32 + unit
-  // this slot's results for the saver: h f32 [16][32], c f32 [16][32], gates bf16 [16][4][32], h bf16 [16][32]
-  constexpr int SV_H = 16 * 32 * 4, SV_C = 16 * 32 * 4, SV_G = 16 * 4 * 32 * 2, SV_HB = 16 * 32 * 2;
-  constexpr int SV_BYTES = SV_H + SV_C + SV_G + SV_HB;           // 9216
+  // this slot's results for the saver: h f32 [RPC][32], c f32 [RPC][32], gates bf16 [RPC][4][32], h bf16 [RPC][32]
+  constexpr int SV_H = RPC * 32 * 4, SV_C = RPC * 32 * 4, SV_G = RPC * 4 * 32 * 2, SV_HB = RPC * 32 * 2;
+  constexpr int SV_BYTES = SV_H + SV_C + SV_G + SV_HB;           // 9216 at 16 rows
   char* svs = (char*)(xgs + 2 * 16 * XG3_LD);                     // [2][SV_BYTES]
   int* abortf = (int*)(svs + 2 * SV_BYTES);                       // [2]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nsets = ((a.N + 15) / 16 + R - 1) / R;
+  const int nsets = ((a.N + RPC - 1) / RPC + R - 1) / R;
   const int set = blockIdx.x / CS, wgc = blockIdx.x % CS;
   const int d = set / nsets, rg0 = (set % nsets) * R;
   const int r16 = lane & 15, g = lane >> 4;
@@ -702,12 +720,18 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
   const int u0 = wgc * X3_UPW;
   const int T = a.T, Q = a.T * R;
   if (tid < 2) abortf[tid] = 0;          // (audit) written by wave 0 in front of its first wg_barrier, read behind it
+  if (RPC < 16) {
+    // rows >= RPC of the operand images are MFMA padding: zeroed in front of every role's first barrier, never written
+    for (int i = tid; i < 2 * 2 * 16 * H / 8; i += X3_WAVES * 64) ((uint4*)hsh)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
+  }
 
   if (wave < X3W) {
     // ================================================================ compute role
     const int ul = wave * 8 + (r16 & 7);                     // unit inside the workgroup's 32
-    const bool cell_lane = r16 < 8;
-    const int pub0 = (((wgc * X3W + wave) * 32) + g * 8 + (r16 & 7)) * 4;    // this lane's 4 granules (rows g*4 .. g*4+3)
+    // lane groups g >= RPC / 4 are padding rows: they publish nothing and store nothing
+    const bool cell_lane = r16 < 8 && (RPC == 16 || g < RPC / 4);
+    const int pub0 = (wgc * X3W + wave) * 8 * RPC + (g * 8 + (r16 & 7)) * 4;   // this lane's 4 granules (rows g*4 .. g*4+3)
     bf16x8 bwh[2][KS], bwl[2][KS];
     {
 #pragma unroll
@@ -727,9 +751,9 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     for (int rg = 0; rg < R; ++rg)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int n = (rg0 + rg) * 16 + g * 4 + r;
+        const int n = (rg0 + rg) * RPC + g * 4 + r;
         cst[rg][r] = 0.f;
-        len[rg][r] = (a.lengths && n < a.N) ? a.lengths[n] : T;
+        len[rg][r] = (a.lengths && (RPC == 16 || g < RPC / 4) && n < a.N) ? a.lengths[n] : T;
       }
     for (int step = 0; step < T; ++step) {
       const int t = d ? T - 1 - step : step;
@@ -798,8 +822,8 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     wg_barrier();
   } else if (wave < X3W + X3_POLL) {
     // ================================================================ poller role: granule lane + 64 * jj of the chain
-    // decodes as r = lane & 3, unit in wave = (lane >> 2) & 7, g = ((jj & 1) << 1) | (lane >> 5), publishing wave =
-    // (jj >> 1) & 3, publishing workgroup = jj >> 3
+    // decodes as r = lane & 3, unit in wave = (lane >> 2) & 7, and with xi = 2 jj + (lane >> 5): g = xi % (RPC / 4),
+    // publishing wave = (xi / (RPC / 4)) & 3, publishing workgroup = xi / RPC
     const int j0 = (wave - X3W) * PPG;
     const int pr_ = lane & 3, pu = (lane >> 2) & 7, pgl = lane >> 5;
     for (int q = 0; q < Q; ++q) {
@@ -826,9 +850,9 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
         bf16_t* dl_ = hsl + (size_t)buf * 16 * H;
 #pragma unroll
         for (int j = 0; j < PPG; ++j) {
-          const int jj = j0 + j;
-          const int row = (((jj & 1) << 1) | pgl) * 4 + pr_;
-          const int k = (jj >> 3) * X3_UPW + ((jj >> 1) & 3) * 8 + pu;
+          const int xi = 2 * (j0 + j) + pgl;
+          const int row = (xi % (RPC / 4)) * 4 + pr_;
+          const int k = (xi / RPC) * X3_UPW + ((xi / (RPC / 4)) & 3) * 8 + pu;
           const float x = __uint_as_float((unsigned)v[j]);
           const bf16_t hi = (bf16_t)x;
           const int so = swz_off(row, k, H);
@@ -842,30 +866,32 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     wg_barrier();
   } else if (wave == X3W + X3_POLL) {
     // ================================================================ saver role (stores only), one slot behind
-    // per slot: h f32 128 chunks of 16 B, c 128, gates 256, h bf16 64 -> 9 per lane
+    // per slot and row: h f32 8 chunks of 16 B, c 8, gates 16, h bf16 4 -> 9 per lane at 16 rows
+    constexpr int NH = RPC * 8, NG = RPC * 16, NB = RPC * 4, NJ = (2 * NH + NG + NB + 63) / 64;
     auto save = [&](int q) {
       const int step = q / R, rg = q % R;
       const int t = d ? T - 1 - step : step;
-      const int n0 = (rg0 + rg) * 16;
+      const int n0 = (rg0 + rg) * RPC;
       const char* sv = svs + (size_t)(q & 1) * SV_BYTES;
 #pragma unroll
-      for (int j = 0; j < 9; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         const int idx = lane + 64 * j;
+        if ((2 * NH + NG + NB) % 64 != 0 && idx >= 2 * NH + NG + NB) break;
         const f32x4 v = *(const f32x4*)(sv + idx * 16);
-        if (idx < 128) {
+        if (idx < NH) {
           const int row = idx >> 3, cc = idx & 7;
           if (n0 + row < a.N)
             *(f32x4*)(a.hf[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)a.ld_h + (unsigned)(u0 + cc * 4))) = v;
-        } else if (idx < 256) {
-          const int jj = idx - 128, row = jj >> 3, cc = jj & 7;
+        } else if (idx < 2 * NH) {
+          const int jj = idx - NH, row = jj >> 3, cc = jj & 7;
           if (n0 + row < a.N)
             *(f32x4*)(a.c[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)H + (unsigned)(u0 + cc * 4))) = v;
-        } else if (idx < 512) {
-          const int jj = idx - 256, row = jj >> 4, gate = (jj >> 2) & 3, cc = jj & 3;
+        } else if (idx < 2 * NH + NG) {
+          const int jj = idx - 2 * NH, row = jj >> 4, gate = (jj >> 2) & 3, cc = jj & 3;
           if (n0 + row < a.N)
             *(f32x4*)(a.gates[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)(4 * H) + (unsigned)(gate * H + u0 + cc * 8))) = v;
         } else {
-          const int jj = idx - 512, row = jj >> 2, cc = jj & 3;
+          const int jj = idx - 2 * NH - NG, row = jj >> 2, cc = jj & 3;
           if (a.hb[d] && n0 + row < a.N)
             *(f32x4*)(a.hb[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)a.ld_hb + (unsigned)(u0 + cc * 8))) = v;
         }
@@ -879,17 +905,17 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     wg_barrier();
     save(Q - 1);
   } else {
-    // ================================================================ prefetcher role: 16 rows x 4 gates x 32 units = 512
-    // float4 per slot, 8 per lane: row 2j + (lane >> 5), gate (lane >> 3) & 3, 4 floats at (lane & 7) * 4
-    f32x4 pf[8];
+    // ================================================================ prefetcher role: RPC rows x 4 gates x 32 units = 32 RPC
+    // float4 per slot, RPC / 2 per lane: row 2j + (lane >> 5), gate (lane >> 3) & 3, 4 floats at (lane & 7) * 4
+    f32x4 pf[RPC / 2];
     const float* xg = a.xg[d];
     const int prow = lane >> 5, pgate = (lane >> 3) & 3, pf4 = (lane & 7) * 4;
     auto pf_load = [&](int q) {
       const int step = q / R, rg = q % R;
       const int t = d ? T - 1 - step : step;
-      const int n0 = (rg0 + rg) * 16;
+      const int n0 = (rg0 + rg) * RPC;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
+      for (int j = 0; j < RPC / 2; ++j) {
         const int n = n0 + 2 * j + prow;
         pf[j] = n < a.N ? *(const f32x4*)(xg + ((unsigned)(n * a.P + a.padl + t) * (unsigned)a.ld_xg + (unsigned)(pgate * H + u0 + pf4)))
                         : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -897,7 +923,7 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     };
     auto pf_store = [&](int buf) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) *(f32x4*)(xgs + ((size_t)buf * 16 + 2 * j + prow) * XG3_LD + pgate * X3_UPW + pf4) = pf[j];
+      for (int j = 0; j < RPC / 2; ++j) *(f32x4*)(xgs + ((size_t)buf * 16 + 2 * j + prow) * XG3_LD + pgate * X3_UPW + pf4) = pf[j];
     };
     pf_load(0);
     pf_store(0);
@@ -1207,11 +1233,12 @@ constexpr int DGI_LD = 256 + 8;          // bf16 per row of the operand image (r
 // between barrier(q) and barrier(q+1), rewritten behind barrier(q+1)).
 // Slot timings (profiles/r03_cluster_bwd_trace.txt): poller-wave form 3.51 us, polling compute lanes 3.09, row-major
 // prefetcher hand-over 2.97, this form see the profile.
-template <int HB, int R>
+template <int HB, int R, int RPC>
 __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int H = HB * 64, K4 = 4 * H, CS = HB;
-  constexpr int GPD = 16 * 32;                                        // granules per (destination, source) block
+  static_assert(RPC == 16 || ((RPC == 8 || RPC == 4) && R == 1), "rows per chain");
+  constexpr int GPD = RPC * 32;                                       // granules per (destination, source) block
   bf16_t* dgi = (bf16_t*)smem;                                        // [2][16][DGI_LD] this slot's gate gradients (row, gate*64 + unit)
   // The operand stage keeps the row-major layout of the global arrays (a transposing prefetcher store was measured:
   // 96 scattered LDS writes per lane, slower than the compute lanes' scalar reads of this layout)
@@ -1222,20 +1249,23 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
   int* abortf = (int*)(c0 + R * 16 * 64);                             // [1]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nsets = ((a.N + 15) / 16 + R - 1) / R;
+  const int nsets = ((a.N + RPC - 1) / RPC + R - 1) / R;
   const int set = blockIdx.x / CS, wgc = blockIdx.x % CS;
   const int d = set / nsets, rg0 = (set % nsets) * R;
   const int r16 = lane & 15, g = lane >> 4;
-  // exchange: [chain][parity][destination][source][16 rows][32 unit pairs]
+  // exchange: [chain][parity][destination][source][RPC / 2 row pairs][64 units]
   u64* xb0 = a.xbuf + (size_t)(d * nsets * R + rg0) * 2 * CS * CS * GPD;
   const int u0 = wgc * 64;
   const int T = a.T, Q = a.T * R;
   if (tid == 0) abortf[0] = 0;           // (audit) by wave 0 in front of its first wg_barrier, read behind it
+  if (RPC < 16 && blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
   auto t_of = [&](int step) { return d ? T - 1 - step : step; };
 
   if (wave < XW) {
     // ================================================================ compute role
     const int wu = wave * 16 + r16;                    // unit inside the workgroup's 64
+    // lane groups g >= RPC / 4 are padding rows: they poll nothing, publish nothing, and put zeros into the operand image
+    const bool live = RPC == 16 || g < RPC / 4;
     // Wh[unit wu of workgroup j][own 256 gate columns], the columns in the operand image's order k = unit * 4 + gate
     bf16x8 bw[HB][8];
 #pragma unroll
@@ -1254,9 +1284,9 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
       ownp[rg] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int n = (rg0 + rg) * 16 + g * 4 + r;
+        const int n = (rg0 + rg) * RPC + g * 4 + r;
         dcc[rg][r] = 0.f; pc[rg][r] = 0.f;
-        len[rg][r] = (a.lengths && n < a.N) ? a.lengths[n] : T;
+        len[rg][r] = (a.lengths && live && n < a.N) ? a.lengths[n] : T;
       }
     }
     // the part of a slot's cell update that does not need the exchanged sums; computed one slot ahead, under the
@@ -1293,13 +1323,13 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
 #pragma unroll
       for (int rg = 0; rg < R; ++rg) {
         const int q = bs * R + rg, buf = q & 1;
-        const int n0 = (rg0 + rg) * 16;
+        const int n0 = (rg0 + rg) * RPC;
         const bool tr = (a.dbg & 16) && blockIdx.x == 0 && tid == 0 && q < 512;
         if (tr) a.trace[q * 8 + 0] = wall_clock64();
         // ---- dh of the step after, summed in a fixed order: own block, then the peers' in workgroup order.
         // Granule (source ws, row pair 2 g + h, unit wu) of this workgroup's block: {tag bs, rows 2h | 2h + 1 of the lane}
         f32x4 rec = ownp[rg];
-        if (bs > 0 && CS > 1) {
+        if (bs > 0 && CS > 1 && live) {
           const u64* cur = xb0 + ((size_t)rg * 2 + (bs & 1)) * CS * CS * GPD + (size_t)wgc * CS * GPD + (g * 2) * 64 + wu;
           u64 v[CS > 1 ? CS - 1 : 1][2];
           unsigned spins = 0, clk0 = 0;
@@ -1341,7 +1371,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
           const float dc = dh * kdc[r] + dcc[rg][r];
           float dgv[4] = {dc * ki[r], dc * kj[r], dc * kf[r], d_o};
           dcc[rg][r] = dc * gfv[r];
-          if (t >= len[rg][r] || n >= a.N) {
+          if (t >= len[rg][r] || n >= a.N || !live) {
             dgv[0] = dgv[1] = dgv[2] = dgv[3] = 0.f;
             dcc[rg][r] = 0.f;
           }
@@ -1374,7 +1404,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
           for (int j = 0; j < HB; ++j) {
             if (j == wgc) {
               ownp[rg] = acc[j];
-            } else {
+            } else if (live) {
               u64* dst = nxt + (size_t)(j * CS + wgc) * GPD + (g * 2) * 64 + wu;
 #pragma unroll
               for (int h = 0; h < 2; ++h)
@@ -1395,15 +1425,15 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
     auto save = [&](int q) {
       const int bs = q / R, rg = q % R;
       const int t = t_of(T - 1 - bs);
-      const int n0 = (rg0 + rg) * 16;
+      const int n0 = (rg0 + rg) * RPC;
       const bf16_t* di = dgi + (size_t)(q & 1) * 16 * DGI_LD;
 #pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
+      for (int jj = 0; jj < (RPC * 8 + 63) / 64; ++jj) {
         const int idx = lane + 64 * jj, c8 = idx & 7, row = idx >> 3;
         uint2 x[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = *(const uint2*)(di + row * DGI_LD + (c8 * 8 + e) * 4);
-        if (n0 + row < a.N) {
+        if ((RPC == 16 || row < RPC) && n0 + row < a.N) {
           bf16_t* out = a.dgates[d] + ((unsigned)((n0 + row) * a.P + a.padl + t) * (unsigned)K4 + (unsigned)(u0 + c8 * 8));
 #pragma unroll
           for (int gate = 0; gate < 4; ++gate) {
@@ -1427,21 +1457,21 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
     save(Q - 1);
   } else {
     // ================================================================ prefetcher role (loads only)
-    f32x4 pg[8], pd[4], pcp[4];
+    f32x4 pg[RPC / 2], pd[RPC / 4], pcp[RPC / 4];      // RPC rows of the chain, nothing of the padding rows
     auto pf_load = [&](int q) {
       const int bs = q / R, rg = q % R, step = T - 1 - bs;
       const int t = t_of(step), tp = d ? t + 1 : t - 1;
       const bool has_prev = step > 0;
-      const int n0 = (rg0 + rg) * 16;
+      const int n0 = (rg0 + rg) * RPC;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
+      for (int j = 0; j < RPC / 2; ++j) {
         const int idx = lane + 64 * j, c8 = idx & 7, gate = (idx >> 3) & 3, row = idx >> 5;
         const int n = n0 + row;
         pg[j] = n < a.N ? *(const f32x4*)(a.gates[d] + ((unsigned)(n * a.P + a.padl + t) * (unsigned)(4 * H) + (unsigned)(gate * H + u0 + c8 * 8)))
                         : (f32x4){0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < RPC / 4; ++j) {
         const int idx = lane + 64 * j, c16 = idx & 15, row = idx >> 4;
         const int n = n0 + row;
         pd[j] = n < a.N ? *(const f32x4*)(a.dh[d] + ((unsigned)(n * a.P + a.padl + t) * (unsigned)a.ld_dh + (unsigned)(u0 + c16 * 4)))
@@ -1453,9 +1483,9 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
     auto pf_store = [&](int buf) {
       char* st = ops + (size_t)buf * OPS_STAGE;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) *(f32x4*)(st + (size_t)(lane + 64 * j) * 16) = pg[j];
+      for (int j = 0; j < RPC / 2; ++j) *(f32x4*)(st + (size_t)(lane + 64 * j) * 16) = pg[j];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < RPC / 4; ++j) {
         *(f32x4*)(st + OPS_G + (size_t)(lane + 64 * j) * 16) = pd[j];
         *(f32x4*)(st + OPS_G + OPS_F + (size_t)(lane + 64 * j) * 16) = pcp[j];
       }
@@ -1465,9 +1495,9 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
 #pragma unroll
       for (int rg = 0; rg < R; ++rg)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < RPC / 4; ++j) {
           const int idx = lane + 64 * j, c16 = idx & 15, row = idx >> 4;
-          const int n = (rg0 + rg) * 16 + row;
+          const int n = (rg0 + rg) * RPC + row;
           const f32x4 v = n < a.N ? *(const f32x4*)(a.c[d] + ((unsigned)(n * a.P + a.padl + t0) * (unsigned)H + (unsigned)(u0 + c16 * 4)))
                                   : (f32x4){0.f, 0.f, 0.f, 0.f};
           *(f32x4*)(c0 + (rg * 16 * 64) + idx * 4) = v;
@@ -1555,6 +1585,9 @@ static void fill(LstmClusterArgs& a, const ns_lstm_seq_params* p0, const ns_lstm
 static bool role_split_ok(const LstmClusterArgs& a, bool bwd) {
   if (a.dbg & 8) return false;
   if (a.H > 256 || a.H % 64) return false;
+  // the flag array belongs to the dense-row backward kernel, which always runs 16-row chains; the narrow forms exchange
+  // through granules only, and their chains (ceil(N / rows) per direction) need no more exchange bytes than the 16-row
+  // layout: ceil(N / rows) * rows <= ceil(N / 16) * 16
   if (2 * ((a.N + 15) / 16 + 1) * 8 * sizeof(unsigned) > FLAG_BYTES) return false;
   const long widest = a.ld_xg > 4L * a.H ? a.ld_xg : 4L * a.H;
   if ((long)a.N * a.P * (widest > a.ld_dh ? widest : a.ld_dh) >= (1L << 31)) return false;   // 32-bit element offsets
@@ -1564,6 +1597,30 @@ static bool role_split_ok(const LstmClusterArgs& a, bool bwd) {
     if (bwd && !(al16(a.dh[d]) && a.ld_dh % 4 == 0 && al16(a.c[d]) && al16(a.gates[d]) && al16(a.dgates[d]))) return false;
   }
   return true;
+}
+
+// Rows per chain of the role-split kernels (lstm_cluster2_fwd, lstm_cluster3_fwd, lstm_cluster2p_bwd): 16, 8 or 4.  A
+// narrower chain moves fewer bytes per hop and takes more workgroups (2 * ceil(N / rows) * wgs_per_chain).  The rule:
+// the narrowest form whose grid stays within half of the device's CUs (every workgroup of a launch has to be resident,
+// and other streams run beside these launches; at batch 32, H 256 that is 4 rows in all three kernels - 64 workgroups,
+// 128 for the fp32 form, measured faster than 8 rows on 64: profiles/cluster_rows.txt).  NS_CLUSTER_ROWS=16|8|4, read
+// per call, forces a form for A/B runs and tests; a forced form is widened until its grid fits the device.  The
+// interleaved (R = 2) forms run at 16.
+// A narrow form writes its row count into the second int of `work` (zeroed with the status word: 0 = 16 rows).
+static int cluster_rows(int N, int wgs_per_chain, bool interleaved) {
+  if (interleaved) return 16;
+  const int cus = ns_device_cus();
+  auto grid = [&](int rows) { return 2 * ((N + rows - 1) / rows) * wgs_per_chain; };
+  const char* e = getenv("NS_CLUSTER_ROWS");
+  const int want = e ? atoi(e) : 0;
+  if (want == 16 || want == 8 || want == 4) {
+    int rows = want;
+    while (rows < 16 && grid(rows) > cus) rows *= 2;
+    return rows;
+  }
+  for (int rows = 4; rows < 16; rows *= 2)
+    if (grid(rows) <= cus / 2) return rows;
+  return 16;
 }
 
 // Both directions of a BiLSTM, whole sequence, one launch.  p0 must be the forward-in-time direction
@@ -1583,20 +1640,25 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
     fill(a, p0, p1, work);
     // NS_CLUSTER_DBG bit 256: one row group per workgroup set (no interleaving), for A/B timing
     const int nrg = (a.N + 15) / 16, R = (nrg >= 2 && (a.dbg & 1024)) ? 2 : 1;        // see the bf16 forward kernel's launch: one set per row group
-    const size_t xbytes = (2 * (size_t)nrg + 2) * 2 * 16 * (size_t)a.H * sizeof(u64);
+    const int RPC = cluster_rows(a.N, a.H / X3_UPW, R == 2), nch = (a.N + RPC - 1) / RPC;   // chains per direction
+    const size_t xbytes = (2 * (size_t)nch + 2) * 2 * RPC * (size_t)a.H * sizeof(u64);
     { const int zrc = ns_zero_async(work, ((256 + FLAG_BYTES + xbytes) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
     const size_t lds3 = (size_t)2 * 2 * 16 * a.H * 2 + sizeof(float) * 2 * 16 * XG3_LD + 2 * 9216 + 32;
-    const dim3 grid((unsigned)(2 * ((nrg + R - 1) / R) * (a.H / X3_UPW))), block(X3_WAVES * 64);
+    const dim3 grid((unsigned)(2 * ((nch + R - 1) / R) * (a.H / X3_UPW))), block(X3_WAVES * 64);
 #define NS_LAUNCH_F3(HB_) \
     do { \
       static bool attr3 = false; \
       if (!attr3) { \
-        (void)hipFuncSetAttribute((const void*)lstm_cluster3_fwd_kernel<HB_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)hipFuncSetAttribute((const void*)lstm_cluster3_fwd_kernel<HB_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        (void)hipFuncSetAttribute((const void*)lstm_cluster3_fwd_kernel<HB_, 2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        (void)hipFuncSetAttribute((const void*)lstm_cluster3_fwd_kernel<HB_, 1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        (void)hipFuncSetAttribute((const void*)lstm_cluster3_fwd_kernel<HB_, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        (void)hipFuncSetAttribute((const void*)lstm_cluster3_fwd_kernel<HB_, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
         attr3 = true; \
       } \
-      if (R == 2) hipLaunchKernelGGL((lstm_cluster3_fwd_kernel<HB_, 2>), grid, block, lds3, s, a); \
-      else hipLaunchKernelGGL((lstm_cluster3_fwd_kernel<HB_, 1>), grid, block, lds3, s, a); \
+      if (R == 2) hipLaunchKernelGGL((lstm_cluster3_fwd_kernel<HB_, 2, 16>), grid, block, lds3, s, a); \
+      else if (RPC == 8) hipLaunchKernelGGL((lstm_cluster3_fwd_kernel<HB_, 1, 8>), grid, block, lds3, s, a); \
+      else if (RPC == 4) hipLaunchKernelGGL((lstm_cluster3_fwd_kernel<HB_, 1, 4>), grid, block, lds3, s, a); \
+      else hipLaunchKernelGGL((lstm_cluster3_fwd_kernel<HB_, 1, 16>), grid, block, lds3, s, a); \
     } while (0)
     switch (a.H / 64) {
       case 1: NS_LAUNCH_F3(1); break;
@@ -1612,9 +1674,13 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
   LstmClusterArgs a = {};
   fill(a, p0, p1, work);
   const size_t chains = 2 * (size_t)((a.N + 15) / 16);
-  const size_t xbytes = (chains + 2) * 2 * 16 * (size_t)(a.H / 2) * sizeof(u64);
+  // two row groups interleaved per workgroup: NS_CLUSTER_DBG bit 512 (see below); the narrow forms run one chain per set
+  const bool split = role_split_ok(a, false);
+  const int R = ((a.N + 15) / 16 >= 2 && (a.dbg & 512)) ? 2 : 1;
+  const int RPC = split ? cluster_rows(a.N, a.CS, R == 2) : 16, nrg = (a.N + RPC - 1) / RPC;
+  const size_t xbytes = (2 * (size_t)nrg + 2) * 2 * RPC * (size_t)(a.H / 2) * sizeof(u64);
   { const int zrc = ns_zero_async(work, ((256 + FLAG_BYTES + xbytes) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
-  if (role_split_ok(a, false)) {
+  if (split) {
     const size_t lds2 = (size_t)2 * 16 * a.H * 2 + sizeof(float) * 2 * 16 * XG_LD + 2 * (2048 + 4096 + 8192) + 32;
     // two row groups interleaved per workgroup (R = 2) pay when a slot's compute chain is clearly shorter than the hop;
     // round 3 (two forward pollers, shorter hop): expand BiLSTM 2.92 ms with R = 2, 2.75 ms with one set per row group
@@ -1623,11 +1689,12 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
     // backward kernel 2.63 against 4.36, the fp32 forward 1.08 against 1.17 (encoder).  Interleaving only doubles the
     // slots a workgroup walks through: every row group gets its own set of workgroups (2 x 4 x row groups <= 256 CUs up
     // to batch 512); NS_CLUSTER_DBG bits 512 / 1024 / 2048 force R = 2 (bf16 forward / fp32 forward / backward).
-    const int nrg = (a.N + 15) / 16, R = (nrg >= 2 && (a.dbg & 512)) ? 2 : 1;
     const dim3 grid((unsigned)(2 * ((nrg + R - 1) / R) * a.CS)), block(FW_WAVES * 64);
 #define NS_LAUNCH_F(HB_) \
-    if (R == 2) hipLaunchKernelGGL((lstm_cluster2_fwd_kernel<HB_, 2>), grid, block, lds2, s, a); \
-    else hipLaunchKernelGGL((lstm_cluster2_fwd_kernel<HB_, 1>), grid, block, lds2, s, a)
+    if (R == 2) hipLaunchKernelGGL((lstm_cluster2_fwd_kernel<HB_, 2, 16>), grid, block, lds2, s, a); \
+    else if (RPC == 8) hipLaunchKernelGGL((lstm_cluster2_fwd_kernel<HB_, 1, 8>), grid, block, lds2, s, a); \
+    else if (RPC == 4) hipLaunchKernelGGL((lstm_cluster2_fwd_kernel<HB_, 1, 4>), grid, block, lds2, s, a); \
+    else hipLaunchKernelGGL((lstm_cluster2_fwd_kernel<HB_, 1, 16>), grid, block, lds2, s, a)
     switch (a.H / 64) {
       case 1: NS_LAUNCH_F(1); break;
       case 2: NS_LAUNCH_F(2); break;
@@ -1656,8 +1723,11 @@ extern "C" int ns_lstm_cluster_bwd(const ns_lstm_seq_params* p0, const ns_lstm_s
   const size_t chains = 2 * (size_t)((a.N + 15) / 16);
   // dense-row role-split kernel: exchanges through the dgates array + flags; partial-sum kernel: [chain][2][CS][CS][512]
   // granules; single-role kernel: [chain][2][16][2H]
+  const bool psum = role_split_ok(a, true) && !(a.dbg & 64);
+  const int RP = ((a.N + 15) / 16 >= 2 && (a.dbg & 2048)) ? 2 : 1;                  // the partial-sum kernel's interleaving
+  const int RPC = psum ? cluster_rows(a.N, a.CS, RP == 2) : 16, nch = (a.N + RPC - 1) / RPC;
   const size_t xbytes = role_split_ok(a, true)
-                            ? ((a.dbg & 64) ? 0 : (chains + 2) * 2 * (size_t)a.CS * a.CS * 512 * sizeof(u64))
+                            ? ((a.dbg & 64) ? 0 : (2 * (size_t)nch + 2) * 2 * (size_t)a.CS * a.CS * RPC * 32 * sizeof(u64))
                             : (chains + 2) * 2 * 16 * (size_t)(4 * a.H / 2) * sizeof(u64);
   { const int zrc = ns_zero_async(work, ((256 + FLAG_BYTES + xbytes) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   static bool attr = false;
@@ -1670,19 +1740,21 @@ extern "C" int ns_lstm_cluster_bwd(const ns_lstm_seq_params* p0, const ns_lstm_s
     (void)hipFuncSetAttribute((const void*)lstm_cluster2_bwd_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  if (role_split_ok(a, true) && !(a.dbg & 64)) {
+  if (psum) {
     // partial-sum exchange (lstm_cluster2p_bwd_kernel); NS_CLUSTER_DBG bit 64: the dense-row exchange below; bit 32: no
     // interleaving of row groups
     // R = 2 (two row groups interleaved per workgroup) pays when the slot's compute chain is shorter than the hop;
     // measured on the expand BiLSTM (T = 1000, H = 256, 2 row groups): R = 1 3.8 ms, R = 2 4.4 ms
-    const int nrg = (a.N + 15) / 16, R = (nrg >= 2 && (a.dbg & 2048)) ? 2 : 1;
+    const int nrg = nch, R = RP;
     const int CS = a.CS;
     const size_t ldsp = (size_t)2 * 16 * DGI_LD * 2 + 2 * 16384 + sizeof(float) * (size_t)R * 16 * 64 + 32;
     const dim3 grid((unsigned)(2 * ((nrg + R - 1) / R) * CS)), block(BP_WAVES * 64);
 #define NS_LAUNCH_BP(HB_) \
     do { \
-      if (R == 2) hipLaunchKernelGGL((lstm_cluster2p_bwd_kernel<HB_, 2>), grid, block, ldsp, s, a); \
-      else hipLaunchKernelGGL((lstm_cluster2p_bwd_kernel<HB_, 1>), grid, block, ldsp, s, a); \
+      if (R == 2) hipLaunchKernelGGL((lstm_cluster2p_bwd_kernel<HB_, 2, 16>), grid, block, ldsp, s, a); \
+      else if (RPC == 8) hipLaunchKernelGGL((lstm_cluster2p_bwd_kernel<HB_, 1, 8>), grid, block, ldsp, s, a); \
+      else if (RPC == 4) hipLaunchKernelGGL((lstm_cluster2p_bwd_kernel<HB_, 1, 4>), grid, block, ldsp, s, a); \
+      else hipLaunchKernelGGL((lstm_cluster2p_bwd_kernel<HB_, 1, 16>), grid, block, ldsp, s, a); \
     } while (0)
     switch (a.H / 64) {
       case 1: NS_LAUNCH_BP(1); break;
