@@ -57,7 +57,7 @@ def main():
         "lstm_wide_bwd": family("wideb", lambda k: "lstm_wide_bwd" in k, "lstm_wide_bwd_kernel / lstm_wide_bwd_ps_kernel"),
         "attn_cluster": family("attn", lambda k: "attn_cluster_fwd_kernel" in k or "attn_cluster_bwd_kernel" in k,
                                "attn_cluster_fwd_kernel + attn_cluster_bwd_kernel"),
-        "lstm_cluster": family("clu", lambda k: "lstm_cluster" in k, "lstm_cluster2_fwd_kernel + lstm_cluster2_bwd_kernel"),
+        "lstm_cluster": family("clu", lambda k: "lstm_cluster" in k, "lstm_cluster2_fwd_kernel + lstm_cluster2p_bwd_kernel"),
     }
     json.dump(summary, open(out + ".json", "w"), indent=1)
     print(json.dumps(summary))

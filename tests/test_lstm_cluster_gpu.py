@@ -65,7 +65,8 @@ def _run(dev, data, cluster):
 
 
 @pytest.mark.parametrize("N,T,H,masked", [(16, 9, 64, False), (20, 33, 256, True), (32, 61, 256, False), (5, 12, 128, True),
-                                              (40, 21, 256, True), (48, 17, 192, False)])
+                                              (40, 21, 256, True), (48, 17, 192, False), (32, 17, 192, False),
+                                              (16, 9, 512, False), (20, 13, 384, True)])
 def test_cluster_matches_per_step_kernels(dev, N, T, H, masked):
     data = _setup(dev, N, T, H, seed=N + T, masked=masked)
     ref = _run(dev, data, cluster=False)
@@ -76,21 +77,6 @@ def test_cluster_matches_per_step_kernels(dev, N, T, H, masked):
         err = (a - b).abs().max().item()
         # same bf16 operands, different fp32 summation order; bf16 rounding of stored states
         assert err <= 3e-2 * scale, (k, err, scale)
-        assert (a - b).abs().mean().item() <= 2e-3 * scale, k
-
-
-@pytest.mark.parametrize("N,T,H,masked", [(40, 21, 256, True), (32, 17, 192, False)])
-def test_interleaved_row_groups_form_still_matches(dev, monkeypatch, N, T, H, masked):
-    """Two row groups interleaved per workgroup (R = 2) is no longer any shape's default (re-measured slower at the end
-    of round 3); NS_CLUSTER_DBG bits 512 / 1024 / 2048 force it, and it has to stay correct."""
-    monkeypatch.setenv("NS_CLUSTER_DBG", str(512 + 1024 + 2048))
-    data = _setup(dev, N, T, H, seed=N + T, masked=masked)
-    ref = _run(dev, data, cluster=False)
-    got = _run(dev, data, cluster=True)
-    for k in ("h", "c_fw", "c_bw", "g_fw", "g_bw", "dg_fw", "dg_bw"):
-        a, b = got[k].float(), ref[k].float()
-        scale = b.abs().max().item() + 1e-6
-        assert (a - b).abs().max().item() <= 3e-2 * scale, k
         assert (a - b).abs().mean().item() <= 2e-3 * scale, k
 
 

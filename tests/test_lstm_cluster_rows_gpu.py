@@ -155,7 +155,7 @@ def test_narrow_chains_bit_equal_fp32_state(dev, monkeypatch, N, T, H, masked):
 
 def test_default_form_is_narrow_at_the_benchmark_width(dev, monkeypatch):
     """No override: batch 32 at H 256 runs a narrow form in all three kernels (the narrowest whose grid stays within
-    half of the device), and the interleaved forms stay at 16 rows."""
+    half of the device)."""
     monkeypatch.delenv("NS_CLUSTER_ROWS", raising=False)
     monkeypatch.delenv("NS_CLUSTER_DBG", raising=False)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -170,8 +170,3 @@ def test_default_form_is_narrow_at_the_benchmark_width(dev, monkeypatch):
     assert forms == [rule(32, 4), rule(32, 4)] and all(f < 16 for f in forms), forms
     _, forms = _run_fp32(dev, _fp32_data(dev, 32, 25, 256, True))
     assert forms == [rule(32, 8)] and forms[0] < 16, forms      # the fp32 form: H / 32 workgroups per chain
-    monkeypatch.setenv("NS_CLUSTER_DBG", str(512 + 1024 + 2048))
-    _, forms = _run_bf16(dev, _bf16_data(dev, 32, 25, 256, True))
-    assert forms == [16, 16], forms
-    _, forms = _run_fp32(dev, _fp32_data(dev, 32, 25, 256, True))
-    assert forms == [16], forms
