@@ -29,7 +29,7 @@ typedef void* ns_stream_t; /* hipStream_t */
 
 enum { NS_OK = 0, NS_ERR_BAD_ARG = -1, NS_ERR_UNSUPPORTED_SHAPE = -2, NS_ERR_LAUNCH = -3,
        NS_ERR_SHORT_BUFFER = -4 /* a caller-owned output buffer is too small; retry with a larger one */ };
-enum { NS_F32 = 0, NS_BF16 = 1 };
+enum { NS_F32 = 0, NS_BF16 = 1, NS_F64 = 2 /* ns_resample's input only */ };
 enum { NS_ACT_NONE = 0, NS_ACT_RELU = 1, NS_ACT_TANH = 2, NS_ACT_SIGMOID = 3,
        NS_ACT_SOFTSIGN = 4 /* x / (1 + |x|): the speaker projections, rnn_wrappers.py:29, modules.py:159,167 */ };
 
@@ -937,6 +937,40 @@ int ns_audio_pointwise(const ns_audio_pointwise_params* p, ns_stream_t stream);
  * (inverse=1: y[n] = x[n] + c y[n-1]), scipy.signal.lfilter with zero initial state. */
 typedef struct { const float* x; float* y; int64_t n; float coef; int inverse; } ns_preemphasis_params;
 int ns_preemphasis(const ns_preemphasis_params* p, ns_stream_t stream);
+
+/* ---------------------------------------------------------------- utterance front end (frontend.hip)
+ * ns_resample: resampy's 'kaiser_best' band-limited interpolation as audio.resample restates it (utils/audio.py),
+ * one launch per waveform, float64 arithmetic in the order of audio._resample_reference: per output sample the left
+ * wing's taps i = 0, 1, ... and then the right wing's are added into one accumulator, each tap as
+ * w = win[k] + eta * delta[k]; acc = acc + w * x[..] with four roundings (never a fused multiply-add), and the float32
+ * result is the round-to-nearest conversion of the accumulator - so the output equals that function's bit for bit.
+ * x [n_in] float32 or float64, y [n_out] float32, n_out = ns_resample_out_len(n_in, sr_in, sr_out).
+ * win / delta: the caller's float64 tables of nwin entries each (win = the interpolation filter at num_table points per
+ * zero crossing, already scaled by sr_out / sr_in when down-sampling; delta[k] = win[k + 1] - win[k], delta[nwin - 1] = 0).
+ * n_out == 0 succeeds without a launch. */
+typedef struct {
+  const void* x; int x_dtype;        /* NS_F32 | NS_F64 */
+  int64_t n_in;
+  float* y; int64_t n_out;
+  int sr_in, sr_out;
+  const double* win; const double* delta; int64_t nwin;
+  int num_table;                     /* 512 for 'kaiser_best' */
+} ns_resample_params;
+int ns_resample(const ns_resample_params* p, ns_stream_t stream);
+/* Host only: what Python's int(n_in * (float(sr_out) / float(sr_in))) returns; negative for a bad argument. */
+int64_t ns_resample_out_len(int64_t n_in, int sr_in, int sr_out);
+
+/* Mean square of the centred frames of a signal: out[f] = sum_t y[f * hop + t]^2 / frame_length, t < frame_length, in
+ * float64, y = x reflect-padded by frame_length / 2 on both sides (never materialised) - the per-sample work of
+ * librosa.effects.split and librosa.feature.rmse (datasets/process.py: trim_wav 1024 / 512, trim_silence 2048 / 512).
+ * x [n] float32, out [n_frames] float64, n_frames = 1 + n / hop; frame_length even, n > frame_length / 2 (reflection
+ * needs it). */
+typedef struct {
+  const float* x; int64_t n;
+  int frame_length, hop;
+  double* out; int64_t n_frames;
+} ns_frame_power_params;
+int ns_frame_power(const ns_frame_power_params* p, ns_stream_t stream);
 
 /* ---------------------------------------------------------------- FLAC input (host code, flac.hip)
  * The reference reads LibriSpeech's .flac files through librosa.core.load (datasets/corpus/ljspeech.py:17,

@@ -13,7 +13,8 @@ Same batching semantics as the reference:
   * a background thread keeps up to 8 prepared batches queued (the reference's FIFOQueue(8), :72).
 
 MI355X-side differences: both spectrograms of an utterance come from ONE pass of the fused GPU
-feature kernel (`audio.spectrogram_and_mel`) instead of two librosa STFTs in worker threads, and for
+feature kernel (`audio.spectrogram_and_mel`) instead of two librosa STFTs in worker threads (with
+`device_cache` the resampler and the silence trim in front of it run on the device too), and for
 data-parallel runs the sorted group is dealt round-robin over the ranks so that every
 rank sees the same length mix: rank r takes examples r, r + world, ... of the sorted group."""
 import glob
@@ -27,7 +28,7 @@ import numpy as np
 
 from ..utils import audio
 from ..utils.text import text_to_sequence
-from .process import trim_wav
+from .process import trim_bounds_device, trim_wav
 
 _p_cmudict = 0.5      # datafeeder.py:16
 _pad = 0              # datafeeder.py:17
@@ -147,6 +148,10 @@ class DataFeeder(object):
         # keeps them in host RAM, `processed_data`, datafeeder.py:165-176) and batches are assembled on the device.
         # All of LJSpeech is 24 h x 80 frames/s x 1105 floats = 30.5 GB of float32 - a tenth of one MI355X's 288 GB.
         self._device_cache = bool(device_cache) and features is None
+        # front_end "device": the native-rate samples go up once and resample -> trim -> features run on the feeder's
+        # stream (audio.load_wav_device, process.trim_bounds_device); "host": load_wav / trim_wav on the host, as ever -
+        # what a custom loader or feature function, or a feeder without the device cache, gets
+        self.front_end = "device" if self._device_cache and loader is None else "host"
         self._stream = None
         self._alloc = _pinned_zeros if pinned else None      # targets prepared in page-locked memory (DeviceStager)
         # the GPU the feature kernels of the prefetch thread must run on: torch's current device is per host thread,
@@ -203,7 +208,8 @@ class DataFeeder(object):
             if self._device_cache:
                 import torch
                 with torch.cuda.stream(self._feeder_stream()):
-                    lin, mel = audio.spectrogram_and_mel_device(self._wav(wav_path))      # [T, F], [T, M] in HBM
+                    wav = self._wav_device(wav_path) if self.front_end == "device" else self._wav(wav_path)
+                    lin, mel = audio.spectrogram_and_mel_device(wav)      # [T, F], [T, M] in HBM
                 self.cache[wav_path] = (mel, lin)
             else:
                 lin, mel = self._features(self._wav(wav_path))
@@ -218,6 +224,14 @@ class DataFeeder(object):
         """process.py:27: the silent ends are cut before the features are taken."""
         wav = self._loader(wav_path)
         return trim_wav(wav) if self._trim else wav
+
+    def _wav_device(self, wav_path):
+        """_wav without the host trips: the trim bounds are the only thing read back (an event on the feeder's stream)."""
+        wav = audio.load_wav_device(wav_path)
+        if self._trim:
+            start, end = trim_bounds_device(wav)
+            wav = wav[start:end]
+        return wav
 
     def _feeder_stream(self):
         if self._stream is None:

@@ -2,8 +2,9 @@
 read from the global get_hparams() at call time - but the DSP runs in hand-written HIP kernels
 (csrc/audio.hip) through the C ABI.  Spectrograms are [F, T] exactly like the reference.
 
-Host-side here: wav file I/O, the immutable tables (Hann window, FFT twiddles, Slaney mel basis,
-built once per configuration in float64 NumPy and uploaded), and find_endpoint's threshold scan.
+Host-side here: wav file I/O, the immutable tables (Hann window, FFT twiddles, Slaney mel basis, the
+resampler's Kaiser-windowed sinc; built once per configuration in float64 NumPy and uploaded), and
+find_endpoint's threshold scan.  The resampler itself is ns_resample (csrc/frontend.hip).
 """
 import wave
 
@@ -98,12 +99,16 @@ def _kaiser_best():
     return _RESAMPLE_FILTER
 
 
-def resample(x, sr_orig, sr_new):
+def _resample_reference(x, sr_orig, sr_new, device=None):
     """librosa.core.load's default resampler (librosa 0.6.0 -> resampy.resample(..., filter='kaiser_best'), audio.py:14)
     restated [3P, parity unpinned]: band-limited sinc interpolation, the table read with linear interpolation between
-    entries, gain and cut-off scaled by the ratio when down-sampling.  Vectorised over the output samples."""
+    entries, gain and cut-off scaled by the ratio when down-sampling.  Vectorised over the output samples.
+
+    The definition of `resample`: ns_resample (csrc/frontend.hip) performs the same float64 operations in the same
+    order in one launch and returns the same bits; this form is what runs without a GPU and what the tests compare the
+    kernel with (`device` pins where its tensors live)."""
     # float64 tensor arithmetic: on the GPU when there is one (a 10 s clip takes milliseconds), else on the host
-    dev = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+    dev = torch.device(device) if device is not None else torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
     x = torch.as_tensor(np.asarray(x, np.float64), device=dev)
     ratio = float(sr_new) / float(sr_orig)
     n_out = int(x.shape[0] * ratio)
@@ -134,6 +139,64 @@ def resample(x, sr_orig, sr_new):
     wing(frac, n + 1, -1, n)                          # left wing: x[n], x[n-1], ...
     wing(scale - frac, n_orig - n - 1, +1, n + 1)     # right wing: x[n+1], x[n+2], ...
     return y.float().cpu().numpy()
+
+
+_resample_tables = {}
+
+
+def _get_resample_tables(sr_orig, sr_new, dev):
+    """The two float64 tables ns_resample reads, built exactly as _resample_reference builds them (the filter scaled by
+    the ratio when down-sampling, one rounding per entry; delta = the forward differences) and kept on the device."""
+    key = (int(sr_orig), int(sr_new), dev.index)
+    if key not in _resample_tables:
+        ratio = float(sr_new) / float(sr_orig)
+        win_np, num_table = _kaiser_best()
+        win = win_np * (ratio if ratio < 1 else 1.0)
+        delta = np.zeros_like(win)
+        delta[:-1] = win[1:] - win[:-1]
+        _resample_tables[key] = (torch.as_tensor(win, dtype=torch.float64).to(dev), torch.as_tensor(delta, dtype=torch.float64).to(dev),
+                                 num_table)
+    return _resample_tables[key]
+
+
+def resample_out_len(n_in, sr_orig, sr_new):
+    """Samples `resample` returns for n_in input samples: int(n_in * (float(sr_new) / float(sr_orig)))."""
+    import ctypes as C
+    fn = L.lib().ns_resample_out_len
+    fn.restype, fn.argtypes = C.c_int64, [C.c_int64, C.c_int, C.c_int]
+    n = fn(int(n_in), int(sr_orig), int(sr_new))
+    if n < 0:
+        raise ValueError("resample: bad length or rates (%d samples, %d -> %d Hz)" % (n_in, sr_orig, sr_new))
+    return n
+
+
+def resample_device(x, sr_orig, sr_new):
+    """`resample` for a waveform that is already on the device: x float32 or float64 CUDA tensor [n] -> float32 CUDA
+    tensor, one ns_resample launch on the current stream, nothing read back."""
+    assert torch.is_tensor(x) and x.is_cuda and x.dim() == 1, "resample_device takes a 1-D CUDA tensor"
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.double()
+    x = x.contiguous()
+    win, delta, num_table = _get_resample_tables(sr_orig, sr_new, x.device)
+    y = torch.empty(resample_out_len(x.numel(), sr_orig, sr_new), dtype=torch.float32, device=x.device)
+    p = L.struct("ns_resample_params")
+    p.x, p.x_dtype, p.n_in = ops.ptr(x), L.NS_F32 if x.dtype == torch.float32 else L.NS_F64, x.numel()
+    p.y, p.n_out, p.sr_in, p.sr_out = ops.ptr(y), y.numel(), int(sr_orig), int(sr_new)
+    p.win, p.delta, p.nwin, p.num_table = ops.ptr(win), ops.ptr(delta), win.numel(), num_table
+    with torch.cuda.device(x.device):
+        L.call("ns_resample", p, ops.stream())
+    return y
+
+
+def resample(x, sr_orig, sr_new):
+    """NumPy in, float32 NumPy out: _resample_reference's result, bit for bit - from ns_resample when there is a GPU
+    (float32 input goes up as it is, anything else as float64: the conversion is exact either way), from the reference
+    itself on the host otherwise."""
+    if not torch.cuda.is_available():
+        return _resample_reference(x, sr_orig, sr_new)
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x if x.dtype == np.float32 else x.astype(np.float64)).reshape(-1)
+    return resample_device(torch.from_numpy(x).to(_dev()), sr_orig, sr_new).cpu().numpy()
 
 
 def _strip_id3(data):
@@ -190,16 +253,14 @@ def _load_flac(path):
     return (out.astype(np.float32) / float(1 << (bps.value - 1))), sr.value
 
 
-def load_wav(path, offset=0.0, duration=None):
-    """PCM16 / float32 RIFF or FLAC reader + mono mix-down + resampling to hparams.sample_rate, as librosa.core.load
-    does for the reference (audio.py:13-14; LJSpeech is 22 050 Hz WAV, LibriSpeech 16 000 Hz FLAC, audio.yaml asks for
-    20 000 Hz)."""
+def _load_native(path, offset=0.0, duration=None):
+    """The host part of load_wav: file -> (mono float32 samples at the file's own rate, cut to offset / duration; that
+    rate)."""
     with open(path, "rb") as f:
         magic = f.read(4)
         if magic[:3] == b"ID3":              # an ID3v2 tag in front of the stream: look behind it
             f.seek(0)
             magic = _strip_id3(f.read())[:4]
-    hp = get_hparams()
     if magic == b"fLaC":                     # LibriSpeech (datasets/corpus/ljspeech.py:17)
         x, sr = _load_flac(path)
         ch = x.shape[1]
@@ -221,10 +282,27 @@ def load_wav(path, offset=0.0, duration=None):
         x = x.reshape(-1, ch).mean(axis=1)
     s = int(offset * sr)                     # librosa seeks / truncates at the native rate, then resamples
     e = None if duration is None else s + int(duration * sr)
-    x = x[s:e]
+    return x[s:e], sr
+
+
+def load_wav(path, offset=0.0, duration=None):
+    """PCM16 / float32 RIFF or FLAC reader + mono mix-down + resampling to hparams.sample_rate, as librosa.core.load
+    does for the reference (audio.py:13-14; LJSpeech is 22 050 Hz WAV, LibriSpeech 16 000 Hz FLAC, audio.yaml asks for
+    20 000 Hz)."""
+    x, sr = _load_native(path, offset, duration)
+    hp = get_hparams()
     if sr != hp.sample_rate:
         x = resample(x, sr, hp.sample_rate)
     return x
+
+
+def load_wav_device(path, offset=0.0, duration=None):
+    """load_wav that ends on the device: decode and mix down on the host, ONE upload of the native-rate samples,
+    resampling by ns_resample on the current stream.  Returns a float32 CUDA tensor with load_wav's values."""
+    x, sr = _load_native(path, offset, duration)
+    hp = get_hparams()
+    xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(_dev())
+    return resample_device(xt, sr, hp.sample_rate) if sr != hp.sample_rate else xt
 
 
 def save_wav(wav, path):
@@ -270,7 +348,10 @@ def _spectrograms(y, want_lin, want_mel, want_stft=False, on_device=False):
     n_fft, hop, win = _stft_parameters()
     tb = _get_tables()
     dev = _dev()
-    wav = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32)).to(dev)
+    if torch.is_tensor(y):      # already on the device (the feeder's device front end): no host trip
+        wav = y.to(dev, torch.float32).contiguous().reshape(-1)
+    else:
+        wav = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32)).to(dev)
     Lw = wav.numel()
     T = 1 + Lw // hop
     lin = torch.empty(T * hp.num_freq, dtype=torch.float32, device=dev) if want_lin else None
