@@ -337,7 +337,7 @@ typedef struct {
    * ns_zone_keep; counter-based, so the backward pass regenerates the masks instead of storing them).  The saved gates
    * are those of the plain cell; `c` holds the zoned state.  The backward calls apply the matching gradient (the carry
    * of dh through kept units needs a second [N*H] row of `work`: ns_lstm_seq_work_bytes()).  Supported by
-   * ns_lstm_seq_fwd / _bwd, ns_lstm_wide_fwd and the partial-sum form of ns_lstm_wide_bwd; the other persistent forms
+   * ns_lstm_seq_fwd / _bwd and ns_lstm_wide_fwd / _bwd; the other persistent forms
    * report "unsupported" and the caller falls back to the step launches. */
   uint32_t zoneout_thr_cell, zoneout_thr_output;
   uint32_t zoneout_seed_cell, zoneout_seed_output;
@@ -373,16 +373,22 @@ int ns_lstm_cluster_fwd(const ns_lstm_seq_params* fw, const ns_lstm_seq_params* 
 int ns_lstm_cluster_bwd(const ns_lstm_seq_params* fw, const ns_lstm_seq_params* bw, void* work, ns_stream_t stream);
 
 /* Persistent variant of ns_lstm_seq_* for WIDE cells at small batch (the decoder LSTMs of tacotron2.py:67-73: 1024
- * units, 32 rows): ONE launch for the whole sequence.  A workgroup keeps its slice of W_h in registers (forward: 8
- * units x 4 gates; backward: 16 units) and only the state travels, through the history arrays themselves: the call
- * first fills h[:, 0..T) (backward: the bf16 gate gradients) with an all-ones NaN sentinel, the producers store
- * h[t] write-through and every workgroup of the row group polls and fetches h[t-1] (backward: the gate gradients of
- * step t+1) with L1/L2-bypassing loads until no element is the sentinel - the data is its own flag.
+ * units, 32 rows): ONE launch for the whole sequence.  A workgroup keeps its slice of W_h on the CU for all steps and
+ * only the state travels between the workgroups of a row group.
+ * Forward (workgroup = 16 rows x 8 units, all four gates): through the history array itself - the call first fills
+ * h[:, 0..T) with an all-ones NaN sentinel (h only), the producers store h[t] write-through and every workgroup of the
+ * row group polls and fetches h[t-1] with L1/L2-bypassing loads until no element is the sentinel: the data is its own
+ * flag.
+ * Backward (workgroup = 8 rows x 32 units): every workgroup forms, from its own gate gradients, its partial sum of
+ * dh[t-1] for all units and sends each peer that peer's block as {step tag, 2 x bf16} granules through an exchange
+ * area in `work` (zeroed by the call; nothing is filled with the sentinel); the receiver adds the blocks in a fixed
+ * order.
  * Forward: dtype NS_BF16, or NS_F32 with whT_hi / whT_lo and f32_passes == 3.  Backward: NS_BF16, or NS_F32 with
- * wh_bf16 + dgates_bf16 and f32_passes == 1.  H in {256, 512, 1024}, reverse == 0, and the grid (16-row groups x H/8
- * forward, x H/16 backward) must fit the device at one workgroup per CU (<= 256).  ns_lstm_wide_supported() says
- * whether a parameter block qualifies.  work: ns_lstm_wide_work_bytes(); work[0] (int) is a status word, non-zero
- * after the call completes = a wait timed out and the outputs are invalid (they may then hold the sentinel). */
+ * wh_bf16 + dgates_bf16 and f32_passes == 1.  H in {256, 512, 1024}, reverse == 0, and 16-row groups x H/8 (forward) or
+ * x H/16 (backward) must not exceed the device's CUs (256): every workgroup of the launch has to be resident at once.
+ * ns_lstm_wide_supported() says whether a parameter block qualifies.  work: ns_lstm_wide_work_bytes() - a status word,
+ * a trace area, the backward call's exchange area; work[0] (int) is the status word, non-zero after the call completes
+ * = a wait timed out and the outputs are invalid (forward: they may then hold the sentinel). */
 int ns_lstm_wide_supported(const ns_lstm_seq_params* p, int backward);
 size_t ns_lstm_wide_work_bytes(const ns_lstm_seq_params* p);
 int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stream_t stream);

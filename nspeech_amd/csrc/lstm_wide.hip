@@ -3,39 +3,45 @@
 //
 // The launch-per-step kernels re-stream the whole recurrent matrix (16.8 MB as hi + lo bf16 planes, forward) through
 // every CU each step and pay a dependent-launch boundary on top: ~9.9 us per step.  Here a workgroup keeps its slice of
-// W_h in REGISTERS for all steps (forward: 8 units x 4 gates x H as hi / lo MFMA B fragments, 64 VGPRs per lane), the
-// cell state too, and only the state travels - through the history array the kernel has to write anyway:
-//   workgroup (rg, ub) = 16 batch rows x 8 units (forward) / 8 or 16 rows x 16 units (backward)
+// W_h resident for all steps, the cell state too, and only the state travels between the workgroups of a row group.
+// The two directions exchange it differently.
+//
+// FORWARD (lstm_wide_fwd_kernel): workgroup = 16 batch rows x 8 units, 8 units x 4 gates x H of W_h^T as hi / lo MFMA
+// B fragments in registers (64 VGPRs per lane).  h travels through the history array the kernel has to write anyway:
 //   before the launch: a fill kernel writes an all-ones NaN pattern (the SENTINEL, a value the recurrence never
-//              stores) over every (row, step) of the exchanged array;
+//              stores) over every (row, step) of h;
 //   per step:  8 SWEEPER waves split K.  Each polls ONE 16-byte piece per producing workgroup of its K slice (sc1 =
 //              L1- and L2-bypassing loads) and fetches the 16 rows of a producer's units as soon as that producer's
 //              piece is no longer the sentinel - the data is its own flag: a step costs one store -> load hop with
 //              no drain, no counter and no second round trip -, then MFMA and partial sums into LDS;
-//              2 (backward: 4) CELL waves add the partials, update the cell, publish h[t] (backward: dgates[t] as
-//              bf16) with 16-byte sc1 write-through stores and do every other memory access of the step.
+//              2 CELL waves add the partials, update the cell, publish h[t] with 16-byte sc1 write-through stores and
+//              do every other memory access of the step.
 // 16-byte sc1 stores arrive as untorn 8-byte halves on gfx950 (MI355X_MICROARCH.md, hand-off table) and every element
 // of every fetched piece is checked, so a piece passes only when all of it is new; a stale piece is fetched again.
 // The cell update never produces the sentinel (a NaN of that bit pattern is rewritten to the canonical quiet NaN).
+// Why a probe instead of polling with the sweep itself: 256 CUs re-reading 64 KB each per pass is 16 MB per pass on the
+// memory side (sc1 loads do not hit in L2) - the passes then take 2.2 us each and the CU's own publish store queues
+// behind them.  Measured per step at the benchmark shape (profiles/r02_wide_trace.txt): arrival counters + drained
+// stores 8.7 us; sentinel polling by full sweeps 7.9; probe, then one sweep 5.2; probe and sweep interleaved 4.9.  What
+// is left is the hop itself: store -> visible + one probe round trip (1.9 us) + one data round trip (1.5 us), then
+// ~1.5 us of MFMA, barrier and cell update.
 //
-// Why the roles are separate waves: a wave's vector-memory operations complete in issue order, so a polling load
-// queued behind the write-through publish store, the late stores or an operand fetch from HBM returns only after
-// those.  Why a probe instead of polling with the sweep itself: 256 CUs re-reading 64 KB each per pass is 16 MB per
-// pass on the memory side (sc1 loads do not hit in L2) - the passes then take 2.2 us each and the CU's own publish
-// store queues behind them.  Measured per step at the benchmark shape (profiles/r02_wide_trace.txt), forward /
-// backward: arrival counters + drained stores 8.7 / 6.65 us; sentinel polling by full sweeps 7.9 / 10.7; probe,
-// then one sweep 5.2 / 7.3; probe and sweep interleaved 4.9 / 7.0; backward with 8-row groups 6.6; backward with a
-// PROBER wave (an idle cell wave polls for the whole workgroup with nothing else in its memory queue and hands the
-// producers' bits over in LDS) 6.0 - the forward kernel got slower with one (5.25) and keeps the sweepers' own probes.
-// What is left is
-// the hop itself: store -> visible + one probe round trip (1.9 us) + one data round trip (1.5 us; 2.2 us for the
-// backward pass's 64 KB per CU), then ~1.5 us of MFMA, barrier and cell update.
-// Round 3: the BACKWARD recurrence runs on lstm_wide_bwd_ps_kernel (further down) - partial sums of dh as self-flagging
-// granules, one hop, 4.1 us per step; the sweep-form backward kernel below stays for NS_WIDE_PS=0 and the shapes the new
-// one does not take (H not a multiple of 128, more than 256 workgroups).
+// BACKWARD (lstm_wide_bwd_ps_kernel): workgroup = 8 batch rows x 32 units.  dh[t-1] = dgates[t] . Wh^T is a sum over
+// the gate columns and a workgroup owns 128 of them, so it sends every peer its PARTIAL SUM for that peer's units as
+// {step tag, 2 x bf16} granules through an exchange area of `work` (zeroed per launch; the tag is the flag): one hop and
+// no probe, 4.1 us per step.  Nothing is filled with the sentinel in this direction.  The comment above the kernel has
+// the details.
+//
+// Tried and replaced: round 2 ran the backward recurrence in the forward kernel's form - 8 or 16 rows x 16 units, the
+// bf16 gate gradients sentinel-filled and swept, all 4H of them per workgroup and step (64 KB at 8 rows) behind a
+// probe.  Two dependent round trips: 7.0 us per step, 6.6 with 8-row groups, 6.0 / 5.9 with a prober wave
+// (profiles/r02_wide_trace.txt).  Round 3's partial sums replaced it (profiles/r03_wide_trace.txt); that
+// kernel and a 16-unit form of the partial-sum kernel (twice the write-through bytes, 4.97 us) stayed behind an
+// environment switch that no test set and were retired (profiles/wide_forms_retired.txt).
+//
 // Every spin is bounded; a timeout raises the status word and all waves of the workgroup leave together.  The grid
-// (row groups x unit blocks <= 256 workgroups, one per CU) must be resident at once: ns_lstm_wide_supported() refuses
-// shapes that do not fit.
+// (row groups x unit blocks, one workgroup per CU) must be resident at once: ns_lstm_wide_supported() refuses shapes
+// that do not fit.
 #include "common.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -49,7 +55,7 @@ struct WideArgs {
   ns_lstm_seq_params p;
   int* status;
   long long* trace;     // NS_WIDE_TRACE=1: [step][8] timestamps (100 MHz) of workgroup 0, else null
-  int nub;              // unit blocks per row group
+  int nub;              // forward kernel only: unit blocks (of 8) per row group, set by ns_lstm_wide_fwd
 };
 __device__ __forceinline__ void wstamp(const WideArgs& a, int st, int k) {
   if (a.trace && blockIdx.x == 0 && threadIdx.x == 0 && st < 256) a.trace[st * 8 + k] = wall_clock64();
@@ -86,15 +92,14 @@ __global__ __launch_bounds__(256) void wide_fill_kernel(T* base, int N, long P, 
   }
 }
 
-// Probe and sweep interleaved: the wave polls one piece per producer of its K slice (as probe()) and issues each of its NL
-// sweep loads as soon as the PPCH producers that load covers (LPC consecutive loads share them) have published, so that
+// Probe and sweep interleaved: the wave polls one piece per producer of its K slice and issues each of its NL sweep
+// loads as soon as the PPCH producers that load covers (LPC consecutive loads share them) have published, so that
 // when the last producer arrives only its own pieces are still to be fetched.  Every piece is checked once all are in
 // (the probe looked at one row only) and a stale one is fetched again.
 template <typename T, int NL, int LPC, int PPCH>
 __device__ __forceinline__ unsigned sweep_progressive(const void* base, size_t bytes, unsigned poff0, unsigned pstride,
                                                       unsigned off0, unsigned in_grp, unsigned per_grp, u32x4 (&v)[NL], int lane,
-                                                      int* status, int* abortf, int code, long long* tslot,
-                                                      const unsigned long long* pmask = nullptr, int pbit0 = 0) {
+                                                      int* status, int* abortf, int code, long long* tslot) {
   constexpr int NP = (NL / LPC) * PPCH;                       // producers of this wave's K slice
   constexpr unsigned long long ALLP = NP >= 64 ? ~0ull : ((1ull << NP) - 1ull);
   constexpr unsigned ALLL = (1u << NL) - 1u;
@@ -106,12 +111,8 @@ __device__ __forceinline__ unsigned sweep_progressive(const void* base, size_t b
   for (;;) {
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, nrec, 0x00020000);
     if (ready != ALLP) {
-      if (pmask) {            // a prober wave polls for the whole workgroup and keeps the producers' bits in LDS
-        ready = (ns_lds_peek(pmask + (pbit0 >> 6)) >> (pbit0 & 63)) & ALLP;      // an LDS read: does not wait for the sweep's loads
-      } else {
-        const u32x4 pv = __builtin_amdgcn_raw_buffer_load_b128(rs, poff, 0, 16);
-        ready |= __builtin_amdgcn_ballot_w64(lane < NP && !has_sentinel<T>(pv));
-      }
+      const u32x4 pv = __builtin_amdgcn_raw_buffer_load_b128(rs, poff, 0, 16);
+      ready |= __builtin_amdgcn_ballot_w64(lane < NP && !has_sentinel<T>(pv));
       if (tslot && ready == ALLP && blockIdx.x == 0 && threadIdx.x == 0) *tslot = wall_clock64();
     }
 #pragma unroll
@@ -132,43 +133,9 @@ __device__ __forceinline__ unsigned sweep_progressive(const void* base, size_t b
       if (!stale) return spins;
       done &= ~stale;
     }
-    if (pmask) {              // the prober owns the time-out and the look at the status word
-      if (ns_lds_peek(abortf)) return 0;
-      if ((spins & 0xffffu) == 0 && ns_spin_timed_out(clk0)) { if (lane == 0) { atomicExch(status, code); *abortf = 1; } return 0; }
-      continue;
-    }
     if ((spins & 255u) == 0) {
       if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { if (lane == 0) *abortf = 1; return 0; }
       if ((spins & 1023u) == 0 && ns_spin_timed_out(clk0)) { if (lane == 0) { atomicExch(status, code); *abortf = 1; } return 0; }
-    }
-  }
-}
-
-// The prober wave of a workgroup: polls ONE 16-byte piece per producing workgroup of the row group (lane l: producers
-// l, l + 64; byte offset poff0 + producer * pstride) with nothing else in its memory queue, and keeps the bits of the
-// producers that have published in pm[0..1] (LDS) for the sweepers.  Returns false on time-out / raised status.
-template <typename T>
-__device__ __forceinline__ bool probe_all(const void* base, size_t bytes, unsigned poff0, unsigned pstride, int np,
-                                          unsigned long long* pm, int lane, int* status, int* abortf, int code) {
-  const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), bhi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-  const unsigned o0 = lane < np ? poff0 + (unsigned)lane * pstride : 0x80000000u;
-  const unsigned o1 = lane + 64 < np ? poff0 + (unsigned)(lane + 64) * pstride : 0x80000000u;
-  const unsigned long long all0 = np >= 64 ? ~0ull : ((1ull << np) - 1ull);
-  const unsigned long long all1 = np > 64 ? (np >= 128 ? ~0ull : ((1ull << (np - 64)) - 1ull)) : 0ull;
-  unsigned long long m0 = 0ull, m1 = 0ull;
-  unsigned spins = 0, clk0 = 0;
-  for (;;) {
-    const u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, o0, 0, 16);
-    const u32x4 v1 = np > 64 ? __builtin_amdgcn_raw_buffer_load_b128(rs, o1, 0, 16) : (u32x4){0u, 0u, 0u, 0u};
-    m0 |= __builtin_amdgcn_ballot_w64(lane < np && !has_sentinel<T>(v0));
-    m1 |= __builtin_amdgcn_ballot_w64(lane + 64 < np && !has_sentinel<T>(v1));
-    if (lane == 0) { ns_lds_poke(pm, m0); ns_lds_poke(pm + 1, m1); }
-    if (m0 == all0 && m1 == all1) return true;
-    ++spins;
-    if ((spins & 255u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { if (lane == 0) *abortf = 1; return false; }
-      if ((spins & 1023u) == 0 && ns_spin_timed_out(clk0)) { if (lane == 0) { atomicExch(status, code); *abortf = 1; } return false; }
     }
   }
 }
@@ -180,9 +147,10 @@ __device__ __forceinline__ bool probe_all(const void* base, size_t bytes, unsign
 // write-through publish store, the late stores or an operand fetch from HBM returns only after those (the one-role
 // version measured 3.7 us for a sweep that succeeded at its first pass).
 // NCH = 32-wide K chunks per sweeper (H / 256); PASSES = 3: fp32 state, hi / lo weight planes; 1: bf16 everywhere
-constexpr bool FWD_PROBER = false;          // measured: 5.25 us per step with a prober wave, 5.04 with the sweepers' own probes
-                                            // (round 3, the mask polled as a plain LDS read instead of a flat load: 5.2 against 5.08)
-constexpr int WTF = WT + 128 + (FWD_PROBER ? 64 : 0);
+// A PROBER wave - a third cell-side wave that polls for the whole workgroup with nothing else in its memory queue and
+// hands the producers' bits to the sweepers in LDS - was tried in round 2 and round 3 and was slower forward, 5.25
+// against 5.04 us per step: the sweepers keep their own probes.
+constexpr int WTF = WT + 128;
 template <typename T, int PASSES, int NCH>
 __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
   // Partial sums, sweepers -> cell waves.  Row stride = 4 mod 16 floats: conflict-free for the MFMA C layout's writes
@@ -194,14 +162,12 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
   __shared__ float red[2][WW][16][36];
   __shared__ __attribute__((aligned(16))) T hst[16][8];
   __shared__ int abortf;
-  __shared__ unsigned long long pmask[2][2];       // [step parity][producers 0..63, 64..127] published bits (prober wave)
   const ns_lstm_seq_params& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = p.H, NUB = a.nub;
   const int rg = blockIdx.x / NUB, ub = blockIdx.x % NUB;
   const int n0 = rg * 16, u0 = ub * 8;
-  if (tid == 0) abortf = 0;                          // (audit) both initialised in front of the barrier below
-  if (tid < 4) pmask[tid >> 1][tid & 1] = 0ull;
+  if (tid == 0) abortf = 0;                          // (audit) initialised in front of the barrier below
   const size_t hbytes = (size_t)p.N * p.P * p.ld_h * sizeof(T);
   constexpr int PPC = 8 * (int)sizeof(T) / 16;        // 16-byte pieces per 8-value fragment (2 for fp32, 1 for bf16)
   __syncthreads();
@@ -238,8 +204,7 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
         u32x4 v[NCH * PPC];
         const unsigned prow = (unsigned)(((long)(n0 + prb) * p.P + p.padl + t - 1) * p.ld_h + k0) * (unsigned)sizeof(T);
         const unsigned got = sweep_progressive<T, NCH * PPC, PPC, 4>(p.h, hbytes, prow, 8u * (unsigned)sizeof(T), rowoff, 16u, 32u * (unsigned)sizeof(T),
-                                                                     v, lane, a.status, &abortf, 1, a.trace && t < 256 ? a.trace + t * 8 + 6 : nullptr,
-                                                                     FWD_PROBER ? &pmask[t & 1][0] : nullptr, wave * (H / (8 * WW)));
+                                                                     v, lane, a.status, &abortf, 1, a.trace && t < 256 ? a.trace + t * 8 + 6 : nullptr);
         wstamp(a, t, 1);
         if (a.trace && blockIdx.x == 0 && tid == 0 && t < 256) a.trace[t * 8 + 5] = got;
         if (got) {
@@ -271,23 +236,6 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
       __syncthreads();
       if (abortf) return;
       wstamp(a, t, 2);
-    }
-    return;
-  }
-  if (FWD_PROBER && wave == WW + 2) {
-    // ------------------------------------------------------------------ prober: one piece per producer of the row group
-    const int prb = ub % min(16, p.N - n0);            // the probed row differs from workgroup to workgroup
-    for (int t = 0; t < p.T; ++t) {
-      if (t > 0) {
-        const unsigned prow = (unsigned)(((long)(n0 + prb) * p.P + p.padl + t - 1) * p.ld_h) * (unsigned)sizeof(T);
-        probe_all<T>(p.h, hbytes, prow, 8u * (unsigned)sizeof(T), H / 8, &pmask[t & 1][0], lane, a.status, &abortf, 1);
-      }
-      // (audit) pmask[parity]: filled by this prober, read by the sweepers of the same step.  The other parity is cleared
-      // here, after this step's probe and before this step's barrier: its last readers were the sweepers of step t-1,
-      // who passed the barrier of step t-1 before this iteration began; its next readers start after this barrier.
-      if (lane < 2) pmask[(t + 1) & 1][lane] = 0ull;
-      __syncthreads();
-      if (abortf) return;
     }
     return;
   }
@@ -364,198 +312,48 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
 }
 
 // ===================================================================================== backward
-// dh[t] = dh_out[t] + dgates[t+1] . Wh^T.  Workgroup = RPG rows x 16 units; RPG = 8 (the MFMA tile's other 8 rows stay
-// zero, their lanes load nothing) when that still fits the device: the sweep is bound by what ONE CU can load per step
-// (RPG x 4H bf16 = 64 KB at 8 rows), and 4 row groups x 64 unit blocks use all 256 CUs where 2 x 64 used half.
-// Workgroup = RPG rows x 16 units (rows of Wh [H, 4H], K = 4H split over the 8
-// sweepers, NCH = 32-wide chunks per sweeper = H / 64) + 4 cell waves (thread = (row, unit)); the exchanged payload is
-// the bf16 copy of the gate gradients (dgates_bf16, or dgates itself when the storage type is bf16).
-constexpr int WTB = WT + 256;
-template <typename T, int NCH, int RPG>
-__global__ __launch_bounds__(WTB) void lstm_wide_bwd_kernel(WideArgs a) {
-  __shared__ float red[2][WW][16][20];    // two images by step parity, as in the forward kernel
-  __shared__ __attribute__((aligned(16))) bf16_t dst[16][4][16];      // this step's gate gradients (row, gate, unit)
-  __shared__ int abortf;
-  __shared__ unsigned long long pmask[2][2];
-  constexpr bool PROBER = RPG == 8;                // 8-row groups leave the last two cell waves idle: one of them probes
-  const ns_lstm_seq_params& p = a.p;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int H = p.H, K = 4 * H, NUB = a.nub;
-  const int rg = blockIdx.x / NUB, ub = blockIdx.x % NUB;
-  const int n0 = rg * RPG, u0 = ub * 16;
-  if (tid == 0) abortf = 0;
-  if (tid < 4) pmask[tid >> 1][tid & 1] = 0ull;
-  bf16_t* xb = sizeof(T) == 2 ? (bf16_t*)p.dgates : (bf16_t*)p.dgates_bf16;     // exchange payload [N*P, 4H] bf16
-  const size_t xbytes = (size_t)p.N * p.P * K * sizeof(bf16_t);
-  __syncthreads();
-
-  if (wave < WW) {
-    // ------------------------------------------------------------------ sweepers
-    const int r16 = lane & 15, g = lane >> 4;
-    const int k0 = wave * (K / WW);
-    const bf16_t* W = sizeof(T) == 2 ? (const bf16_t*)p.wh : (const bf16_t*)p.wh_bf16;
-    bf16x8 bw[NCH];
-    {
-      const bf16_t* row = W + (long)(u0 + r16) * K + k0 + g * 8;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) bw[c] = *(const bf16x8*)(row + c * 32);
-    }
-    const bool ok = r16 < RPG && n0 + r16 < p.N;
-    const int prb = (ub * WW + wave) % min(RPG, p.N - n0);     // as in the forward kernel
-    for (int t = p.T - 1; t >= 0; --t) {
-      const int bs = p.T - 1 - t;                       // backward step index
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      wstamp(a, bs, 0);
-      if (bs > 0) {
-        const unsigned rowoff = ok ? (unsigned)(((long)(n0 + r16) * p.P + p.padl + t + 1) * K + k0 + g * 8) * 2u : 0x80000000u;
-        u32x4 av[NCH];
-        const unsigned prow = (unsigned)(((long)(n0 + prb) * p.P + p.padl + t + 1) * K + k0) * 2u;
-        const unsigned got = sweep_progressive<bf16_t, NCH, 1, 2>(xb, xbytes, prow, 32u, rowoff, 0u, 64u, av, lane, a.status, &abortf, 2,
-                                                                  a.trace && bs < 256 ? a.trace + bs * 8 + 6 : nullptr,
-                                                                  PROBER ? &pmask[bs & 1][0] : nullptr, (wave & 1) * (H / 32));
-        wstamp(a, bs, 1);
-        if (a.trace && blockIdx.x == 0 && tid == 0 && bs < 256) a.trace[bs * 8 + 5] = got;
-        if (got) {
-          f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int c = 0; c < NCH; c += 2) {
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(bf16x8*)&av[c], bw[c], acc, 0, 0, 0);
-            if (c + 1 < NCH) acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(bf16x8*)&av[c + 1], bw[c + 1], acc2, 0, 0, 0);
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[q] += acc2[q];
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) red[bs & 1][wave][g * 4 + q][r16] = acc[q];
-      __syncthreads();
-      if (abortf) return;
-      wstamp(a, bs, 2);
-    }
-    return;
-  }
-  if (PROBER && wave == WW + 3) {
-    // ------------------------------------------------------------------ prober (see the forward kernel): gate 0's piece of
-    //                                                                      every producer's 16 units
-    const int prb = ub % min(RPG, p.N - n0);
-    for (int t = p.T - 1; t >= 0; --t) {
-      const int bs = p.T - 1 - t;
-      if (bs > 0) {
-        const unsigned prow = (unsigned)(((long)(n0 + prb) * p.P + p.padl + t + 1) * K) * 2u;
-        probe_all<bf16_t>(xb, xbytes, prow, 32u, H / 16, &pmask[bs & 1][0], lane, a.status, &abortf, 2);
-      }
-      if (lane < 2) pmask[(bs + 1) & 1][lane] = 0ull;
-      __syncthreads();
-      if (abortf) return;
-    }
-    return;
-  }
-  // -------------------------------------------------------------------- cell waves: thread = (row er, unit eu)
-  const int e = tid - WT, er = e >> 4, eu = e & 15;
-  const int en = n0 + er;
-  const bool eok = er < RPG && en < p.N;
-  const int elen = (eok && p.lengths) ? p.lengths[en] : p.T;
-  const auto xrs = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)xbytes, 0x00020000);
-  const bool tr = a.trace && blockIdx.x == 0 && e == 0;
-  float dcc = 0.f;
-  float pg[4] = {0.f, 0.f, 0.f, 0.f}, pdh = 0.f, pc = 0.f, pcp = 0.f;
-  auto load_ops = [&](int t) {
-    if (eok) {
-      const long rowi = (long)en * p.P + p.padl + t;
-      const T* gp = (const T*)p.gates + rowi * 4 * H + u0 + eu;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) pg[j] = ldf(gp + (long)j * H);
-      pdh = p.dh[rowi * p.ld_dh + u0 + eu];
-      pc = p.c[rowi * H + u0 + eu];
-      pcp = t > 0 ? p.c[(rowi - 1) * H + u0 + eu] : 0.f;
-    }
-  };
-  load_ops(p.T - 1);
-  for (int t = p.T - 1; t >= 0; --t) {
-    const int bs = p.T - 1 - t;
-    __syncthreads();
-    if (abortf) return;
-    if (tr && bs < 256) a.trace[bs * 8 + 3] = wall_clock64();
-    float dh = pdh;
-#pragma unroll
-    for (int w = 0; w < WW; ++w) dh += red[bs & 1][w][er][eu];
-    const float gi = pg[0], gj = pg[1], gf = pg[2], go = pg[3];
-    const float tc = tanhf_(pc);
-    const float dc = dh * go * (1.f - tc * tc) + dcc;
-    float dgv[4];
-    dgv[0] = dc * gj * gi * (1.f - gi);
-    dgv[1] = dc * gi * (1.f - gj * gj);
-    dgv[2] = dc * pcp * gf * (1.f - gf);
-    dgv[3] = dh * tc * go * (1.f - go);
-    dcc = dc * gf;
-    if (t >= elen || !eok) { dgv[0] = dgv[1] = dgv[2] = dgv[3] = 0.f; dcc = 0.f; }
-#pragma unroll
-    // (audit) dst: rows 4w .. 4w+3 are written (er = e >> 4) and published (row = 4w + lane / 8) by the same cell wave w
-    for (int j = 0; j < 4; ++j) dst[er][j][eu] = clean(dgv[j], (bf16_t*)nullptr);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // LDS write -> read inside this wave (its own 4 rows)
-    __builtin_amdgcn_wave_barrier();
-    // ---- publish dgates[t] (bf16): this wave's 4 rows x 4 gates x 32 bytes = 32 pieces of 16 bytes
-    if (lane < 32) {
-      const int row = (wave - WW) * 4 + (lane >> 3), gate = (lane >> 1) & 3, hf = lane & 1;
-      if (row < RPG && n0 + row < p.N) {
-        const u32x4 x = *(const u32x4*)((const char*)&dst[row][gate][0] + hf * 16);
-        const unsigned off = (unsigned)(((long)(n0 + row) * p.P + p.padl + t) * K + (long)gate * H + u0) * 2u + hf * 16;
-        __builtin_amdgcn_raw_buffer_store_b128(x, xrs, off, 0, 16);
-      }
-    }
-    if (tr && bs < 256) a.trace[bs * 8 + 4] = wall_clock64();
-    // ---- fp32 copy of the gate gradients for the weight-gradient products (storage type float), next operands
-    if (eok && sizeof(T) == 4) {
-      float* dg = (float*)p.dgates + ((long)en * p.P + p.padl + t) * K + u0 + eu;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) dg[(long)j * H] = dgv[j];
-    }
-    if (t > 0) load_ops(t - 1);
-  }
-}
-
-// ===================================================================================== backward, partial sums (round 3)
-// The backward kernel above gathers, per workgroup and step, ALL 4H gate gradients of its 8 rows (64 KB at H = 1024)
-// behind a probe: two dependent memory round trips, 5.9 us per step.  dh[t-1] = dgates[t] . Wh^T is a sum over the gate
-// columns, and a workgroup OWNS 64 of them (4 gates x its 16 units): as in lstm_cluster2p_bwd_kernel it forms, from its
-// own gate gradients alone and straight after the cell update, its partial sum for EVERY unit of the layer - P[8, H] =
-// dg_own[8, 64] . Wh[:, own columns]^T, H / 16 MFMA tiles of K = 64 - and sends each peer only the 8 x 16 block of that
-// peer's units, as {step tag, 2 x bf16} granules (two rows of one unit): 64 granules per (destination, source), the data
-// is its own flag - no probe, no second round trip, and half the bytes (32 KB in and out per workgroup and step).
-// The receiver adds the blocks in a fixed order (own block fp32 first, then sources in the polling order below).
-//   8 product waves  : resident Wh[units of their H/128 destination tiles][own 64 columns] (64 VGPRs per lane at
-//                      H = 1024); per step: poll the granules of 1/8 of the sources (lane = one (unit, row pair) item),
-//                      sum them, LDS -> barrier A -> (cell waves) -> barrier B -> MFMA over the operand image ->
-//                      publish (the own tile goes to LDS as fp32)
-//   2 cell waves     : thread = (row, unit); behind barrier A add the eight partial sums, own block and dh_out, update
-//                      the cell, write the bf16 operand image, barrier B; then the stores only later kernels read and
-//                      the next step's operand loads.
-// Exchange buffer (work): [row group][step parity][destination][source][64 items] of 8 bytes, zeroed per launch.
+// dh[t-1] = dgates[t] . Wh^T is a sum over the gate columns, and a workgroup (8 batch rows x UPB = 32 units) OWNS 128 of
+// them (4 gates x its 32 units): as in lstm_cluster2p_bwd_kernel it forms, from its own gate gradients alone and
+// straight after the cell update, its partial sum for EVERY unit of the layer - P[8, H] = dg_own[8, 128] . Wh[:, own
+// columns]^T, H / 16 MFMA tiles of K = 128 - and sends each peer only the 8 x 32 block of that peer's units, as {step tag,
+// 2 x bf16} granules (two rows of one unit): 128 granules per (destination, source), the data is its own flag - one
+// store -> load hop per step, no probe and no second round trip.  The receiver adds the blocks in a fixed order (own
+// block fp32 first, then sources in the polling order below).
+//   8 product waves  : resident Wh[units of their H/128 destination tiles][own 128 columns] - 256 KB per workgroup at
+//                      H = 1024, three k-steps in registers (96 VGPRs per lane), the last in LDS; per step: poll the
+//                      granules of 1/8 of the sources (lane = two (unit, row pair) items), sum them, LDS -> barrier A ->
+//                      (cell waves) -> barrier B -> MFMA over the operand image -> publish (the own tiles go to LDS as
+//                      fp32)
+//   2 cell waves     : thread = (row, two units); behind barrier A add the eight partial sums, own block and dh_out,
+//                      update the cell, write the bf16 operand image, barrier B; then the stores only later kernels read
+//                      and the next step's operand loads.
+// What a step costs is the write-through traffic: every (row, destination unit) gets one partial sum from every SOURCE
+// block, rows x H x (H / UPB) values per step chip-wide, and the fabric takes write-through stores at ~3.3 TB/s.  With
+// 16-unit blocks (round 3's first form: 8 MB of granules per step at the benchmark shape, 2.4 us just to issue them)
+// the step measured 4.97 us; 32-unit blocks halve the sources and with them every byte written and polled, on half the
+// workgroups: 4.1 us.
+// Exchange area (in work): [row group][step parity][destination][source][128 items] of 8 bytes, zeroed per launch.
 constexpr int PSW = 8;                       // product waves
 constexpr int PST = PSW * 64 + 128;          // + two cell waves
 typedef unsigned long long ps_u64;
 // orders LDS only: __syncthreads() would also drain the vector-memory queue (the publish stores' acknowledgements)
 __device__ __forceinline__ void ps_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// UPB = units per workgroup (16 or 32).  What a step costs is the write-through traffic: every (row, destination unit)
-// gets one partial sum from every SOURCE block, rows x H x (H / UPB) values per step chip-wide - 8 MB of granules at
-// UPB = 16, and the fabric takes write-through stores at ~3.3 TB/s (2.4 us per step just to issue them, measured); 32-unit
-// blocks halve the sources and with them every byte written and polled (the resident weights double: Wh[H units][own
-// 128 columns] = 256 KB per workgroup, three quarters in registers, the last k-step in LDS), on half the workgroups.
-template <typename T, int NT, int UPB>       // NT = destination tiles per product wave = H / 128
+constexpr int UPB = 32;                      // units per workgroup
+template <typename T, int NT>                // NT = destination tiles per product wave = H / 128
 __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u64* xbuf) {
   constexpr int TB = UPB / 16;               // 16-unit tiles per block
   constexpr int KO = 4 * UPB, KS = KO / 32;  // own gate columns, k-steps of the product
   constexpr int ITEMS = UPB * 4;             // (unit, row pair) items per (destination, source) block
   constexpr int IPL = ITEMS / 64;            // items per polling lane
   constexpr int LDW = KO + 8;                // bf16 per row of the operand image
-  constexpr int KSR = UPB == 32 ? KS - 1 : KS;          // k-steps of the weights kept in registers (the rest: LDS)
+  constexpr int KSR = KS - 1;                // k-steps of the weights kept in registers (the last one: LDS)
   extern __shared__ __attribute__((aligned(16))) char ps_smem[];
   bf16_t* dgi = (bf16_t*)ps_smem;                               // [16][LDW], rows 8 .. 15 stay zero
   float* red = (float*)(dgi + 16 * LDW);                        // [PSW][ITEMS][2]
   float* ownp = red + PSW * ITEMS * 2;                          // [ITEMS][2]
   int* abortf = (int*)(ownp + ITEMS * 2);                       // [4]
-  bf16x8* wl = (bf16x8*)(abortf + 4);                           // [PSW * NT tiles][64 lanes] the last k-step's fragments (UPB = 32)
+  bf16x8* wl = (bf16x8*)(abortf + 4);                           // [PSW * NT tiles][64 lanes] the last k-step's fragments
   const ns_lstm_seq_params& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = p.H, K = 4 * H, NUB = H / UPB;
@@ -769,46 +567,49 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
   }
 }
 
-bool wide_shape_ok(const ns_lstm_seq_params* p, int backward, int* nub_out) {
+// What both calls accept.  The set is part of the interface (the model picks its path by it, the tests pin it down):
+// a condition stays even where the kernel that runs today would take more.
+bool wide_shape_ok(const ns_lstm_seq_params* p, int backward) {
   if (!p || p->reverse || p->T < 2) return false;
   const int H = p->H;
   if (H != 256 && H != 512 && H != 1024) return false;
-  const int nrg = (p->N + 15) / 16;
-  const int nub = backward ? H / 16 : H / 8;
-  if (nub % 8 != 0 || nrg * nub > ns_device_cus()) return false;
-  if (nub_out) *nub_out = nub;
+  // One workgroup per CU, all resident at once.  Forward: 16-row groups x H/8 unit blocks, the grid itself.  Backward:
+  // 16-row groups x H/16 is the grid of round 2's kernel; the partial-sum kernel launches ceil(N/8) x H/32 <= 2 ceil(N/16)
+  // x H/32, so every shape within the bound fits (on 256 CUs the two bounds admit exactly the same N)
+  if ((p->N + 15) / 16 * (backward ? H / 16 : H / 8) > ns_device_cus()) return false;
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   const long esz = p->dtype == NS_BF16 ? 2 : 4;
   if (!backward) {
     if (p->dtype == NS_F32 && !(p->f32_passes == 3 && p->whT_hi && p->whT_lo)) return false;
     if (p->dtype == NS_BF16 && !p->whT) return false;
     if (!p->xg || !p->h || !p->c || !al16(p->h) || (p->ld_h * esz) % 16 != 0) return false;
-    if ((double)p->N * p->P * p->ld_h * esz >= 2.0e9) return false;
+    if ((double)p->N * p->P * p->ld_h * esz >= 2.0e9) return false;       // h is addressed through a buffer resource
   } else {
-    if (p->zoneout_thr_cell || p->zoneout_thr_output) {       // only the partial-sum backward kernel applies the masks
-      const char* ps_env = getenv("NS_WIDE_PS");
-      const int ps_mode = ps_env ? atoi(ps_env) : 32;
-      const int upb = ps_mode == 16 ? 16 : 32;
-      if (!(H % 128 == 0 && ps_mode != 0 && ((p->N + 7) / 8) * (H / upb) <= ns_device_cus())) return false;
-    }
     if (p->dtype == NS_F32 && !(p->f32_passes == 1 && p->wh_bf16 && p->dgates_bf16)) return false;
     if (p->dtype == NS_BF16 && !p->wh) return false;
     if (!p->gates || !p->c || !p->dh || !p->dgates) return false;
+    // the bf16 gate gradients: 16-byte aligned and below 2e9 bytes, as round 2's kernel (which exchanged them through a
+    // buffer resource) required; the partial-sum kernel writes them with plain stores and needs neither
     if (!al16(p->dtype == NS_BF16 ? p->dgates : p->dgates_bf16)) return false;
     if ((double)p->N * p->P * 4 * H * 2 >= 2.0e9) return false;
   }
   return true;
 }
+
+// the backward kernel's exchange area: [8-row group][step parity][destination][source][UPB * 4 items] granules
+size_t ps_exchange_bytes(const ns_lstm_seq_params* p) {
+  const size_t nb = p->H / UPB;
+  return (size_t)((p->N + 7) / 8) * 2 * nb * nb * (UPB * 4) * sizeof(ps_u64);
+}
 }  // namespace
 
-extern "C" int ns_lstm_wide_supported(const ns_lstm_seq_params* p, int backward) { return wide_shape_ok(p, backward, nullptr) ? 1 : 0; }
+extern "C" int ns_lstm_wide_supported(const ns_lstm_seq_params* p, int backward) { return wide_shape_ok(p, backward) ? 1 : 0; }
+// work: status word (256 bytes reserved), the NS_WIDE_TRACE timestamps, the 16-byte-aligned exchange area of the
+// backward kernel for every shape ns_lstm_wide_bwd can take (the call is not told the direction)
 extern "C" size_t ns_lstm_wide_work_bytes(const ns_lstm_seq_params* p) {
   if (!p) return 0;
-  // status word, the NS_WIDE_TRACE timestamps, the partial-sum backward kernel's exchange buffer
-  size_t ex = 0;
-  if (p->H % 128 == 0 && p->H >= 256 && p->H <= 1024 && ((p->N + 7) / 8) * (p->H / 32) <= 256)
-    ex = (size_t)((p->N + 7) / 8) * 2 * (p->H / 16) * (p->H / 16) * 64 * sizeof(ps_u64);      // the 16-unit form's (the 32-unit form needs half)
-  return 256 + WIDE_TRACE_BYTES + ex + 64;
+  const bool bwd_fits = (p->H == 256 || p->H == 512 || p->H == 1024) && (p->N + 15) / 16 * (p->H / 16) <= ns_device_cus();
+  return 256 + WIDE_TRACE_BYTES + (bwd_fits ? ps_exchange_bytes(p) : 0) + 64;
 }
 
 template <typename T, int PASSES>
@@ -827,16 +628,15 @@ static int launch_wide_fwd(const WideArgs& a, int grid, hipStream_t s) {
 // after the call completes = a wait timed out and the outputs are invalid.
 extern "C" int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
-  int nub = 0;
   NS_CHECK_ARG(p && work, "ns_lstm_wide_fwd: null");
-  NS_CHECK_ARG(wide_shape_ok(p, 0, &nub), "ns_lstm_wide_fwd: unsupported (needs H in {256, 512, 1024}, row groups x H/8 <= 256, "
+  NS_CHECK_ARG(wide_shape_ok(p, 0), "ns_lstm_wide_fwd: unsupported (needs H in {256, 512, 1024}, row groups x H/8 <= 256, "
                "fp32 with pre-split whT_hi / whT_lo and f32_passes 3, or bf16)");
   WideArgs a;
-  a.p = *p; a.status = (int*)work; a.nub = nub;
+  a.p = *p; a.status = (int*)work; a.nub = p->H / 8;
   a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
   int rc = ns_zero_async(work, 256, s);
   if (rc) return rc;
-  const int grid = ((p->N + 15) / 16) * nub;
+  const int grid = ((p->N + 15) / 16) * a.nub;
   if (p->dtype == NS_BF16) {
     hipLaunchKernelGGL(wide_fill_kernel<bf16_t>, dim3(512), dim3(256), 0, s, (bf16_t*)p->h, p->N, (long)p->P, p->padl, p->T, (long)p->ld_h, p->H);
     NS_CHECK_LAUNCH("lstm_wide_fill");
@@ -847,68 +647,38 @@ extern "C" int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stre
   return launch_wide_fwd<float, 3>(a, grid, s);
 }
 
-template <typename T, int RPG>
-static int launch_wide_bwd(const WideArgs& a, int grid, hipStream_t s) {
-  switch (a.p.H) {
-    case 256: hipLaunchKernelGGL((lstm_wide_bwd_kernel<T, 4, RPG>), dim3(grid), dim3(WTB), 0, s, a); break;
-    case 512: hipLaunchKernelGGL((lstm_wide_bwd_kernel<T, 8, RPG>), dim3(grid), dim3(WTB), 0, s, a); break;
-    default: hipLaunchKernelGGL((lstm_wide_bwd_kernel<T, 16, RPG>), dim3(grid), dim3(WTB), 0, s, a); break;
-  }
-  NS_CHECK_LAUNCH("lstm_wide_bwd");
-  return NS_OK;
-}
+// The instantiations of the backward kernel, [storage type bf16, fp32][H / 128 = 2, 4, 8]
+typedef void (*wide_bwd_kernel_t)(WideArgs, ps_u64*);
+#define NS_WIDE_BWD_FORMS(T_) {lstm_wide_bwd_ps_kernel<T_, 2>, lstm_wide_bwd_ps_kernel<T_, 4>, lstm_wide_bwd_ps_kernel<T_, 8>}
+static const wide_bwd_kernel_t wide_bwd_forms[2][3] = {NS_WIDE_BWD_FORMS(bf16_t), NS_WIDE_BWD_FORMS(float)};
+#undef NS_WIDE_BWD_FORMS
 
+// Whole-sequence backward recurrence (the gate gradients of every step), one launch.  Same parameter block and outputs
+// as ns_lstm_seq_bwd; with fp32 storage dgates_bf16 receives the bf16 copy as well.  work as for ns_lstm_wide_fwd.
 extern "C" int ns_lstm_wide_bwd(const ns_lstm_seq_params* p, void* work, ns_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
-  int nub = 0;
   NS_CHECK_ARG(p && work, "ns_lstm_wide_bwd: null");
-  NS_CHECK_ARG(wide_shape_ok(p, 1, &nub), "ns_lstm_wide_bwd: unsupported (needs H in {256, 512, 1024}, row groups x H/16 <= 256, "
+  NS_CHECK_ARG(wide_shape_ok(p, 1), "ns_lstm_wide_bwd: unsupported (needs H in {256, 512, 1024}, row groups x H/16 <= 256, "
                "bf16, or fp32 with wh_bf16 + dgates_bf16 and f32_passes 1)");
   WideArgs a;
-  a.p = *p; a.status = (int*)work; a.nub = nub;
+  a.p = *p; a.status = (int*)work; a.nub = 0;
   a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
   int rc = ns_zero_async(work, 256, s);
   if (rc) return rc;
-  const bool r8 = ((p->N + 7) / 8) * nub <= ns_device_cus();
-  // the partial-sum exchange (lstm_wide_bwd_ps_kernel): 8-row groups, H a multiple of 128; NS_WIDE_PS=0 keeps the sweep
-  // form, 16 the 16-unit blocks
-  {
-    const char* ps_env = getenv("NS_WIDE_PS");
-    const int ps_mode = ps_env ? atoi(ps_env) : 32;
-    const int nrg = (p->N + 7) / 8;
-    const int upb = ps_mode == 16 ? 16 : 32, nb = p->H / upb, items = upb * 4;
-    if (p->H % 128 == 0 && ps_mode != 0 && nrg * nb <= ns_device_cus()) {      // 8-row groups x unit blocks, one workgroup per CU
-      ps_u64* xbuf = (ps_u64*)(((uintptr_t)work + 256 + WIDE_TRACE_BYTES + 15) & ~(uintptr_t)15);
-      const size_t xbytes = (size_t)nrg * 2 * nb * nb * items * sizeof(ps_u64);
-      rc = ns_zero_async(xbuf, xbytes, s);
-      if (rc) return rc;
-      const int grid = nrg * nb;
-      const int nt = p->H / 128;
-      const size_t ldsb = (size_t)16 * (4 * upb + 8) * 2 + sizeof(float) * (PSW * items * 2 + items * 2) + 16 +
-                          (upb == 32 ? (size_t)PSW * nt * 64 * 16 : 0);
-#define NS_LAUNCH_PS2(T_, NT_, UPB_) \
-      do { \
-        static bool attr_ = false; \
-        if (!attr_) { (void)hipFuncSetAttribute((const void*)lstm_wide_bwd_ps_kernel<T_, NT_, UPB_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_ = true; } \
-        hipLaunchKernelGGL((lstm_wide_bwd_ps_kernel<T_, NT_, UPB_>), dim3(grid), dim3(PST), ldsb, s, a, xbuf); \
-      } while (0)
-#define NS_LAUNCH_PS(T_) \
-      if (upb == 16) { \
-        switch (nt) { case 2: NS_LAUNCH_PS2(T_, 2, 16); break; case 4: NS_LAUNCH_PS2(T_, 4, 16); break; default: NS_LAUNCH_PS2(T_, 8, 16); break; } \
-      } else { \
-        switch (nt) { case 2: NS_LAUNCH_PS2(T_, 2, 32); break; case 4: NS_LAUNCH_PS2(T_, 4, 32); break; default: NS_LAUNCH_PS2(T_, 8, 32); break; } \
-      }
-      if (p->dtype == NS_BF16) { NS_LAUNCH_PS(bf16_t) } else { NS_LAUNCH_PS(float) }
-#undef NS_LAUNCH_PS
-#undef NS_LAUNCH_PS2
-      NS_CHECK_LAUNCH("lstm_wide_bwd_ps");
-      return NS_OK;
-    }
+  ps_u64* xbuf = (ps_u64*)(((uintptr_t)work + 256 + WIDE_TRACE_BYTES + 15) & ~(uintptr_t)15);
+  rc = ns_zero_async(xbuf, ps_exchange_bytes(p), s);
+  if (rc) return rc;
+  const int grid = (p->N + 7) / 8 * (p->H / UPB);      // 8-row groups x unit blocks, one workgroup per CU
+  const int nt = p->H / 128, items = UPB * 4;
+  // the operand image, the polled sums + the own block, the abort flag, the last k-step's weight fragments
+  const size_t ldsb = (size_t)16 * (4 * UPB + 8) * 2 + sizeof(float) * (PSW * items * 2 + items * 2) + 16 + (size_t)PSW * nt * 64 * 16;
+  static bool attr = false;
+  if (!attr) {
+    for (const auto& widths : wide_bwd_forms)
+      for (wide_bwd_kernel_t k : widths) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
   }
-  const int grid = (r8 ? (p->N + 7) / 8 : (p->N + 15) / 16) * nub;
-  bf16_t* xb = p->dtype == NS_BF16 ? (bf16_t*)p->dgates : (bf16_t*)p->dgates_bf16;
-  hipLaunchKernelGGL(wide_fill_kernel<bf16_t>, dim3(1024), dim3(256), 0, s, xb, p->N, (long)p->P, p->padl, p->T, 4L * p->H, 4 * p->H);
-  NS_CHECK_LAUNCH("lstm_wide_fill");
-  if (p->dtype == NS_BF16) return r8 ? launch_wide_bwd<bf16_t, 8>(a, grid, s) : launch_wide_bwd<bf16_t, 16>(a, grid, s);
-  return r8 ? launch_wide_bwd<float, 8>(a, grid, s) : launch_wide_bwd<float, 16>(a, grid, s);
+  hipLaunchKernelGGL(wide_bwd_forms[p->dtype == NS_BF16 ? 0 : 1][nt == 2 ? 0 : nt == 4 ? 1 : 2], dim3(grid), dim3(PST), ldsb, s, a, xbuf);
+  NS_CHECK_LAUNCH("lstm_wide_bwd_ps");
+  return NS_OK;
 }

@@ -17,6 +17,7 @@ from nspeech_amd.models import create_model  # noqa: E402
 
 
 def report(name, work, S):
+    """lstm_wide_fwd_kernel (sentinel sweep): the forward buffers."""
     tr = work[64:64 + 256 * 8 * 2].view(torch.int64).view(256, 8).cpu().numpy().astype(np.float64)
     r, nx = tr[4:min(S, 256) - 1], tr[5:min(S, 256)]
     us = lambda x: x.mean() * 1e-2
@@ -56,10 +57,7 @@ def main():
     m.check_status()
     for k in sorted(m._bufs):
         if k.startswith("lstm_wide_work_"):
-            if k.endswith("_bwd") and os.environ.get("NS_WIDE_PS", "1") != "0":
-                report_ps(k[len("lstm_wide_work_"):], m._bufs[k], 200)
-            else:
-                report(k[len("lstm_wide_work_"):], m._bufs[k], 200)
+            (report_ps if k.endswith("_bwd") else report)(k[len("lstm_wide_work_"):], m._bufs[k], 200)
 
 
 if __name__ == "__main__":

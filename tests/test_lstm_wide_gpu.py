@@ -104,3 +104,40 @@ def test_wide_refuses_what_it_cannot_hold(dev):
         ops.lstm_wide("fwd", p, torch.zeros(1024, device="cuda"))
     p = ops.lstm_seq_params(48, 3, 1024, 4, 1, z, 4096, zb, None, None, False, zb, 1024, z, zb)     # 3 row groups x 128 > 256
     assert not ops.lstm_wide_supported(p, False)
+
+
+def test_wide_accepts_exactly_what_fits_the_device(dev):
+    """ns_lstm_wide_supported against its closed form (no launch): 16-row groups x H/8 unit blocks forward, x H/16
+    backward, within the device's CUs - for bf16 and the mixed fp32 arrangement, zoneout off and on - and
+    ns_lstm_wide_work_bytes holds the backward launch's exchange area behind the status and trace areas."""
+    from nspeech_amd import ops
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    z = torch.zeros(64, device=dev)
+    zb = z.bfloat16()
+    T, P, padl = 3, 4, 1
+    thr = ops.zoneout_threshold(0.1)
+    wrong = []
+    for f32 in (False, True):
+        s = z if f32 else zb                                     # storage type of h, gates and dgates
+        for zone in (None, (thr, thr, 11, 12)):
+            for H in (256, 512, 1024):
+                for N in (1, 8, 9, 16, 17, 32, 33, 64, 65, 128, 129, 256, 257):
+                    ops.F32_PASSES = 3 if f32 else 0
+                    fp = ops.lstm_seq_params(N, T, H, P, padl, z, 4 * H, s, None, None, False, s, H, z, s,
+                                             whT_hi=zb if f32 else None, whT_lo=zb if f32 else None, zoneout=zone)
+                    ops.F32_PASSES = 1 if f32 else 0
+                    bp = ops.lstm_seq_params(N, T, H, P, padl, z, 4 * H, None, s, None, False, s, H, z, s, dh=z, ld_dh=H,
+                                             dgates=s, wh_bf16=zb if f32 else None, dgates_bf16=zb if f32 else None,
+                                             zoneout=zone)
+                    ops.F32_PASSES = 0
+                    groups = (N + 15) // 16
+                    for p, backward, fits in ((fp, False, groups * (H // 8) <= cus), (bp, True, groups * (H // 16) <= cus)):
+                        if ops.lstm_wide_supported(p, backward) != fits:
+                            wrong.append((f32, zone is not None, H, N, backward, fits))
+                    if groups * (H // 16) <= cus:
+                        # status word (256 bytes reserved) + 256 x 8 trace stamps, then the exchange area at the next
+                        # 16-byte boundary: [8-row group][step parity][H/32 destinations][H/32 sources][128 granules of 8 bytes]
+                        need = 256 + 256 * 8 * 8 + 15 + ((N + 7) // 8) * 2 * (H // 32) ** 2 * 128 * 8
+                        for p in (fp, bp):
+                            assert 4 * ops.lstm_wide_work_floats(p) >= need, (f32, H, N, need)
+    assert not wrong, wrong
