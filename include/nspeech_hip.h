@@ -68,6 +68,17 @@ int ns_wait_counter(const int* counter, int target, double timeout_usec, ns_stre
  *             give the same bits (no float atomics).
  *   accumulate 0: store   1: C += (fp32 C, split_k must be 1)   2: atomic C += (fp32)
  */
+/* Optional tail of a statistics-carrying product (ns_gemm_params.bn): the thread of the second statistics stage that
+ * holds a column's final sum and sum of squares goes on to what ns_bn_fwd does before its apply pass - batch mean and
+ * variance over `count` rows, the moving statistics' update (training) or the moving statistics themselves (training
+ * = 0), mean and 1/std for the apply pass and the backward pass - in the same expressions, so the bits are those of
+ * the two-call form.  The block is set when mean_out is non-NULL; ns_bn_fwd is then called with stats_final = 1. */
+typedef struct {
+  float count, eps, momentum;
+  int training;
+  float* moving_mean; float* moving_var;   /* [N] each; both NULL in training: no moving statistics are kept */
+  float* mean_out; float* istd_out;        /* [N] each */
+} ns_gemm_bn_params;
 typedef struct {
   int dtype; /* element type of A and B: NS_F32 | NS_BF16 */
   int M, N, K;
@@ -114,6 +125,9 @@ typedef struct {
    * the partial tiles up in slice order 0, 1, ... - whichever slice it is - and runs the epilogue once: a fixed
    * summation order, no waiting, no float atomics.  Both NULL: the atomic form.  batch must be 1. */
   float* splitk_work; int* splitk_count;
+  /* BatchNorm statistics finished in the product's own second stage (version 101); needs col_sum and col_sumsq, which
+   * are still written, and no stat_z */
+  ns_gemm_bn_params bn;
 } ns_gemm_params;
 int ns_gemm(const ns_gemm_params* p, ns_stream_t stream);
 size_t ns_gemm_stat_part_floats(int M, int N);
@@ -178,6 +192,8 @@ typedef struct {
   void* y_hi; void* y_lo;
   int64_t ld_y;     /* row stride of y in elements; 0 = C.  A wider one writes the output as a column block of a concatenated
                        activation (the CBHG convolution bank, modules.py:121-128, without the copy) */
+  int stats_final;  /* 1: mean_out / istd_out are final already and the moving statistics updated (ns_gemm_params.bn):
+                       only the apply pass runs; col_sum / col_sumsq / count are not read (version 101) */
 } ns_bn_fwd_params;
 int ns_bn_fwd(const ns_bn_fwd_params* p, ns_stream_t stream);
 
@@ -201,8 +217,14 @@ typedef struct {
                        products read it at half the bytes; the bias gradient is summed on the rounded values) */
   const float* sum_dy; const float* sum_dyxh;
   int64_t ld_dy;    /* row stride of dy in elements; 0 = C (dy as a column block of a concatenated activation's gradient) */
+  int no_finalize;  /* 1: stop after dpre is written; the dbias partials stay in `work` and ns_bn_bwd_finalize, given the
+                       same block, adds dbias / dgamma / dbeta later - on another stream, say, with the layer's weight
+                       gradient: nothing but the optimiser reads them.  `work`, sum_dy and sum_dyxh must stay untouched
+                       until then.  Needs sum_dy / sum_dyxh, C % 4 == 0 and 16-byte aligned operands (the form that has
+                       a finaliser of its own); NS_ERR_BAD_ARG otherwise (version 101) */
 } ns_bn_bwd_params;
 int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t stream);
+int ns_bn_bwd_finalize(const ns_bn_bwd_params* p, ns_stream_t stream);
 
 /* out[c] += sum over rows of x[row,c]  (bias gradients).  With `work` (caller-owned fp32 scratch of
  * ns_colsum_work_floats(C) floats whose FIRST 1024 words are zero before the first call; every call leaves them zero) the

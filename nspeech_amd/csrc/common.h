@@ -45,6 +45,30 @@ template <typename T> struct dt_of;
 template <> struct dt_of<float> { static constexpr int v = NS_F32; };
 template <> struct dt_of<bf16_t> { static constexpr int v = NS_BF16; };
 
+// ---------------------------------------------------------------- BatchNorm statistics of one column
+// The one place that turns a column's sum and sum of squares into mean / 1/std and moves the moving statistics: shared by
+// bn_finalize_kernel (elementwise.hip) and the folded tail of gemm_stats_finalize_kernel (gemm.hip), so that both give
+// the same bits.
+__device__ __forceinline__ void bn_finalize_column(int c, float sum, float sumsq, float count, float eps, float momentum,
+                                                   int training, float* moving_mean, float* moving_var, float* mean_out,
+                                                   float* istd_out) {
+  float mean, var;
+  if (training) {
+    mean = sum / count;
+    var = sumsq / count - mean * mean;
+    var = var < 0.f ? 0.f : var;
+    if (moving_mean) {
+      moving_mean[c] = moving_mean[c] * momentum + mean * (1.f - momentum);
+      moving_var[c] = moving_var[c] * momentum + var * (1.f - momentum);
+    }
+  } else {
+    mean = moving_mean[c];
+    var = moving_var[c];
+  }
+  mean_out[c] = mean;
+  istd_out[c] = rsqrtf(var + eps);
+}
+
 __device__ __forceinline__ float ldf(const float* p) { return *p; }
 __device__ __forceinline__ float ldf(const bf16_t* p) { return (float)*p; }
 __device__ __forceinline__ void stf(float* p, float v) { *p = v; }

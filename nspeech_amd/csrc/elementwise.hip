@@ -135,21 +135,8 @@ extern "C" int ns_embedding_bwd(const ns_embedding_bwd_params* p, ns_stream_t s)
 __global__ void bn_finalize_kernel(ns_bn_fwd_params p) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= p.C) return;
-  float mean, var;
-  if (p.training) {
-    mean = p.col_sum[c] / p.count;
-    var = p.col_sumsq[c] / p.count - mean * mean;
-    var = var < 0.f ? 0.f : var;
-    if (p.moving_mean) {
-      p.moving_mean[c] = p.moving_mean[c] * p.momentum + mean * (1.f - p.momentum);
-      p.moving_var[c] = p.moving_var[c] * p.momentum + var * (1.f - p.momentum);
-    }
-  } else {
-    mean = p.moving_mean[c];
-    var = p.moving_var[c];
-  }
-  p.mean_out[c] = mean;
-  p.istd_out[c] = rsqrtf(var + p.eps);
+  bn_finalize_column(c, p.training ? p.col_sum[c] : 0.f, p.training ? p.col_sumsq[c] : 0.f, p.count, p.eps, p.momentum,
+                     p.training, p.moving_mean, p.moving_var, p.mean_out, p.istd_out);
 }
 
 template <typename T>
@@ -216,11 +203,12 @@ __global__ __launch_bounds__(256) void bn_apply4_kernel(ns_bn_fwd_params p) {
 
 extern "C" int ns_bn_fwd(const ns_bn_fwd_params* p, ns_stream_t s) {
   NS_CHECK_ARG(p && p->z && (p->y || p->y_hi) && p->gamma && p->beta && p->mean_out && p->istd_out, "ns_bn_fwd: null");
-  NS_CHECK_ARG(!p->training || (p->col_sum && p->col_sumsq && p->count > 0), "ns_bn_fwd: training needs stats");
-  NS_CHECK_ARG(p->training || (p->moving_mean && p->moving_var), "ns_bn_fwd: inference needs moving stats");
+  NS_CHECK_ARG(p->stats_final || !p->training || (p->col_sum && p->col_sumsq && p->count > 0), "ns_bn_fwd: training needs stats");
+  NS_CHECK_ARG(p->stats_final || p->training || (p->moving_mean && p->moving_var), "ns_bn_fwd: inference needs moving stats");
   NS_CHECK_ARG((p->y_hi != nullptr) == (p->y_lo != nullptr), "ns_bn_fwd: y_hi and y_lo come together");
   NS_CHECK_ARG(p->ld_y == 0 || (p->ld_y >= p->C && p->y), "ns_bn_fwd: ld_y < C, or no y");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(p->C, 256)), dim3(256), 0, (hipStream_t)s, *p);
+  // stats_final: the product that formed z has written mean_out / istd_out already (ns_gemm_params.bn)
+  if (!p->stats_final) hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(p->C, 256)), dim3(256), 0, (hipStream_t)s, *p);
   const long total = (long)p->rows * p->C;
   auto al = [](const void* q, int b) { return ((uintptr_t)q % b) == 0; };
   const int esz = p->dtype == NS_BF16 ? 2 : 4;
@@ -504,20 +492,38 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(ns_bn_bwd_params p
   }
 }
 
-extern "C" int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
-  NS_CHECK_ARG(p && p->dy && p->z && p->dpre && p->mean && p->istd && p->gamma && p->work, "ns_bn_bwd: null");
-  NS_CHECK_ARG(!p->sum_dy == !p->sum_dyxh, "ns_bn_bwd: sum_dy and sum_dyxh come together");
+// row blocks of the vector form (= the bias-gradient partials that its finaliser adds up)
+static int bn_bwd_row_blocks(int rows) { return max(1, min(BN4_MAX_RB, ceil_div(rows, 128))); }
+static bool bn_bwd_vector_form(const ns_bn_bwd_params* p) {
   const bool al16 = ((uintptr_t)p->dy % 16 == 0) && ((uintptr_t)p->z % 8 == 0) && ((uintptr_t)p->dpre % 8 == 0) &&
                     ((uintptr_t)p->mean % 16 == 0) && ((uintptr_t)p->istd % 16 == 0) && ((uintptr_t)p->gamma % 16 == 0) &&
                     ((uintptr_t)p->work % 16 == 0) && (p->dtype == NS_BF16 || ((uintptr_t)p->z % 16 == 0 &&
                     (uintptr_t)p->dpre % (p->dpre_dtype == NS_BF16 ? 8 : 16) == 0)) &&
                     (!p->sum_dy || ((uintptr_t)p->sum_dy % 16 == 0 && (uintptr_t)p->sum_dyxh % 16 == 0));
+  return p->C % 4 == 0 && p->ld_dy % 4 == 0 && al16;
+}
+
+extern "C" int ns_bn_bwd_finalize(const ns_bn_bwd_params* p, ns_stream_t s_) {
+  NS_CHECK_ARG(p && p->dy && p->z && p->dpre && p->mean && p->istd && p->gamma && p->work, "ns_bn_bwd_finalize: null");
+  NS_CHECK_ARG(p->sum_dy && p->sum_dyxh && bn_bwd_vector_form(p),
+               "ns_bn_bwd_finalize: needs sum_dy / sum_dyxh, C %% 4 == 0 and 16-byte aligned operands");
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(p->C, 32)), dim3(256), 0, (hipStream_t)s_, *p, p->sum_dy,
+                     p->sum_dyxh, p->work + 2L * p->C, bn_bwd_row_blocks(p->rows));
+  NS_CHECK_LAUNCH("bn_bwd_finalize");
+  return NS_OK;
+}
+
+extern "C" int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  NS_CHECK_ARG(p && p->dy && p->z && p->dpre && p->mean && p->istd && p->gamma && p->work, "ns_bn_bwd: null");
+  NS_CHECK_ARG(!p->sum_dy == !p->sum_dyxh, "ns_bn_bwd: sum_dy and sum_dyxh come together");
   NS_CHECK_ARG(p->ld_dy == 0 || p->ld_dy >= p->C, "ns_bn_bwd: ld_dy < C");
-  if (p->C % 4 == 0 && p->ld_dy % 4 == 0 && al16) {
+  NS_CHECK_ARG(!p->no_finalize || (p->sum_dy && bn_bwd_vector_form(p)),
+               "ns_bn_bwd: no_finalize needs sum_dy / sum_dyxh, C %% 4 == 0 and 16-byte aligned operands");
+  if (bn_bwd_vector_form(p)) {
     // work: [0, C) sum dy | [C, 2C) sum dy*xhat (fallback only) | [2C, 2C + RB*C) bias-gradient partials |
     //       [2C + 64C, 2C + 64C + 2*RB*C) the fallback reduction's partials
-    const int rb = max(1, min(BN4_MAX_RB, ceil_div(p->rows, 128)));
+    const int rb = bn_bwd_row_blocks(p->rows);
     const dim3 grid4(rb, ceil_div(p->C / 4, BN4_QUADS));
     const float* s1 = p->sum_dy;
     const float* s2 = p->sum_dyxh;
@@ -535,7 +541,8 @@ extern "C" int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t s_) {
     }
     if (p->dtype == NS_BF16) hipLaunchKernelGGL(bn_bwd_apply4_kernel<bf16_t>, grid4, dim3(256), 0, s, *p, s1, s2, part);
     else hipLaunchKernelGGL(bn_bwd_apply4_kernel<float>, grid4, dim3(256), 0, s, *p, s1, s2, part);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(p->C, 32)), dim3(256), 0, s, *p, s1, s2, part, rb);
+    if (!p->no_finalize)      // else: ns_bn_bwd_finalize, later, from the same block
+      hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(p->C, 32)), dim3(256), 0, s, *p, s1, s2, part, rb);
     NS_CHECK_LAUNCH("bn_bwd");
     return NS_OK;
   }

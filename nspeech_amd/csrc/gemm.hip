@@ -255,8 +255,10 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(ns_gemm_params p) {
 
 // second stage of the BatchNorm statistics: adds the 64-row slots up in a fixed order.  Block = 32 columns x 32 slot
 // lanes (1024 threads): lane q adds slots q, q + 32, ... in order, then the 32 partial sums pairwise in a fixed tree.
+// With bn.mean_out set the thread that holds a column's final sums goes on to BatchNorm's mean / 1/std and moving
+// statistics (bn_finalize_column, the code of ns_bn_fwd's own finalize kernel): one launch less per normalised layer.
 __global__ __launch_bounds__(1024) void gemm_stats_finalize_kernel(const float* part, int slots, int N, float* col_sum,
-                                                                   float* col_sumsq) {
+                                                                   float* col_sumsq, ns_gemm_bn_params bn) {
   __shared__ float red[32][33][2];
   const int c = threadIdx.x & 31, q = threadIdx.x >> 5;
   const int n = blockIdx.x * 32 + c;
@@ -277,6 +279,9 @@ __global__ __launch_bounds__(1024) void gemm_stats_finalize_kernel(const float* 
   if (q == 0 && n < N) {
     col_sum[n] = red[0][c][0];
     if (col_sumsq) col_sumsq[n] = red[0][c][1];
+    if (bn.mean_out)
+      bn_finalize_column(n, red[0][c][0], red[0][c][1], bn.count, bn.eps, bn.momentum, bn.training, bn.moving_mean,
+                         bn.moving_var, bn.mean_out, bn.istd_out);
   }
 }
 
@@ -1197,7 +1202,8 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream);
 
 // the fixed-order second stage on its own (ns_bn_bwd's fallback reduction and its bias-gradient partials use it too)
 int ns_stats_finalize(const float* part, int slots, int N, float* s1, float* s2, hipStream_t stream) {
-  hipLaunchKernelGGL(gemm_stats_finalize_kernel, dim3(ceil_div(N, 32)), dim3(1024), 0, stream, part, slots, N, s1, s2);
+  hipLaunchKernelGGL(gemm_stats_finalize_kernel, dim3(ceil_div(N, 32)), dim3(1024), 0, stream, part, slots, N, s1, s2,
+                     ns_gemm_bn_params{});
   NS_CHECK_LAUNCH("gemm_stats_finalize");
   return NS_OK;
 }
@@ -1217,12 +1223,21 @@ extern "C" int ns_gemm(const ns_gemm_params* pp, ns_stream_t stream_) {
   NS_CHECK_ARG(!p.col_sum || p.stat_part, "ns_gemm: col_sum needs the stat_part scratch (ns_gemm_stat_part_floats)");
   NS_CHECK_ARG(!p.stat_z || (p.col_sum && p.col_sumsq && p.stat_mean && p.stat_istd && p.accumulate != 2 && p.split_k <= 1),
                "ns_gemm: stat_z needs col_sum, col_sumsq, stat_mean, stat_istd and a non-atomic store");
+  const ns_gemm_bn_params bn = p.bn;
+  if (bn.mean_out) {
+    NS_CHECK_ARG(p.col_sum && p.col_sumsq && !p.stat_z, "ns_gemm: bn needs col_sum and col_sumsq, and no stat_z");
+    NS_CHECK_ARG(bn.istd_out && (bn.training ? bn.count > 0 && !bn.moving_mean == !bn.moving_var
+                                             : bn.moving_mean && bn.moving_var),
+                 "ns_gemm: bn needs istd_out and, in training, count > 0 / otherwise the moving statistics");
+    NS_CHECK_ARG(p.M > 0 && p.N > 0, "ns_gemm: bn on an empty product");
+  }
+  p.bn = ns_gemm_bn_params{};      // the product kernels take the block by value and have no use for this part
   if (!p.col_sum) p.stat_part = nullptr;
   p.stat_slots = 0;
   int rc = gemm_dispatch(p, stream);
   if (rc || !p.stat_part || p.M == 0 || p.N == 0) return rc;
   hipLaunchKernelGGL(gemm_stats_finalize_kernel, dim3(ceil_div(p.N, 32)), dim3(1024), 0, stream, p.stat_part, p.stat_slots,
-                     p.N, p.col_sum, p.col_sumsq);
+                     p.N, p.col_sum, p.col_sumsq, bn);
   NS_CHECK_LAUNCH("gemm_stats_finalize");
   return NS_OK;
 }

@@ -368,6 +368,21 @@ class Tacotron2(object):
     # only the postnet group is queued (its bucket goes out behind the attention recurrence either way) and `head` keeps
     # its eager products and its release beside the postnet backward.
     _queue_env = os.environ.get("NS_WGRAD_QUEUE")
+    # Optimiser-only work that rides the second stream with its group (profiles/main_stream.txt): NS_MAIN_STREAM lists the
+    # items to keep on the main stream instead, for measuring each on its own - fold (BatchNorm's forward finaliser as a
+    # launch of its own), head (the linear head's weight gradient), postdense (the postnet projection's), bn_final
+    # (BatchNorm-backward's dbias / dgamma / dbeta adds), cast (bf16 operand copies); the last two also per group, as
+    # in "bn_final:postnet".
+    # bn_final and cast move for the groups of _LATE_GROUPS only.  The encoder group's window is the end of the pass, where
+    # the main stream already waits 0.6 ms for the second one: what moves there comes back as wait (measured, with the
+    # memory layer's, the location layer's and the embedding's weight gradients, which therefore stay where they were).
+    main_stream_items = tuple(i for i in os.environ.get("NS_MAIN_STREAM", "").split(",") if i)
+    _LATE_GROUPS = ("head", "postnet")
+
+    def _on_main(self, item, group=None):
+        if group is not None and (group not in self._LATE_GROUPS or "%s:%s" % (item, group) in self.main_stream_items):
+            return True
+        return item in self.main_stream_items
 
     @property
     def queue_groups(self):
@@ -385,13 +400,14 @@ class Tacotron2(object):
         self._side_busy = True
         return self._side
 
-    def _defer(self, group, fn, eager=False):
-        """Run fn in line, or - with overlap_wgrads - on the second stream: now (eager) or at _flush_deferred.  group =
-        the gradient bucket (parallel.bucket_ranges) the call writes into: its release to the reducer follows the call
-        onto that stream.  The caller guarantees that nothing overwrites fn's operands before _join_deferred."""
+    def _defer(self, group, fn, eager=False, now=False):
+        """Run fn in line, or - with overlap_wgrads - on the second stream: now (eager, unless its group is queued; `now`:
+        even then) or at _flush_deferred.  group = the gradient bucket (parallel.bucket_ranges) the call writes into: its
+        release to the reducer follows the call onto that stream.  The caller guarantees that nothing overwrites fn's
+        operands before _join_deferred."""
         if not (self.overlap_wgrads and self.device.type == "cuda"):
             fn()
-        elif eager and group not in self.queue_groups:
+        elif now or (eager and group not in self.queue_groups):
             self._side_groups.add(group)
             with torch.cuda.stream(self._side_stream()):
                 fn()
@@ -580,9 +596,15 @@ class Tacotron2(object):
         z = self._buf(tag + "_z", rows * cout, D)
         st = self._stats_buf(tag, cout)
         wT = self.tsh.get("expT_" + tag[3:]) if tag.startswith("exp") and D == torch.bfloat16 else None
+        mm_off = self.stat_layout.off(scope + "/batch_normalization/moving_mean")
+        mv_off = self.stat_layout.off(scope + "/batch_normalization/moving_variance")
         common = dict(a_off=a_rows * cin, c_off=self.padl * cout, bias=self.flat_p, bias_off=self._o(scope + "/conv1d/bias"),
                       act=act, row_mask=(Pp, self.padl, self.padl + T, self.padl),
                       col_sum=st if training else None, col_sumsq=st[cout:] if training else None)
+        fold = training and not self._on_main("fold")
+        if fold:        # the statistics' second stage finishes mean / 1/std and the moving statistics: no launch of its own
+            common["bn"] = dict(count=N * T, training=True, moving_mean=self.flat_stats, mm_off=mm_off,
+                                moving_var=self.flat_stats, mv_off=mv_off, mean_out=st[2 * cout:], istd_out=st[3 * cout:])
         if xsplit is not None:      # pre-split operands: (hi, hi), (hi, lo), (lo, hi) on the 256-tile kernel
             key = "postT_" + tag[4:]
             ops.gemm(xsplit[0], self.tsh[key + "_hi"], z, Mg, cout, k * cin, cin, k * cin, cout, a_mode=0, b_mode=0,
@@ -606,8 +628,7 @@ class Tacotron2(object):
                    self.flat_stats, st[2 * cout:], st[3 * cout:], training, row_mask=(Pp, self.padl, self.padl + T),
                    gamma_off=self._o(scope + "/batch_normalization/gamma"),
                    beta_off=self._o(scope + "/batch_normalization/beta"),
-                   mm_off=self.stat_layout.off(scope + "/batch_normalization/moving_mean"),
-                   mv_off=self.stat_layout.off(scope + "/batch_normalization/moving_variance"), y_hi=yh, y_lo=yl, **ykw)
+                   mm_off=mm_off, mv_off=mv_off, y_hi=yh, y_lo=yl, stats_final=fold, **ykw)
         return (yh, yl) if emit_split else y
 
     def _conv_bwd(self, scope, xin, dy, cin, cout, k, act, N, T, Pp, tag, dx, need_dx=True, dx_accumulate=False,
@@ -627,6 +648,7 @@ class Tacotron2(object):
         Dg = torch.bfloat16 if w16 is not None else D
         own = "_" + tag if (defer and self.overlap_wgrads) else ""
         dpre = self._buf("dpre_%d%s" % (cout, own), rows * cout, Dg)
+        cast = None                         # (bf16 buffer, fp32 source): the copy is made with its only reader, wgrad()
         if isinstance(xin, tuple):          # pre-split layer input (mixed mode): its high part IS the bf16 copy
             assert w16 is not None
             xin = xin[0]
@@ -636,25 +658,39 @@ class Tacotron2(object):
             x16 = cache.get(key) if cache is not None else None
             if x16 is None:
                 x16 = self._buf("xin16_%d%s" % (cin, own), rows * cin, torch.bfloat16)
-                ops.cast2d(xin, rows, cin, cin, x16, cin, False)
+                cast = (x16, xin)
                 if cache is not None:
+                    for stale in [k_ for k_, v_ in cache.items() if v_ is x16]:     # the buffer is about to hold another
+                        del cache[stale]                                            # input: its older entries go
                     cache[key] = x16
             xin = x16
-        work = self._buf("bn_work", 200 * max(1024, cout), torch.float32)
         g = self.flat_g
         dykw = {}
         if isinstance(dy, tuple):           # (buffer, first column, row stride): dy as a column block of a wider gradient
             dy, dykw = dy[0], dict(dy_off=dy[1], ld_dy=dy[2])
-        ops.bn_bwd(dy, z, dpre, rows, cout, st[2 * cout:], st[3 * cout:], self.flat_p, g, g, g, work, N * T, act,
-                   sums=self._bwd_sums.pop(tag, None), row_mask=(Pp, self.padl, self.padl + T), **dykw,
-                   gamma_off=self._o(scope + "/batch_normalization/gamma"),
-                   dgamma_off=self._o(scope + "/batch_normalization/gamma"),
-                   dbeta_off=self._o(scope + "/batch_normalization/beta"),
-                   dbias_off=self._o(scope + "/conv1d/bias"))
+        sums = self._bwd_sums.pop(tag, None)
+        # The dbias / dgamma / dbeta adds feed the optimiser alone: with a deferred weight gradient they travel with it (and
+        # with the group's bucket release).  Their partial sums then have to outlive the next layer's pass: a work buffer
+        # of the layer's own, like dpre.  Without fused sums ns_bn_bwd keeps its in-line finaliser.
+        late = bool(own) and sums is not None and cout % 4 == 0 and not self._on_main("bn_final", defer)
+        work = self._buf("bn_work" + (own if late else ""), 200 * max(1024, cout), torch.float32)
+        fin = ops.bn_bwd(dy, z, dpre, rows, cout, st[2 * cout:], st[3 * cout:], self.flat_p, g, g, g, work, N * T, act,
+                         sums=sums, row_mask=(Pp, self.padl, self.padl + T), **dykw,
+                         gamma_off=self._o(scope + "/batch_normalization/gamma"),
+                         dgamma_off=self._o(scope + "/batch_normalization/gamma"),
+                         dbeta_off=self._o(scope + "/batch_normalization/beta"),
+                         dbias_off=self._o(scope + "/conv1d/bias"), no_finalize=late)
         # weight gradient: dW[(k,ci),co] += sum_rows X[row+k, ci] * dpre[row, co]
         a_rows = self.padl - kl
         Mg = rows - (k - 1) - a_rows
-        def wgrad():
+        if cast is not None and (not own or self._on_main("cast", defer)):
+            ops.cast2d(cast[1], rows, cin, cin, cast[0], cin, False)
+            cast = None
+        def wgrad():        # operands of the layer's own: dpre, work, the sums, the bf16 copy; the layer input stays as it is
+            if fin is not None:
+                ops.bn_bwd_finalize(fin)
+            if cast is not None:
+                ops.cast2d(cast[1], rows, cin, cin, cast[0], cin, False)
             ops.gemm(xin, dpre, g, k * cin, cout, Mg, cin, cout, cout, a_mode=1, b_mode=1,
                      a_off=a_rows * cin, b_off=self.padl * cout, c_off=self._o(scope + "/conv1d/kernel"),
                      accumulate=2, split_k=self._splitk(Mg, k * cin, cout))
@@ -788,12 +824,18 @@ class Tacotron2(object):
         g = self.flat_g
         hbuf = self._bufs[tag + "_h"]
         f32c = getattr(self, "_bilstm_f32c", {}).get(tag, False)
+        cast = None
         if f32c:
             # the forward pass saved bf16 gates and a bf16 copy of h: everything below runs as in the bf16 mode, on the
             # bf16 weight shadow (the single-pass backward of `mixed` rounds these operands to bf16 on load anyway)
             hbuf = self._bufs[tag + "_h16"]
+            # the bf16 copy of the layer input has one reader, the first weight-gradient product below (the input-gradient
+            # products read dgates and the weights): it is made there, off the main stream when that call is deferred
             x16 = self._buf("%s_x16" % tag, rows * cin, torch.bfloat16)
-            ops.cast2d(x, rows, cin, cin, x16, cin, False)
+            cast = (x16, x)
+            if not defer or self._on_main("cast", defer):
+                ops.cast2d(x, rows, cin, cin, x16, cin, False)
+                cast = None
             x = x16
             D = torch.bfloat16
         pair = []
@@ -818,6 +860,8 @@ class Tacotron2(object):
 
             def wgrads(d=d, di=di, ko=ko, dg=dg):
                 # dWx += X^T dgates ; dWh += Hprev^T dgates ; db += colsum
+                if cast is not None and di == 0:
+                    ops.cast2d(cast[1], rows, cin, cin, cast[0], cin, False)
                 ops.gemm(x, dg, g, cin, 4 * H, rows, cin, 4 * H, 4 * H, a_mode=1, b_mode=1, c_off=ko, accumulate=2,
                          split_k=self._splitk(rows, cin, 4 * H))
                 if d == "fw":   # h_prev(row) = h(row-1)
@@ -1098,13 +1142,22 @@ class Tacotron2(object):
         ex = B["expl_h"]
         rows_o = N * Po
         dwl = self._buf("d_wl_pad", 2 * Hx * Fp, torch.float32)
-        ops.zero(dwl)
-        ops.gemm(ex, dlin, dwl, 2 * Hx, Fp, rows_o, 2 * Hx, Fp, Fp, a_mode=1, b_mode=1, accumulate=2,
-                 split_k=self._splitk(rows_o, 2 * Hx, Fp))
-        ops.copy3d(dwl, g, 1, 2 * Hx, F, (0, Fp), (0, F), dst_off=self._o("dense/kernel"), accumulate=1)
-        ops.colsum(dlin, Fp, rows_o, F, g, out_off=self._o("dense/bias"))
+
+        def head_wgrad():       # operands: d_lin, the expand BiLSTM's saved output and d_wl_pad - the backward pass writes
+            ops.zero(dwl)       # none of them anywhere else
+            ops.gemm(ex, dlin, dwl, 2 * Hx, Fp, rows_o, 2 * Hx, Fp, Fp, a_mode=1, b_mode=1, accumulate=2,
+                     split_k=self._splitk(rows_o, 2 * Hx, Fp))
+            ops.copy3d(dwl, g, 1, 2 * Hx, F, (0, Fp), (0, F), dst_off=self._o("dense/kernel"), accumulate=1)
+            ops.colsum(dlin, Fp, rows_o, F, g, out_off=self._o("dense/bias"))
+        head_late = not self._on_main("head")
+        if not head_late:
+            head_wgrad()
         dex = self._buf("d_exp_h", rows_o * 2 * Hx, torch.float32)
         ops.gemm(dlin, self.tsh["wl_pad"], dex, rows_o, 2 * Hx, Fp, Fp, Fp, 2 * Hx, a_mode=0, b_mode=0)
+        if head_late:
+            # behind the product the recurrence waits for, and at once even where the head group is queued: the expand
+            # BiLSTM's backward recurrence that follows holds 64 CUs for 1.9 ms and nothing else has work for the rest
+            self._defer("head", head_wgrad, now=True)
         self._tick("linear_bwd")
         # ---- expand BiLSTM + convs
         Cx = hp.expand_conv_channels
@@ -1130,9 +1183,16 @@ class Tacotron2(object):
         dmel_t = self._buf("d_mel_t", rows_o * M, T_)
         ops.copy3d(dmel, dmel_t, 1, rows_o, M, (0, M), (0, M))
         ko = self._o("decoder_postnet/dense/kernel")
-        ops.gemm(self._post_in[-1], dmel_t, g, Cp, M, rows_o, Cp, M, M, a_mode=1, b_mode=1, c_off=ko, accumulate=2,
-                 split_k=self._splitk(rows_o, Cp, M))
-        ops.colsum(dmel_t, M, rows_o, M, g, out_off=self._o("decoder_postnet/dense/bias"))
+        post_h = self._post_in[-1]
+
+        def postdense_wgrad():      # operands: the postnet's saved output and d_mel_t, a buffer of this call's own
+            ops.gemm(post_h, dmel_t, g, Cp, M, rows_o, Cp, M, M, a_mode=1, b_mode=1, c_off=ko, accumulate=2,
+                     split_k=self._splitk(rows_o, Cp, M))
+            ops.colsum(dmel_t, M, rows_o, M, g, out_off=self._o("decoder_postnet/dense/bias"))
+        if self._on_main("postdense"):
+            postdense_wgrad()
+        else:
+            self._defer("postnet", postdense_wgrad, eager=True)
         cur, nxt = dx, dx2
         ops.gemm(dmel_t, self._W(self.T), cur, rows_o, Cp, M, M, M, Cp, a_mode=0, b_mode=0, b_off=ko,
                  row_mask=(Po, self.padl, self.padl + To, 0), **self._dy_stats_kw("post%d" % (hp.postnet_conv_layers - 1)))

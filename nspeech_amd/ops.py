@@ -43,8 +43,11 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, a_off=0, b_off=0,
          bias=None, bias_off=0, act=0, alpha=1.0, accumulate=0, row_mask=None, col_sum=None,
          col_sumsq=None, split_k=1, b_seg=None, addend=None, addend_off=0, ld_add=0, f32_passes=None,
          gate=None, gate_off=0, ld_gate=0, a_lo=None, b_lo=None, batch=1, batch_strides=(0, 0, 0),
-         stat_z=None, ld_stat_z=0, stat_mean=None, stat_istd=None, stat_z_off=0):
+         stat_z=None, ld_stat_z=0, stat_mean=None, stat_istd=None, stat_z_off=0, bn=None):
     """C = act(alpha * A.B + bias); see ns_gemm in include/nspeech_hip.h.
+    bn = dict(count, eps, momentum, training, moving_mean, mm_off, moving_var, mv_off, mean_out, istd_out): the
+    statistics' second stage also finishes BatchNorm's mean / 1/std and moving statistics (ns_gemm_params.bn); bn_fwd is
+    then called with stats_final=True.
     stat_z (+ ld_stat_z, stat_mean, stat_istd): col_sum / col_sumsq become the BatchNorm-backward sums of C as `dy`
     against the saved BatchNorm input stat_z (sum dy, sum dy * xhat); stat_z_off: element offset of the row that pairs
     with output row 0 (as c_off for C)."""
@@ -70,6 +73,11 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, a_off=0, b_off=0,
     if stat_z is not None:
         p.stat_z, p.ld_stat_z, p.stat_z_dtype = ptr(stat_z, stat_z_off), ld_stat_z, dt(stat_z)
         p.stat_mean, p.stat_istd = ptr(stat_mean), ptr(stat_istd)
+    if bn is not None:
+        _fill(p.bn, count=float(bn["count"]), eps=bn.get("eps", 1e-3), momentum=bn.get("momentum", 0.99),
+              training=int(bn["training"]), moving_mean=ptr(bn.get("moving_mean"), bn.get("mm_off", 0)),
+              moving_var=ptr(bn.get("moving_var"), bn.get("mv_off", 0)), mean_out=ptr(bn["mean_out"]),
+              istd_out=ptr(bn["istd_out"]))
     p.split_k = split_k
     if addend is not None:
         p.addend, p.ld_add, p.addend_dtype = ptr(addend, addend_off), ld_add, dt(addend)
@@ -163,9 +171,12 @@ def embedding_bwd(ids, dout, dtable, N, T, P, padl, D, V, dtable_off=0):
 
 def bn_fwd(z, y, rows, C, col_sum, col_sumsq, count, gamma, beta, moving_mean, moving_var, mean_out, istd_out,
            training, row_mask=None, eps=1e-3, momentum=0.99, gamma_off=0, beta_off=0, mm_off=0, mv_off=0,
-           y_hi=None, y_lo=None, y_off=0, ld_y=0):
-    """y_off / ld_y: y as a column block of a wider [rows, ld_y] array (element offset of its first column)."""
+           y_hi=None, y_lo=None, y_off=0, ld_y=0, stats_final=False):
+    """y_off / ld_y: y as a column block of a wider [rows, ld_y] array (element offset of its first column).
+    stats_final: the product that formed z finished mean_out / istd_out and the moving statistics (gemm(..., bn=...)):
+    only the apply pass is launched."""
     p = L.struct("ns_bn_fwd_params")
+    p.stats_final = int(stats_final)
     if y_hi is not None:
         p.y_hi, p.y_lo = ptr(y_hi), ptr(y_lo)
     p.ld_y = ld_y
@@ -179,11 +190,14 @@ def bn_fwd(z, y, rows, C, col_sum, col_sumsq, count, gamma, beta, moving_mean, m
 
 
 def bn_bwd(dy, z, dpre, rows, C, mean, istd, gamma, dgamma, dbeta, dbias, work, count, act, row_mask=None,
-           gamma_off=0, dgamma_off=0, dbeta_off=0, dbias_off=0, sums=None, dy_off=0, ld_dy=0):
+           gamma_off=0, dgamma_off=0, dbeta_off=0, dbias_off=0, sums=None, dy_off=0, ld_dy=0, no_finalize=False):
     """sums = (sum dy, sum dy * xhat) per column as left by the product that formed dy (gemm(..., stat_z=...)).
-    dy_off / ld_dy: dy as a column block of a wider [rows, ld_dy] gradient."""
+    dy_off / ld_dy: dy as a column block of a wider [rows, ld_dy] gradient.
+    no_finalize: stop once dpre is written and return the parameter block; bn_bwd_finalize(block) adds dbias / dgamma /
+    dbeta later (on whatever stream is current then) - `work` and `sums` must be left alone until it has run."""
     p = L.struct("ns_bn_bwd_params")
     p.ld_dy = ld_dy
+    p.no_finalize = int(no_finalize)
     if sums is not None:
         p.sum_dy, p.sum_dyxh = ptr(sums[0]), ptr(sums[1])
     assert work.numel() >= 200 * C, "ns_bn_bwd: work needs 200 * C floats"
@@ -195,6 +209,12 @@ def bn_bwd(dy, z, dpre, rows, C, mean, istd, gamma, dgamma, dbeta, dbias, work, 
     if row_mask is not None:
         p.row_period, p.row_lo, p.row_hi = row_mask
     L.call("ns_bn_bwd", p, stream())
+    return p if no_finalize else None
+
+
+def bn_bwd_finalize(p):
+    """The dbias / dgamma / dbeta adds of a bn_bwd(..., no_finalize=True) call, from the block it returned."""
+    L.call("ns_bn_bwd_finalize", p, stream())
 
 
 _COLSUM_WORK = {}
