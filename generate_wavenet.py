@@ -6,7 +6,10 @@ The reference script builds WaveNetModel and needs a wavenet_params.json that th
 (generate_wavenet.py:21,51); here the network is wavenet.yaml's (+ --hparams; --gc_channels / --gc_cardinality / --gc_id
 for a speaker-conditioned checkpoint of train_wavenet.py --model wavenet, :214-231), restored from
 train_wavenet.py's model.ckpt-<step>.  --fast_generation true (default) at temperature 1.0 = the persistent incremental
-generator on the GPU (one workgroup per waveform; float64 softmax and inverse-CDF draw in the kernel).  Any other
+generator on the GPU (one workgroup per waveform; float64 softmax and inverse-CDF draw in the kernel).
+--lc_channels N --local_condition FILE.npy --lc_hold H draw from a locally conditioned checkpoint: the file is float
+[rows, N], row r conditions generated samples r * H .. r * H + H - 1 (a mel spectrogram: H = the hop), the seed in
+front takes row 0; this path is the incremental generator's alone.  Any other
 temperature, or --fast_generation false, takes the full-window path of generate_wavenet.py:104-142: predict_proba over the
 last receptive_field samples, temperature scaling and the draw on the host, including the reference's own consistency
 check at temperature 1.0 (:133-138, scaled == unscaled)."""
@@ -64,6 +67,24 @@ def main(args):
     if args.gc_channels is not None:                # generate_wavenet.py:221-231: the speaker whose voice is drawn
         hp.gc_channels, hp.gc_category_cardinality = args.gc_channels, args.gc_cardinality
         gc = np.asarray([args.gc_id])
+    lc = None
+    if args.lc_channels:
+        hp.lc_channels = args.lc_channels
+        if not args.local_condition:
+            raise ValueError("--lc_channels needs --local_condition FILE.npy")
+        if not (args.fast_generation and args.temperature == 1.0):
+            raise ValueError("A local condition is drawn from by the incremental generator only: --fast_generation true and "
+                             "--temperature 1.0 (predict_proba takes no local condition).")
+        lc = np.asarray(np.load(args.local_condition), np.float32)
+        if lc.ndim != 2 or lc.shape[1] != args.lc_channels:
+            raise ValueError("--local_condition holds %s, expected [rows, %d]" % (lc.shape, args.lc_channels))
+        if args.lc_hold < 1:
+            raise ValueError("--lc_hold must be at least 1 (generated samples per row of --local_condition), got %d" % args.lc_hold)
+        if lc.shape[0] * args.lc_hold < args.samples:
+            raise ValueError("--local_condition has %d rows of --lc_hold %d samples: fewer than --samples %d"
+                             % (lc.shape[0], args.lc_hold, args.samples))
+    elif args.local_condition:
+        raise ValueError("--local_condition needs --lc_channels N with N > 0: the checkpoint's local condition channels")
     full = bool(hp.use_biases or hp.scalar_input or hp.gc_channels or hp.lc_channels)
     net = create_model("wavenet" if full else "simple_wavenet", hp, device="cuda:0", dtype=args.precision)
     cond = dict(global_conditions=gc) if full else {}
@@ -83,6 +104,12 @@ def main(args):
         done = 0
         while done < args.samples:                  # in chunks, so that --save_every can write partial results
             n = min(args.samples - done, args.save_every or args.samples)
+            if lc is not None:
+                # row 0 belongs to the first generated sample, so this chunk's rf seed samples stand at done - rf .. done - 1
+                # of the condition's time axis (in front of it they take row 0); only the chunk's own rows go to the device
+                t0, H = done - rf, args.lc_hold
+                r0, r1 = max(0, t0) // H, (done + n - 1) // H
+                cond.update(local_conditions=lc[None, r0:r1 + 1], hold=H, t0=t0 - r0 * H)
             ids = net.generate(np.asarray(waveform[-rf:], np.int32), n, uniforms=rng.random((1, n)), **cond)
             waveform.extend(int(x) for x in ids[0, rf:].cpu().numpy())
             done += n
@@ -133,6 +160,9 @@ if __name__ == "__main__":
     parser.add_argument("--gc_channels", type=int, default=None)
     parser.add_argument("--gc_cardinality", type=int, default=None)
     parser.add_argument("--gc_id", type=int, default=None)
+    parser.add_argument("--lc_channels", type=int, default=None)
+    parser.add_argument("--local_condition", type=str, default=None, help="float [rows, lc_channels] .npy, row 0 at the first generated sample")
+    parser.add_argument("--lc_hold", type=int, default=1, help="generated samples per row of --local_condition")
     parser.add_argument("--hparams", default="")
     parser.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     parser.add_argument("--seed", type=int, default=0)

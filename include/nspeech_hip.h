@@ -875,9 +875,11 @@ typedef struct {
   const void* fgT; const void* deT;
   int engine;   /* with fgT / deT: 0 / 1 = single-wave VALU chain, 2 = MFMA chain + concurrent skip waves (R == Dc == 32) */
   /* The full WaveNetModel's incremental generator (neural_speech/models/wavenet.py:398-437, 487-557), all optional and
-   * fp32; with any of them the per-layer kernel runs (fgT / deT must be NULL):
+   * fp32; with any of them the per-layer kernel runs (fgT / deT = NULL) or, with fgT / deT and engine = 2, the MFMA
+   * chain's conditioned instantiation (engines 1 and 3 refuse them):
    *   cond [B, L, 2Dc]  added to a layer's [filter | gate] pre-activations: the global condition's 1x1 convolution
    *                     (:409-419) and filter_bias | gate_bias (:421-423), formed once per call by the caller;
+   *                     [B, cond_rows, L, 2Dc] when cond_rows > 1, see below;
    *   dense_bias [L, R] (:428-429);  skip_bias [S] = the sum of the layers' skip biases (:432-434, summed :543);
    *   post1_bias [S], post2_bias [Q] (:546-553). */
   const float* cond; const float* dense_bias; const float* skip_bias; const float* post1_bias; const float* post2_bias;
@@ -891,9 +893,20 @@ typedef struct {
    * call's own (ns_streams_concurrent) - the helper kernel is launched on it first; post_x[0] (int) is a status word
    * (non-zero after the call = a wait timed out, the samples are invalid).  S = 512, Q = 256, B * (1 + 4) <= the CUs. */
   void* post_x; void* helper_stream;   /* helper_stream: an ns_stream_t */
+  /* A condition that changes along the waveform (a local condition, which the reference's generator never built:
+   * wavenet.py:487).  cond_rows 0 or 1: cond is [B, L, 2Dc] as above.  cond_rows > 1: cond is [B, cond_rows, L, 2Dc],
+   * one row per cond_hold (>= 1) samples; cond_t0 is the position of ids[.., 0] on the condition's time axis (may be
+   * negative).  The step that reads ids[t-1], ids[t] and predicts ids[t+1] uses row max(0, t + cond_t0) / cond_hold -
+   * training's alignment, where the condition of network-input position m joins the pre-activations at m; the clamp
+   * lets a seed stand in front of row 0.  Rows up to that of t = total - 1 must exist: NS_ERR_BAD_ARG otherwise. */
+  int cond_rows, cond_hold; int64_t cond_t0;
 } ns_wavenet_generate_params;
 #define NS_WN_HELPERS 4
 size_t ns_wavenet_post_bytes(int B);
+/* 1 when the MFMA chain's LDS state (engine 2 / 3) for L layers of width R at S skip channels and Q classes passes the
+ * launcher's limit, else 0; cond != 0: the conditioned instantiation, which also keeps the condition row and the dense
+ * biases there (L * 384 bytes more).  A caller with conditions asks first and takes the per-layer kernel on 0. */
+int ns_wavenet_chain_fits(int L, int R, int S, int Q, int cond);
 int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t stream);
 
 /* ------------------------------------------------------------------ audio DSP (utils/audio.py)

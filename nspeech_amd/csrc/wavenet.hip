@@ -247,6 +247,12 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
   GenLayerW<W> wa, wbuf;
   for (int t = 1; t < p.total; ++t) {
     const bool emit = t + 1 >= p.n_seed && t + 1 < p.total;      // sample t+1 must be drawn
+    // the condition row of network-input position t (cond_rows > 1: one row per cond_hold samples from cond_t0 on)
+    const float* cond = p.cond;
+    if (cond) {
+      const long crow = p.cond_rows > 1 ? max(0L, (long)t + (long)p.cond_t0) / p.cond_hold : 0L;
+      cond += ((long)b * max(p.cond_rows, 1) + crow) * p.L * 2 * Dc;
+    }
     gen_load(wa, p, wb, 0, tid, emit);
     if (tid < R) {                                               // causal layer
       const int a = ids[t - 1], c = ids[t];
@@ -282,7 +288,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
       }
       __syncthreads();
       if (tid < 2 * Dc) {
-        float v = p.cond ? p.cond[((long)b * p.L + l) * 2 * Dc + tid] : 0.f;      // condition + filter | gate bias
+        float v = cond ? cond[(long)l * 2 * Dc + tid] : 0.f;                      // condition + filter | gate bias
         for (int i = 0; i < kzs; ++i) v += part[i * 2 * Dc + tid];
         z[tid] = v;
       }
@@ -386,9 +392,10 @@ __device__ __forceinline__ float lane_bcast(float v, int k) {
 // y[0..N) = act(sum_k x[k] * Wm[k*N + n]) for a bf16 [K, N] matrix streamed from L2 once: a thread owns 8 adjacent
 // columns (one 16-byte load per row) and the workgroup splits K, 8 rows in flight per thread; the partial sums meet
 // in LDS.  x, y and part are LDS; part needs (GEN_THREADS / (N/8)) * N floats.  N % 8 == 0, N/8 <= GEN_THREADS.
-template <int RIF = 8>      // weight rows in flight per thread (16 measured no faster for the post-processing products: 43.5 vs 43.2 us per sample)
+// bias (optional, fp32 [N] in global memory) is the first term of every sum.
+template <int RIF = 8, bool BIAS = false>      // weight rows in flight per thread (16 measured no faster for the post-processing products: 43.5 vs 43.2 us per sample)
 __device__ __forceinline__ void gen_matvec8(const bf16_t* Wm, int K, int N, const float* x, float* y, float* part, bool relu,
-                                            int tid) {
+                                            int tid, const float* bias = nullptr) {
   const int ncg = N >> 3, nks = GEN_THREADS / ncg;
   const int cg = tid % ncg, ks = tid / ncg;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -417,6 +424,7 @@ __device__ __forceinline__ void gen_matvec8(const bf16_t* Wm, int K, int N, cons
   __syncthreads();
   for (int n = tid; n < N; n += GEN_THREADS) {
     float v = 0.f;
+    if constexpr (BIAS) v = bias ? bias[n] : 0.f;
     for (int i = 0; i < nks; ++i) v += part[i * N + n];
     y[n] = relu ? fmaxf(v, 0.f) : v;
   }
@@ -654,6 +662,15 @@ __device__ __forceinline__ bf16x8 mf_bits(uint4 w) {
   return c.b;
 }
 
+// COND: the full model's terms (ns_wavenet_generate_params.cond .. post2_bias) ride on the chain.  The current
+// condition row and the dense biases stay in LDS as ctab [L][96] = per layer [cond filter 32 | cond gate 32 | dense
+// bias 32] in natural channel order; waves 1 - 7 rewrite the condition part in front of the barrier that opens a sample
+// whenever the sample's row differs from the last one's (the chain wave reads ctab only between that barrier and the
+// one that closes its layers, so no barrier is added), and the chain wave carries no row bookkeeping.  The gate lanes
+// 16 g + s read their channel's three values ahead of the layer's products: the two condition terms join zf / zg behind
+// the DPP gather, the dense bias goes back to lane 16 g on the row shifts that bring the gated outputs back.  COND =
+// false compiles to the kernel as it was.
+template <bool COND>
 __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p) {
   extern __shared__ float gsm[];
   constexpr int C = 32;
@@ -666,6 +683,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   float* red = lg + ((Q + 1) & ~1);        // [16]
   float* part = red + 16;                  // [GEN_THREADS * 8]
   double* ex = (double*)(part + GEN_THREADS * 8);   // [Q]
+  float* ctab = (float*)(ex + Q);          // COND: [L][3 C]
   __shared__ int dil[128];
   __shared__ long qoff[128];
   __shared__ int chain_pos;
@@ -680,6 +698,10 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
     long q = 0;
     for (int i = 0; i < L; ++i) { dil[i] = p.dilations[i]; qoff[i] = q; q += p.dilations[i]; }
   }
+  if constexpr (COND) {
+    for (int i = tid; i < L * C; i += GEN_THREADS)
+      ctab[(i / C) * 3 * C + 2 * C + i % C] = p.dense_bias ? p.dense_bias[i] : 0.f;
+  }
   __syncthreads();
   const int l15 = lane & 15, kq = lane >> 4;
   const bool afl = l15 == 0;               // lanes that carry row 0 of an A fragment
@@ -687,6 +709,11 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   // their own (one loop with a role branch inside made the allocator spill ~300 registers, and every scratch access
   // forces vmcnt(0) behind the prefetches); both loops execute the same sequence of workgroup barriers
   auto gen_post = [&](int t) -> bool {
+        // COND: the addresses of the post-processing products are formed per drawn sample - hoisted out of the sample loop
+        // (as in the unconditioned kernel) they sit in registers through the chain, which then has none left for its
+        // condition terms and spills
+        int tp = tid;
+        if constexpr (COND) asm volatile("" : "+v"(tp));
         for (int j = tid; j < S; j += GEN_THREADS) {
           float v = 0.f;
     #pragma unroll
@@ -712,8 +739,8 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
           if (tid < Q) lg[tid] = h1[tid] + h1[256 + tid];
           __syncthreads();
         } else {
-          gen_matvec8(wb + p.off_post1, S, S, h0, h1, part, true, tid);
-          gen_matvec8(wb + p.off_post2, S, Q, h1, lg, part, false, tid);
+          gen_matvec8<8, COND>(wb + p.off_post1, S, S, h0, h1, part, true, tp, p.post1_bias);
+          gen_matvec8<8, COND>(wb + p.off_post2, S, Q, h1, lg, part, false, tp, p.post2_bias);
         }
         float m = -3.0e38f;
         for (int j = tid; j < Q; j += GEN_THREADS) m = fmaxf(m, lg[j]);
@@ -745,7 +772,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
           const unsigned long long bal = __ballot(tid < Q && off + sc <= u);
           if (lane == 0) wcnt[wave] = __popcll(bal);
           if (p.probs && t + 2 == p.total && tid < Q)        // the distribution of the LAST drawn sample
-            p.probs[(long)b * Q + tid] = (float)(v / se);
+            p.probs[(long)b * Q + tp] = (float)(v / se);
           __syncthreads();
           if (tid == 0) {
             int cnt = 0;
@@ -817,6 +844,9 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
 #define MF_LOAD(W_, l_) do { MF_LOAD_FG(W_, l_); MF_LOAD_DE(W_, l_); MF_LOAD_RING(W_, l_); } while (0)
 #define MF_DECL(W_) uint4 W_##_fg[8], W_##_de[2]; float4 W_##_r0, W_##_r1
       MF_DECL(w0); MF_DECL(w1);
+      // COND: this gate lane's channel in a layer's ctab line (lanes 16 g + 8 .. 15 read the values of s & 7: unused)
+      const float* ctl = nullptr;
+      if constexpr (COND) ctl = ctab + 4 * kq + (l15 & 3) + 16 * ((l15 >> 2) & 1);
       MF_LOAD(w0, 0);
       if (L > 1) MF_LOAD(w1, 1);
 #define MF_LAYER(l_, W_)                                                                                                 \
@@ -824,6 +854,8 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
     const int l = (l_);                                                                                                  \
     const bf16x8 b_cur = mf_pack(make_float4(xv[0], xv[1], xv[2], xv[3]), make_float4(xv[4], xv[5], xv[6], xv[7]));        \
     const bf16x8 b_old = mf_pack(W_##_r0, W_##_r1);                                                                       \
+    float cf, cg, cd;                                                                                                     \
+    if constexpr (COND) { cf = ctl[l * 3 * C]; cg = ctl[l * 3 * C + C]; cd = ctl[l * 3 * C + 2 * C]; }                      \
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;                                             \
     acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mf_bits(W_##_fg[0]), b_old, acc0, 0, 0, 0);                            \
     acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mf_bits(W_##_fg[1]), b_old, acc1, 0, 0, 0);                            \
@@ -848,6 +880,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
     zf = MF_DPP_KEEP(zf, acc1[1], 0x115); zg = MF_DPP_KEEP(zg, acc3[1], 0x115);                                           \
     zf = MF_DPP_KEEP(zf, acc1[2], 0x116); zg = MF_DPP_KEEP(zg, acc3[2], 0x116);                                           \
     zf = MF_DPP_KEEP(zf, acc1[3], 0x117); zg = MF_DPP_KEEP(zg, acc3[3], 0x117);                                           \
+    if constexpr (COND) { zf += cf; zg += cg; }           /* condition + filter | gate bias of this lane's channel         */ \
     const float og = tanhf_(zf) * sigmoidf_(zg);          /* lane 16 g + s: slot s = channel 4 g + (s & 3) + 16 (s >> 2) */ \
     /* for the skip waves (natural channel order); LDS is in order inside a wave: the counter lands behind the data */    \
     if (emit && l15 < 8) outs[l * C + 4 * kq + (l15 & 3) + 16 * (l15 >> 2)] = og;                                         \
@@ -868,6 +901,11 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
     }                                                                                                                     \
     xv[0] += d0[0]; xv[1] += d0[1]; xv[2] += d0[2]; xv[3] += d0[3];                                                       \
     xv[4] += d1[0]; xv[5] += d1[1]; xv[6] += d1[2]; xv[7] += d1[3];                                                       \
+    if constexpr (COND) { /* dense bias: slot j of lane 16 g sits in lane 16 g + j (the other lanes' sums are unused) */   \
+      xv[0] += cd;                       xv[1] += MF_DPP_ZERO(cd, 0x101); xv[2] += MF_DPP_ZERO(cd, 0x102);                   \
+      xv[3] += MF_DPP_ZERO(cd, 0x103); xv[4] += MF_DPP_ZERO(cd, 0x104); xv[5] += MF_DPP_ZERO(cd, 0x105);                   \
+      xv[6] += MF_DPP_ZERO(cd, 0x106); xv[7] += MF_DPP_ZERO(cd, 0x107);                                                     \
+    }                                                                                                                     \
     /* (the ring line issued at the top of the layer as well measured slower: 43.2 against 40.8 us per drawn sample)  */  \
     if (l + MF_AHEAD < L) { MF_LOAD_DE(W_, l + MF_AHEAD); MF_LOAD_RING(W_, l + MF_AHEAD); }                              \
   } while (0)
@@ -887,8 +925,19 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
       if (!gen_post(t)) return;                              // (engine 3: a hand-over timed out)
     }
   } else {
+    // COND: the condition row in ctab is `crow`, and the first position (on the condition's time axis) of the next row
+    long crow = -1, cnext = 0;
     for (int t = 1; t < p.total; ++t) {
       const bool emit = t + 1 >= p.n_seed && t + 1 < p.total;
+      if constexpr (COND) {
+        if (crow < 0 || (long)t + (long)p.cond_t0 >= cnext) {
+          const bool rows = p.cond && p.cond_rows > 1;
+          crow = rows ? max(0L, (long)t + (long)p.cond_t0) / p.cond_hold : 0L;       // (one division per row, not per sample)
+          cnext = rows ? (crow + 1) * p.cond_hold : 0x7fffffffffffffffL;
+          const float* cr = p.cond ? p.cond + ((long)b * max(p.cond_rows, 1) + crow) * L * 2 * C : nullptr;
+          for (int i = tid - 64; i < L * 2 * C; i += GEN_THREADS - 64) ctab[(i / (2 * C)) * 3 * C + i % (2 * C)] = cr ? cr[i] : 0.f;
+        }
+      }
       __syncthreads();
       if (emit) {
       // ================================================================ skip waves
@@ -926,6 +975,12 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
     if (l + 3 < L) SK_LOAD(W_, l + 3);                                                                                \
   } while (0)
       float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
+      if constexpr (COND) {                  // the skip bias is the first term of wave 1's partial sums
+        if (wave == 1 && colok && p.skip_bias) {
+          const float* sb = p.skip_bias + 8 * lane;
+          a0 = sb[0]; a1 = sb[1]; a2 = sb[2]; a3 = sb[3]; a4 = sb[4]; a5 = sb[5]; a6 = sb[6]; a7 = sb[7];
+        }
+      }
       uint4 s0[5], s1[5], s2[5];
       SK_LOAD(s0, 0);
       if (L > 1) SK_LOAD(s1, 1);
@@ -951,6 +1006,15 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   }
 }
 
+static size_t wn_chain_lds_bytes(int L, int R, int S, int Q, int cond) {
+  const size_t lds2 = sizeof(float) * ((size_t)L * R + 2 * S + ((Q + 1) & ~1) + 16 + GEN_THREADS * 8) + sizeof(double) * Q;
+  return lds2 + sizeof(float) * 32 + (cond ? sizeof(float) * (size_t)L * 96 : 0);      // + the gather line, + ctab [L][3 * 32]
+}
+constexpr size_t WN_CHAIN_LDS_MAX = 60 * 1024;
+extern "C" int ns_wavenet_chain_fits(int L, int R, int S, int Q, int cond) {
+  return L > 0 && R > 0 && S > 0 && Q > 0 && wn_chain_lds_bytes(L, R, S, Q, cond) <= WN_CHAIN_LDS_MAX;
+}
+
 extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t s) {
   NS_CHECK_ARG(p && p->weights && p->ids && p->queues && p->uniform && p->dilations, "ns_wavenet_generate: null");
   NS_CHECK_ARG(p->B > 0 && p->n_seed >= 2 && p->total > p->n_seed && p->L > 0 && p->L <= 128, "ns_wavenet_generate: bad sizes");
@@ -960,7 +1024,16 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
   const size_t lds = sizeof(float) * (2 * p->R + 3 * p->Dc + GEN_THREADS + 2 * p->S + ((p->Q + 1) & ~1)) + sizeof(double) * p->Q;
   NS_CHECK_ARG(lds <= 60 * 1024, "ns_wavenet_generate: state does not fit in LDS");
   const bool full = p->cond || p->dense_bias || p->skip_bias || p->post1_bias || p->post2_bias;
-  NS_CHECK_ARG(!full || (!p->fgT && !p->deT), "ns_wavenet_generate: conditions / biases run on the per-layer kernel (fgT, deT = NULL)");
+  NS_CHECK_ARG(!full || (!p->fgT && !p->deT) || p->engine == 2,
+               "ns_wavenet_generate: conditions / biases run on the per-layer kernel (fgT, deT = NULL) or on the MFMA chain (engine 2)");
+  if (p->cond && p->cond_rows > 1) {       // one condition row per cond_hold samples: every row a step reads must exist
+    NS_CHECK_ARG(p->cond_hold >= 1, "ns_wavenet_generate: cond_hold must be at least 1 with cond_rows > 1");
+    const int64_t lim = (int64_t)1 << 40;
+    NS_CHECK_ARG(p->cond_t0 > -lim && p->cond_t0 < lim, "ns_wavenet_generate: cond_t0 out of range");
+    const int64_t last = ((int64_t)p->total - 1 + p->cond_t0 > 0 ? (int64_t)p->total - 1 + p->cond_t0 : 0) / p->cond_hold;
+    NS_CHECK_ARG(last < p->cond_rows, "ns_wavenet_generate: position %lld of the condition needs row %lld, cond has %d rows of %d samples",
+                 (long long)((int64_t)p->total - 1 + p->cond_t0), (long long)last, p->cond_rows, p->cond_hold);
+  }
   if (p->fgT && p->deT) {
     NS_CHECK_ARG(p->w_dtype == NS_BF16 && p->R == p->Dc && (p->R == 32 || p->R == 16) && p->S % 8 == 0 && p->Q % 8 == 0 && p->S / 8 <= GEN_THREADS &&
                      GEN_THREADS % (p->S / 8) == 0 && GEN_THREADS % (p->Q / 8) == 0,
@@ -987,8 +1060,15 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
         hipLaunchKernelGGL(wn_post_helper_kernel, dim3(p->B * NS_WN_HELPERS), dim3(512), 0, (hipStream_t)p->helper_stream, *p);
         NS_CHECK_LAUNCH("wavenet_post_helper");
       }
-      const size_t lds3 = lds2 + sizeof(float) * 32;
-      hipLaunchKernelGGL(wn_generate_mfma_kernel, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p);
+      const size_t lds3 = wn_chain_lds_bytes(p->L, p->R, p->S, p->Q, 0);
+      if (full) {                            // + the condition row and the dense biases
+        const size_t lds4 = wn_chain_lds_bytes(p->L, p->R, p->S, p->Q, 1);
+        NS_CHECK_ARG(lds4 <= WN_CHAIN_LDS_MAX, "ns_wavenet_generate: state and condition row do not fit in LDS (ns_wavenet_chain_fits)");
+        hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p);
+        NS_CHECK_LAUNCH("wavenet_generate_mfma_cond");
+        return NS_OK;
+      }
+      hipLaunchKernelGGL(wn_generate_mfma_kernel<false>, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p);
       NS_CHECK_LAUNCH("wavenet_generate_mfma");
       return NS_OK;
     }

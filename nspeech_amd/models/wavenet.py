@@ -332,11 +332,12 @@ class SimpleWaveNet(object):
         ids = torch.from_numpy(mu_law_encode(audio, self.Q)).to(self.device)
         return self.initialize_ids(ids, audio=audio, global_conditions=global_conditions, local_conditions=local_conditions)
 
-    def _condition_rows(self, N, T0, global_conditions, local_conditions):
+    def _condition_rows(self, N, T0, global_conditions, local_conditions, local=True):
         """The conditions per network-input row, in the compute dtype (wavenet.py:573-608 _embed_gc; :324-340).
         Global: [N] category ids (gc_category_cardinality) or [N, gc_channels] vectors, the same for every row of an
         item.  Local: [N, 1, lc] (every row) or [N, T0, lc] (row t's own; oracle/wavenet_oracle.py: network_full says
-        how that relates to the reference's graph)."""
+        how that relates to the reference's graph).  local=False: the global rows alone (the generator forms its local term
+        per condition row, _generator_terms)."""
         dev = self.device
         gcrows = lcrows = None
         self._gc_ids = None
@@ -360,7 +361,7 @@ class SimpleWaveNet(object):
             ops.copy3d(h, gcrows, N, T0, self.gc, (self.gc, 0), (T0 * self.gc, self.gc))
         else:
             assert global_conditions is None, "gc_channels is 0: no global condition expected"
-        if self.lc:
+        if self.lc and local:
             assert local_conditions is not None, "lc_channels is set: initialize needs local_conditions"
             c = np.asarray(local_conditions, np.float32)
             assert c.ndim == 3 and c.shape[0] == N and c.shape[2] == self.lc and c.shape[1] in (1, T0), \
@@ -371,7 +372,7 @@ class SimpleWaveNet(object):
                 ops.copy3d(src, lcrows, N, T0, self.lc, (self.lc, 0), (T0 * self.lc, self.lc))
             else:
                 ops.copy3d(src, lcrows, 1, N * T0, self.lc, (0, self.lc), (0, self.lc))
-        else:
+        elif local:
             assert local_conditions is None, "lc_channels is 0: no local condition expected"
         return gcrows, lcrows
 
@@ -581,19 +582,43 @@ class SimpleWaveNet(object):
         ops.wavenet_softmax(logits, self.Q, 1, self.Q, probs, logits_off=(ow - 1) * self.Q)
         return probs
 
-    def generate(self, seed_ids, n_samples, uniforms=None, seed=0, exact=None, fast=True, engine=None, global_conditions=None):
+    def generate(self, seed_ids, n_samples, uniforms=None, seed=0, exact=None, fast=True, engine=None, global_conditions=None,
+                 local_conditions=None, hold=1, t0=0):
         """Incremental generation (generate_wavenet.py:56-142): seed_ids int [B, n_seed] (or [n_seed]) of mu-law codes,
         n_seed >= receptive field; returns int32 [B, n_seed + n_samples].  uniforms [B, n_samples] in [0,1) drive the
         categorical draws (default: numpy Generator(seed)).  Weights: the fp32 master copy when exact (default in fp32
-        mode), else the bf16 shadow (half the bytes streamed per sample)."""
+        mode), else the bf16 shadow (half the bytes streamed per sample).
+        local_conditions (lc_channels > 0; the reference's generator has none, wavenet.py:487): float [B, rows,
+        lc_channels], one row per `hold` samples; t0 is the position of seed_ids[.., 0] on the condition's time axis, so
+        row r conditions positions r * hold - t0 .. r * hold - t0 + hold - 1 of the returned array, and positions in
+        front of row 0 (t0 < 0: a seed) take row 0.  The condition of a position enters where training puts it
+        (_forward: lc_rows row m joins the pre-activations at network-input position m).  Rows are never repeated past
+        the end: too few for n_seed + n_samples positions is a ValueError.
+        A model with conditions or biases runs on the MFMA chain (last_engine 2) where the unconditioned one does - bf16
+        weights, R == Dc == 32 - and on the per-layer kernel (last_engine 0) elsewhere; engines 1 and 3 take neither."""
         if self.scalar_input:
             raise NotImplementedError("Incremental generation does not support scalar input yet.")       # wavenet.py:643-645
-        if self.lc:
-            raise NotImplementedError("Incremental generation takes no local condition (wavenet.py:487)")
+        if self.lc and local_conditions is None:
+            raise NotImplementedError("lc_channels is set: generate(..., local_conditions=[B, rows, lc_channels], hold=, t0=) "
+                                      "- without its condition a locally conditioned model draws nothing (the reference "
+                                      "builds no such path, wavenet.py:487)")
+        assert self.lc or local_conditions is None, "lc_channels is 0: no local condition expected"
         seed_ids = np.atleast_2d(np.asarray(seed_ids, np.int32))
         B, n_seed = seed_ids.shape
         assert n_seed >= self.rf, "seed shorter than the receptive field (%d)" % self.rf
         total = n_seed + int(n_samples)
+        lc = None
+        if self.lc:
+            lc = np.asarray(local_conditions, np.float32)
+            if lc.ndim != 3 or lc.shape[0] != B or lc.shape[2] != self.lc:
+                raise ValueError("local_conditions %s: expected [%d, rows, %d]" % (lc.shape, B, self.lc))
+            hold, t0 = int(hold), int(t0)
+            if hold < 1:
+                raise ValueError("hold must be at least 1")
+            need = max(0, total - 1 + t0) // hold + 1
+            if lc.shape[1] < need:
+                raise ValueError("local_conditions has %d rows of %d samples: %d positions from t0 = %d need %d"
+                                 % (lc.shape[1], hold, total, t0, need))
         if uniforms is None:
             uniforms = np.random.default_rng(seed).random((B, n_samples))
         uniforms = np.atleast_2d(np.asarray(uniforms, np.float32))
@@ -612,12 +637,24 @@ class SimpleWaveNet(object):
                     dense_in_layer=self._o("dense0") - self._o("fg0"), skip=self._o("skip"), post1=self._o("post1"),
                     post2=self._o("post2"))
         self.last_probs = torch.zeros(B * self.Q, dtype=torch.float32, device=dev)
-        extra = self._generator_terms(B, W, global_conditions) if self.full else {}
-        if extra:
-            fast = False            # conditions / biases: the per-layer kernel
+        extra = self._generator_terms(B, W, global_conditions, lc) if self.full else {}
+        if lc is not None:          # (one row needs no row arithmetic: cond is [B, L, 2Dc] then)
+            extra.update(cond_rows=lc.shape[1], cond_hold=hold, cond_t0=t0)
+        if extra and engine in (1, 3):
+            raise ValueError("engine %d takes no conditions or biases: engine 2 (the MFMA chain) or fast=False" % engine)
         fgT = deT = None
         ok = self.S % 8 == 0 and self.Q % 8 == 0 and 512 % (self.S // 8) == 0 and 512 % (self.Q // 8) == 0
-        if fast and not exact and self.R == self.Dc and self.R in (16, 32) and ok:
+        shadows = fast and not exact and self.R == self.Dc and self.R in (16, 32) and ok
+        if engine is None:          # MFMA chain + concurrent skip waves at the shipped widths, else the single-wave VALU chain
+            engine = 2 if (shadows and self.R == 32 and self.S <= 512) else 1
+            # conditions / biases off the chain's widths, or with more layers than its LDS holds a condition row for: the
+            # per-layer kernel, as before the chain took them
+            if extra and (engine == 1 or not ops.wavenet_chain_fits(self.L, self.R, self.S, self.Q, True)):
+                shadows, engine = False, 0
+            if not extra and engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
+                    and self._helper(dev) is not None:
+                engine = 3          # + the post-processing products on four helper workgroups per waveform (weights in registers)
+        if shadows:
             # column-major bf16 shadows of the layer kernels for the single-wave chain (a lane loads its whole column)
             R, Dc = self.R, self.Dc
             fg = torch.stack([self.flat_p[self._o("fg%d" % l):self._o("fg%d" % l) + 2 * R * 2 * Dc].view(2 * R, 2 * Dc).t()
@@ -625,12 +662,9 @@ class SimpleWaveNet(object):
             de = torch.stack([self.flat_p[self._o("dense%d" % l):self._o("dense%d" % l) + Dc * R].view(Dc, R).t()
                               for l in range(self.L)])
             fgT, deT = fg.contiguous().to(torch.bfloat16), de.contiguous().to(torch.bfloat16)
-        if engine is None:          # MFMA chain + concurrent skip waves at the shipped widths, else the single-wave VALU chain
-            engine = 2 if (fgT is not None and self.R == 32 and self.S <= 512) else 1
-            if engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
-                    and self._helper(dev) is not None:
-                engine = 3          # + the post-processing products on four helper workgroups per waveform (weights in registers)
         if engine in (2, 3):
+            if fgT is None:
+                raise ValueError("engine %d needs the bf16 shadows: fast=True, exact=False, R == Dc in (16, 32)" % engine)
             # the MFMA chain keeps the activations in fragment layout between layers: operand slot 8 g + j of a
             # 32-wide K block holds channel 4 g + (j & 3) + 16 (j >> 2) (wavenet.hip, wn_generate_mfma_kernel)
             perm = torch.tensor([4 * (i // 8) + (i % 4) + 16 * ((i % 8) // 4) for i in range(32)], device=dev)
@@ -649,7 +683,7 @@ class SimpleWaveNet(object):
                 raise RuntimeError("ns_wavenet_generate: a hand-over between the chain and its helper workgroups timed out "
                                    "(their workgroups were not resident together?) - the samples are invalid; engine=2 "
                                    "runs without helpers")
-        self.last_engine = engine
+        self.last_engine = engine if fgT is not None else 0
         self._gen_keep = (fgT, deT, un, queues, dil, extra)  # keep the operands alive until the stream has used them
         return ids
 
@@ -661,17 +695,39 @@ class SimpleWaveNet(object):
             self._helper_stream = s if ops.streams_concurrent(torch.cuda.current_stream(dev), s) else False
         return self._helper_stream or None
 
-    def _generator_terms(self, B, W, global_conditions):
+    def _generator_terms(self, B, W, global_conditions, local_conditions=None):
         """What the full model's incremental generator adds per layer (wavenet.py:398-437), formed once per call:
-        cond [B, L, 2Dc] = h . [gc_filter | gc_gate] + [filter_bias | gate_bias], and the other biases gathered."""
+        cond [B, L, 2Dc] = h . [gc_filter | gc_gate] + [filter_bias | gate_bias], and the other biases gathered.
+        local_conditions float32 [B, rows, lc]: cond is [B, rows, L, 2Dc] - the terms above on every row, plus row r's own
+        c[b, r] . [lc_filter | lc_gate], one accumulated product per layer in the weights' dtype."""
         L, Dc, R, S = self.L, self.Dc, self.R, self.S
         f32 = torch.float32
         out = {}
+        if local_conditions is not None:
+            rows = local_conditions.shape[1]
+            cond = self._buf("gen_cond_rows", B * rows * L * 2 * Dc, f32)
+            base = None
+            if self.gc or self.use_biases:
+                base = self._generator_terms(B, W, global_conditions)
+                out.update(base)
+                ops.copy3d(base["cond"], cond, B, rows, L * 2 * Dc, (L * 2 * Dc, 0), (rows * L * 2 * Dc, L * 2 * Dc))
+            else:
+                assert global_conditions is None, "gc_channels is 0: no global condition expected"
+                ops.zero(cond)
+            src = torch.from_numpy(np.ascontiguousarray(local_conditions)).to(self.device).view(-1)
+            c = self._buf("gen_lc", B * rows * self.lc, W.dtype)
+            ops.copy3d(src, c, 1, 1, B * rows * self.lc, (0, 0), (0, 0))
+            ops.F32_PASSES = self.passes
+            for l in range(L):
+                ops.gemm(c, W, cond, B * rows, 2 * Dc, self.lc, self.lc, 2 * Dc, L * 2 * Dc, b_mode=1, b_off=self._o("lc%d" % l),
+                         c_off=l * 2 * Dc, accumulate=1)
+            out["cond"] = cond
+            return out
         if self.gc or self.use_biases:
             cond = self._buf("gen_cond", B * L * 2 * Dc, f32)
             ops.zero(cond)
             if self.gc:
-                gcrows, _ = self._condition_rows(B, 1, global_conditions, None)     # [B, gc] in the compute dtype
+                gcrows, _ = self._condition_rows(B, 1, global_conditions, None, local=False)     # [B, gc] in the compute dtype
                 h = gcrows
                 if h.dtype != W.dtype:
                     h = self._buf("gen_h", B * self.gc, W.dtype)
