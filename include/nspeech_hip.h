@@ -834,13 +834,31 @@ typedef struct {
 } ns_wavenet_input_params;
 int ns_wavenet_input(const ns_wavenet_input_params* p, ns_stream_t stream);
 /* Gated unit (wavenet_simple.py:325): z fp32 [rows, 2C] = [filter | gate]; forward out = tanh * sigmoid into
- * out[row * ld_out + c] (dtype); with dout != NULL backward: dz (dtype) [rows, 2C].  Rows with t < start give 0. */
+ * out[row * ld_out + c] (dtype); with dout != NULL backward: dz (dtype) [rows, 2C].  Rows with t < start give 0.
+ * cond (optional, fp32 [N * cond_rows, ld_cond], ld_cond >= 2C, N = rows / T): a held condition term, one row per
+ * cond_hold (>= 1) positions.  Position t of item n reads row r = min(cond_rows - 1, max(0, t + cond_t0[n]) / cond_hold)
+ * - the generator's alignment (ns_wavenet_generate_params below) - and cond[(n * cond_rows + r) * ld_cond + c] joins the
+ * filter pre-activation, column C + c of the same row the gate's, forward and backward alike (the backward pass forms
+ * tanh and sigmoid from z again).  cond_t0: device array [N], NULL = all zero.  Both clamps keep every read inside
+ * cond; all-zero fields are the call without a condition, which runs the kernel it always ran. */
 typedef struct {
   const float* z; int rows, C, T, start;
   void* out; int64_t ld_out; int dtype;
   const void* dout; int64_t ld_dout; void* dz;
+  const float* cond; int64_t ld_cond; int cond_rows, cond_hold; const int* cond_t0;
 } ns_wavenet_gate_params;
 int ns_wavenet_gate(const ns_wavenet_gate_params* p, ns_stream_t stream);
+/* The held condition's gradient: out fp32 [N * cond_rows, ld_out] (ld_out >= 2C), out[n, r, :] = the sum of the rows
+ * dz[n * T + t, :] (dtype fp32 or bf16, [N * T, 2C]) over the positions t whose condition row - the formula of
+ * ns_wavenet_gate - is r: one contiguous range per row, row 0 with the clamped positions in front of it, the last row
+ * with whatever follows.  Rows without a position are written as zeros.  No atomics, a fixed order of summation: the
+ * same bits on every run.  cond_t0: device array [N], NULL = all zero. */
+typedef struct {
+  const void* dz; int dtype; int N, T, C;
+  float* out; int64_t ld_out;
+  int cond_rows, cond_hold; const int* cond_t0;
+} ns_wavenet_hold_sum_params;
+int ns_wavenet_hold_sum(const ns_wavenet_hold_sum_params* p, ns_stream_t stream);
 /* tf.nn.softmax_cross_entropy_with_logits + reduce_mean (wavenet_simple.py:479-502) against integer targets:
  * loss_acc[0] += scale * sum_rows (logsumexp - logit[target]); dlogits (optional) = scale * (softmax - onehot). */
 typedef struct {

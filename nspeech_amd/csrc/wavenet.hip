@@ -5,6 +5,7 @@
 // never read by a valid output.
 //   ns_wavenet_input      one-hot causal layer as two table look-ups           (wavenet_simple.py:246-252, 385-397)
 //   ns_wavenet_gate       tanh(filter) * sigmoid(gate) and its gradient         (:325)
+//   ns_wavenet_hold_sum   gradient of a condition term held over several positions
 //   ns_wavenet_softmax    float64 softmax of logit rows (predict_proba)                  (:436-453)
 //   ns_wavenet_softmax_ce mean softmax cross-entropy against integer targets    (:479-502) and d/dlogits
 //   ns_wavenet_generate   incremental sample-by-sample generation (persistent)  (generate_wavenet.py:56-142)
@@ -87,14 +88,32 @@ extern "C" int ns_wavenet_input(const ns_wavenet_input_params* p, ns_stream_t s)
 // z [rows, 2C] fp32 = [filter | gate] pre-activations.  forward: out[rows, C] (ld_out) = tanh(zf) * sigmoid(zg);
 // backward (dout given): dz[rows, 2C] = [dout * sg * (1 - th^2) | dout * th * sg * (1 - sg)].
 // Rows with t < start (t = row % T) are written as zero so that later GEMMs over the whole buffer stay finite.
-template <typename T, typename TD>
+// COND: a held condition term joins both pre-activations (nspeech_hip.h); its own instantiation, so that the call
+// without a condition keeps the instructions it had.
+
+// condition row of position t of item n: clamped at both ends, so no (t0, rows) can lead a read outside cond
+// (the position on the condition's axis is brought into an int first, so the division is a 32-bit one: past 2^31 the
+// upper clamp decides anyway)
+__device__ __forceinline__ int wn_hold_row(int t, int t0, int hold, int cond_rows) {
+  const int s = (int)min(max((long)t + (long)t0, 0L), 0x7fffffffL);
+  return min(cond_rows - 1, s / hold);
+}
+
+template <typename T, typename TD, bool COND>
 __global__ void wn_gate_kernel(ns_wavenet_gate_params p) {
   const long total = (long)p.rows * p.C;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int c = i % p.C;
     const long row = i / p.C;
     const bool valid = (row % p.T) >= p.start;
-    const float zf = p.z[row * 2 * p.C + c], zg = p.z[row * 2 * p.C + p.C + c];
+    float zf = p.z[row * 2 * p.C + c], zg = p.z[row * 2 * p.C + p.C + c];
+    if (COND) {
+      const long n = row / p.T;
+      const int r = wn_hold_row((int)(row - n * p.T), p.cond_t0 ? p.cond_t0[n] : 0, p.cond_hold, p.cond_rows);
+      const float* cr = p.cond + (n * p.cond_rows + r) * p.ld_cond;
+      zf += cr[c];
+      zg += cr[p.C + c];
+    }
     const float th = tanhf(zf), sg = 1.f / (1.f + expf(-zg));
     if (p.dout) {
       const float g = valid ? ldf((const TD*)p.dout + row * p.ld_dout + c) : 0.f;
@@ -108,18 +127,87 @@ __global__ void wn_gate_kernel(ns_wavenet_gate_params p) {
 extern "C" int ns_wavenet_gate(const ns_wavenet_gate_params* p, ns_stream_t s) {
   NS_CHECK_ARG(p && p->z && p->rows > 0 && p->C > 0 && p->T > 0, "ns_wavenet_gate: bad arguments");
   NS_CHECK_ARG(p->dtype == NS_F32 || p->dtype == NS_BF16, "ns_wavenet_gate: bad dtype");
+  if (p->cond) {
+    NS_CHECK_ARG(p->cond_hold >= 1, "ns_wavenet_gate: cond_hold %d: a condition row holds for at least one position", p->cond_hold);
+    NS_CHECK_ARG(p->cond_rows >= 1, "ns_wavenet_gate: cond_rows %d: a condition has at least one row", p->cond_rows);
+    NS_CHECK_ARG(p->ld_cond >= 2 * (int64_t)p->C, "ns_wavenet_gate: ld_cond %lld is less than 2C = %d", (long long)p->ld_cond, 2 * p->C);
+    NS_CHECK_ARG(p->rows % p->T == 0, "ns_wavenet_gate: a condition needs whole items (rows %d, T %d)", p->rows, p->T);
+  }
+  if (p->dout) NS_CHECK_ARG(p->dz, "ns_wavenet_gate: backward needs dz");
+  else NS_CHECK_ARG(p->out, "ns_wavenet_gate: forward needs out");
   const long total = (long)p->rows * p->C;
   const int grid = (int)min((long)16384, (total + 255) / 256);
-  if (p->dout) {
-    NS_CHECK_ARG(p->dz, "ns_wavenet_gate: backward needs dz");
-    if (p->dtype == NS_BF16) hipLaunchKernelGGL((wn_gate_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
-    else hipLaunchKernelGGL((wn_gate_kernel<float, float>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
+  if (p->cond) {
+    if (p->dtype == NS_BF16) hipLaunchKernelGGL((wn_gate_kernel<bf16_t, bf16_t, true>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
+    else hipLaunchKernelGGL((wn_gate_kernel<float, float, true>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
   } else {
-    NS_CHECK_ARG(p->out, "ns_wavenet_gate: forward needs out");
-    if (p->dtype == NS_BF16) hipLaunchKernelGGL((wn_gate_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
-    else hipLaunchKernelGGL((wn_gate_kernel<float, float>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
+    if (p->dtype == NS_BF16) hipLaunchKernelGGL((wn_gate_kernel<bf16_t, bf16_t, false>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
+    else hipLaunchKernelGGL((wn_gate_kernel<float, float, false>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
   }
   NS_CHECK_LAUNCH("wavenet_gate");
+  return NS_OK;
+}
+
+// ------------------------------------------------------------------ gradient of a held condition term
+// out[n, r, :] = sum of dz[n * T + t, :] over the positions t of condition row r - a contiguous range [lo, hi) known in
+// closed form.  One workgroup per output row: lanes along the 2C columns (a wave reads whole dz rows), the threads left
+// over as parallel slices of the range; the slices' partial sums meet in LDS and are added in slice order, so the result
+// does not depend on timing.  An empty range stores zeros.
+constexpr int HS_THREADS = 256;
+template <typename TD>
+__global__ __launch_bounds__(HS_THREADS) void wn_hold_sum_kernel(ns_wavenet_hold_sum_params p) {
+  __shared__ float part[HS_THREADS];
+  const int n = blockIdx.x / p.cond_rows, r = blockIdx.x % p.cond_rows;
+  const int W = 2 * p.C;
+  const int wt = min(W, HS_THREADS);                    // columns in flight at once
+  const int slices = HS_THREADS / wt;
+  const int col = threadIdx.x % wt, slice = threadIdx.x / wt;
+  const long t0 = p.cond_t0 ? p.cond_t0[n] : 0;
+  long lo = r == 0 ? 0 : (long)r * p.cond_hold - t0;
+  long hi = r == p.cond_rows - 1 ? (long)p.T : ((long)r + 1) * p.cond_hold - t0;
+  lo = min(max(lo, 0L), (long)p.T);
+  hi = min(max(hi, 0L), (long)p.T);
+  const TD* src = (const TD*)p.dz + (long)n * p.T * W;
+  float* dst = p.out + ((long)n * p.cond_rows + r) * p.ld_out;
+  for (int cb = 0; cb < W; cb += wt) {                  // uniform trip count: the barriers below are safe
+    const int c = cb + col;
+    float acc = 0.f;
+    if (slice < slices && c < W) {
+      // four independent partial sums: the loads of a slice do not wait for one another's adds
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      const TD* q = src + c;
+      const long s = slices;
+      long t = lo + slice;
+      for (; t + 3 * s < hi; t += 4 * s) {
+        a0 += ldf(q + t * W);
+        a1 += ldf(q + (t + s) * W);
+        a2 += ldf(q + (t + 2 * s) * W);
+        a3 += ldf(q + (t + 3 * s) * W);
+      }
+      for (; t < hi; t += s) a0 += ldf(q + t * W);
+      acc = (a0 + a1) + (a2 + a3);
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    if (slice == 0 && c < W) {
+      float v = part[col];
+      for (int k = 1; k < slices; ++k) v += part[k * wt + col];
+      dst[c] = v;
+    }
+    __syncthreads();
+  }
+}
+extern "C" int ns_wavenet_hold_sum(const ns_wavenet_hold_sum_params* p, ns_stream_t s) {
+  NS_CHECK_ARG(p && p->dz && p->out && p->N > 0 && p->T > 0 && p->C > 0, "ns_wavenet_hold_sum: bad arguments");
+  NS_CHECK_ARG(p->dtype == NS_F32 || p->dtype == NS_BF16, "ns_wavenet_hold_sum: bad dtype");
+  NS_CHECK_ARG(p->cond_hold >= 1, "ns_wavenet_hold_sum: cond_hold %d: a condition row holds for at least one position", p->cond_hold);
+  NS_CHECK_ARG(p->cond_rows >= 1, "ns_wavenet_hold_sum: cond_rows %d: a condition has at least one row", p->cond_rows);
+  NS_CHECK_ARG(p->ld_out >= 2 * (int64_t)p->C, "ns_wavenet_hold_sum: ld_out %lld is less than 2C = %d", (long long)p->ld_out, 2 * p->C);
+  NS_CHECK_ARG((long)p->N * p->cond_rows <= 0x7fffffffL, "ns_wavenet_hold_sum: N * cond_rows does not fit a grid");
+  const dim3 grid((unsigned)((long)p->N * p->cond_rows));
+  if (p->dtype == NS_BF16) hipLaunchKernelGGL(wn_hold_sum_kernel<bf16_t>, grid, dim3(HS_THREADS), 0, (hipStream_t)s, *p);
+  else hipLaunchKernelGGL(wn_hold_sum_kernel<float>, grid, dim3(HS_THREADS), 0, (hipStream_t)s, *p);
+  NS_CHECK_LAUNCH("wavenet_hold_sum");
   return NS_OK;
 }
 

@@ -266,9 +266,11 @@ class SimpleWaveNet(object):
         """ns_gemm keywords for an epilogue bias (the fp32 master copy), or {}."""
         return dict(bias=self.flat_p, bias_off=self._o(name)) if self.use_biases else {}
 
-    def _forward(self, net_in, N, T0, keep, gcrows=None, lcrows=None):
+    def _forward(self, net_in, N, T0, keep, gcrows=None, lcrows=None, held=None):
         """net_in: ids int32 [N, T0] on the device, or with scalar_input the samples [N * T0] in the compute dtype.
         gcrows / lcrows: the conditions per network-input row, [N * T0, gc] / [N * T0, lc] in the compute dtype.
+        held (_held_condition): the local condition at frame rate instead of lcrows - its term joins the pre-activations
+        inside the gate kernel.
         Returns (logits fp32 [N*ow, Q], ow).  keep: save what backward needs."""
         T_, W = self.T, self.flat_s
         R, Dc, S, Q, L = self.R, self.Dc, self.S, self.Q, self.L
@@ -301,7 +303,7 @@ class SimpleWaveNet(object):
                     ops.gemm(cr, W, zs, rows - d, 2 * Dc, Cc, Cc, 2 * Dc, 2 * Dc, b_mode=1, a_off=d * Cc,
                              b_off=self._o("%s%d" % (tag, l)), c_off=zo + d * 2 * Dc, accumulate=1)
             start += d
-            ops.wavenet_gate(zs[zo:], rows, Dc, T0, start, out=outs, out_off=l * Dc, ld_out=L * Dc)
+            ops.wavenet_gate(zs[zo:], rows, Dc, T0, start, out=outs, out_off=l * Dc, ld_out=L * Dc, **self._gate_cond(held, l))
             # x_next = out . dense + x
             ops.gemm(outs, W, xs, rows, R, Dc, L * Dc, R, R, b_mode=1, a_off=l * Dc, b_off=self._o("dense%d" % l), c_off=xn,
                      addend=xs, addend_off=xo, ld_add=R, **self._bias("deb%d" % l))
@@ -322,15 +324,72 @@ class SimpleWaveNet(object):
         ops.gemm(c1, W, logits, N * ow, Q, S, S, Q, Q, b_mode=1, b_off=self._o("post2"), **self._bias("p2b"))
         return logits, ow
 
-    def initialize(self, audio_inputs, global_conditions=None, local_conditions=None):
+    def initialize(self, audio_inputs, global_conditions=None, local_conditions=None, hold=None, t0=0):
         """wavenet_simple.py:455-477 + add_loss :479-502: audio float [N, T] in [-1, 1]; runs the forward pass and
-        the loss (its gradient wrt the logits comes out of the same kernel)."""
+        the loss (its gradient wrt the logits comes out of the same kernel).
+        hold (lc_channels > 0): local_conditions is [N, F, lc_channels] at frame rate, one row per `hold` samples, and t0
+        (an int, or one per item) is the position of network-input position 0 on the condition's time axis: position m
+        of item n takes row max(0, m + t0[n]) // hold - generate()'s alignment.  Rows are never repeated past the end:
+        fewer than the last position needs is a ValueError."""
         audio = np.asarray(audio_inputs, np.float32)
         if audio.ndim == 1:
             audio = audio[None]
         assert self.full or (global_conditions is None and local_conditions is None), "simple_wavenet takes no conditions"
         ids = torch.from_numpy(mu_law_encode(audio, self.Q)).to(self.device)
-        return self.initialize_ids(ids, audio=audio, global_conditions=global_conditions, local_conditions=local_conditions)
+        return self.initialize_ids(ids, audio=audio, global_conditions=global_conditions, local_conditions=local_conditions,
+                                   hold=hold, t0=t0)
+
+    def _gate_cond(self, held, l):
+        """ns_wavenet_gate keywords for layer l's columns of a held condition term, or {}."""
+        if held is None:
+            return {}
+        return dict(cond=held["cterm"], cond_off=l * 2 * self.Dc, ld_cond=self.L * 2 * self.Dc, cond_rows=held["F"],
+                    cond_hold=held["hold"], cond_t0=held["t0"])
+
+    def _check_held(self, N, T0, local_conditions, hold, t0):
+        """The refusals of a held local condition, before anything is launched.  Returns (frames float32 [N, F, lc],
+        hold, [t0 per item])."""
+        if not self.lc:
+            raise ValueError("hold is given but lc_channels is 0: there is no local condition to hold")
+        hold = int(hold)
+        if hold < 1:
+            raise ValueError("hold must be at least 1")
+        if local_conditions is None:
+            raise ValueError("lc_channels is set: initialize needs local_conditions")
+        c = np.asarray(local_conditions, np.float32)
+        if c.ndim != 3 or c.shape[0] != N or c.shape[2] != self.lc:
+            raise ValueError("local_conditions %s: expected [%d, frames, %d]" % (c.shape, N, self.lc))
+        t0 = np.asarray(t0, np.int64).reshape(-1)
+        if t0.size == 1:
+            t0 = np.repeat(t0, N)
+        if t0.size != N:
+            raise ValueError("t0 has %d entries for %d items" % (t0.size, N))
+        if np.abs(t0).max() >= 2 ** 30:
+            raise ValueError("t0 out of range")
+        need = int(np.maximum(0, T0 - 1 + t0).max()) // hold + 1
+        if c.shape[1] < need:
+            raise ValueError("local_conditions has %d rows of %d samples: %d positions from t0 = %s need %d"
+                             % (c.shape[1], hold, T0, [int(v) for v in t0], need))
+        return c, hold, [int(v) for v in t0]
+
+    def _held_condition(self, frames, hold, t0):
+        """The local condition's 1x1 convolutions at frame rate (they are linear, so the term of a held row is the term of
+        its frame): cterm fp32 [N * F, L * 2Dc] = frames . [lc_filter | lc_gate] of every layer."""
+        N, F, lc = frames.shape
+        L, Dc = self.L, self.Dc
+        src = torch.from_numpy(np.ascontiguousarray(frames)).to(self.device).view(-1)
+        fr = self._buf("lc_frames", N * F * lc, self.T)
+        ops.copy3d(src, fr, 1, 1, N * F * lc, (0, 0), (0, 0))
+        fr32 = fr
+        if self.T != torch.float32:          # the weight gradient's operand beside the fp32 sums of dz: the same values
+            fr32 = self._buf("lc_frames32", N * F * lc, torch.float32)
+            ops.copy3d(fr, fr32, 1, 1, N * F * lc, (0, 0), (0, 0))
+        cterm = self._buf("lc_cterm", N * F * L * 2 * Dc, torch.float32)
+        ops.F32_PASSES = self.passes
+        for l in range(L):
+            ops.gemm(fr, self.flat_s, cterm, N * F, 2 * Dc, lc, lc, 2 * Dc, L * 2 * Dc, b_mode=1, b_off=self._o("lc%d" % l),
+                     c_off=l * 2 * Dc)
+        return dict(cterm=cterm, frames32=fr32, F=F, hold=hold, t0=torch.tensor(t0, dtype=torch.int32, device=self.device))
 
     def _condition_rows(self, N, T0, global_conditions, local_conditions, local=True):
         """The conditions per network-input row, in the compute dtype (wavenet.py:573-608 _embed_gc; :324-340).
@@ -376,9 +435,10 @@ class SimpleWaveNet(object):
             assert local_conditions is None, "lc_channels is 0: no local condition expected"
         return gcrows, lcrows
 
-    def initialize_ids(self, ids, audio=None, global_conditions=None, local_conditions=None):
+    def initialize_ids(self, ids, audio=None, global_conditions=None, local_conditions=None, hold=None, t0=0):
         N, T = ids.shape
         T0 = T - 1
+        checked = self._check_held(N, T0, local_conditions, hold, t0) if hold is not None else None
         self.ids = ids.to(self.device, torch.int32).contiguous()
         self.dims = dict(N=N, T0=T0)
         if self.scalar_input:       # the waveform itself is the network input (wavenet.py:679-682), its last sample cut
@@ -388,9 +448,15 @@ class SimpleWaveNet(object):
             ops.copy3d(a.view(-1), net_in, 1, 1, N * T0, (0, 0), (0, 0))
         else:
             net_in = self.ids[:, :T0].contiguous()
-        gcrows, lcrows = self._condition_rows(N, T0, global_conditions, local_conditions) if self.full else (None, None)
+        held = None
+        if checked is not None:
+            gcrows, lcrows = self._condition_rows(N, T0, global_conditions, None, local=False)
+            held = self._held_condition(*checked)
+        else:
+            gcrows, lcrows = self._condition_rows(N, T0, global_conditions, local_conditions) if self.full else (None, None)
         self._cond = (gcrows, lcrows)
-        logits, ow = self._forward(net_in, N, T0, keep=True, gcrows=gcrows, lcrows=lcrows)
+        self._held = held
+        logits, ow = self._forward(net_in, N, T0, keep=True, gcrows=gcrows, lcrows=lcrows, held=held)
         self.dims["ow"] = ow
         self.targets = self.ids[:, self.rf:].contiguous()                   # [N, ow]
         self.raw_output = logits[:N * ow * self.Q].view(N, ow, self.Q)
@@ -399,7 +465,7 @@ class SimpleWaveNet(object):
         ops.wavenet_softmax_ce(logits, self.Q, self.targets, N * ow, self.Q, 1.0 / (N * ow), self.scal, dlogits=self.dlogits,
                                ld_d=self.Q)
         self._net_in = net_in
-        self._last = (audio, global_conditions, local_conditions)
+        self._last = (audio, global_conditions, local_conditions, hold, t0)
         return self
 
     def add_loss(self, l2_regularization_strength=None):
@@ -473,6 +539,10 @@ class SimpleWaveNet(object):
         dx = self._buf("dx", 2 * rows * R, T_)
         ops.zero(dx)
         gcrows, lcrows = self._cond if self.full else (None, None)
+        held = getattr(self, "_held", None)
+        dterm = None
+        if held is not None:         # the gradient of the held term, [N * F, L * 2Dc]: every element is written below
+            dterm = self._buf("lc_dterm", N * held["F"] * L * 2 * Dc, f32)
         dgc = None
         if self.gc_card:             # gradient wrt the condition rows -> the embedding rows they were looked up from
             dgc = self._buf("dgc_rows", rows * self.gc, f32)
@@ -494,7 +564,9 @@ class SimpleWaveNet(object):
                      split_k=self._sk(rows))
             if self.use_biases:      # dx_{l+1} is zero on the rows layer l does not produce
                 ops.colsum(dx, R, rows, R, g, x_off=nxt, out_off=self._o("deb%d" % l))
-            ops.wavenet_gate(zs[zo:], rows, Dc, T0, starts[l + 1], dout=dol, ld_dout=Dc, dz=dz)
+            ops.wavenet_gate(zs[zo:], rows, Dc, T0, starts[l + 1], dout=dol, ld_dout=Dc, dz=dz, **self._gate_cond(held, l))
+            if held is not None:     # dz is zero on the rows layer l does not produce
+                ops.wavenet_hold_sum(dz, N, T0, Dc, dterm, L * 2 * Dc, held["F"], held["hold"], held["t0"], out_off=l * 2 * Dc)
             if self.use_biases:
                 ops.colsum(dz, 2 * Dc, rows, 2 * Dc, g, out_off=self._o("fgb%d" % l))
             for tag, cr, Cc in (("gc", gcrows, self.gc), ("lc", lcrows, self.lc)):
@@ -517,6 +589,11 @@ class SimpleWaveNet(object):
                      addend_off=nxt, ld_add=R)
             ops.gemm(dz, W, dx, rows, R, 2 * Dc, 2 * Dc, 2 * Dc, R, b_mode=0, b_off=fg + R * 2 * Dc, c_off=cur, addend=dxt,
                      ld_add=R)
+        if held is not None:         # d(lc_l) = frames^T . dterm[:, l]: K = N * F frames, not N * T0 samples
+            NF = N * held["F"]
+            for l in range(L):
+                ops.gemm(held["frames32"], dterm, g, self.lc, 2 * Dc, NF, self.lc, L * 2 * Dc, 2 * Dc, a_mode=1, b_mode=1,
+                         b_off=l * 2 * Dc, c_off=self._o("lc%d" % l), accumulate=2, split_k=self._sk(NF))
         if self.scalar_input:        # dW[k] = sum_m s[m - (IFW-1) + k] * dx0[m]
             K = self.IFW
             ops.gemm(self._net_in, dx, g, K, R, rows - (K - 1), 1, R, R, a_mode=1, b_mode=1, b_off=(K - 1) * R,
@@ -550,9 +627,9 @@ class SimpleWaveNet(object):
         self.loss = float(self.scal[0].item())
         return self.loss
 
-    def step(self, audio_inputs=None, global_conditions=None, local_conditions=None):
+    def step(self, audio_inputs=None, global_conditions=None, local_conditions=None, hold=None, t0=0):
         if audio_inputs is not None:
-            self.initialize(audio_inputs, global_conditions, local_conditions)
+            self.initialize(audio_inputs, global_conditions, local_conditions, hold=hold, t0=t0)
         else:                       # the batch of the last call again
             self.initialize_ids(self.ids, *self._last)
         self.backward()

@@ -733,12 +733,28 @@ def wavenet_input(ids, w, x, N, T, C, Q, w_off=0, dx=None, dw=None, dw_off=0, st
     L.call("ns_wavenet_input", p, stream())
 
 
-def wavenet_gate(z, rows, C, T, start, out=None, out_off=0, ld_out=0, dout=None, dout_off=0, ld_dout=0, dz=None):
+def wavenet_gate(z, rows, C, T, start, out=None, out_off=0, ld_out=0, dout=None, dout_off=0, ld_dout=0, dz=None,
+                 cond=None, cond_off=0, ld_cond=0, cond_rows=0, cond_hold=0, cond_t0=None):
+    """cond fp32 [N * cond_rows, ld_cond] (from element cond_off): a condition term held for cond_hold positions per row,
+    added to the pre-activations; cond_t0 int32 [N] on the device or None (include/nspeech_hip.h)."""
     p = L.struct("ns_wavenet_gate_params")
     ref = out if out is not None else dz
     _fill(p, z=ptr(z), rows=rows, C=C, T=T, start=start, out=ptr(out, out_off), ld_out=ld_out, dtype=dt(ref),
           dout=ptr(dout, dout_off), ld_dout=ld_dout, dz=ptr(dz))
+    if cond is not None:
+        assert cond.dtype == torch.float32 and (cond_t0 is None or cond_t0.dtype == torch.int32)
+        _fill(p, cond=ptr(cond, cond_off), ld_cond=ld_cond, cond_rows=cond_rows, cond_hold=cond_hold, cond_t0=ptr(cond_t0))
     L.call("ns_wavenet_gate", p, stream())
+
+
+def wavenet_hold_sum(dz, N, T, C, out, ld_out, cond_rows, cond_hold, cond_t0=None, out_off=0):
+    """out fp32 [N * cond_rows, ld_out] (from element out_off) = the rows of dz [N * T, 2C] summed per condition row of
+    ns_wavenet_gate's alignment; rows without a position come out zero (include/nspeech_hip.h)."""
+    assert out.dtype == torch.float32 and (cond_t0 is None or cond_t0.dtype == torch.int32)
+    p = L.struct("ns_wavenet_hold_sum_params")
+    _fill(p, dz=ptr(dz), dtype=dt(dz), N=N, T=T, C=C, out=ptr(out, out_off), ld_out=ld_out, cond_rows=cond_rows,
+          cond_hold=cond_hold, cond_t0=ptr(cond_t0))
+    L.call("ns_wavenet_hold_sum", p, stream())
 
 
 def wavenet_softmax_ce(logits, ld, targets, rows, Q, scale, loss_acc, acc_off=0, dlogits=None, ld_d=0):

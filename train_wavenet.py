@@ -6,8 +6,11 @@
 --model wavenet (the reference's default, :108) is WaveNetModel with its options - e.g. --hparams gc_channels=32 conditions
 every piece on its speaker (the feeder's speaker ids, :40-46; the embedding table is sized from the corpora BEFORE the
 model is built - the reference builds the model first, with the yaml's cardinality 0); with the shipped options it is
-simple_wavenet.  lc_channels > 0 is refused here: the reference's pieces carry a mel image of receptive_field rows
-(WavenetDataFeeder.py:127-135), which no layer's output length equals - its graph does not build either.
+simple_wavenet.  --hparams lc_channels=<num_mels> conditions every piece on its own waveform's mel spectrogram at frame
+rate: the feeder hands out the rows, the hop and each piece's offset, and the model holds a row for `hop` samples
+(WaveNetModel.step(hold=, t0=)) - the alignment generate_wavenet.py --local_condition mel.npy --lc_hold <hop> draws with.
+Any other positive lc_channels is refused: the feeder has no such condition (the reference's pieces carry a mel image of
+receptive_field rows, WavenetDataFeeder.py:127-135, which no layer's output length equals - its graph does not build).
 
 LOGDIR/RUN/train.log, model.ckpt-STEP (torch.save of a name -> tensor dict under the TF variable names), a scalars line
 in events.jsonl every --summary-interval steps.  The shipped train.yaml has sample_size = 1 (one predicted sample per
@@ -36,8 +39,9 @@ def train_wavenet(log_dir, args, hp):
     log(hparams_mod.debug_string(hp), logf)
     from nspeech_amd.models.wavenet import receptive_field
     full = args.model == "wavenet"
+    use_lc = full and (hp.lc_channels or 0) > 0         # main() admits num_mels alone: the feeder's mel
     feeder = WavenetFeeder(hp, receptive_field(hp, full), ljspeech=args.ljspeech or None, vctk=args.vctk or None,
-                           librispeech=args.librispeech or None, seed=1234)
+                           librispeech=args.librispeech or None, seed=1234, local_condition="mel" if use_lc else None)
     log("Loaded data refs for %d examples" % len(feeder.items), logf)
     log("Loaded %d different speaker(s)" % len(feeder.speaker2id), logf)
     hp.num_speakers = len(feeder.speaker2id)            # train_wavenet.py:40-41
@@ -61,7 +65,11 @@ def train_wavenet(log_dir, args, hp):
     while args.max_steps is None or model.global_step < args.max_steps:
         t0 = time.time()
         batch = feeder.next_batch()
-        loss = model.step(batch, feeder.speaker_ids if use_gc else None)        # train_wavenet.py:46-49, 75
+        gc = feeder.speaker_ids if use_gc else None                             # train_wavenet.py:46-49, 75
+        if use_lc:
+            loss = model.step(batch, gc, feeder.local_conditions, hold=feeder.lc_hold, t0=feeder.lc_t0)
+        else:
+            loss = model.step(batch, gc)
         step = model.global_step
         time_window.append(time.time() - t0)
         loss_window.append(loss)
@@ -104,9 +112,11 @@ def main():
     os.makedirs(log_dir, exist_ok=True)
     hp = hparams_mod.load("wavenet")
     hp.parse(args.hparams)
-    if (hp.lc_channels or 0) > 0:
-        sys.exit("train_wavenet.py: lc_channels > 0 - the feeder's local-condition images have receptive_field rows "
-                 "(WavenetDataFeeder.py:127-135) and fit no layer; pass local conditions to WaveNetModel.initialize yourself")
+    lc = hp.lc_channels or 0
+    if lc > 0 and (args.model != "wavenet" or lc != hp.num_mels):
+        sys.exit("train_wavenet.py: lc_channels = %d - the feeder's local condition is the mel spectrogram: --model wavenet "
+                 "with lc_channels = num_mels = %d; pass any other local condition to WaveNetModel.initialize yourself"
+                 % (lc, hp.num_mels))
     train_wavenet(log_dir, args, hp)
 
 
