@@ -49,7 +49,8 @@ int ns_occupy(int blocks, int threads, int lds_bytes, int heavy, double usec, in
 int ns_wait_counter(const int* counter, int target, double timeout_usec, ns_stream_t stream);
 
 /* ------------------------------------------------------------------ GEMM / conv1d
- * C[M,N] (=|+=) alpha * act( A·B + bias ), fp32 accumulate.
+ * C[M,N] (=|+=) act( alpha * A·B + bias + addend ), fp32 accumulate; then the gate (0 where gate <= 0) and the row mask
+ * (0 in masked rows) are applied to that value, and the result is stored or added to C (alpha = 0 is read as 1).
  * Replaces tf.layers.dense / tf.layers.conv1d / the matmuls inside LSTMBlockCell and
  * GRUCell (modules.py:25,58,188-198; tacotron2.py:73,107; rnn_wrappers.py:29) and
  * their gradients (tacotron2.py:153 compute_gradients).
@@ -95,8 +96,9 @@ typedef struct {
   int split_k;
   const void* addend; int64_t ld_add;    /* optional [M,N] (fp32, or bf16 when addend_dtype = NS_BF16) added before the activation */
   const void* gate; int64_t ld_gate;     /* optional (dtype of A) [M,N]: result *= (gate > 0)  (ReLU backward) */
-  int f32_passes;   /* fp32 operands only: 0 = exact fp32 FMA kernel; 3 = split-bf16 on MFMA
-                       (x = hi + lo, hi*hi + hi*lo + lo*hi, ~2^-17 relative); 1 = hi*hi only */
+  int f32_passes;   /* fp32 operands: 0 = exact fp32 FMA kernel; 3 = split-bf16 on MFMA
+                       (x = hi + lo, hi*hi + hi*lo + lo*hi, ~2^-17 relative); 1 = hi*hi only; any other value is an
+                       argument error.  bf16 operands: read only with A_lo / B_lo (2: see there), otherwise ignored */
   int addend_dtype; /* 0 / NS_F32: addend is fp32; NS_BF16: addend is bf16 */
   /* optional pre-split low parts of fp32 values (dtype NS_BF16, a_mode 0, b_mode 0, same strides as A / B): with
    * A = hi(a), A_lo = lo(a), B = hi(b), B_lo = lo(b) the call computes hi.hi + hi.lo + lo.hi on the matrix cores

@@ -1259,6 +1259,9 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
                "ns_gemm: split_k>1 needs atomic accumulate, no activation, no stats");
   NS_CHECK_ARG(p.b_seg_len == 0 || (p.b_seg_len > 0 && p.K % p.b_seg_len == 0),
                "ns_gemm: K must be a multiple of b_seg_len");
+  NS_CHECK_ARG(p.dtype != NS_F32 || p.f32_passes == 0 || p.f32_passes == 1 || p.f32_passes == 3,
+               "ns_gemm: f32_passes = %d on fp32 operands (0, 1 or 3; 2 is the two-segment product of pre-split bf16 operands)",
+               p.f32_passes);
   if (p.alpha == 0.f) p.alpha = 1.f;
   if (p.batch < 1) p.batch = 1;
   NS_CHECK_ARG(p.batch == 1 || (!p.col_sum && !p.bias && !p.addend && !p.gate && !p.A_lo && p.batch <= 65535),
@@ -1273,10 +1276,11 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     if (p.b_mode == 0) fast = fast && (p.K % 8 == 0); else fast = fast && (p.N % 8 == 0);
     if (p.b_seg_len > 0) fast = fast && (p.b_seg_len % GBK == 0);
   }
+  // (pre-split operands never come here: this kernel reads A and B only, and the check below refuses them)
   if (fast && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 &&
-      !p.col_sum && p.batch == 1) {
+      !p.col_sum && p.batch == 1 && !p.A_lo && !p.B_lo) {
     // enough workgroups to spread the weight stream over the chip
-    g_last_kernel = "gemm_skinny_kernel";
+    g_last_kernel = p.N >= 32 * 128 ? "gemm_skinny_kernel<2>" : "gemm_skinny_kernel<1>";
     if (p.N >= 32 * 128) hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3(ceil_div(p.N, 32)), dim3(SKW * 64), 0, stream, p);
     else hipLaunchKernelGGL(gemm_skinny_kernel<1>, dim3(ceil_div(p.N, 16)), dim3(SKW * 64), 0, stream, p);
     NS_CHECK_LAUNCH("gemm_skinny");
@@ -1370,12 +1374,13 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     const bool three = p.f32_passes >= 3;
     if (ok && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 && !p.col_sum &&
         p.K % 8 == 0 && p.lda % 4 == 0 && p.batch == 1) {
-      g_last_kernel = "gemm_skinny_f32_kernel";
       if (ceil_div(p.N, 16) <= 64) {      // few column tiles: 16 rows x 8 columns per workgroup
+        g_last_kernel = three ? "gemm_skinny_f32_kernel<3, 1, 8>" : "gemm_skinny_f32_kernel<1, 1, 8>";
         const dim3 grid(ceil_div(p.N, 8), ceil_div(p.M, 16));
         if (three) hipLaunchKernelGGL((gemm_skinny_f32_kernel<3, 1, 8>), grid, dim3(SKW * 64), 0, stream, p);
         else hipLaunchKernelGGL((gemm_skinny_f32_kernel<1, 1, 8>), grid, dim3(SKW * 64), 0, stream, p);
       } else {
+        g_last_kernel = three ? "gemm_skinny_f32_kernel<3, 2, 16>" : "gemm_skinny_f32_kernel<1, 2, 16>";
         if (three) hipLaunchKernelGGL((gemm_skinny_f32_kernel<3, 2, 16>), dim3(ceil_div(p.N, 16)), dim3(SKW * 64), 0, stream, p);
         else hipLaunchKernelGGL((gemm_skinny_f32_kernel<1, 2, 16>), dim3(ceil_div(p.N, 16)), dim3(SKW * 64), 0, stream, p);
       }
