@@ -241,6 +241,48 @@ typedef struct {
 int ns_colsum(const ns_colsum_params* p, ns_stream_t stream);
 size_t ns_colsum_work_floats(int C);
 
+/* ------------------------------------------------------------------ grouped weight gradients (version 102)
+ * ns_gemm_group runs a list of INDEPENDENT weight-gradient items - atomic / split-K products C += A^T.B and column sums
+ * (tacotron2.py:153 compute_gradients: the dW and db of the layers of one queue) - as ONE launch instead of one each:
+ * the workgroups of all items form one grid, so a small product sits beside a large one instead of behind it and one
+ * item's split-K reduction is covered by the next item's tile loops.  Every item keeps the partition into tiles and k
+ * slices, and the order of every sum, of its single launch: the results are bit for bit those of ns_gemm / ns_colsum.
+ * An item is
+ *   kind 0  a bf16 product with both operands k-slow (a_mode 1, b_mode 1) that ns_gemm runs on its 128-tile BK = 64 kernel
+ *   kind 1  an fp32-operand one-pass product (f32_passes 1, a_mode 1, b_mode 1) on the 128-tile kernel
+ *   kind 2  a column sum that ns_colsum runs in its vector form (rows 16-byte aligned, C rounded up to 4 <= ld)
+ * with accumulate = 2, alpha 1, fp32 C, batch 1 and no bias / activation / gate / addend / statistics / row mask /
+ * pre-split operands.  Anything else - a product ns_gemm would send to another kernel, two items whose outputs overlap
+ * or that share a split-K scratch, counter array or column-sum work buffer, a null or empty list - is NS_ERR_BAD_ARG
+ * before anything is launched.  Items with an empty output are accepted and launch nothing.
+ * The item table travels as the kernel's argument (no upload, no device-resident table): NS_GEMM_GROUP_MAX items per
+ * launch, a longer list is split.  Items are ordered by descending K extent per workgroup (ties in caller order) and each
+ * starts at a multiple of 8 workgroups, so it meets the 8 XCDs as it does alone.
+ * ns_gemm_group_plan is the host part alone: entries[0 .. n_products + n_sums) in launch order (nullable), *n_launches
+ * (nullable).  ns_gemm_group_item is the table's entry as the kernel reads it. */
+enum { NS_GEMM_GROUP_MAX = 32 };
+typedef struct {
+  const void* A; const void* B; void* C;   /* kind 2: A = x, C = out */
+  float* work; int* count;                 /* splitk_work, splitk_count; kind 2: work */
+  int64_t lda, ldb, ldc, b_seg_stride;     /* kind 2: lda = ld */
+  int M, N, K, b_seg_len;                  /* kind 2: K = rows, N = C */
+  int split_k, dtype, kind;
+  int wg0, nwg;                            /* first workgroup of the launch (a multiple of 8) and workgroup count */
+  int reserved;
+} ns_gemm_group_item;
+typedef struct {
+  int index;       /* the caller's item: products 0 .. n_products - 1, then the sums */
+  int kind;
+  int launch;      /* which launch of the call */
+  int wg0, nwg;
+  int k_extent;    /* rows of K one workgroup walks (the sort key) */
+} ns_gemm_group_plan_entry;
+int ns_gemm_group(const ns_gemm_params* products, int n_products, const ns_colsum_params* sums, int n_sums,
+                  ns_stream_t stream);
+int ns_gemm_group_plan(const ns_gemm_params* products, int n_products, const ns_colsum_params* sums, int n_sums,
+                       ns_gemm_group_plan_entry* entries, int* n_launches);
+size_t ns_gemm_group_arg_bytes(void);   /* size of the kernel's argument block (<= 4096) */
+
 /* L1 losses of tacotron2.py:130-139 and their gradient in one pass.
  * pred fp32 padded [N,P,ldp] (valid rows padl..padl+T), target fp32 [N,T,F].
  * loss_acc[0] += sum|d| over all bins, loss_acc[1] += sum|d| over bins < n_prio.

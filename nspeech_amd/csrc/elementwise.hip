@@ -2,6 +2,7 @@
 // backward (+ activation and bias gradient), column sums, L1 loss + gradient, Adam with global
 // norm clipping, transposing casts.  All grid-stride, vectorised where layouts allow.
 #include "common.h"
+#include "colsum4.h"
 #include <stdlib.h>
 
 __device__ __forceinline__ float ld_dyn(const void* p, int dtype, long i) {
@@ -560,8 +561,6 @@ extern "C" int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t s_) {
 
 // ------------------------------------------------------------------ column sums
 constexpr int CS_ROWS = 32;
-constexpr int COLSUM_MAX_BLOCKS = 64;     // row blocks of a launch = partial sums per column
-constexpr int COLSUM_CNT = 1024;          // ns_colsum_params.work: [0, 1024) arrival counters (as int), then the partial sums
 __global__ void colsum_kernel(ns_colsum_params p) {
   const int r0 = blockIdx.x * CS_ROWS;
   for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
@@ -574,72 +573,12 @@ __global__ void colsum_kernel(ns_colsum_params p) {
     atomicAdd(p.out + c, s);
   }
 }
-// vector form: block = 16 channel quads x 16 row lanes over rows/32 rows, LDS reduction, then at most 32 adders per
-// address (contended float atomics collapse, see the BatchNorm backward kernels)
+// vector form: colsum4_body (colsum4.h; a grouped weight-gradient launch of gemm.hip runs the same body)
 template <typename T>
 __global__ __launch_bounds__(256) void colsum4_kernel(ns_colsum_params p) {
   __shared__ float red[256][4];
-  const T* x = (const T*)p.x;
-  const int tid = threadIdx.x, ql = tid % BN4_QUADS, rl = tid / BN4_QUADS;
-  const int q = blockIdx.y * BN4_QUADS + ql;
-  const bool active = 4 * q < p.C;
-  const int rpb = (p.rows + gridDim.x - 1) / gridDim.x;
-  const int r0 = blockIdx.x * rpb, r1 = min(p.rows, r0 + rpb);
-  float s4[4] = {0.f, 0.f, 0.f, 0.f};
-  constexpr int CU = 8;          // rows in flight per thread (a bf16 row quad is only 8 bytes)
-  if (active) {
-    for (int base = r0 + rl; base < r1; base += CU * BN4_LANES) {
-      float4 v[CU];
-#pragma unroll
-      for (int u = 0; u < CU; ++u) {
-        const int row = base + u * BN4_LANES;
-        v[u] = row < r1 ? ld4(x + (long)row * p.ld + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < CU; ++u) { s4[0] += v[u].x; s4[1] += v[u].y; s4[2] += v[u].z; s4[3] += v[u].w; }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[tid][i] = s4[i];
-  __syncthreads();
-  if (rl == 0 && active) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float a = 0.f;
-      for (int r = 0; r < BN4_LANES; ++r) a += red[r * BN4_QUADS + ql][i];
-      if (4 * q + i < p.C) {
-        if (p.work) ns_st_sc1(p.work + COLSUM_CNT + (long)blockIdx.x * p.C + 4 * q + i, a);      // parked: the last row block adds them in order
-        else atomicAdd(p.out + 4 * q + i, a);
-      }
-    }
-  }
-  if (!p.work) return;
-  // fixed-order finish: write-through partials, drained -> this column block's counter; the last one adds partials 0, 1, ...
   __shared__ int last;
-  ns_drain_stores();
-  __syncthreads();
-  int* counter = (int*)p.work + blockIdx.y;
-  if (tid == 0) last = atomicAdd(counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!last) return;
-  // 64 columns x 4 groups of 16 row blocks: every thread has its 16 loads in flight at once and adds them in block order,
-  // the four group sums are added in group order (the serial 64-load chain of one thread per column cost 20 us a call)
-  const int c0 = blockIdx.y * BN4_QUADS * 4;
-  constexpr int GB = COLSUM_MAX_BLOCKS / 4;
-  const int cc = tid & 63, grp = tid >> 6;
-  float pv[GB];
-#pragma unroll
-  for (int i = 0; i < GB; ++i) {
-    const int b = grp * GB + i;
-    pv[i] = (b < (int)gridDim.x && c0 + cc < p.C) ? ns_ld_sc1(p.work + COLSUM_CNT + (long)b * p.C + c0 + cc) : 0.f;
-  }
-  float a = 0.f;
-#pragma unroll
-  for (int i = 0; i < GB; ++i) a += pv[i];
-  red[tid][0] = a;
-  __syncthreads();
-  if (tid < 64 && c0 + tid < p.C) p.out[c0 + tid] += ((red[tid][0] + red[64 + tid][0]) + red[128 + tid][0]) + red[192 + tid][0];
-  if (tid == 0) *counter = 0;
+  colsum4_body<T>(p, blockIdx.x, blockIdx.y, gridDim.x, red, &last);
 }
 extern "C" size_t ns_colsum_work_floats(int C) { return (size_t)COLSUM_CNT + (size_t)COLSUM_MAX_BLOCKS * (size_t)(C > 0 ? C : 0); }
 
@@ -672,11 +611,9 @@ __global__ __launch_bounds__(256) void colsum_det_kernel(ns_colsum_params p) {
 extern "C" int ns_colsum(const ns_colsum_params* p, ns_stream_t s) {
   NS_CHECK_ARG(p && p->x && p->out, "ns_colsum: null");
   if (p->rows <= 0 || p->C <= 0) return NS_OK;
-  const int esz = p->dtype == NS_BF16 ? 2 : 4;
   NS_CHECK_ARG(!p->work || p->C <= 64 * COLSUM_CNT, "ns_colsum: the deterministic form takes C <= 65536");
-  // a ragged last quad reads into the row's padding (C rounded up to 4 <= ld) and adds only its valid columns
-  if ((p->C + 3) / 4 * 4 <= p->ld && p->ld % 4 == 0 && ((uintptr_t)p->x % (4 * esz)) == 0) {
-    const dim3 grid(max(1, min(64, ceil_div(p->rows, 128))), ceil_div((p->C + 3) / 4, BN4_QUADS));
+  if (colsum4_ok(*p)) {
+    const dim3 grid(colsum4_grid_x(p->rows), colsum4_grid_y(p->C));
     if (p->dtype == NS_BF16) hipLaunchKernelGGL(colsum4_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, *p);
     else hipLaunchKernelGGL(colsum4_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, *p);
     NS_CHECK_LAUNCH("colsum");

@@ -7,6 +7,8 @@
 //   gemm_generic_kernel any dtype / alignment (fp32 "exact" mode used by the parity tests,
 //                      and odd shapes)
 #include "common.h"
+#include "colsum4.h"
+#include <limits.h>
 
 // ------------------------------------------------------------------ shared epilogue
 struct Epi {
@@ -409,18 +411,31 @@ __device__ __forceinline__ void mfma_epilogue(const ns_gemm_params& p, f32x4 (&a
 //    of one XCD read ONE k range of both operands and every byte of it is fetched by one L2 only.  Before, an XCD had a
 //    fixed tenth of the tiles for every k slice: the weight gradient of a 5-tap convolution (2560 x 512 x 32124, split 6)
 //    fetched 385 MB per launch for 66 MB of unique operand bytes - all of dY once per XCD, the input once per tap.
+// item of a list of W that workgroup L of the dispatch order takes: XCD L & 7 walks its own contiguous run of the list
+__device__ __forceinline__ int xcd_deal(int W, int L) {
+  const int xcd = L & 7, q = W >> 3, r = W & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
+}
 __device__ __forceinline__ void xcd_work_item(const ns_gemm_params& p, int nwg, int& tile, int& ksl) {
   if (p.split_k > 1 && p.batch == 1) {
-    const int W = nwg * p.split_k;
-    const int L = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xcd = L & 7, q = W >> 3, r = W & 7;
-    const int j = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
+    const int j = xcd_deal(nwg * p.split_k, blockIdx.x + gridDim.x * blockIdx.y);
     ksl = j / nwg;
     tile = j - ksl * nwg;
   } else {
-    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    tile = xcd_deal(nwg, blockIdx.x);
     ksl = blockIdx.y;
+  }
+}
+// the same for an item of a grouped launch (gemm_group_kernel; batch = 1): `local` counts the item's workgroups from its
+// first one, which sits on XCD 0 (a multiple of 8 in the launch), so every (tile, k slice) meets the XCD it meets alone
+__device__ __forceinline__ void xcd_group_item(int split_k, int nwg, int local, int& tile, int& ksl) {
+  if (split_k > 1) {
+    const int j = xcd_deal(nwg * split_k, local);
+    ksl = j / nwg;
+    tile = j % nwg;
+  } else {
+    tile = xcd_deal(nwg, local);
+    ksl = 0;
   }
 }
 
@@ -518,8 +533,10 @@ __device__ __forceinline__ void x256_quadrant(const ns_gemm_params& p, f32x4 (&a
 // workgroup, so three workgroups share a CU where BK = 64 allows two.
 // TM = 64 (k-contiguous A, vector epilogue only): 64 x 128 tiles, the four waves side by side (64 x 32 each), for
 // products whose 128-row tiles would leave a third of the CUs without a workgroup (M ~ 5 000 rows: 164 tiles).
+// The body takes its work item - output tile wgid, k slice ksl - from the caller: the kernel below reads it off blockIdx,
+// a grouped launch (gemm_group_kernel) off its item table.  p is the (batch-shifted) product of this workgroup.
 template <int AMODE, int BMODE, bool VEC, int BK = GBK, int TM = GBM>
-__global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_kernel(ns_gemm_params p) {
+__device__ __forceinline__ void gemm_mfma_body(const ns_gemm_params& p, const int wgid, const int ksl) {
   static_assert(TM == 128 || (TM == 64 && AMODE == 0 && VEC && BK == 64), "TM = 64: k-contiguous A, vector epilogue");
   constexpr int WN = TM == 128 ? 2 : 4;         // waves along N
   constexpr int NJ = 8 / WN;                    // 16-column tiles per wave
@@ -530,18 +547,12 @@ __global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_kernel(ns_gem
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int tiles_n = (p.N + GBN - 1) / GBN;
-  const int tiles_m = (p.M + TM - 1) / TM;
-  // XCD-aware bijective remap: workgroups that share an XCD (id % 8) walk neighbouring tiles
-  const int nwg = tiles_m * tiles_n;
-  int wgid, ksl;                                 // output tile, k slice
-  xcd_work_item(p, nwg, wgid, ksl);
   const int tm = wgid / tiles_n, tn = wgid % tiles_n;
   const int m0 = tm * TM, n0 = tn * GBN;
 
   const int nk = (p.K + BK - 1) / BK;
   const int per = (nk + p.split_k - 1) / p.split_k;
   const int kt0 = ksl * per, kt1 = min(nk, kt0 + per);
-  batch_shift(p, blockIdx.z);
 
   const bf16_t* A = (const bf16_t*)p.A;
   const bf16_t* B = (const bf16_t*)p.B;
@@ -620,6 +631,15 @@ __global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_kernel(ns_gem
   }
   if constexpr (VEC) x256_quadrant(p, acc, m0 + wm * 64, n0 + wn * (NJ * 16), lane);
   else mfma_epilogue(p, acc, m0, n0, wm, wn, lane, add_bias);
+}
+template <int AMODE, int BMODE, bool VEC, int BK = GBK, int TM = GBM>
+__global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_kernel(ns_gemm_params p) {
+  // XCD-aware bijective remap: workgroups that share an XCD (id % 8) walk neighbouring tiles
+  const int nwg = ((p.M + TM - 1) / TM) * ((p.N + GBN - 1) / GBN);
+  int wgid, ksl;                                 // output tile, k slice
+  xcd_work_item(p, nwg, wgid, ksl);
+  batch_shift(p, blockIdx.z);
+  gemm_mfma_body<AMODE, BMODE, VEC, BK, TM>(p, wgid, ksl);
 }
 
 // ------------------------------------------------------------------ 256 x 256 tiles, 8 phases per two K-tiles
@@ -981,8 +1001,8 @@ __device__ __forceinline__ void stagef_store(const StageF& s, char* img_hi, char
   }
 }
 
-template <int AMODE, int BMODE, int PASSES, bool VEC, int TM = GBM>      // VEC, TM: as in gemm_mfma_kernel
-__global__ __launch_bounds__(256, 2) void gemm_mfma_f32_kernel(ns_gemm_params p) {
+template <int AMODE, int BMODE, int PASSES, bool VEC, int TM = GBM>      // VEC, TM, (wgid, ksl): as in gemm_mfma_body
+__device__ __forceinline__ void gemm_mfma_f32_body(const ns_gemm_params& p, const int wgid, const int ksl) {
   static_assert(TM == 128 || (TM == 64 && AMODE == 0 && VEC), "TM = 64: k-contiguous A, vector epilogue");
   constexpr int WN = TM == 128 ? 2 : 4;
   constexpr int NJ = 8 / WN;
@@ -991,16 +1011,11 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_f32_kernel(ns_gemm_params p)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int tiles_n = (p.N + GBN - 1) / GBN;
-  const int tiles_m = (p.M + TM - 1) / TM;
-  const int nwg = tiles_m * tiles_n;
-  int wgid, ksl;                                 // output tile, k slice
-  xcd_work_item(p, nwg, wgid, ksl);
   const int tm = wgid / tiles_n, tn = wgid % tiles_n;
   const int m0 = tm * TM, n0 = tn * GBN;
   const int nk = (p.K + FBK - 1) / FBK;
   const int per = (nk + p.split_k - 1) / p.split_k;
   const int kt0 = ksl * per, kt1 = min(nk, kt0 + per);
-  batch_shift(p, blockIdx.z);
   const float* A = (const float*)p.A;
   const float* B = (const float*)p.B;
   f32x4 acc[4][NJ];
@@ -1096,6 +1111,14 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_f32_kernel(ns_gemm_params p)
   }
   if constexpr (VEC) x256_quadrant(p, acc, m0 + wm * 64, n0 + wn * (NJ * 16), lane);
   else mfma_epilogue(p, acc, m0, n0, wm, wn, lane, add_bias);
+}
+template <int AMODE, int BMODE, int PASSES, bool VEC, int TM = GBM>
+__global__ __launch_bounds__(256, 2) void gemm_mfma_f32_kernel(ns_gemm_params p) {
+  const int nwg = ((p.M + TM - 1) / TM) * ((p.N + GBN - 1) / GBN);
+  int wgid, ksl;                                 // output tile, k slice
+  xcd_work_item(p, nwg, wgid, ksl);
+  batch_shift(p, blockIdx.z);
+  gemm_mfma_f32_body<AMODE, BMODE, PASSES, VEC, TM>(p, wgid, ksl);
 }
 
 // skinny (M <= 32) variant: fp32 fragments straight from memory, split in registers (common.h).
@@ -1242,9 +1265,8 @@ extern "C" int ns_gemm(const ns_gemm_params* pp, ns_stream_t stream_) {
   return NS_OK;
 }
 
-static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
-  NS_CHECK_ARG(p.M >= 0 && p.N >= 0 && p.K >= 0, "ns_gemm: negative dims");
-  if (p.M == 0 || p.N == 0) return NS_OK;
+// argument checks and defaults of a non-empty product (ns_gemm and every product of ns_gemm_group)
+static int gemm_normalize(ns_gemm_params& p) {
   NS_CHECK_ARG(p.A && p.B && p.C, "ns_gemm: null operand");
   NS_CHECK_ARG(p.dtype == NS_F32 || p.dtype == NS_BF16, "ns_gemm: bad dtype %d", p.dtype);
   NS_CHECK_ARG(p.c_dtype == NS_F32 || p.c_dtype == NS_BF16, "ns_gemm: bad c_dtype %d", p.c_dtype);
@@ -1266,7 +1288,14 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
   if (p.batch < 1) p.batch = 1;
   NS_CHECK_ARG(p.batch == 1 || (!p.col_sum && !p.bias && !p.addend && !p.gate && !p.A_lo && p.batch <= 65535),
                "ns_gemm: batched calls take no bias / addend / gate / statistics / pre-split operands");
+  return NS_OK;
+}
 
+// Which kernel form a (normalised) product takes.  gemm_dispatch launches by it and the grouped launch's plan asks it
+// too, so the two cannot drift: a group item is a product this function sends to one of the two forms the group carries.
+enum { GF_SKINNY, GF_X256, GF_PRESPLIT_REFUSED, GF_MFMA, GF_SKINNY_F32, GF_F32, GF_GENERIC };
+struct gemm_form { int kind; bool vec, half, bk32; };
+static gemm_form gemm_classify(const ns_gemm_params& p) {
   bool fast = (p.dtype == NS_BF16) && aligned16(p.A) && aligned16(p.B) && (p.lda % 8 == 0) &&
               (p.ldb % 8 == 0) && (p.b_seg_stride % 8 == 0) && (p.batch_stride_a % 8 == 0) &&
               (p.batch_stride_b % 8 == 0);
@@ -1276,9 +1305,48 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     if (p.b_mode == 0) fast = fast && (p.K % 8 == 0); else fast = fast && (p.N % 8 == 0);
     if (p.b_seg_len > 0) fast = fast && (p.b_seg_len % GBK == 0);
   }
-  // (pre-split operands never come here: this kernel reads A and B only, and the check below refuses them)
   if (fast && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 &&
-      !p.col_sum && p.batch == 1 && !p.A_lo && !p.B_lo) {
+      !p.col_sum && p.batch == 1 && !p.A_lo && !p.B_lo) return {GF_SKINNY, false, false, false};
+  if (fast && p.batch == 1 && x256_ok(p)) return {GF_X256, false, false, false};
+  if (p.A_lo || p.B_lo) return {GF_PRESPLIT_REFUSED, false, false, false};
+  if (fast) {
+    const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
+    const bool vec = vec_epilogue_ok(p);
+    // 64-row tiles when the 128-row ones leave CUs without a workgroup (<= 192 tiles) and A is k-contiguous
+    const bool half = vec && p.a_mode == 0 && half_tiles_wanted(p, tiles);
+    static const int bk32_env = [] { const char* e = getenv("NS_GEMM_BK32"); return e ? atoi(e) : -1; }();
+    // BK = 32 (four workgroups per CU instead of two) pays when a launch has more workgroups than the 512 the BK = 64
+    // form keeps resident: 1280 workgroups 202 -> 169 us, 640: 73 -> 52 us; at <= 512 (what the models' split-K rule
+    // asks for) it is slower alone (84 -> 99 us) and no faster beside another stream's kernels
+    // (profiles/r03_gemm_128_ablation.txt).  NS_GEMM_BK32 = 0 / 1 forces it off / on.
+    const bool bk32w = bk32_env >= 0 ? bk32_env != 0 : (long)tiles * p.split_k * p.batch >= 600;
+    const bool bk32 = !half && p.a_mode == 1 && p.b_mode == 1 && bk32w && (p.b_seg_len == 0 || p.b_seg_len % 32 == 0);
+    return {GF_MFMA, vec, half, bk32};
+  }
+  if (p.dtype == NS_F32 && p.f32_passes > 0) {
+    bool ok = aligned16(p.A) && aligned16(p.B) && (p.lda % 4 == 0) && (p.ldb % 4 == 0) && (p.b_seg_stride % 4 == 0) &&
+              (p.batch_stride_a % 4 == 0) && (p.batch_stride_b % 4 == 0);
+    if (p.a_mode == 0) ok = ok && (p.K % 4 == 0); else ok = ok && (p.M % 4 == 0);
+    if (p.b_mode == 0) ok = ok && (p.K % 4 == 0); else ok = ok && (p.N % 4 == 0);
+    if (p.b_seg_len > 0) ok = ok && (p.b_seg_len % FBK == 0);
+    if (ok && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 && !p.col_sum &&
+        p.K % 8 == 0 && p.lda % 4 == 0 && p.batch == 1) return {GF_SKINNY_F32, false, false, false};
+    if (ok) {
+      const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
+      const bool vec = vec_epilogue_ok(p);
+      return {GF_F32, vec, vec && p.a_mode == 0 && half_tiles_wanted(p, tiles), false};
+    }
+  }
+  return {GF_GENERIC, false, false, false};
+}
+
+static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
+  NS_CHECK_ARG(p.M >= 0 && p.N >= 0 && p.K >= 0, "ns_gemm: negative dims");
+  if (p.M == 0 || p.N == 0) return NS_OK;
+  if (int rc = gemm_normalize(p)) return rc;
+  const gemm_form form = gemm_classify(p);
+  // (pre-split operands never come here: this kernel reads A and B only, and the check below refuses them)
+  if (form.kind == GF_SKINNY) {
     // enough workgroups to spread the weight stream over the chip
     g_last_kernel = p.N >= 32 * 128 ? "gemm_skinny_kernel<2>" : "gemm_skinny_kernel<1>";
     if (p.N >= 32 * 128) hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3(ceil_div(p.N, 32)), dim3(SKW * 64), 0, stream, p);
@@ -1286,7 +1354,7 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     NS_CHECK_LAUNCH("gemm_skinny");
     return NS_OK;
   }
-  if (fast && p.batch == 1 && x256_ok(p)) {
+  if (form.kind == GF_X256) {
     const int tiles = ceil_div(p.M, 256) * ceil_div(p.N, 256);
     const size_t lds = 2 * XBUF;
     static bool attr_set = false;
@@ -1305,16 +1373,14 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     NS_CHECK_LAUNCH("gemm_x256");
     return NS_OK;
   }
-  NS_CHECK_ARG(!p.A_lo && !p.B_lo, "ns_gemm: pre-split operands (A_lo / B_lo) need the 256-tile path "
+  NS_CHECK_ARG(form.kind != GF_PRESPLIT_REFUSED, "ns_gemm: pre-split operands (A_lo / B_lo) need the 256-tile path "
                "(bf16, a_mode 0, b_mode 0, K %% 64 == 0, M >= 1024, N %% 128 == 0, >= 96 tiles, no split_k)");
-  if (fast) {
+  if (form.kind == GF_MFMA) {
     const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
     dim3 grid(tiles, p.split_k, p.batch);
     const size_t lds = 65536;
     p.stat_slots = 2 * ceil_div(p.M, GBM);
-    const bool vec = vec_epilogue_ok(p);
-    // 64-row tiles when the 128-row ones leave CUs without a workgroup (<= 192 tiles) and A is k-contiguous
-    const bool half = vec && p.a_mode == 0 && half_tiles_wanted(p, tiles);
+    const bool vec = form.vec, half = form.half;
     if (half) {
       grid.x = ceil_div(p.M, 64) * ceil_div(p.N, GBN);
       p.stat_slots = ceil_div(p.M, 64);
@@ -1344,15 +1410,9 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     g_last_kernel = "gemm_mfma_kernel<0, " #BM_ ", true, 64, 64>";                                \
     hipLaunchKernelGGL((gemm_mfma_kernel<0, BM_, true, 64, 64>), grid, dim3(256), lds, stream, p);    \
   } while (0)
-    static const int bk32_env = [] { const char* e = getenv("NS_GEMM_BK32"); return e ? atoi(e) : -1; }();
-    const bool bk32 = bk32_env >= 0 ? bk32_env != 0 : (long)tiles * p.split_k * p.batch >= 600;
-    // BK = 32 (four workgroups per CU instead of two) pays when a launch has more workgroups than the 512 the BK = 64
-    // form keeps resident: 1280 workgroups 202 -> 169 us, 640: 73 -> 52 us; at <= 512 (what the models' split-K rule
-    // asks for) it is slower alone (84 -> 99 us) and no faster beside another stream's kernels
-    // (profiles/r03_gemm_128_ablation.txt).  NS_GEMM_BK32 = 0 / 1 forces it off / on.
     if (half) {
       if (p.b_mode == 0) LAUNCH_MFMA_HALF(0); else LAUNCH_MFMA_HALF(1);
-    } else if (p.a_mode == 1 && p.b_mode == 1 && bk32 && (p.b_seg_len == 0 || p.b_seg_len % 32 == 0)) {
+    } else if (form.bk32) {
       g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 32, 128>" : "gemm_mfma_kernel<1, 1, false, 32, 128>";
       if (vec) hipLaunchKernelGGL((gemm_mfma_kernel<1, 1, true, 32>), grid, dim3(256), 32768, stream, p);
       else hipLaunchKernelGGL((gemm_mfma_kernel<1, 1, false, 32>), grid, dim3(256), 32768, stream, p);
@@ -1365,15 +1425,9 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     NS_CHECK_LAUNCH("gemm_mfma");
     return NS_OK;
   }
-  if (p.dtype == NS_F32 && p.f32_passes > 0) {
-    bool ok = aligned16(p.A) && aligned16(p.B) && (p.lda % 4 == 0) && (p.ldb % 4 == 0) && (p.b_seg_stride % 4 == 0) &&
-              (p.batch_stride_a % 4 == 0) && (p.batch_stride_b % 4 == 0);
-    if (p.a_mode == 0) ok = ok && (p.K % 4 == 0); else ok = ok && (p.M % 4 == 0);
-    if (p.b_mode == 0) ok = ok && (p.K % 4 == 0); else ok = ok && (p.N % 4 == 0);
-    if (p.b_seg_len > 0) ok = ok && (p.b_seg_len % FBK == 0);
+  if (form.kind == GF_SKINNY_F32 || form.kind == GF_F32) {
     const bool three = p.f32_passes >= 3;
-    if (ok && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 && !p.col_sum &&
-        p.K % 8 == 0 && p.lda % 4 == 0 && p.batch == 1) {
+    if (form.kind == GF_SKINNY_F32) {
       if (ceil_div(p.N, 16) <= 64) {      // few column tiles: 16 rows x 8 columns per workgroup
         g_last_kernel = three ? "gemm_skinny_f32_kernel<3, 1, 8>" : "gemm_skinny_f32_kernel<1, 1, 8>";
         const dim3 grid(ceil_div(p.N, 8), ceil_div(p.M, 16));
@@ -1387,13 +1441,12 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
       NS_CHECK_LAUNCH("gemm_skinny_f32");
       return NS_OK;
     }
-    if (ok) {
+    {
       const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
       dim3 grid(tiles, p.split_k, p.batch);
       const size_t lds = 65536;
       p.stat_slots = 2 * ceil_div(p.M, GBM);
-      const bool vec = vec_epilogue_ok(p);
-      const bool half = vec && p.a_mode == 0 && half_tiles_wanted(p, tiles);
+      const bool vec = form.vec, half = form.half;
       if (half) {
         grid.x = ceil_div(p.M, 64) * ceil_div(p.N, GBN);
         p.stat_slots = ceil_div(p.M, 64);
@@ -1448,4 +1501,229 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
   else hipLaunchKernelGGL(gemm_generic_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
   NS_CHECK_LAUNCH("gemm_generic");
   return NS_OK;
+}
+
+// ------------------------------------------------------------------ grouped weight gradients (ns_gemm_group)
+// One grid for a list of independent items: workgroup b finds its item through the prefix table wg0[] (unused entries
+// hold INT_MAX), rebuilds the item's parameter block and calls the body its single launch calls, with the (tile, k slice)
+// - or (row block, column block) - that workgroup `b - wg0` of the single launch takes.  The table is the kernel's
+// argument: the lookups are scalar loads from the argument segment.  Workgroups between an item's last one and the next
+// multiple of 8 return at once.
+struct gemm_group_args {
+  int wg0[NS_GEMM_GROUP_MAX];
+  ns_gemm_group_item item[NS_GEMM_GROUP_MAX];
+};
+static_assert(sizeof(ns_gemm_group_item) == 112, "ns_gemm_group_item: layout of include/nspeech_hip.h");
+static_assert(sizeof(gemm_group_args) <= 4096, "the item table must fit the kernel argument block");
+extern "C" size_t ns_gemm_group_arg_bytes(void) { return sizeof(gemm_group_args); }
+
+__device__ __forceinline__ ns_gemm_params group_product(const ns_gemm_group_item& it) {
+  ns_gemm_params p = {};
+  p.dtype = it.dtype;
+  p.M = it.M; p.N = it.N; p.K = it.K;
+  p.A = it.A; p.lda = it.lda; p.a_mode = 1;
+  p.B = it.B; p.ldb = it.ldb; p.b_mode = 1;
+  p.b_seg_len = it.b_seg_len; p.b_seg_stride = it.b_seg_stride;
+  p.C = it.C; p.ldc = it.ldc; p.c_dtype = NS_F32;
+  p.accumulate = 2;
+  p.alpha = 1.f;
+  p.split_k = it.split_k;
+  p.f32_passes = 1;
+  p.batch = 1;
+  p.splitk_work = it.work; p.splitk_count = it.count;
+  return p;
+}
+
+__global__ __launch_bounds__(256, 2) void gemm_group_kernel(const gemm_group_args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.x;
+  int idx = 0;
+#pragma unroll
+  for (int i = 1; i < NS_GEMM_GROUP_MAX; ++i) idx += b >= a.wg0[i];
+  const ns_gemm_group_item& it = a.item[idx];
+  const int local = b - it.wg0;
+  if (local >= it.nwg) return;
+  if (it.kind == 2) {
+    ns_colsum_params c;
+    c.x = it.A; c.dtype = it.dtype; c.ld = it.lda; c.rows = it.K; c.C = it.N; c.out = (float*)it.C; c.work = it.work;
+    const int gx = colsum4_grid_x(c.rows);
+    float (*red)[4] = (float (*)[4])smem;
+    int* last = (int*)(smem + 256 * 4 * sizeof(float));
+    if (it.dtype == NS_BF16) colsum4_body<bf16_t>(c, local % gx, local / gx, gx, red, last);
+    else colsum4_body<float>(c, local % gx, local / gx, gx, red, last);
+    return;
+  }
+  const ns_gemm_params p = group_product(it);
+  const int tiles = ((it.M + GBM - 1) / GBM) * ((it.N + GBN - 1) / GBN);
+  int tile, ksl;
+  xcd_group_item(it.split_k, tiles, local, tile, ksl);
+  if (it.kind == 0) gemm_mfma_body<1, 1, false, GBK, GBM>(p, tile, ksl);
+  else gemm_mfma_f32_body<1, 1, 1, false, GBM>(p, tile, ksl);
+}
+
+namespace {
+struct group_entry {
+  ns_gemm_group_item it;
+  int index, k_extent;
+  const char* c0; const char* c1;          // output byte range
+  const char* s0[2]; const char* s1[2];    // scratch byte ranges (work, counters)
+};
+bool ranges_meet(const char* a0, const char* a1, const char* b0, const char* b1) { return a0 < b1 && b0 < a1 && a0 < a1 && b0 < b1; }
+}  // namespace
+
+// classification, workgroup counts, order and launch cut of a list; `out` gets the accepted items in launch order
+static int gemm_group_build(const ns_gemm_params* products, int n_products, const ns_colsum_params* sums, int n_sums,
+                            group_entry* out, int* n_out) {
+  NS_CHECK_ARG(n_products >= 0 && n_sums >= 0 && n_products + n_sums > 0, "ns_gemm_group: empty list");
+  NS_CHECK_ARG((n_products == 0 || products) && (n_sums == 0 || sums), "ns_gemm_group: null list");
+  int n = 0;
+  for (int i = 0; i < n_products; ++i) {
+    ns_gemm_params p = products[i];
+    NS_CHECK_ARG(p.M >= 0 && p.N >= 0 && p.K >= 0, "ns_gemm_group: product %d: negative dims", i);
+    group_entry e = {};
+    e.index = i;
+    e.it.kind = p.dtype == NS_F32 ? 1 : 0;
+    if (p.M > 0 && p.N > 0) {
+      if (int rc = gemm_normalize(p)) return rc;
+      NS_CHECK_ARG(p.accumulate == 2 && p.alpha == 1.f && p.c_dtype == NS_F32 && p.batch == 1,
+                   "ns_gemm_group: product %d: items are atomic fp32 accumulations (accumulate 2, alpha 1, batch 1)", i);
+      NS_CHECK_ARG(!p.bias && p.act == NS_ACT_NONE && !p.gate && !p.addend && !p.col_sum && !p.col_sumsq && !p.stat_z &&
+                   p.row_period <= 0 && !p.A_lo && !p.B_lo && !p.bn.mean_out,
+                   "ns_gemm_group: product %d carries an epilogue operand the item table has no field for", i);
+      const gemm_form f = gemm_classify(p);
+      const bool k0 = f.kind == GF_MFMA && !f.vec && !f.half && !f.bk32;
+      const bool k1 = f.kind == GF_F32 && !f.vec && !f.half && p.f32_passes == 1;
+      NS_CHECK_ARG((k0 || k1) && p.a_mode == 1 && p.b_mode == 1,
+                   "ns_gemm_group: product %d is not one ns_gemm runs on gemm_mfma_kernel<1, 1, false, 64, 128> or "
+                   "gemm_mfma_f32_kernel<1, 1, 1, false, 128>", i);
+      const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
+      const int bk = k0 ? GBK : FBK, nk = ceil_div(p.K, bk), per = ceil_div(nk, p.split_k);
+      ns_gemm_group_item& it = e.it;
+      it.A = p.A; it.B = p.B; it.C = p.C; it.work = p.split_k > 1 ? p.splitk_work : nullptr;
+      it.count = p.split_k > 1 ? p.splitk_count : nullptr;
+      it.lda = p.lda; it.ldb = p.ldb; it.ldc = p.ldc; it.b_seg_stride = p.b_seg_stride;
+      it.M = p.M; it.N = p.N; it.K = p.K; it.b_seg_len = p.b_seg_len;
+      it.split_k = p.split_k; it.dtype = p.dtype; it.kind = k0 ? 0 : 1;
+      it.nwg = tiles * p.split_k;
+      e.k_extent = min((long)p.K, (long)per * bk);
+      e.c0 = (const char*)p.C; e.c1 = e.c0 + ((long)(p.M - 1) * p.ldc + p.N) * 4;
+      if (it.work) {
+        e.s0[0] = (const char*)it.work; e.s1[0] = e.s0[0] + ns_gemm_splitk_work_bytes(p.M, p.N, p.split_k);
+        e.s0[1] = (const char*)it.count; e.s1[1] = e.s0[1] + (size_t)tiles * 4;
+      }
+    }
+    out[n++] = e;
+  }
+  for (int i = 0; i < n_sums; ++i) {
+    const ns_colsum_params& c = sums[i];
+    group_entry e = {};
+    e.index = n_products + i;
+    e.it.kind = 2;
+    if (c.rows > 0 && c.C > 0) {
+      NS_CHECK_ARG(c.x && c.out, "ns_gemm_group: sum %d: null", i);
+      NS_CHECK_ARG(c.dtype == NS_F32 || c.dtype == NS_BF16, "ns_gemm_group: sum %d: bad dtype %d", i, c.dtype);
+      NS_CHECK_ARG(!c.work || c.C <= 64 * COLSUM_CNT, "ns_gemm_group: sum %d: the deterministic form takes C <= 65536", i);
+      NS_CHECK_ARG(colsum4_ok(c), "ns_gemm_group: sum %d is not one ns_colsum runs on colsum4_kernel", i);
+      ns_gemm_group_item& it = e.it;
+      it.A = c.x; it.C = c.out; it.work = c.work; it.lda = c.ld; it.N = c.C; it.K = c.rows; it.dtype = c.dtype;
+      const int gx = colsum4_grid_x(c.rows);
+      it.nwg = gx * colsum4_grid_y(c.C);
+      e.k_extent = ceil_div(c.rows, gx);
+      e.c0 = (const char*)c.out; e.c1 = e.c0 + (size_t)c.C * 4;
+      if (c.work) { e.s0[0] = (const char*)c.work; e.s1[0] = e.s0[0] + ns_colsum_work_floats(c.C) * 4; }
+    }
+    out[n++] = e;
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j) {
+      NS_CHECK_ARG(!ranges_meet(out[i].c0, out[i].c1, out[j].c0, out[j].c1),
+                   "ns_gemm_group: items %d and %d write overlapping outputs", out[i].index, out[j].index);
+      for (int u = 0; u < 2; ++u)
+        for (int v = 0; v < 2; ++v)
+          NS_CHECK_ARG(!ranges_meet(out[i].s0[u], out[i].s1[u], out[j].s0[v], out[j].s1[v]),
+                       "ns_gemm_group: items %d and %d share a split-K scratch, counter array or column-sum work buffer",
+                       out[i].index, out[j].index);
+    }
+  // descending K extent per workgroup, ties in caller order: the short items fill the tail of the launch
+  for (int i = 1; i < n; ++i) {
+    const group_entry e = out[i];
+    int j = i;
+    for (; j > 0 && out[j - 1].k_extent < e.k_extent; --j) out[j] = out[j - 1];
+    out[j] = e;
+  }
+  // launches of NS_GEMM_GROUP_MAX non-empty items; every item starts at a multiple of 8 workgroups (XCD 0)
+  int in_launch = 0, wg = 0;
+  for (int i = 0; i < n; ++i) {
+    ns_gemm_group_item& it = out[i].it;
+    if (it.nwg > 0 && in_launch == NS_GEMM_GROUP_MAX) { in_launch = 0; wg = 0; }
+    it.wg0 = wg;
+    it.reserved = 0;
+    if (it.nwg > 0) { ++in_launch; wg = (wg + it.nwg + 7) & ~7; }
+  }
+  *n_out = n;
+  return NS_OK;
+}
+
+// launch l of a built list = the maximal run of items whose wg0 does not restart; returns one past its last entry
+static int group_launch_end(const group_entry* e, int n, int first) {
+  int i = first, seen = 0;
+  for (; i < n; ++i) {
+    if (e[i].it.nwg > 0 && seen == NS_GEMM_GROUP_MAX) break;
+    if (e[i].it.nwg > 0) ++seen;
+  }
+  return i;
+}
+
+extern "C" int ns_gemm_group_plan(const ns_gemm_params* products, int n_products, const ns_colsum_params* sums, int n_sums,
+                                  ns_gemm_group_plan_entry* entries, int* n_launches) {
+  if (n_launches) *n_launches = 0;
+  NS_CHECK_ARG(n_products >= 0 && n_sums >= 0 && n_products + n_sums > 0, "ns_gemm_group: empty list");
+  group_entry* e = new group_entry[n_products + n_sums];
+  int n = 0;
+  const int rc = gemm_group_build(products, n_products, sums, n_sums, e, &n);
+  if (rc == NS_OK) {
+    int launches = 0;
+    for (int first = 0; first < n; ++launches) {
+      const int end = group_launch_end(e, n, first);
+      for (int i = first; i < end && entries; ++i)
+        entries[i] = ns_gemm_group_plan_entry{e[i].index, e[i].it.kind, launches, e[i].it.wg0, e[i].it.nwg, e[i].k_extent};
+      first = end;
+    }
+    if (n_launches) *n_launches = launches;
+  }
+  delete[] e;
+  return rc;
+}
+
+extern "C" int ns_gemm_group(const ns_gemm_params* products, int n_products, const ns_colsum_params* sums, int n_sums,
+                             ns_stream_t stream_) {
+  NS_CHECK_ARG(n_products >= 0 && n_sums >= 0 && n_products + n_sums > 0, "ns_gemm_group: empty list");
+  group_entry* e = new group_entry[n_products + n_sums];
+  int n = 0;
+  int rc = gemm_group_build(products, n_products, sums, n_sums, e, &n);
+  static bool attr_set = false;
+  if (rc == NS_OK && !attr_set) {
+    (void)hipFuncSetAttribute((const void*)gemm_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    attr_set = true;
+  }
+  for (int first = 0; rc == NS_OK && first < n;) {
+    const int end = group_launch_end(e, n, first);
+    gemm_group_args a;
+    int k = 0, total = 0;
+    for (int i = first; i < end; ++i) {
+      if (e[i].it.nwg <= 0) continue;
+      a.wg0[k] = e[i].it.wg0;
+      a.item[k++] = e[i].it;
+      total = e[i].it.wg0 + e[i].it.nwg;
+    }
+    for (int i = k; i < NS_GEMM_GROUP_MAX; ++i) { a.wg0[i] = INT_MAX; a.item[i] = ns_gemm_group_item{}; }
+    if (k > 0) {
+      g_last_kernel = "gemm_group_kernel";
+      hipLaunchKernelGGL(gemm_group_kernel, dim3(total), dim3(256), 65536, (hipStream_t)stream_, a);
+      if (hipGetLastError() != hipSuccess) { ns_set_error("gemm_group: launch failed"); rc = NS_ERR_LAUNCH; }
+    }
+    first = end;
+  }
+  delete[] e;
+  return rc;
 }

@@ -64,7 +64,8 @@ class Tacotron(Tacotron2):
     def queue_groups(self):
         return () if self.WG_POLICY == "eager" else (self.WG,)
 
-    def _defer(self, group, fn, eager=False):
+    def _defer(self, group, fn, eager=False, pure=False):
+        # (pure is dropped: this model releases its products as they form and keeps one launch per product)
         return Tacotron2._defer(self, group, fn, eager=eager or self.WG_POLICY == "eager")
 
     def _make_streams(self):

@@ -123,6 +123,9 @@ class Tacotron2(object):
         # "dec1:bwd": "wide" | "step", "encl:fwd" / "expl:fwd": "cluster" | "step", ...}.  Tests assert on it; train.py
         # logs it once, so a shape that falls off the persistent kernels is visible.
         self.last_paths = {}
+        # grouped weight-gradient launches of the last backward pass: [(queues, [items per launch, ...]), ...], one entry
+        # per flush that grouped anything (NS_WGRAD_GROUP; kept beside last_paths, whose values are kernel families)
+        self.wgrad_group = []
         pv, sv = P_.init_values(self.layout, self.stat_layout, seed)
         self.load_numpy(pv, sv)
         # attributes the reference exposes
@@ -400,11 +403,30 @@ class Tacotron2(object):
         self._side_busy = True
         return self._side
 
-    def _defer(self, group, fn, eager=False, now=False):
+    # Queues whose products and column sums go out as ONE grouped launch per flush (ops.gemm_group, ns_gemm_group) instead
+    # of one launch each: launches of one stream run strictly one after another, so a queue of twenty ended after twenty
+    # partial waves and twenty split-K tails; grouped, the small items sit beside the large ones.  NS_WGRAD_GROUP lists
+    # the queues (decoder, postnet, head); "" restores the single launches.  Default: the decoder queue only.  Measured
+    # (profiles/wgrad_group.txt): decoder -0.35 ms (wgrad_join 0.61 -> 0.23); postnet + head +0.4 ms - their one launch
+    # of 18 convolution products holds two workgroups on every CU for the whole window of the decoder LSTMs' recurrences
+    # and the main stream's data-gradient product between them (dec_lstm_bwd:wgrad2 0.20 -> 1.05 ms) no longer finds the
+    # gaps that the boundaries between single launches gave it, which costs more than the shorter straddle of the
+    # attention recurrence returns (attn_rnn_bwd 2.59 -> 2.39).
+    @property
+    def group_queues(self):
+        env = os.environ.get("NS_WGRAD_GROUP")       # read per pass: an A/B can switch it between two steps of one process
+        if env is None:
+            return ("decoder",)
+        return tuple(q for q in env.split(",") if q)
+
+    def _defer(self, group, fn, eager=False, now=False, pure=False):
         """Run fn in line, or - with overlap_wgrads - on the second stream: now (eager, unless its group is queued; `now`:
         even then) or at _flush_deferred.  group = the gradient bucket (parallel.bucket_ranges) the call writes into: its
         release to the reducer follows the call onto that stream.  The caller guarantees that nothing overwrites fn's
-        operands before _join_deferred."""
+        operands before _join_deferred.
+        pure: no call of fn that is not a weight-gradient product or a column sum reads the output of one that is (casts
+        and BatchNorm finalisers in front of their product are fine, a copy behind it is not) - the condition under which
+        a queued fn may run inside ops.gemm_group, where the products and sums are held back to the end of the context."""
         if not (self.overlap_wgrads and self.device.type == "cuda"):
             fn()
         elif now or (eager and group not in self.queue_groups):
@@ -412,16 +434,29 @@ class Tacotron2(object):
             with torch.cuda.stream(self._side_stream()):
                 fn()
         else:
-            self._deferred.append((group, fn))
+            self._deferred.append((group, fn, pure))
 
     def _flush_deferred(self):
         if not self._deferred:
             return
         calls, self._deferred = self._deferred, []
-        self._side_groups.update(grp for grp, _ in calls)        # a later bucket release follows them onto that stream
+        self._side_groups.update(c[0] for c in calls)            # a later bucket release follows them onto that stream
+        grouped = self.group_queues
         with torch.cuda.stream(self._side_stream()):
-            for _, fn in calls:
-                fn()
+            i = 0
+            while i < len(calls):
+                j = i
+                while j < len(calls) and calls[j][2] and calls[j][0] in grouped:
+                    j += 1
+                if j == i:       # a closure that is not group-pure (a queued bucket release among them): on its own, in place
+                    calls[i][1]()
+                    i += 1
+                    continue
+                with ops.gemm_group() as grp:        # consecutive group-pure closures: one launch when the context closes
+                    for _, fn, _ in calls[i:j]:
+                        fn()
+                self.wgrad_group.append(("+".join(sorted(set(c[0] for c in calls[i:j]))), list(grp.launches)))
+                i = j
 
     def _join_deferred(self):
         self._flush_deferred()
@@ -435,8 +470,8 @@ class Tacotron2(object):
     def _tick(self, label):
         if self.reducer is not None and label in self._BUCKET_AFTER:
             name = self._BUCKET_AFTER[label]                       # gradients of this group are final ...
-            if any(grp == name for grp, _ in self._deferred):      # ... once its queued weight gradients have run
-                self._deferred.append((name, lambda: self.reducer.bucket_ready(name)))
+            if any(c[0] == name for c in self._deferred):          # ... once its queued weight gradients have run
+                self._deferred.append((name, lambda: self.reducer.bucket_ready(name), False))
             elif name in self._side_groups:                        # ... or the ones already on the second stream
                 with torch.cuda.stream(self._side_stream()):
                     self.reducer.bucket_ready(name)
@@ -695,7 +730,7 @@ class Tacotron2(object):
                      a_off=a_rows * cin, b_off=self.padl * cout, c_off=self._o(scope + "/conv1d/kernel"),
                      accumulate=2, split_k=self._splitk(Mg, k * cin, cout))
         if defer:
-            self._defer(defer, wgrad, eager=True)
+            self._defer(defer, wgrad, eager=True, pure=True)
         else:
             wgrad()
         if need_dx:
@@ -874,7 +909,7 @@ class Tacotron2(object):
                              split_k=self._splitk(rows, H, 4 * H))
                 ops.colsum(dg, 4 * H, rows, 4 * H, g, out_off=self._o("%s/%s/lstm_cell/bias" % (scope, d)))
             if defer:       # x, the state history and the gate gradients are this layer's own buffers
-                self._defer(defer, wgrads, eager=True)
+                self._defer(defer, wgrads, eager=True, pure=True)
             else:
                 wgrads()
             # dx (+)= dgates . Wx^T
@@ -1121,6 +1156,7 @@ class Tacotron2(object):
         ops.DETERMINISTIC_SPLITK = self.deterministic
         ops.zero_many((g, self.scal))
         self._deferred = []
+        self.wgrad_group = []           # (queues, items per launch) of every grouped flush of this pass
         self._bwd_sums = {}
         B = self._bufs
         ops.F32_PASSES = self.passes_bwd
@@ -1192,7 +1228,7 @@ class Tacotron2(object):
         if self._on_main("postdense"):
             postdense_wgrad()
         else:
-            self._defer("postnet", postdense_wgrad, eager=True)
+            self._defer("postnet", postdense_wgrad, eager=True, pure=True)
         cur, nxt = dx, dx2
         ops.gemm(dmel_t, self._W(self.T), cur, rows_o, Cp, M, M, M, Cp, a_mode=0, b_mode=0, b_off=ko,
                  row_mask=(Po, self.padl, self.padl + To, 0), **self._dy_stats_kw("post%d" % (hp.postnet_conv_layers - 1)))
@@ -1219,7 +1255,7 @@ class Tacotron2(object):
             ops.gemm(h2, ddec, g, D, M * r, rows, D, M * r, M * r, a_mode=1, b_mode=1, c_off=kp, accumulate=2,
                      split_k=self._splitk(rows, D, M * r))
             ops.colsum(ddec, M * r, rows, M * r, g, out_off=self._o("decoder/output_projection/bias"))
-        self._defer("decoder", proj_wgrad)
+        self._defer("decoder", proj_wgrad, pure=True)
         dh2 = self._buf("d_h2", rows * D, torch.float32)
         ops.gemm(ddec, self._W(self.T), dh2, rows, D, M * r, M * r, M * r, D, a_mode=0, b_mode=0, b_off=kp)
         # ---- LSTM2, LSTM1 through time
@@ -1250,7 +1286,7 @@ class Tacotron2(object):
             cast16(h1b, h1, D)
             cast16(h2b, h2, D)
             self._lstm_wgrads(h1b, D, h2b, D, dg2b if dg2b is not None else dg2, rows, k2, "decoder/lstm_2/bias")
-        self._defer("decoder", lstm2_wgrads)
+        self._defer("decoder", lstm2_wgrads, pure=True)
         if "decoder2" in self.queue_groups:      # LSTM 2's weight gradients under LSTM 1's recurrence (measured: worse)
             self._flush_deferred()
         dh1 = self._buf("d_h1", rows * D, torch.float32)
@@ -1272,7 +1308,7 @@ class Tacotron2(object):
         def lstm1_wgrads():
             cast16(hcb, hc, A + E)
             self._lstm_wgrads(hcb, A + E, h1b, D, dg1b if dg1b is not None else dg1, rows, k1, "decoder/lstm_1/bias")
-        self._defer("decoder", lstm1_wgrads)
+        self._defer("decoder", lstm1_wgrads, pure=True)
         dhc = self._buf("d_hc", rows * (A + E), torch.float32)
         if dg1b is not None:
             ops.gemm(dg1b, w16, dhc, rows, A + E, 4 * D, 4 * D, 4 * D, A + E, a_mode=0, b_mode=0, b_off=k1)
@@ -1352,7 +1388,7 @@ class Tacotron2(object):
             ops.colsum(dga, 4 * A, rows, 4 * A, g, out_off=self._o("decoder/attention_lstm/bias"))
             ops.gemm(hc, dq, g, A, A, rows, A + E, A, A, a_mode=1, b_mode=1, c_off=wq, accumulate=2,
                      split_k=sk(rows, A, A))
-        self._defer("decoder", attn_wgrads)
+        self._defer("decoder", attn_wgrads, pure=True)
         if self.Dsp:
             self._speaker_bwd(dga, N, S1)
         # unfold dWcl[k,u] into location_conv [7,1,20] and location_layer [20,A]   (fp32, tiny)

@@ -89,7 +89,10 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, a_off=0, b_off=0,
         p.batch_stride_a, p.batch_stride_b, p.batch_stride_c = batch_strides
     if a_lo is not None:        # pre-split fp32 values: A / B hold the high parts (same offsets and strides)
         p.A_lo, p.B_lo = ptr(a_lo, a_off), ptr(b_lo, b_off)
-    if split_k > 1 and batch == 1 and DETERMINISTIC_SPLITK:
+    det = split_k > 1 and batch == 1 and DETERMINISTIC_SPLITK
+    if _GROUP is not None and _GROUP.take_product(p, Cm.device, det):
+        return
+    if det:
         work, count = _splitk_scratch(Cm.device, M, N, split_k)
         p.splitk_work, p.splitk_count = ptr(work), ptr(count)
     L.call("ns_gemm", p, stream())
@@ -235,9 +238,128 @@ def colsum(x, ld, rows, C, out, x_off=0, out_off=0):
     p = L.struct("ns_colsum_params")
     fn = L.lib().ns_colsum_work_floats
     fn.restype = C_.c_size_t
-    work = _scratch(_COLSUM_WORK, x.device, int(fn(int(C))))
-    _fill(p, x=ptr(x, x_off), dtype=dt(x), ld=ld, rows=rows, C=C, out=ptr(out, out_off), work=ptr(work))
+    _fill(p, x=ptr(x, x_off), dtype=dt(x), ld=ld, rows=rows, C=C, out=ptr(out, out_off))
+    if _GROUP is not None and _GROUP.take_sum(p, x.device):
+        return
+    p.work = ptr(_scratch(_COLSUM_WORK, x.device, int(fn(int(C)))))
     L.call("ns_colsum", p, stream())
+
+
+# ---- grouped weight gradients (ns_gemm_group): the products and column sums of a queue as one launch
+_GROUP = None
+_GROUP_SPLITK = {}
+_GROUP_COLSUM = {}
+GROUP_MAX = 32          # NS_GEMM_GROUP_MAX
+
+
+class _Group:
+    """The open recording of gemm_group().  A gemm / colsum call that ns_gemm_group_plan accepts as an item is kept;
+    the caller runs everything else at once.  An item whose output overlaps a recorded one's launches what is recorded
+    first, so accumulations into one range keep their call order."""
+
+    def __init__(self):
+        self.launches = []           # items per launch, for the caller's records
+        self._reset()
+
+    def _reset(self):
+        self.products, self.sums, self.det, self.ranges, self.device = [], [], [], [], None
+
+    def _accepts(self, products, sums):
+        lib = L.lib()
+        ap = (L.STRUCTS["ns_gemm_params"] * len(products))(*products) if products else None
+        asum = (L.STRUCTS["ns_colsum_params"] * len(sums))(*sums) if sums else None
+        return lib.ns_gemm_group_plan(ap, len(products), asum, len(sums), None, None) == 0
+
+    def _claim(self, lo, hi):
+        if any(lo < b and a < hi for a, b in self.ranges):
+            self.launch()
+        self.ranges.append((lo, hi))
+
+    def take_product(self, p, device, det):
+        if det:                      # placeholders: the scratch is handed out when the group is launched
+            p.splitk_work = p.splitk_count = p.C
+        if not self._accepts([p], []):
+            p.splitk_work = p.splitk_count = None
+            return False
+        if p.M > 0 and p.N > 0:
+            self._claim(p.C, p.C + ((p.M - 1) * p.ldc + p.N) * 4)
+        self.device = device
+        self.products.append(p)
+        self.det.append(det)
+        return True
+
+    def take_sum(self, p, device):
+        p.work = p.out               # placeholder, as above
+        if not self._accepts([], [p]):
+            p.work = None
+            return False
+        if p.rows > 0 and p.C > 0:
+            self._claim(p.out, p.out + p.C * 4)
+        self.device = device
+        self.sums.append(p)
+        return True
+
+    def launch(self):
+        products, sums, det, device = self.products, self.sums, self.det, self.device
+        self._reset()
+        if not products and not sums:
+            return
+        lib = L.lib()
+        key = (device, stream())
+        # deterministic split-K: one scratch and one zeroed counter array per (device, stream), a slice per item
+        fb, fc = lib.ns_gemm_splitk_work_bytes, lib.ns_gemm_splitk_counters
+        fb.restype = fc.restype = L.C.c_size_t
+        need = [(int(fb(p.M, p.N, p.split_k)), int(fc(p.M, p.N))) if d else (0, 0) for p, d in zip(products, det)]
+        nb, nc = sum(b for b, _ in need), sum(c for _, c in need)
+        if nb:
+            cur = _GROUP_SPLITK.get(key)
+            if cur is None or cur[0].numel() * 4 < nb or cur[1].numel() < nc:
+                cur = _GROUP_SPLITK[key] = (
+                    torch.empty(max(nb // 4, cur[0].numel() if cur else 0), dtype=torch.float32, device=device),
+                    torch.zeros(max(nc, cur[1].numel() if cur else 0, 4096), dtype=torch.int32, device=device))
+            ob = oc = 0
+            for p, (b, c) in zip(products, need):
+                if b:
+                    p.splitk_work, p.splitk_count = cur[0].data_ptr() + ob, cur[1].data_ptr() + 4 * oc
+                    ob, oc = ob + b, oc + c
+        # column sums: slots of one zeroed array; a slot's first words are its arrival counters, so the slots never move
+        if sums:
+            fw = lib.ns_colsum_work_floats
+            fw.restype = L.C.c_size_t
+            slot = max(int(fw(int(p.C))) for p in sums)
+            cur = _GROUP_COLSUM.get(key)
+            if cur is None or cur.shape[0] < len(sums) or cur.shape[1] < slot:
+                cur = _GROUP_COLSUM[key] = torch.zeros(max(len(sums), cur.shape[0] if cur is not None else 0),
+                                                       max(slot, cur.shape[1] if cur is not None else 0),
+                                                       dtype=torch.float32, device=device)
+            for i, p in enumerate(sums):
+                p.work = cur.data_ptr() + 4 * i * cur.shape[1]
+        ap = (L.STRUCTS["ns_gemm_params"] * len(products))(*products) if products else None
+        asum = (L.STRUCTS["ns_colsum_params"] * len(sums))(*sums) if sums else None
+        L.check(lib.ns_gemm_group(ap, len(products), asum, len(sums), C_.c_void_p(stream())), "ns_gemm_group")
+        live = sum(1 for p in products if p.M > 0 and p.N > 0) + sum(1 for p in sums if p.rows > 0 and p.C > 0)
+        self.launches += [min(GROUP_MAX, live - i) for i in range(0, live, GROUP_MAX)]
+
+
+class gemm_group:
+    """Context on the current stream: the gemm / colsum calls inside it that ns_gemm_group takes as items (atomic
+    weight-gradient products on the 128-tile kernels, vector column sums) are recorded and go out as ONE launch when the
+    context is left; every other call - and a product the plan refuses - runs at once, in call order.  Correct only
+    where no call that runs at once reads a recorded call's output.  `launches` (items per launch) is filled on exit."""
+
+    def __enter__(self):
+        global _GROUP
+        assert _GROUP is None, "ops.gemm_group does not nest"
+        self._g = _GROUP = _Group()
+        self.launches = self._g.launches
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        global _GROUP
+        _GROUP = None
+        if exc_type is None:
+            self._g.launch()
+        return False
 
 
 def l1_loss(pred, ldp, target, dpred, ldd, N, T, P, padl, F, n_prio, w_all, w_prio, loss_acc, acc_off=0):
