@@ -2,8 +2,11 @@
 //
 // A "chain" = (direction, group of batch rows) is an independent recurrence: 16 rows (the MFMA tile's other
 // dimension) in the single-role kernels, 16, 8 or 4 in the role-split kernels (template parameter RPC,
-// picked per launch by cluster_rows(); the rows of the tile beyond RPC are padding that is never loaded, published or
-// stored).  Batch rows are independent, so every form writes the same bits; a narrow chain moves RPC / 16 of the bytes
+// picked per launch by cluster_rows(); the rows of the tile beyond RPC are never loaded, published or stored: the narrow
+// forms fill them with replicas of the live rows - the operand fragment of a padding column is read from a live row - and
+// deal the element-wise work of a slot over all 64 lanes, each lane owning RPC / 16 of what its column computes; see the
+// ownership rules above the two kernels, profiles/cluster_lanes.txt).  Batch rows are independent and an MFMA output column
+// depends on its own operand column only, so every form writes the same bits; a narrow chain moves RPC / 16 of the bytes
 // per hop - the hop is what bounds a step - and the batch takes 16 / RPC times the workgroups: at batch 32, H 256 the
 // expand BiLSTM runs on 64 CUs instead of 16, forward 2.16 -> 1.59 ms, backward 2.16 -> 1.90 ms
 // (profiles/cluster_rows.txt).  It runs on a
@@ -410,6 +413,12 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
 // saver's images take 6 vector writes instead of 24.  The workgroup's own h block goes into the next operand image
 // directly (LDS), only the peers' blocks are polled.  The xg operands of slot s + 1 are read at the end of slot s (the
 // prefetcher runs one interval ahead), so behind the slot barrier the chain starts with the MFMAs.
+// Ownership at 8 / 4 rows per chain (R = 16 / RPC replicas): lane (r16, g) reads the h fragment and the xg operands of row
+// r16 % RPC, so after the MFMAs each of the R lanes of a row holds the same four pre-activations per gate; replica
+// j = r16 / RPC keeps 4 / R of the units - the pair wq + 2 j, wq + 2 j + 1 (one granule) at 8 rows, the unit wq + j at 4 -
+// and does gate math, cell state, mask, clip, publish and saves for those alone (0.61 -> 0.43 us of the slot at 4 rows).
+// At 4 rows two neighbouring replicas share a granule: the even one takes the odd one's h with one DPP move and stores
+// it.  Granule indices, tags, LDS addresses and the saver images' bytes are those of the 16-row form.
 // (audit) one barrier per slot, joined by every role: hs[s&1] is filled by the pollers (peers' blocks) and the compute
 // waves (own block, in slot s-1 behind barrier(s-1)) in front of barrier(s), read behind it, refilled behind
 // barrier(s+1); xgs[(s+1)&1] is stored between barrier(s-1) and barrier(s), read between barrier(s) and barrier(s+1);
@@ -436,18 +445,17 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
   const int u0 = wgc * 64;
   const int T = a.T;
   if (tid < 3) abortf[tid] = 0;
-  if (RPC < 16) {
-    // rows >= RPC of the operand images are padding of the MFMA's B operand: zeroed here, in front of every role's first
-    // barrier, and never written again
-    for (int i = tid; i < 2 * 16 * H / 8; i += FW_WAVES * 64) ((uint4*)hs)[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
-  }
+  // rows >= RPC of the operand images are never read (the narrow forms' B fragments come from rows < RPC only) and stay unwritten
+  if (RPC < 16 && blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
 
   if (wave < XW) {
-    // ================================================================ compute role: batch row r16, units wq .. wq + 3;
-    // lanes with r16 >= RPC are padding: they publish nothing, store nothing, and what they compute is never read
-    const bool live = RPC == 16 || r16 < RPC;
-    const int wq = wave * 16 + g * 4;                  // first of the lane's 4 units inside the workgroup's 64
+    // ================================================================ compute role.  16 rows: lane (r16, g) owns batch row
+    // r16, units wq .. wq + 3.  8 / 4 rows: column r16 of the tile is replica `rep` of row r16 % RPC, and the lane owns
+    // UPL = RPC / 4 of the four units its column computes - wq + rep * UPL .. - for everything behind the MFMAs
+    constexpr int UPL = RPC / 4;                       // units per lane in the cell update: 4, 2 (one granule), 1
+    const int row = r16 % RPC, rep = r16 / RPC;
+    const int wq = wave * 16 + g * 4;                  // first of the 4 units of the lane's column inside the workgroup's 64
+    const int wo = wq + rep * UPL;                     // first of the lane's own units
     bf16x8 bw[4][KS];                                  // A fragments: row (unit) wave * 16 + r16, k chunk g
     {
       const bf16_t* W = a.whT[d];
@@ -458,14 +466,23 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         for (int ks = 0; ks < KS; ++ks) bw[gate][ks] = *(const bf16x8*)(row + ks * 32 + g * 8);
       }
     }
-    float cst[4] = {0.f, 0.f, 0.f, 0.f};
-    const int n = rg * RPC + r16;
-    const int len = (a.lengths && live && n < a.N) ? a.lengths[n] : T;
+    float cst[UPL];
+#pragma unroll
+    for (int r = 0; r < UPL; ++r) cst[r] = 0.f;
+    const int n = rg * RPC + row;
+    const int len = (a.lengths && n < a.N) ? a.lengths[n] : T;
     f32x4 acc[4];
     auto load_xg = [&](int step) {
-      const float* xr = xgs + ((size_t)(step & 1) * 16 + r16) * XG_LD + wq;
+      const float* xr = xgs + ((size_t)(step & 1) * 16 + row) * XG_LD + wq;
 #pragma unroll
       for (int gate = 0; gate < 4; ++gate) acc[gate] = *(const f32x4*)(xr + gate * 64);
+    };
+    // pre-activation of the lane's own unit r out of its column's four: explicit selects (a dynamically indexed
+    // accumulator would go to scratch)
+    auto own = [&](const f32x4& v, int r) -> float {
+      if constexpr (RPC == 16) return v[r];
+      else if constexpr (RPC == 8) return rep ? v[2 + r] : v[r];
+      else return (rep & 2) ? ((rep & 1) ? v[3] : v[2]) : ((rep & 1) ? v[1] : v[0]);
     };
     wg_barrier();                                      // xg of slot 0 and abortf are in place
     load_xg(0);
@@ -482,18 +499,19 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         const bf16_t* hb = hs + (size_t)buf * 16 * H;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const bf16x8 hf = *(const bf16x8*)(hb + swz_off(r16, ks * 32 + g * 8, H));
+          // narrow forms: the replicas of a row read the same address (a broadcast, no bank conflict)
+          const bf16x8 hf = *(const bf16x8*)(hb + swz_off(row, ks * 32 + g * 8, H));
 #pragma unroll
           for (int gate = 0; gate < 4; ++gate)
             acc[gate] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[gate][ks], hf, acc[gate], 0, 0, 0);
         }
       }
       const bool masked = t >= len;
-      float hv[4], sg[4][4];
+      float hv[UPL], sg[UPL][4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float gi = sigmoidf_(acc[0][r]), gj = tanhf_(acc[1][r]);
-        const float gf = sigmoidf_(acc[2][r] + a.forget_bias), go = sigmoidf_(acc[3][r]);
+      for (int r = 0; r < UPL; ++r) {
+        const float gi = sigmoidf_(own(acc[0], r)), gj = tanhf_(own(acc[1], r));
+        const float gf = sigmoidf_(own(acc[2], r) + a.forget_bias), go = sigmoidf_(own(acc[3], r));
         float cn = ns_cell_clip(gf * cst[r] + gi * gj, a.cell_clip);
         float hn = go * tanhf_(cn);
         if (masked) { cn = 0.f; hn = 0.f; }
@@ -502,22 +520,22 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         sg[r][0] = masked ? 0.f : gi; sg[r][1] = masked ? 0.f : gj; sg[r][2] = masked ? 0.f : gf; sg[r][3] = masked ? 0.f : go;
       }
       if (tr) a.trace[step * 8 + 1] = wall_clock64();
-      // publish first (tag = step + 1): units (wq, wq + 1) and (wq + 2, wq + 3) of row r16
-      uint2 hp;
-      hp.x = pack_bf16(hv[0], hv[1]);
-      hp.y = pack_bf16(hv[2], hv[3]);
-      if (step + 1 < T) {
-        if (CS > 1 && live) {
-          u64* nxt = xb0 + (size_t)((step + 1) & 1) * CS * GPD + (size_t)wgc * GPD + (wave * 4 * RPC + g * RPC + r16) * 2;
-          __hip_atomic_store(nxt, ((u64)(unsigned)(step + 1) << 32) | hp.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(nxt + 1, ((u64)(unsigned)(step + 1) << 32) | hp.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      char* sv = svs + (size_t)buf * SV_BYTES;
+      if constexpr (RPC == 16) {
+        // publish first (tag = step + 1): units (wq, wq + 1) and (wq + 2, wq + 3) of row r16
+        uint2 hp;
+        hp.x = pack_bf16(hv[0], hv[1]);
+        hp.y = pack_bf16(hv[2], hv[3]);
+        if (step + 1 < T) {
+          if (CS > 1) {
+            u64* nxt = xb0 + (size_t)((step + 1) & 1) * CS * GPD + (size_t)wgc * GPD + (wave * 4 * RPC + g * RPC + r16) * 2;
+            __hip_atomic_store(nxt, ((u64)(unsigned)(step + 1) << 32) | hp.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(nxt + 1, ((u64)(unsigned)(step + 1) << 32) | hp.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          *(uint2*)(hs + (size_t)((step + 1) & 1) * 16 * H + swz_off(r16, u0 + wq, H)) = hp;   // the own block
         }
-        if (live) *(uint2*)(hs + (size_t)((step + 1) & 1) * 16 * H + swz_off(r16, u0 + wq, H)) = hp;   // the own block
-      }
-      if (tr) a.trace[step * 8 + 2] = wall_clock64();
-      // results for the backward pass / the consumers of h go to LDS; the saver wave writes them out
-      if (live) {
-        char* sv = svs + (size_t)buf * SV_BYTES;
+        if (tr) a.trace[step * 8 + 2] = wall_clock64();
+        // results for the backward pass / the consumers of h go to LDS; the saver wave writes them out
         *(uint2*)((bf16_t*)sv + r16 * 64 + wq) = hp;
         *(f32x4*)((float*)(sv + SV_H) + r16 * 64 + wq) = (f32x4){cst[0], cst[1], cst[2], cst[3]};
         bf16_t* gp = (bf16_t*)(sv + SV_H + SV_C) + r16 * 4 * 64 + wq;
@@ -527,6 +545,42 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
           pk.x = pack_bf16(sg[0][gate], sg[1][gate]);
           pk.y = pack_bf16(sg[2][gate], sg[3][gate]);
           *(uint2*)(gp + gate * 64) = pk;
+        }
+      } else {
+        // One granule = the unit pair (wq + 2 pair, wq + 2 pair + 1) of `row`, at the index and with the tag of the 16-row
+        // form.  8 rows: the lane's own two units are granule `rep`.  4 rows: the lanes of replicas 2 pair and 2 pair + 1
+        // each hold one unit of it; the even one fetches its neighbour's h (lane + 4, one DPP move inside the 16-lane
+        // row) and stores for both.
+        unsigned hp;
+        bool holder = true;
+        int pair = rep;
+        if constexpr (RPC == 8) {
+          hp = pack_bf16(hv[0], hv[1]);
+        } else {
+          hp = pack_bf16(hv[0], NS_DPP_F(hv[0], 0x104));   // row_shl:4: lane i takes lane i + 4's value
+          holder = !(rep & 1);
+          pair = rep >> 1;
+        }
+        if (step + 1 < T && holder) {
+          if (CS > 1) {
+            u64* nxt = xb0 + (size_t)((step + 1) & 1) * CS * GPD + (size_t)wgc * GPD + (wave * 4 * RPC + g * RPC + row) * 2 + pair;
+            __hip_atomic_store(nxt, ((u64)(unsigned)(step + 1) << 32) | hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          *(unsigned*)(hs + (size_t)((step + 1) & 1) * 16 * H + swz_off(row, u0 + wq + 2 * pair, H)) = hp;   // the own block
+        }
+        if (tr) a.trace[step * 8 + 2] = wall_clock64();
+        // the saver's images: the bytes and offsets of the 16-row form, each written by the lane that owns the unit
+        if (holder) *(unsigned*)((bf16_t*)sv + row * 64 + wq + 2 * pair) = hp;
+        float* cp = (float*)(sv + SV_H) + row * 64 + wo;
+        bf16_t* gp = (bf16_t*)(sv + SV_H + SV_C) + row * 4 * 64 + wo;
+        if constexpr (RPC == 8) {
+          *(float2*)cp = make_float2(cst[0], cst[1]);
+#pragma unroll
+          for (int gate = 0; gate < 4; ++gate) *(unsigned*)(gp + gate * 64) = pack_bf16(sg[0][gate], sg[1][gate]);
+        } else {
+          *cp = cst[0];
+#pragma unroll
+          for (int gate = 0; gate < 4; ++gate) gp[gate * 64] = (bf16_t)sg[0][gate];
         }
       }
       if (step + 1 < T) load_xg(step + 1);
@@ -926,7 +980,11 @@ constexpr int DGI_LD = 256 + 8;          // bf16 per row of the operand image (r
 //   * compute wave w owns units [16 w, 16 w + 16) of the workgroup's 64 in the cell update, and in the product the HB
 //     output tiles {(destination workgroup wd, units 16 w .. 16 w + 16 of ITS 64)}: the tile for wd = this workgroup is
 //     the own block of exactly the units the wave updates next step, in exactly the accumulator layout the cell update
-//     uses (lane (r16, g): unit r16, rows 4 g .. 4 g + 3) - it stays in registers;
+//     uses (lane (r16, g): unit r16, rows 4 g .. 4 g + 3 at 16 rows per chain; at 8 / 4 rows the product's A fragment of
+//     a padding tile row is read from a live image row, so that lane group g finds the RPC / 4 rows it OWNS - 2 g, 2 g + 1
+//     or g - in its own accumulators, and everything element-wise - the stage reads and tanh of indep(), the poll, the
+//     sums, the cell update - is done per owned row: 1 row per lane instead of 4 at 4 rows per chain) - it stays in
+//     registers;
 //   * the peers' blocks are polled by the lane that consumes them (a lane needs only the sums of ITS unit and rows:
 //     4 rows x (CS - 1) peers; the forward kernels cannot do this, every lane of theirs needs the whole gathered vector
 //     as an MFMA operand): no poller waves, no LDS image of the gathered sums, no hand-over;
@@ -970,8 +1028,13 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
   if (wave < XW) {
     // ================================================================ compute role
     const int wu = wave * 16 + r16;                    // unit inside the workgroup's 64
-    // lane groups g >= RPC / 4 are padding rows: they poll nothing, publish nothing, and put zeros into the operand image
-    const bool live = RPC == 16 || g < RPC / 4;
+    // Lane group g owns OR = RPC / 4 of the chain's rows - g * OR .. - for everything element-wise.  16 rows: those are the
+    // accumulator rows 4 g .. 4 g + 3 of the product.  8 / 4 rows: the product's A fragment of tile row i is read from image
+    // row arow(i), so that the padding rows of the tile are replicas and every lane group finds its own rows in its own
+    // accumulators: 8 rows, arow = 2 (i / 4) + i % 2 - group g holds rows 2 g, 2 g + 1 (one granule) in elements 0, 1;
+    // 4 rows, arow = i % 4 - every group holds all four rows, group g takes element g
+    constexpr int OR = RPC / 4;
+    const int arow = RPC == 16 ? r16 : RPC == 8 ? 2 * (r16 >> 2) + (r16 & 1) : (r16 & 3);
     // Wh[unit wu of workgroup j][own 256 gate columns], the columns in the operand image's order k = unit * 4 + gate
     bf16x8 bw[HB][8];
 #pragma unroll
@@ -982,26 +1045,31 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
 #pragma unroll
         for (int e = 0; e < 8; ++e) bw[j][ks][e] = row[(e & 3) * H + ks * 8 + g * 2 + (e >> 2)];
     }
-    float dcc[4], pc[4];
-    f32x4 ownp = {0.f, 0.f, 0.f, 0.f};                 // own block of the partial sums of the step before
-    int len[4];
+    float dcc[OR], pc[OR];
+    f32x4 ownp = {0.f, 0.f, 0.f, 0.f};                 // own block of the partial sums of the step before (elements < OR)
+    int len[OR];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int n = rg * RPC + g * 4 + r;
+    for (int r = 0; r < OR; ++r) {
+      const int n = rg * RPC + g * OR + r;
       dcc[r] = 0.f; pc[r] = 0.f;
-      len[r] = (a.lengths && live && n < a.N) ? a.lengths[n] : T;
+      len[r] = (a.lengths && n < a.N) ? a.lengths[n] : T;
     }
+    // element of the own row r in a tile of the product (see arow): explicit selects, no dynamically indexed accumulator
+    auto own = [&](const f32x4& v, int r) -> float {
+      if constexpr (RPC == 4) return (g & 2) ? ((g & 1) ? v[3] : v[2]) : ((g & 1) ? v[1] : v[0]);
+      else return v[r];
+    };
     // the part of a slot's cell update that does not need the exchanged sums; computed one slot ahead, under the
     // product's MFMAs (the stage of slot s + 1 is complete behind barrier(s))
-    float kdo[4], kdc[4], ki[4], kj[4], kf[4], dhx[4], cpv[4], gfv[4];
+    float kdo[OR], kdc[OR], ki[OR], kj[OR], kf[OR], dhx[OR], cpv[OR], gfv[OR];
     auto indep = [&](int bs) {
       const char* st = ops + (size_t)(bs & 1) * OPS_STAGE;
       const bf16_t* sgt = (const bf16_t*)st;
       const float* sdh = (const float*)(st + OPS_G);
       const float* scp = (const float*)(st + OPS_G + OPS_F);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = g * 4 + r;
+      for (int r = 0; r < OR; ++r) {
+        const int row = g * OR + r;
         const float gi = (float)sgt[(row * 4 + 0) * 64 + wu], gj = (float)sgt[(row * 4 + 1) * 64 + wu];
         const float gf = (float)sgt[(row * 4 + 2) * 64 + wu], go = (float)sgt[(row * 4 + 3) * 64 + wu];
         const float cprev = scp[row * 64 + wu];
@@ -1026,11 +1094,14 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
       const bool tr = (a.dbg & 16) && blockIdx.x == 0 && tid == 0 && bs < 512;
       if (tr) a.trace[bs * 8 + 0] = wall_clock64();
       // ---- dh of the step after, summed in a fixed order: own block, then the peers' in workgroup order.
-      // Granule (source ws, row pair 2 g + h, unit wu) of this workgroup's block: {tag bs, rows 2h | 2h + 1 of the lane}
+      // Granule (source ws, row pair p, unit wu) of this workgroup's block: {tag bs, rows 2p | 2p + 1}.  A lane polls the
+      // granules that hold its own rows: pairs 2 g, 2 g + 1 at 16 rows, pair g at 8, and at 4 pair g / 2, of which it
+      // takes the half of row g
+      constexpr int NV = OR >= 2 ? OR / 2 : 1;
       f32x4 rec = ownp;
-      if (bs > 0 && CS > 1 && live) {
-        const u64* cur = xb0 + (size_t)(bs & 1) * CS * CS * GPD + (size_t)wgc * CS * GPD + (g * 2) * 64 + wu;
-        u64 v[CS > 1 ? CS - 1 : 1][2];
+      if (bs > 0 && CS > 1) {
+        const u64* cur = xb0 + (size_t)(bs & 1) * CS * CS * GPD + (size_t)wgc * CS * GPD + (g * OR / 2) * 64 + wu;
+        u64 v[CS > 1 ? CS - 1 : 1][NV];
         unsigned spins = 0, clk0 = 0;
         bool ok;
         do {
@@ -1039,12 +1110,12 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
           for (int sx = 0; sx < CS - 1; ++sx) {
             const int ws = sx < wgc ? sx : sx + 1;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) v[sx][h] = __hip_atomic_load(cur + (size_t)ws * GPD + h * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int h = 0; h < NV; ++h) v[sx][h] = __hip_atomic_load(cur + (size_t)ws * GPD + h * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
 #pragma unroll
           for (int sx = 0; sx < CS - 1; ++sx)
 #pragma unroll
-            for (int h = 0; h < 2; ++h) ok = ok && ((unsigned)(v[sx][h] >> 32) == (unsigned)bs);
+            for (int h = 0; h < NV; ++h) ok = ok && ((unsigned)(v[sx][h] >> 32) == (unsigned)bs);
           if (!ok && (++spins & 1023u) == 0) {
             if (__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { abortf[0] = 1; ok = true; }
             else if (ns_spin_timed_out(clk0)) { atomicExch(a.status, 2); abortf[0] = 1; ok = true; }
@@ -1054,23 +1125,27 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
 #pragma unroll
         for (int sx = 0; sx < CS - 1; ++sx)
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
+          for (int h = 0; h < NV; ++h) {
             const unsigned pay = (unsigned)v[sx][h];
-            rec[2 * h] += __uint_as_float(pay << 16);
-            rec[2 * h + 1] += __uint_as_float(pay & 0xffff0000u);
+            if constexpr (OR >= 2) {
+              rec[2 * h] += __uint_as_float(pay << 16);
+              rec[2 * h + 1] += __uint_as_float(pay & 0xffff0000u);
+            } else {
+              rec[0] += __uint_as_float((g & 1) ? (pay & 0xffff0000u) : (pay << 16));
+            }
           }
       }
       bf16_t* di = dgi + (size_t)buf * 16 * DGI_LD;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = g * 4 + r;
+      for (int r = 0; r < OR; ++r) {
+        const int row = g * OR + r;
         const int n = n0 + row;
         const float dh = dhx[r] + rec[r];
         const float d_o = dh * kdo[r];
         const float dc = dh * kdc[r] + dcc[r];
         float dgv[4] = {dc * ki[r], dc * kj[r], dc * kf[r], d_o};
         dcc[r] = dc * gfv[r];
-        if (t >= len[r] || n >= a.N || !live) {
+        if (t >= len[r] || n >= a.N) {
           dgv[0] = dgv[1] = dgv[2] = dgv[3] = 0.f;
           dcc[r] = 0.f;
         }
@@ -1091,24 +1166,34 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
         for (int j = 0; j < HB; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-          const bf16x8 af = *(const bf16x8*)(di + r16 * DGI_LD + ks * 32 + g * 8);
+          // narrow forms: the replicas of a row read the same address (a broadcast); image rows >= RPC are never read
+          const bf16x8 af = *(const bf16x8*)(di + arow * DGI_LD + ks * 32 + g * 8);
 #pragma unroll
           for (int j = 0; j < HB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bw[j][ks], acc[j], 0, 0, 0);
         }
         indep(bs + 1);
         if (tr) a.trace[bs * 8 + 3] = wall_clock64();
-        // D: column r16 = unit wu of workgroup j, rows g*4 + r.  A peer's tile -> its granules; the own tile stays here
+        // D: column r16 = unit wu of workgroup j, tile rows g*4 + r = image rows arow(g*4 + r).  A peer's tile -> its
+        // granules; the own tile's own rows stay here.  Who stores a granule: at 16 and 8 rows the group that owns the row
+        // pair; at 4 rows every group holds both pairs, groups 0 and 1 store pair g
         u64* nxt = xb0 + (size_t)((bs + 1) & 1) * CS * CS * GPD;
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
           if (j == wgc) {
-            ownp = acc[j];
-          } else if (live) {
+            if constexpr (RPC == 16) ownp = acc[j];
+            else
+#pragma unroll
+              for (int r = 0; r < OR; ++r) ownp[r] = own(acc[j], r);
+          } else if constexpr (RPC == 16) {
             u64* dst = nxt + (size_t)(j * CS + wgc) * GPD + (g * 2) * 64 + wu;
 #pragma unroll
             for (int h = 0; h < 2; ++h)
               __hip_atomic_store(dst + h * 64, ((u64)(unsigned)(bs + 1) << 32) | pack_bf16(acc[j][2 * h], acc[j][2 * h + 1]),
                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          } else if (RPC == 8 || g < 2) {
+            const unsigned pay = (RPC == 4 && g) ? pack_bf16(acc[j][2], acc[j][3]) : pack_bf16(acc[j][0], acc[j][1]);
+            __hip_atomic_store(nxt + (size_t)(j * CS + wgc) * GPD + g * 64 + wu, ((u64)(unsigned)(bs + 1) << 32) | pay,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
         if (tr) a.trace[bs * 8 + 7] = wall_clock64();
