@@ -412,6 +412,11 @@ typedef struct {
    * are unchanged.  0 (the default) = no clipping = the reference's cells as this build reads them (modules.py:41-42,
    * tacotron2.py:69-70 pass no cell_clip; hparam lstm_cell_clip). */
   float cell_clip;
+  /* ns_lstm_wide_fwd, dtype NS_F32 with f32_passes 3: with h_bf16 AND h_lo_bf16 the call writes the pre-split planes
+   * hi = bf16(h) into h_bf16 and lo = bf16(h - hi) here (both with leading dimension ld_h_bf16, rows as h; pad rows
+   * are not written) and exchanges h pre-split, through N * P * H * 4 more bytes of work (ns_lstm_wide_work_bytes()
+   * sees the planes).  h_lo_bf16 without h_bf16 is an argument error.  Ignored by every other call. */
+  void* h_lo_bf16;
 } ns_lstm_seq_params;
 int ns_lstm_seq_fwd(const ns_lstm_seq_params* p, ns_stream_t stream);
 int ns_lstm_seq_bwd(const ns_lstm_seq_params* p, ns_stream_t stream);
@@ -444,7 +449,8 @@ int ns_lstm_cluster_bwd(const ns_lstm_seq_params* fw, const ns_lstm_seq_params* 
  * Forward (workgroup = 16 rows x 8 units, all four gates): through the history array itself - the call first fills
  * h[:, 0..T) with an all-ones NaN sentinel (h only), the producers store h[t] write-through and every workgroup of the
  * row group polls and fetches h[t-1] with L1/L2-bypassing loads until no element is the sentinel: the data is its own
- * flag.
+ * flag.  With fp32 storage and the planes h_bf16 + h_lo_bf16 (ns_lstm_seq_params) the state travels pre-split as
+ * (hi, lo) bf16 pairs through an array in `work` instead, and the call writes the planes beside h.
  * Backward (workgroup = 8 rows x 32 units): every workgroup forms, from its own gate gradients, its partial sum of
  * dh[t-1] for all units and sends each peer that peer's block as {step tag, 2 x bf16} granules through an exchange
  * area in `work` (zeroed by the call; nothing is filled with the sentinel); the receiver adds the blocks in a fixed
@@ -454,7 +460,8 @@ int ns_lstm_cluster_bwd(const ns_lstm_seq_params* fw, const ns_lstm_seq_params* 
  * x H/16 (backward) must not exceed the device's CUs (256): every workgroup of the launch has to be resident at once.
  * ns_lstm_wide_supported() says whether a parameter block qualifies.  work: ns_lstm_wide_work_bytes() - a status word,
  * a trace area, the backward call's exchange area; work[0] (int) is the status word, non-zero after the call completes
- * = a wait timed out and the outputs are invalid (forward: they may then hold the sentinel). */
+ * = a wait timed out and the outputs are invalid (forward: h may then hold the sentinel; with h_lo_bf16 h and the planes
+ * are then incomplete instead). */
 int ns_lstm_wide_supported(const ns_lstm_seq_params* p, int backward);
 size_t ns_lstm_wide_work_bytes(const ns_lstm_seq_params* p);
 int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stream_t stream);

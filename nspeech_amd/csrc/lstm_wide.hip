@@ -19,6 +19,9 @@
 // 16-byte sc1 stores arrive as untorn 8-byte halves on gfx950 (MI355X_MICROARCH.md, hand-off table) and every element
 // of every fetched piece is checked, so a piece passes only when all of it is new; a stale piece is fetched again.
 // The cell update never produces the sentinel (a NaN of that bit pattern is rewritten to the canonical quiet NaN).
+// With fp32 storage and the optional planes h_bf16 / h_lo_bf16 (the SPLIT form, see the kernel) h travels pre-split as
+// (hi, lo) bf16 pairs through an exchange array in `work` instead: the producer splits each value once, the sweepers
+// load MFMA operands, and the planes, written on the side, serve the later products that would split or cast h again.
 // Why a probe instead of polling with the sweep itself: 256 CUs re-reading 64 KB each per pass is 16 MB per pass on the
 // memory side (sc1 loads do not hit in L2) - the passes then take 2.2 us each and the CU's own publish store queues
 // behind them.  Measured per step at the benchmark shape (profiles/r02_wide_trace.txt): arrival counters + drained
@@ -56,6 +59,7 @@ struct WideArgs {
   int* status;
   long long* trace;     // NS_WIDE_TRACE=1: [step][8] timestamps (100 MHz) of workgroup 0, else null
   int nub;              // forward kernel only: unit blocks (of 8) per row group, set by ns_lstm_wide_fwd
+  void* xch;            // forward kernel, split form: the exchange array [N * P][H / 8][hi x 8 | lo x 8] bf16 (in work)
 };
 __device__ __forceinline__ void wstamp(const WideArgs& a, int st, int k) {
   if (a.trace && blockIdx.x == 0 && threadIdx.x == 0 && st < 256) a.trace[st * 8 + k] = wall_clock64();
@@ -66,11 +70,14 @@ template <typename T> __device__ __forceinline__ bool has_sentinel(const u32x4& 
 template <> __device__ __forceinline__ bool has_sentinel<float>(const u32x4& v) {
   return (v[0] == 0xffffffffu) | (v[1] == 0xffffffffu) | (v[2] == 0xffffffffu) | (v[3] == 0xffffffffu);
 }
+// bf16: 0xffff is the largest 16-bit pattern, so a piece holds it iff the packed unsigned maximum of its halves is it
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
 template <> __device__ __forceinline__ bool has_sentinel<bf16_t>(const u32x4& v) {
-  bool b = false;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) b = b | ((v[i] & 0xffffu) == 0xffffu) | (v[i] >= 0xffff0000u);
-  return b;
+  const unsigned m = pk_max_u16(pk_max_u16(v[0], v[1]), pk_max_u16(v[2], v[3]));
+  return ((m & 0xffffu) == 0xffffu) | (m >= 0xffff0000u);
 }
 __device__ __forceinline__ float clean(float x, float*) { return __float_as_uint(x) == 0xffffffffu ? __uint_as_float(0x7fc00000u) : x; }
 __device__ __forceinline__ bf16_t clean(float x, bf16_t*) {
@@ -127,6 +134,14 @@ __device__ __forceinline__ unsigned sweep_progressive(const void* base, size_t b
     }
     ++spins;
     if (done == ALLL) {
+      if constexpr (sizeof(T) == 2) {        // all pieces at once first (the usual outcome: none is stale)
+        u32x4 m = v[0];
+#pragma unroll
+        for (int l = 1; l < NL; ++l)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) m[i] = pk_max_u16(m[i], v[l][i]);
+        if (!__any(has_sentinel<T>(m))) return spins;
+      }
       unsigned stale = 0u;
 #pragma unroll
       for (int l = 0; l < NL; ++l) if (__any(has_sentinel<T>(v[l]))) stale |= 1u << l;
@@ -150,9 +165,22 @@ __device__ __forceinline__ unsigned sweep_progressive(const void* base, size_t b
 // A PROBER wave - a third cell-side wave that polls for the whole workgroup with nothing else in its memory queue and
 // hands the producers' bits to the sweepers in LDS - was tried in round 2 and round 3 and was slower forward, 5.25
 // against 5.04 us per step: the sweepers keep their own probes.
+// SPLIT (T = float, PASSES = 3, both planes given): h travels pre-split, hi = bf16(h) and lo = bf16(h - hi), instead of
+// as fp32.  The cell waves have each value in a register exactly once and split it there; a sweeper's pieces are then
+// the MFMA A operands as loaded - no conversion between "state arrives" and the products, where the fp32 form has every
+// sweeper lane of every workgroup of the row group split its 32 values per step (the same 16 x H values, H / 8 times
+// over).  The exchange goes through an array of its own (in work): [row][unit block][hi x 8 | lo x 8], so a producer
+// still owns 32 contiguous bytes of a row and every store, probe and sweep address is the fp32 form's.  (Exchanging
+// through the two planes themselves was measured first: 1.08 ms a launch against 1.06 for this layout with the same
+// sentinel check - a producer's two 16-byte stores then land in lines it shares with its neighbours - and both lost
+// to the fp32 form's 1.02 until the bf16 check became the packed maximum of has_sentinel<bf16_t>: eight compares a
+// piece cost what the split had saved.  profiles/wide_split.txt.)
+// That array carries the sentinel; the planes p.h_bf16 / p.h_lo_bf16 and the fp32 h are written with plain stores
+// behind the publish (later kernels read them) and are not filled.
 constexpr int WTF = WT + 128;
-template <typename T, int PASSES, int NCH>
+template <typename T, int PASSES, int NCH, bool SPLIT>
 __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
+  static_assert(!SPLIT || (sizeof(T) == 4 && PASSES == 3), "the split form is the fp32 three-pass arrangement");
   // Partial sums, sweepers -> cell waves.  Row stride = 4 mod 16 floats: conflict-free for the MFMA C layout's writes
   // (+1 is not).  Two images by step parity (LDS hand-over audit, round 3): the barrier of step t orders the sweepers'
   // writes before the cell waves' reads, but a sweeper whose K slice does not hold this workgroup's own units needs
@@ -160,7 +188,7 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
   // the two memory round trips every sweep takes.  With two, image (t & 1) is written again in step t+2, which a sweeper
   // enters through the barrier of step t+1, and the cell waves reach that barrier after their reads of step t.
   __shared__ float red[2][WW][16][36];
-  __shared__ __attribute__((aligned(16))) T hst[16][8];
+  __shared__ __attribute__((aligned(16))) T hst[16][8];      // SPLIT: [plane][16][8] bf16, the same 512 bytes
   __shared__ int abortf;
   const ns_lstm_seq_params& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -168,7 +196,11 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
   const int rg = blockIdx.x / NUB, ub = blockIdx.x % NUB;
   const int n0 = rg * 16, u0 = ub * 8;
   if (tid == 0) abortf = 0;                          // (audit) initialised in front of the barrier below
-  const size_t hbytes = (size_t)p.N * p.P * p.ld_h * sizeof(T);
+  // what is exchanged: the history array, or (SPLIT) the array of (hi x 8 | lo x 8) pieces in work
+  const void* const xbase = SPLIT ? (const void*)a.xch : (const void*)p.h;
+  const long xld = SPLIT ? (long)p.H : (long)p.ld_h;             // in units of XSZ bytes: a unit's (hi, lo) pair or its value
+  constexpr unsigned XSZ = (unsigned)sizeof(T);
+  const size_t hbytes = (size_t)p.N * p.P * xld * XSZ;
   constexpr int PPC = 8 * (int)sizeof(T) / 16;        // 16-byte pieces per 8-value fragment (2 for fp32, 1 for bf16)
   __syncthreads();
 
@@ -200,18 +232,27 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       wstamp(a, t, 0);
       if (t > 0) {
-        const unsigned rowoff = ok ? (unsigned)(((long)(n0 + r16) * p.P + p.padl + t - 1) * p.ld_h + k0 + g * 8) * (unsigned)sizeof(T) : 0x80000000u;
+        const unsigned rowoff = ok ? (unsigned)(((long)(n0 + r16) * p.P + p.padl + t - 1) * xld + k0 + g * 8) * XSZ : 0x80000000u;
         u32x4 v[NCH * PPC];
-        const unsigned prow = (unsigned)(((long)(n0 + prb) * p.P + p.padl + t - 1) * p.ld_h + k0) * (unsigned)sizeof(T);
-        const unsigned got = sweep_progressive<T, NCH * PPC, PPC, 4>(p.h, hbytes, prow, 8u * (unsigned)sizeof(T), rowoff, 16u, 32u * (unsigned)sizeof(T),
-                                                                     v, lane, a.status, &abortf, 1, a.trace && t < 256 ? a.trace + t * 8 + 6 : nullptr);
+        const unsigned prow = (unsigned)(((long)(n0 + prb) * p.P + p.padl + t - 1) * xld + k0) * XSZ;
+        long long* const tslot = a.trace && t < 256 ? a.trace + t * 8 + 6 : nullptr;
+        unsigned got;
+        // SPLIT: the same addresses as the fp32 form; piece 0 of a chunk is the lane's hi fragment, piece 1 its lo
+        // fragment (a lo piece that lags its hi piece fails the check of every piece and is fetched again)
+        if constexpr (SPLIT)
+          got = sweep_progressive<bf16_t, 2 * NCH, 2, 4>(xbase, hbytes, prow, 32u, rowoff, 16u, 128u, v, lane, a.status, &abortf, 1, tslot);
+        else
+          got = sweep_progressive<T, NCH * PPC, PPC, 4>(xbase, hbytes, prow, 8u * XSZ, rowoff, 16u, 32u * XSZ, v, lane, a.status, &abortf, 1, tslot);
         wstamp(a, t, 1);
         if (a.trace && blockIdx.x == 0 && tid == 0 && t < 256) a.trace[t * 8 + 5] = got;
         if (got) {
 #pragma unroll
           for (int c = 0; c < NCH; ++c) {
             bf16x8 ah, al;
-            if constexpr (sizeof(T) == 4) {
+            if constexpr (SPLIT) {
+              ah = *(bf16x8*)&v[2 * c];
+              al = *(bf16x8*)&v[2 * c + 1];
+            } else if constexpr (sizeof(T) == 4) {
               const u32x4 x = v[2 * c], y = v[2 * c + 1];
               const float f[8] = {__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), __uint_as_float(x[3]),
                                   __uint_as_float(y[0]), __uint_as_float(y[1]), __uint_as_float(y[2]), __uint_as_float(y[3])};
@@ -244,7 +285,7 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
   const int en = n0 + er;
   const bool eok = en < p.N;
   const int elen = (eok && p.lengths) ? p.lengths[en] : p.T;
-  const auto hrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.h, 0, (int)hbytes, 0x00020000);
+  const auto hrs = __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, (int)hbytes, 0x00020000);
   const bool tr = a.trace && blockIdx.x == 0 && e == 0;
   float cst = 0.f;
   float hprev = 0.f;          // zoneout: this thread's h of the step before (fp32, before the store's rounding)
@@ -285,22 +326,44 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
     if (t >= elen) { cst = 0.f; hv = 0.f; gi = gj = gf = go = 0.f; }
     // (audit) hst: written and read by the SAME cell wave (wave w owns rows 8w .. 8w+7 on both sides), so the release
     // fence + wave barrier below is all the ordering it needs; no other role touches it
-    hst[er][eu] = clean(hv, (T*)nullptr);
+    if constexpr (SPLIT) {
+      bf16_t* hsp = (bf16_t*)&hst[0][0];
+      const bf16_t hi = clean(hv, (bf16_t*)nullptr);
+      hsp[er * 8 + eu] = hi;
+      hsp[128 + er * 8 + eu] = clean(hv - (float)hi, (bf16_t*)nullptr);
+    } else {
+      hst[er][eu] = clean(hv, (T*)nullptr);
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // LDS write -> read inside this wave (its own 8 rows)
     __builtin_amdgcn_wave_barrier();
-    // ---- publish h[t]: 16-byte write-through stores, each cell wave its own 8 rows
+    // ---- publish h[t]: 16-byte write-through stores, each cell wave its own 8 rows (SPLIT: the hi and the lo piece)
     if (lane < 8 * PPC) {
       const int row = (wave - WW) * 8 + lane / PPC, pc = lane % PPC;
       if (n0 + row < p.N) {
-        const u32x4 x = *(const u32x4*)((const char*)&hst[row][0] + pc * 16);
-        const unsigned off = (unsigned)(((long)(n0 + row) * p.P + p.padl + t) * p.ld_h + u0) * (unsigned)sizeof(T) + pc * 16;
-        __builtin_amdgcn_raw_buffer_store_b128(x, hrs, off, 0, 16);            // aux 16 = sc1
+        if constexpr (SPLIT) {
+          const u32x4 x = *(const u32x4*)((const char*)&hst[0][0] + pc * 256 + row * 16);
+          const unsigned off = (unsigned)(((long)(n0 + row) * p.P + p.padl + t) * xld + u0) * XSZ + pc * 16;
+          __builtin_amdgcn_raw_buffer_store_b128(x, hrs, off, 0, 16);
+        } else {
+          const u32x4 x = *(const u32x4*)((const char*)&hst[row][0] + pc * 16);
+          const unsigned off = (unsigned)(((long)(n0 + row) * p.P + p.padl + t) * p.ld_h + u0) * (unsigned)sizeof(T) + pc * 16;
+          __builtin_amdgcn_raw_buffer_store_b128(x, hrs, off, 0, 16);            // aux 16 = sc1
+        }
       }
     }
     if (tr && t < 256) a.trace[t * 8 + 4] = wall_clock64();
-    // ---- what only the backward pass reads, next step's input gates
+    // ---- what only later kernels read (SPLIT: the two planes, 16-byte pieces by the next 16 lanes), next step's input gates
+    if constexpr (SPLIT) {
+      if (lane >= 16 && lane < 32) {
+        const int row = (wave - WW) * 8 + (lane - 16) / 2, pc = lane & 1;
+        if (n0 + row < p.N)
+          *(u32x4*)((bf16_t*)(pc ? p.h_lo_bf16 : p.h_bf16) + ((long)(n0 + row) * p.P + p.padl + t) * p.ld_h_bf16 + u0) =
+              *(const u32x4*)((const char*)&hst[0][0] + pc * 256 + row * 16);
+      }
+    }
     if (eok) {
       const long rowi = (long)en * p.P + p.padl + t;
+      if constexpr (SPLIT) ((float*)p.h)[rowi * p.ld_h + u0 + eu] = clean(hv, (float*)nullptr);     // read by later kernels only
       p.c[rowi * H + u0 + eu] = cst;
       if (p.gates) {
         T* gp = (T*)p.gates + rowi * 4 * H + u0 + eu;
@@ -340,7 +403,13 @@ typedef unsigned long long ps_u64;
 __device__ __forceinline__ void ps_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int UPB = 32;                      // units per workgroup
-template <typename T, int NT>                // NT = destination tiles per product wave = H / 128
+// LANES: the operand image has 8 rows and an MFMA tile 16, so half of every product is padding.  With LANES the A
+// fragment of tile row r16 is read from image row r16 & 7 (an LDS broadcast, as in lstm_cluster2p_bwd_kernel): lane
+// groups 2 and 3 then hold bit-identical replicas of rows 0 .. 3 and 4 .. 7, and EVERY lane converts, packs and stores
+// one granule per tile (group g: row pair 2 (g & 1) + (g >> 1)) instead of groups 0 and 1 two each - 8 store
+// instructions per wave and step instead of 16, on a phase that is bound by instruction issue.  Same granules, same
+// addresses, same bits.  LANES = false is the form before that (NS_WIDE_LANES=0, read per call; the tests compare them).
+template <typename T, int NT, bool LANES>    // NT = destination tiles per product wave = H / 128
 __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u64* xbuf) {
   constexpr int TB = UPB / 16;               // 16-unit tiles per block
   constexpr int KO = 4 * UPB, KS = KO / 32;  // own gate columns, k-steps of the product
@@ -349,7 +418,7 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
   constexpr int LDW = KO + 8;                // bf16 per row of the operand image
   constexpr int KSR = KS - 1;                // k-steps of the weights kept in registers (the last one: LDS)
   extern __shared__ __attribute__((aligned(16))) char ps_smem[];
-  bf16_t* dgi = (bf16_t*)ps_smem;                               // [16][LDW], rows 8 .. 15 stay zero
+  bf16_t* dgi = (bf16_t*)ps_smem;                               // [16][LDW], rows 8 .. 15 stay zero (LANES: unread)
   float* red = (float*)(dgi + 16 * LDW);                        // [PSW][ITEMS][2]
   float* ownp = red + PSW * ITEMS * 2;                          // [ITEMS][2]
   int* abortf = (int*)(ownp + ITEMS * 2);                       // [4]
@@ -441,7 +510,7 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
       if (bs + 1 < p.T) {
         bf16x8 af[KS];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) af[ks] = *(const bf16x8*)(dgi + r16 * LDW + 32 * ks + 8 * g);
+        for (int ks = 0; ks < KS; ++ks) af[ks] = *(const bf16x8*)(dgi + (LANES ? (r16 & 7) : r16) * LDW + 32 * ks + 8 * g);
         ps_u64* nxt = xb0 + (size_t)((bs + 1) & 1) * NUB * NUB * ITEMS;
         // four tiles at a time, k-step outermost: four independent accumulator chains keep the matrix pipe issuing
         // (one tile after the other is a chain of KS dependent MFMAs each), and the first group's stores go out under
@@ -463,18 +532,31 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
             // D: column r16 = unit of the destination tile, rows 4 g + q (rows 0 .. 7 are this workgroup's):
             // item = unit in the destination block + UPB * (row pair)
             const int tile = wave * NT + j0 + jj, dest = tile / TB, ui = (tile % TB) * 16 + r16;
-            if (g < 2) {
+            const ps_u64 tg = (ps_u64)(unsigned)(bs + 1) << 32;
+            auto granule = [&](float x0, float x1) {
+              const bf16_t b0 = (bf16_t)x0, b1 = (bf16_t)x1;
+              return tg | (ps_u64)((unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16));
+            };
+            if constexpr (LANES) {
+              // rows 4 g + q of D replicate rows 4 (g & 1) + q: this lane takes the pair q = 2 hf, 2 hf + 1 (selects, no
+              // dynamic register index) = row pair 2 (g & 1) + hf
+              const int gp = g & 1, hf = g >> 1;
+              const float x0 = hf ? acc[jj][2] : acc[jj][0], x1 = hf ? acc[jj][3] : acc[jj][1];
+              const int item = ui + UPB * (2 * gp + hf);
+              if (dest == ub) {
+                ownp[item * 2] = x0; ownp[item * 2 + 1] = x1;
+              } else {
+                __hip_atomic_store((NS_GLOBAL ps_u64*)(nxt + ((size_t)dest * NUB + ub) * ITEMS + item), granule(x0, x1), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+              }
+            } else if (g < 2) {
               if (dest == ub) {
                 ownp[(ui + UPB * (2 * g)) * 2] = acc[jj][0]; ownp[(ui + UPB * (2 * g)) * 2 + 1] = acc[jj][1];
                 ownp[(ui + UPB * (2 * g + 1)) * 2] = acc[jj][2]; ownp[(ui + UPB * (2 * g + 1)) * 2 + 1] = acc[jj][3];
               } else {
                 NS_GLOBAL ps_u64* dst = (NS_GLOBAL ps_u64*)(nxt + ((size_t)dest * NUB + ub) * ITEMS + ui + 2 * UPB * g);
-                const ps_u64 tg = (ps_u64)(unsigned)(bs + 1) << 32;
-                const bf16_t b0 = (bf16_t)acc[jj][0], b1 = (bf16_t)acc[jj][1], b2 = (bf16_t)acc[jj][2], b3 = (bf16_t)acc[jj][3];
-                const unsigned p01 = (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
-                const unsigned p23 = (unsigned)__builtin_bit_cast(unsigned short, b2) | ((unsigned)__builtin_bit_cast(unsigned short, b3) << 16);
-                __hip_atomic_store(dst, tg | p01, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(dst + UPB, tg | p23, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(dst, granule(acc[jj][0], acc[jj][1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(dst + UPB, granule(acc[jj][2], acc[jj][3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               }
             }
           }
@@ -606,18 +688,26 @@ size_t ps_exchange_bytes(const ns_lstm_seq_params* p) {
 extern "C" int ns_lstm_wide_supported(const ns_lstm_seq_params* p, int backward) { return wide_shape_ok(p, backward) ? 1 : 0; }
 // work: status word (256 bytes reserved), the NS_WIDE_TRACE timestamps, the 16-byte-aligned exchange area of the
 // backward kernel for every shape ns_lstm_wide_bwd can take (the call is not told the direction)
-extern "C" size_t ns_lstm_wide_work_bytes(const ns_lstm_seq_params* p) {
-  if (!p) return 0;
+static size_t wide_work_base(const ns_lstm_seq_params* p) {
   const bool bwd_fits = (p->H == 256 || p->H == 512 || p->H == 1024) && (p->N + 15) / 16 * (p->H / 16) <= ns_device_cus();
   return 256 + WIDE_TRACE_BYTES + (bwd_fits ? ps_exchange_bytes(p) : 0) + 64;
 }
+// the split forward form's exchange array: behind everything else, at the next 256-byte boundary of the address
+static void* wide_xch(const ns_lstm_seq_params* p, void* work) {
+  return (void*)(((uintptr_t)work + wide_work_base(p) + 255) & ~(uintptr_t)255);
+}
+extern "C" size_t ns_lstm_wide_work_bytes(const ns_lstm_seq_params* p) {
+  if (!p) return 0;
+  // with both planes given (the split forward form): + [N * P][H] (hi, lo) pairs
+  return wide_work_base(p) + ((p->h_bf16 && p->h_lo_bf16) ? 256 + (size_t)p->N * p->P * p->H * 4 : 0);
+}
 
-template <typename T, int PASSES>
+template <typename T, int PASSES, bool SPLIT>
 static int launch_wide_fwd(const WideArgs& a, int grid, hipStream_t s) {
   switch (a.p.H) {
-    case 256: hipLaunchKernelGGL((lstm_wide_fwd_kernel<T, PASSES, 1>), dim3(grid), dim3(WTF), 0, s, a); break;
-    case 512: hipLaunchKernelGGL((lstm_wide_fwd_kernel<T, PASSES, 2>), dim3(grid), dim3(WTF), 0, s, a); break;
-    default: hipLaunchKernelGGL((lstm_wide_fwd_kernel<T, PASSES, 4>), dim3(grid), dim3(WTF), 0, s, a); break;
+    case 256: hipLaunchKernelGGL((lstm_wide_fwd_kernel<T, PASSES, 1, SPLIT>), dim3(grid), dim3(WTF), 0, s, a); break;
+    case 512: hipLaunchKernelGGL((lstm_wide_fwd_kernel<T, PASSES, 2, SPLIT>), dim3(grid), dim3(WTF), 0, s, a); break;
+    default: hipLaunchKernelGGL((lstm_wide_fwd_kernel<T, PASSES, 4, SPLIT>), dim3(grid), dim3(WTF), 0, s, a); break;
   }
   NS_CHECK_LAUNCH("lstm_wide_fwd");
   return NS_OK;
@@ -625,14 +715,25 @@ static int launch_wide_fwd(const WideArgs& a, int grid, hipStream_t s) {
 
 // Whole-sequence forward recurrence of one wide LSTM cell, one launch (see the header of this file).  Same parameter
 // block and outputs as ns_lstm_seq_fwd.  work: ns_lstm_wide_work_bytes(); work[0] (int) is a status word, non-zero
-// after the call completes = a wait timed out and the outputs are invalid.
+// after the call completes = a wait timed out and the outputs are invalid (h may then hold the sentinel; in the
+// split form h and the planes are then incomplete).  With fp32 storage and both h_bf16 and h_lo_bf16 the call takes the
+// split form: it also writes hi = bf16(h) and lo = bf16(h - hi) there (leading dimension ld_h_bf16) and exchanges h
+// as those pairs through an array of its own in work.
 extern "C" int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   NS_CHECK_ARG(p && work, "ns_lstm_wide_fwd: null");
+  NS_CHECK_ARG(!p->h_lo_bf16 || p->h_bf16, "ns_lstm_wide_fwd: h_lo_bf16 without h_bf16 (the lo plane goes with the hi plane)");
+  const bool split = p->dtype == NS_F32 && p->f32_passes == 3 && p->h_bf16 && p->h_lo_bf16;
   NS_CHECK_ARG(wide_shape_ok(p, 0), "ns_lstm_wide_fwd: unsupported (needs H in {256, 512, 1024}, row groups x H/8 <= 256, "
                "fp32 with pre-split whT_hi / whT_lo and f32_passes 3, or bf16)");
+  if (split) {
+    NS_CHECK_ARG(p->ld_h_bf16 >= p->H && p->ld_h_bf16 % 8 == 0 && ((uintptr_t)p->h_bf16 & 15) == 0 && ((uintptr_t)p->h_lo_bf16 & 15) == 0,
+                 "ns_lstm_wide_fwd: h_bf16 / h_lo_bf16 need 16-byte alignment and ld_h_bf16 %% 8 == 0, >= H");
+    NS_CHECK_ARG((double)p->N * p->P * p->H * 4 < 2.0e9, "ns_lstm_wide_fwd: exchange array beyond a buffer resource");
+  }
   WideArgs a;
   a.p = *p; a.status = (int*)work; a.nub = p->H / 8;
+  a.xch = split ? wide_xch(p, work) : nullptr;
   a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
   int rc = ns_zero_async(work, 256, s);
   if (rc) return rc;
@@ -640,17 +741,23 @@ extern "C" int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stre
   if (p->dtype == NS_BF16) {
     hipLaunchKernelGGL(wide_fill_kernel<bf16_t>, dim3(512), dim3(256), 0, s, (bf16_t*)p->h, p->N, (long)p->P, p->padl, p->T, (long)p->ld_h, p->H);
     NS_CHECK_LAUNCH("lstm_wide_fill");
-    return launch_wide_fwd<bf16_t, 1>(a, grid, s);
+    return launch_wide_fwd<bf16_t, 1, false>(a, grid, s);
+  }
+  if (split) {               // the exchange array carries the sentinel (the same bytes as the fp32 fill); h is not filled
+    hipLaunchKernelGGL(wide_fill_kernel<float>, dim3(512), dim3(256), 0, s, (float*)a.xch, p->N, (long)p->P, p->padl, p->T, (long)p->H, p->H);
+    NS_CHECK_LAUNCH("lstm_wide_fill");
+    return launch_wide_fwd<float, 3, true>(a, grid, s);
   }
   hipLaunchKernelGGL(wide_fill_kernel<float>, dim3(512), dim3(256), 0, s, (float*)p->h, p->N, (long)p->P, p->padl, p->T, (long)p->ld_h, p->H);
   NS_CHECK_LAUNCH("lstm_wide_fill");
-  return launch_wide_fwd<float, 3>(a, grid, s);
+  return launch_wide_fwd<float, 3, false>(a, grid, s);
 }
 
-// The instantiations of the backward kernel, [storage type bf16, fp32][H / 128 = 2, 4, 8]
+// The instantiations of the backward kernel, [all-lane publish off, on][storage type bf16, fp32][H / 128 = 2, 4, 8]
 typedef void (*wide_bwd_kernel_t)(WideArgs, ps_u64*);
-#define NS_WIDE_BWD_FORMS(T_) {lstm_wide_bwd_ps_kernel<T_, 2>, lstm_wide_bwd_ps_kernel<T_, 4>, lstm_wide_bwd_ps_kernel<T_, 8>}
-static const wide_bwd_kernel_t wide_bwd_forms[2][3] = {NS_WIDE_BWD_FORMS(bf16_t), NS_WIDE_BWD_FORMS(float)};
+#define NS_WIDE_BWD_FORMS(T_, L_) {lstm_wide_bwd_ps_kernel<T_, 2, L_>, lstm_wide_bwd_ps_kernel<T_, 4, L_>, lstm_wide_bwd_ps_kernel<T_, 8, L_>}
+static const wide_bwd_kernel_t wide_bwd_forms[2][2][3] = {{NS_WIDE_BWD_FORMS(bf16_t, false), NS_WIDE_BWD_FORMS(float, false)},
+                                                          {NS_WIDE_BWD_FORMS(bf16_t, true), NS_WIDE_BWD_FORMS(float, true)}};
 #undef NS_WIDE_BWD_FORMS
 
 // Whole-sequence backward recurrence (the gate gradients of every step), one launch.  Same parameter block and outputs
@@ -661,7 +768,7 @@ extern "C" int ns_lstm_wide_bwd(const ns_lstm_seq_params* p, void* work, ns_stre
   NS_CHECK_ARG(wide_shape_ok(p, 1), "ns_lstm_wide_bwd: unsupported (needs H in {256, 512, 1024}, row groups x H/16 <= 256, "
                "bf16, or fp32 with wh_bf16 + dgates_bf16 and f32_passes 1)");
   WideArgs a;
-  a.p = *p; a.status = (int*)work; a.nub = 0;
+  a.p = *p; a.status = (int*)work; a.nub = 0; a.xch = nullptr;
   a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
   int rc = ns_zero_async(work, 256, s);
   if (rc) return rc;
@@ -674,11 +781,14 @@ extern "C" int ns_lstm_wide_bwd(const ns_lstm_seq_params* p, void* work, ns_stre
   const size_t ldsb = (size_t)16 * (4 * UPB + 8) * 2 + sizeof(float) * (PSW * items * 2 + items * 2) + 16 + (size_t)PSW * nt * 64 * 16;
   static bool attr = false;
   if (!attr) {
-    for (const auto& widths : wide_bwd_forms)
-      for (wide_bwd_kernel_t k : widths) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const auto& lanes : wide_bwd_forms)
+      for (const auto& widths : lanes)
+        for (wide_bwd_kernel_t k : widths) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL(wide_bwd_forms[p->dtype == NS_BF16 ? 0 : 1][nt == 2 ? 0 : nt == 4 ? 1 : 2], dim3(grid), dim3(PST), ldsb, s, a, xbuf);
+  const char* le = getenv("NS_WIDE_LANES");           // "0": the publish by lane groups 0 and 1 only (the form before)
+  const int lanes = (le && le[0] == '0' && !le[1]) ? 0 : 1;
+  hipLaunchKernelGGL(wide_bwd_forms[lanes][p->dtype == NS_BF16 ? 0 : 1][nt == 2 ? 0 : nt == 4 ? 1 : 2], dim3(grid), dim3(PST), ldsb, s, a, xbuf);
   NS_CHECK_LAUNCH("lstm_wide_bwd_ps");
   return NS_OK;
 }

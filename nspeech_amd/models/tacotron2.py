@@ -752,15 +752,19 @@ class Tacotron2(object):
     def _x256_fits(self, rows, cout):
         return rows >= 1024 and ((rows + 255) // 256) * ((cout + 255) // 256) >= 96
 
-    def _xg_gemm(self, x, xg, rows, cin, cout, key, woff, boff, D=None):
+    def _xg_gemm(self, x, xg, rows, cin, cout, key, woff, boff, D=None, presplit=None):
         """Hoisted LSTM input product xg = x . W_x + b.  With a k-contiguous shadow of W_x (refresh_shadows) it runs on the
-        256-tile kernel: three segments over pre-split operands where the storage is fp32 (mixed), one where it is bf16."""
+        256-tile kernel: three segments over pre-split operands where the storage is fp32 (mixed), one where it is bf16.
+        presplit: the (hi, lo) bf16 planes of x where its producer wrote them already (no split_hi_lo then)."""
         D = D or self.T
         sh = self.tsh.get(key)
         if self._x256_fits(rows, cout) and D == torch.float32 and key + "_hi" in self.tsh:
-            xh = self._buf("xgs_hi_" + key, rows * cin, torch.bfloat16)
-            xl = self._buf("xgs_lo_" + key, rows * cin, torch.bfloat16)
-            ops.split_hi_lo(x, xh, xl, rows * cin)
+            if presplit is not None:
+                xh, xl = presplit
+            else:
+                xh = self._buf("xgs_hi_" + key, rows * cin, torch.bfloat16)
+                xl = self._buf("xgs_lo_" + key, rows * cin, torch.bfloat16)
+                ops.split_hi_lo(x, xh, xl, rows * cin)
             ops.gemm(xh, self.tsh[key + "_hi"], xg, rows, cout, cin, cin, cin, cout, a_mode=0, b_mode=0, a_lo=xl,
                      b_lo=self.tsh[key + "_lo"], bias=self.flat_p, bias_off=boff)
         elif sh is not None and self._x256_fits(rows, cout) and D == torch.bfloat16 and sh.dtype == torch.bfloat16:
@@ -814,16 +818,27 @@ class Tacotron2(object):
                 ops.zoneout_seed(base, self.global_step, 2 * layer + 1))
 
     def _run_lstm(self, direction, tag, *a, **kw):
-        """One decoder LSTM over all steps: the persistent wide-cell kernel when it applies, else one launch per step."""
+        """One decoder LSTM over all steps: the persistent wide-cell kernel when it applies, else one launch per step.
+        Returns True where the wide kernel ran (only it writes the h planes of h_bf16 / h_lo_bf16)."""
         p = ops.lstm_seq_params(*a, **kw)
         if self.use_wide and ops.lstm_wide_supported(p, direction == "bwd"):
             w = self._buf("lstm_wide_work_%s_%s" % (tag, direction), ops.lstm_wide_work_floats(p), torch.float32)
             ops.lstm_wide(direction, p, w)
             self._status_words[(tag, direction)] = w
             self.last_paths["%s:%s" % (tag, direction)] = "wide"
-        else:
-            ops.lstm_seq_call(direction, p)
-            self.last_paths["%s:%s" % (tag, direction)] = "step"
+            return True
+        ops.lstm_seq_call(direction, p)
+        self.last_paths["%s:%s" % (tag, direction)] = "step"
+        return False
+
+    def _h_planes(self, name, rows, D):
+        """The (hi, lo) bf16 planes of a decoder LSTM's h for the wide forward kernel in `mixed` mode, or (None, None).  Two
+        halves of ONE buffer, in the slot layout of h (the pad rows stay zero): the hi half is the bf16 copy of h that the
+        weight gradients read (the buffer of that name), hi / lo the pre-split operand of the next input product."""
+        if self.mode != "mixed" or not self.use_wide:
+            return None, None
+        b = self._buf(name, 2 * rows * D, torch.bfloat16)
+        return b, b[rows * D:]
 
     use_cluster = True      # persistent whole-sequence BiLSTM kernels where the shape allows
     use_attn_cluster = True # persistent attention-RNN cluster kernels where the shape allows
@@ -1068,17 +1083,24 @@ class Tacotron2(object):
         c1 = self._buf("dec_c1", rows * D, torch.float32)
         g1 = self._buf("dec_g1", rows * 4 * D, T_)
         self._tick("dec_lstm:xg1")
-        self._run_lstm("fwd", "dec1", N, S, D, S1, 1, xg1, 4 * D, self.tsh["l1_whT"], None, None, False, h1, D, c1, g1,
-                       whT_hi=self.tsh.get("l1_whT_hi"), whT_lo=self.tsh.get("l1_whT_lo"), zoneout=self.zoneout_args(1))
+        h1hi, h1lo = self._h_planes("dec_h1_16", rows, D)
+        wide1 = self._run_lstm("fwd", "dec1", N, S, D, S1, 1, xg1, 4 * D, self.tsh["l1_whT"], None, None, False, h1, D, c1, g1,
+                               whT_hi=self.tsh.get("l1_whT_hi"), whT_lo=self.tsh.get("l1_whT_lo"), zoneout=self.zoneout_args(1),
+                               h_bf16=h1hi, ld_h_bf16=D, h_lo_bf16=h1lo)
         self._tick("dec_lstm:loop1")
         xg2 = self._buf("dec_xg2", rows * 4 * D, torch.float32)
-        self._xg_gemm(h1, xg2, rows, D, 4 * D, "l2_xT", k2, self._o("decoder/lstm_2/bias"))
+        self._xg_gemm(h1, xg2, rows, D, 4 * D, "l2_xT", k2, self._o("decoder/lstm_2/bias"),
+                      presplit=(h1hi, h1lo) if (wide1 and h1hi is not None) else None)
         h2 = self._buf("dec_h2", rows * D, T_)
         c2 = self._buf("dec_c2", rows * D, torch.float32)
         g2 = self._buf("dec_g2", rows * 4 * D, T_)
         self._tick("dec_lstm:xg2")
-        self._run_lstm("fwd", "dec2", N, S, D, S1, 1, xg2, 4 * D, self.tsh["l2_whT"], None, None, False, h2, D, c2, g2,
-                       whT_hi=self.tsh.get("l2_whT_hi"), whT_lo=self.tsh.get("l2_whT_lo"), zoneout=self.zoneout_args(2))
+        h2hi, h2lo = self._h_planes("dec_h2_16", rows, D)
+        wide2 = self._run_lstm("fwd", "dec2", N, S, D, S1, 1, xg2, 4 * D, self.tsh["l2_whT"], None, None, False, h2, D, c2, g2,
+                               whT_hi=self.tsh.get("l2_whT_hi"), whT_lo=self.tsh.get("l2_whT_lo"), zoneout=self.zoneout_args(2),
+                               h_bf16=h2hi, ld_h_bf16=D, h_lo_bf16=h2lo)
+        # the forward kernels wrote bf16(h1) / bf16(h2) into the weight gradients' copies: no cast in the backward pass
+        self._h16_written = (wide1 and h1hi is not None, wide2 and h2hi is not None)
         self._tick("dec_lstm:loop2")
         dec = self._buf("dec_out", rows * M * r, torch.float32)
         ops.gemm(h2, self._W(self.T), dec, rows, M * r, D, D, M * r, M * r, b_mode=1,
@@ -1282,9 +1304,13 @@ class Tacotron2(object):
                 ops.cast2d(src, rows, cols, cols, dst, cols, False)
         h1b, h2b = b16("dec_h1_16", h1, D), b16("dec_h2_16", h2, D)
 
+        h1_done, h2_done = getattr(self, "_h16_written", (False, False))      # the hi planes of the wide forward kernels
+
         def lstm2_wgrads():
-            cast16(h1b, h1, D)
-            cast16(h2b, h2, D)
+            if not h1_done:
+                cast16(h1b, h1, D)
+            if not h2_done:
+                cast16(h2b, h2, D)
             self._lstm_wgrads(h1b, D, h2b, D, dg2b if dg2b is not None else dg2, rows, k2, "decoder/lstm_2/bias")
         self._defer("decoder", lstm2_wgrads, pure=True)
         if "decoder2" in self.queue_groups:      # LSTM 2's weight gradients under LSTM 1's recurrence (measured: worse)

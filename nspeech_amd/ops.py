@@ -505,9 +505,13 @@ class CastBatch(object):
 def lstm_seq_params(N, T, H, P, padl, xg, ld_xg, whT, wh, lengths, reverse, h, ld_h, c, gates,
                     dh=None, ld_dh=0, dgates=None, work=None, xg_off=0, whT_off=0, wh_off=0, h_off=0, dh_off=0,
                     forget_bias=1.0, whT_hi=None, whT_lo=None, wh_bf16=None, wh_bf16_off=0, dgates_bf16=None,
-                    h_bf16=None, h_bf16_off=0, ld_h_bf16=0, dtype=None, zoneout=None):
-    """zoneout = (thr_cell, thr_output, seed_cell, seed_output) or None (plain cell), see zoneout_threshold()."""
+                    h_bf16=None, h_bf16_off=0, ld_h_bf16=0, dtype=None, zoneout=None, h_lo_bf16=None, h_lo_bf16_off=0):
+    """zoneout = (thr_cell, thr_output, seed_cell, seed_output) or None (plain cell), see zoneout_threshold().
+    h_bf16 + h_lo_bf16 (ns_lstm_wide_fwd, fp32 storage): the pre-split planes of h, written by the call; the work buffer
+    is sized from a block that names them (lstm_wide_work_floats)."""
     p = L.struct("ns_lstm_seq_params")
+    if h_lo_bf16 is not None:
+        p.h_lo_bf16 = ptr(h_lo_bf16, h_lo_bf16_off)
     if zoneout is not None:
         p.zoneout_thr_cell, p.zoneout_thr_output, p.zoneout_seed_cell, p.zoneout_seed_output = [int(x) for x in zoneout]
     if h_bf16 is not None:
