@@ -11,24 +11,23 @@
 //                     * the rows of W_query that belong to those units (all A query columns)
 //                     * all of W_prenet2 (every workgroup computes the whole p2: cheaper than a third exchange)
 //                     * memory positions [g*ts, (g+1)*ts), ts = ceil(length / 8): keys and memory.W1c rows
-// and a step needs only TWO exchanges inside the cluster (8-byte {step tag, fp32} granules, written and polled with
-// relaxed agent-scope atomics = sc1; the data is its own flag, cdna guide G16 / R2):
+// and a step needs only TWO exchanges inside the cluster ({step tag, fp32} granules: exchange.h; the protocol - granule,
+// poll cadence, bound, status word - is DESIGN.md, "The tagged-granule exchange"):
 //   X2: partial queries h_slice . Wq[slice, :]  (A values) + the new h slice          -> every workgroup sums q, has h
 //   X3: partial next-prenet sums  sum_t w[t] pv[t, :]  (D1 values) + the local softmax max / sum + the local
 //       unnormalised weights w[t]                          -> every workgroup forms p1[s+1] and the whole alignment
 // (the softmax is combined flash-attention style: local max m_g, w = exp(e - m_g), global rescale exp(m_g - m) / L).
 // One buffer per exchange suffices: X2 of step s+1 is published only after X3 of step s has been gathered from every
 // peer, and a peer publishes that only after it has gathered X2 of step s - nobody can still be reading it.
-// Every spin is bounded; on timeout the kernel raises *status and every workgroup of the cluster leaves.
+// On a time-out every workgroup of the cluster leaves (status codes: the number of the gather, see the call sites).
 // All history the backward pass and the hoisted products read (p1, xa, hc, ca, ga, q, align, align_t) is written in
 // the layouts of ns_taco2_attn_fwd, which stays as the fallback for shapes this kernel does not cover.
-#include "common.h"
+#include "exchange.h"
 #include <stdlib.h>
 
 int ns_attn_contexts_after_loop(const ns_taco2_attn_params& p, hipStream_t s);     // attn.hip
 template <typename T> int ns_attn_bwd_post(const ns_taco2_attn_params& p, hipStream_t s);
 
-typedef unsigned long long u64;
 namespace {
 constexpr int CG = 8;              // workgroups per utterance
 constexpr int CT = 512;            // threads per workgroup
@@ -70,95 +69,9 @@ __device__ __forceinline__ void stamp(const ACArgs& a, int st, int k) {
   if (a.trace && blockIdx.x == 0 && threadIdx.x == 0 && st < 256) a.trace[st * 16 + k] = wall_clock64();
 }
 
-// Workgroup barrier that orders LDS only.  __syncthreads() also drains the vector-memory queue (s_waitcnt vmcnt(0)):
-// inside the step loops that would wait, at every barrier, for whatever is in flight - the history prefetch from HBM,
-// the write-through acknowledgement of a publish (1.3 us).  The waves of a workgroup talk through LDS only; what goes
-// through global memory is either tag-polled (the exchanges) or read by later kernels.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void put_granule(u64* g_, unsigned tag, float v) {
-  NS_GLOBAL u64* g = (NS_GLOBAL u64*)g_;
-  __hip_atomic_store(g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Every thread waits for its own granules (PER per thread, stride CT) and drops the values into LDS.
-// Returns false when this thread gave up (a peer raised the status word, or the wall-clock bound passed): the caller
-// raises the workgroup's LDS abort word then - no thread reads the status word from memory on the step's critical path
-// (round 2 had thread 0 load it behind every gather: one more memory round trip in front of the barrier, 2 per step).
-template <int PER>
-__device__ __forceinline__ bool gather_granules(const u64* src_, int total, unsigned tag, float* dst, int tid,
-                                                int* status, int code) {
-  const NS_GLOBAL u64* src = (const NS_GLOBAL u64*)src_;      // global_load, not flat_load: the poll leaves lgkmcnt alone
-  u64 v[PER];
-  unsigned spins = 0, clk0 = 0;
-  bool ok, gave_up = false;
-  do {
-    ok = true;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int i = tid + j * CT;
-      v[j] = i < total ? __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((u64)tag << 32);
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
-    if (!ok) {
-      if ((++spins & 1023u) == 0) {        // every 1024 polls: has a peer given up, or is the wall-clock bound passed
-        if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ok = gave_up = true;
-        else if (ns_spin_timed_out(clk0)) { atomicExch(status, code); ok = gave_up = true; }
-      }
-    }
-  } while (!ok);
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int i = tid + j * CT;
-    if (i < total) dst[i] = __uint_as_float((unsigned)v[j]);
-  }
-  return !gave_up;
-}
-
 template <typename T> __device__ __forceinline__ float ldw(const T* p, long i) { return ldf(p + i); }
 
-// sum_i w[i] * x[i] with the weights in registers and x in LDS (wave-uniform addresses: broadcast reads).  The chunks
-// are fenced so that the compiler keeps at most two chunks of x in flight instead of hoisting every LDS read of the
-// product to its top (the weights already take most of the register file).
-template <int NK>
-__device__ __forceinline__ float dot_regs(const float (&w)[NK], const float* x) {
-  static_assert(NK % 4 == 0 || NK < 4, "chunking");
-  float s0 = 0.f, s1 = 0.f;
-  if constexpr (NK < 4) {
-#pragma unroll
-    for (int i = 0; i < NK; ++i) s0 = fmaf(w[i], x[i], s0);
-    return s0;
-  } else {
-    float4 cur = *(const float4*)x;
-#pragma unroll
-    for (int i = 0; i < NK; i += 4) {
-      float4 nxt = cur;
-      if (i + 4 < NK) nxt = *(const float4*)(x + i + 4);
-      s0 = fmaf(w[i], cur.x, s0); s1 = fmaf(w[i + 1], cur.y, s1);
-      s0 = fmaf(w[i + 2], cur.z, s0); s1 = fmaf(w[i + 3], cur.w, s1);
-      // the sums pass through the fence: this chunk's FMAs cannot sink below it, later reads cannot rise above it
-      asm volatile("" : "+v"(s0), "+v"(s1) :: "memory");
-      cur = nxt;
-    }
-    return s0 + s1;
-  }
-}
-
 // ===================================================================================== forward
-// One granule, polled by its owner thread (the decode kernel's frame feedback).  Returns false on time-out / raised status.
-__device__ __forceinline__ bool poll_granule(const u64* g, unsigned tag, float& out, int* status, int code) {
-  unsigned spins = 0, clk0 = 0;
-  for (;;) {
-    const u64 v = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned)(v >> 32) == tag) { out = __uint_as_float((unsigned)v); return true; }
-    if ((++spins & 1023u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
-      if (ns_spin_timed_out(clk0)) { atomicExch(status, code); return false; }
-    }
-  }
-}
-
 // The forward recurrence of one workgroup (bid = utterance * CG + member).  INFER = free-running decode: the frame term
 // of the next step is not hoisted (it depends on this step's output through the two decoder LSTMs) but polled from
 // a.f1x, and the alignment is published to a.alx for the workgroups that run the first decoder LSTM.
@@ -279,7 +192,7 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
     stamp(a, st, 0);
     // ---- (1) p2 = relu(p1 . W2 + b2): every workgroup computes all of it
     red[tid] = dot_regs<P2K>(w2r, p1s + p2q * P2K);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < D2) {
       float s = b2c;
 #pragma unroll
@@ -288,12 +201,12 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       xs[tid] = s;
       if (tid / (D2 / CG) == g) stf((T*)p.xa + ((long)n * S1 + slot) * XA + tid, s);
     }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, st, 1);
     // ---- (2) gates of this workgroup's units, cell update
     float sv[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     red[tid] = hpart + dot_regs<GKP>(wgp, xs + gq * GKP);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < UPW) {
       float z[4];
 #pragma unroll
@@ -307,10 +220,10 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       cstate = ns_cell_clip(gf * cstate + gi * gj, p.cell_clip);
       const float h = go * tanhf_(cstate);
       hloc[tid] = h;
-      put_granule(x2 + (size_t)g * X2N + A + tid, tag, h);                 // the peers wait for this
+      ns_put_granule(x2 + (size_t)g * X2N + A + tid, tag, h);                 // the peers wait for this
       sv[0] = gi; sv[1] = gj; sv[2] = gf; sv[3] = go; sv[4] = h;           // saved after the gather (see below)
     }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, st, 2);
     // ---- (3) partial query of this workgroup's h rows, published
     {
@@ -319,12 +232,12 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       for (int i = 0; i < QK; ++i) s = fmaf(wq_s[(qq * QK + i) * A + qu], hloc[qq * QK + i], s);
       red[tid] = s;
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < A) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < QG; ++q) s += red[q * A + tid];
-      put_granule(x2 + (size_t)g * X2N + tid, tag, s);
+      ns_put_granule(x2 + (size_t)g * X2N + tid, tag, s);
     }
     stamp(a, st, 3);
     // ---- (5a) in the shadow of exchange 2: the part of the energies that does not need the query.  The location term
@@ -350,8 +263,8 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       }
     }
     // ---- (4) gather X2: q = sum of the partials (fixed order), h of every unit
-    if (!gather_granules<(CG * X2N + CT - 1) / CT>(x2, CG * X2N, tag, gath, tid, a.status, 1)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
-    lds_barrier();
+    if (!ns_gather_granules<(CG * X2N + CT - 1) / CT, CT>(x2, CG * X2N, tag, gath, tid, a.status, 1)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;                 // uniform: every thread reads the same LDS word
     stamp(a, st, 4);
     if (tid < A) {
@@ -391,7 +304,7 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
           if (c == 0) ered[wave * TSMAX + rt * 16 + g4 * 4 + q] = e;
         }
     }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, st, 6);
     if (tid < UPW) {
       // what the backward pass / the hoisted products read of this step's cell: stored only now (behind the energy pass, while wave 1 takes the softmax), so that these
@@ -417,7 +330,7 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       if (lane < TSMAX) es[lane] = w;
       if (lane == 0) { sc[0] = m; sc[1] = l; }
     }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, st, 7);
     // ---- (6) partial next-prenet sums over the own positions, published with the softmax pieces
     {
@@ -426,23 +339,23 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       for (int tl = th; tl < tn; tl += CXG) s = fmaf(es[tl], pv_s[tl * D1 + c], s);
       red[tid] = s;
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < D1) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < CXG; ++q) s += red[q * D1 + tid];
-      put_granule(x3 + (size_t)g * X3N + tid, tag, s);
+      ns_put_granule(x3 + (size_t)g * X3N + tid, tag, s);
     } else if (tid < D1 + 2) {
-      put_granule(x3 + (size_t)g * X3N + tid, tag, sc[tid - D1]);
+      ns_put_granule(x3 + (size_t)g * X3N + tid, tag, sc[tid - D1]);
     } else if (tid < D1 + 2 + TSMAX) {
-      put_granule(x3 + (size_t)g * X3N + tid, tag, es[tid - D1 - 2]);
+      ns_put_granule(x3 + (size_t)g * X3N + tid, tag, es[tid - D1 - 2]);
     }
     stamp(a, st, 8);
     // ---- in the shadow of exchange 3: the h half of the NEXT step's gates (xs[D2 ..] = h(s) since (4))
     hpart = dot_regs<GKH>(wgh, xs + D2 + gq * GKH);
     // ---- (7) gather X3, combine
-    if (!gather_granules<(CG * X3N + CT - 1) / CT>(x3, CG * X3N, tag, gath, tid, a.status, 2)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
-    lds_barrier();
+    if (!ns_gather_granules<(CG * X3N + CT - 1) / CT, CT>(x3, CG * X3N, tag, gath, tid, a.status, 2)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     stamp(a, st, 9);
     float mall = -INFINITY;
@@ -456,7 +369,7 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       lsum = fmaf(lq, scl[q], lsum);
     }
     const float inv = 1.f / lsum;
-    lds_barrier();                                   // al / p1s are rewritten below: everyone is done with step s
+    ns_lds_barrier();                                   // al / p1s are rewritten below: everyone is done with step s
     // the whole alignment (every workgroup needs its neighbours' positions for the location filter)
     for (int t = tid; t < p.Tia; t += CT) {
       float v = 0.f;
@@ -469,13 +382,19 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       if (mine) {
         p.align[((long)n * S1 + slot) * p.Tia + t] = v;
         if (p.align_t) stf((T*)p.align_t + ((long)n * S1 + slot) * p.Tia + t, v);
-        if (INFER) put_granule(a.alx + (size_t)n * p.Tia + t, tag, v);      // the first decoder LSTM waits for it
+        if (INFER) ns_put_granule(a.alx + (size_t)n * p.Tia + t, tag, v);      // the first decoder LSTM waits for it
       }
     }
     if (tid < D1) {
       // free-running: the next frame term comes back through both decoder LSTMs (its tag = the consuming step + 1);
       // the alignment above went out first - they cannot answer before they have it
-      if (INFER && st + 1 < p.S && !poll_granule(a.f1x + (size_t)n * D1 + tid, tag + 1, f1n, a.status, 3)) sc[3] = 1.f;
+      if (INFER && st + 1 < p.S) {
+        const u64* fg = a.f1x + (size_t)n * D1 + tid;      // one granule, polled by its owner thread
+        u64 fv[1];
+        ns_spin sp;
+        if (ns_poll_granules(fv, tag + 1, sp, a.status, 3, [&](int) { return ns_ld_granule(fg); })) f1n = ns_granule_value(fv[0]);
+        else sc[3] = 1.f;
+      }
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < CG; ++q) s = fmaf(scl[q], gath[q * X3N + tid], s);
@@ -483,7 +402,7 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       p1s[tid] = v;
       if (st + 1 < p.S && tid / (D1 / CG) == g) stf((T*)p.p1 + ((long)n * S1 + slot + 1) * D1 + tid, v);
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (INFER && sc[3] != 0.f) return;
   }
 }
@@ -725,7 +644,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
     // ---- P0/P1: the history images of this step were filled in the middle of the step before; the loads of step
     //      s-1 go out now and stay in flight until the middle of this step
     if (st > 0) load_history(st - 1, tid);
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, p.S - 1 - st, 1);
     // ---- P2: dalign of the own positions: thread = (position tid / 16, 16 columns each); then this workgroup's share
     //      of the softmax-backward dot product sum_t align[t] dalign[t] goes out (exchange 1, one granule)
@@ -746,10 +665,10 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       s = row16_sum(s);
       if (cq == 0 && tl < TSMAX) dav[tl] = tl < tn ? da0s[tl] + s + carry[tl] : 0.f;
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (wave == 7) {                         // a wave that takes no part in the energy pass for A = 64 either
       const float d = wave_sum(lane < tn ? acur[lane] * dav[lane] : 0.f);
-      if (lane == 0) put_granule(e1 + g, tag, d);
+      if (lane == 0) ns_put_granule(e1 + g, tag, d);
     }
     stamp(a, p.S - 1 - st, 2);
     // ---- P3 (runs one step AHEAD, see energy_pass above): energy pass.  x^T[u][t] = (keys[t][u] + q[u]) + sum_k Wcl[k][u] align[t + k - half] is taken on the matrix
@@ -761,12 +680,12 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
     const int r = lane & 15, kq = lane >> 4;
     // ---- exchange 1 has been under way all along: the dot product, then the energy gradients
     if (wave == 7) {
-      if (!gather_granules<1>(e1, CG, tag, gath, lane < CG ? lane : CG, a.status, 5)) sc[2] = 1.f;      // lanes >= CG read nothing
+      if (!ns_gather_granules<1, CT>(e1, CG, tag, gath, lane < CG ? lane : CG, a.status, 5)) sc[2] = 1.f;      // lanes >= CG read nothing
       float d = lane < CG ? gath[lane] : 0.f;
       d = wave_sum(d);
       if (lane == 0) sc[0] = d;
     }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, p.S - 1 - st, 3);
     if (tid < TSMAX) {
       float de = 0.f;
@@ -776,7 +695,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       }
       dev[tid] = de;
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P4: dq partial of unit u = sum over the positions of de[t] g1[t, u] (a DPP row holds 16 positions, the two
     //      tiles add in-thread), published as exchange 2;  G[t][k] = de[t] * sum over the unit blocks of Z
     if (wave < A / 32) {
@@ -785,7 +704,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       for (int j = 0; j < 8; ++j) g1v[j] = row16_sum(fmaf(de0, g1v[(j >> 2) * 8 + (j & 3)], de1 * g1v[(j >> 2) * 8 + 4 + (j & 3)]));
       if (r == 0) {        // j = 4 ut + q: unit ub + 16 ut + 4 kq + q
 #pragma unroll
-        for (int j = 0; j < 8; ++j) put_granule(e2 + (size_t)g * A + wave * 32 + (j >> 2) * 16 + 4 * kq + (j & 3), tag, g1v[j]);
+        for (int j = 0; j < 8; ++j) ns_put_granule(e2 + (size_t)g * A + wave * 32 + (j >> 2) * 16 + 4 * kq + (j & 3), tag, g1v[j]);
       }
     }
     if (tid < TSMAX * 8) {
@@ -795,7 +714,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       for (int w = 0; w < A / 32; ++w) z += zred[(w * TSMAX + tl) * 8 + k];
       Gs[tid] = (tl < tn && k < p.kw) ? dev[tl] * z : 0.f;
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P5: this workgroup's contributions to the carry of step s-1 (positions t0-half .. t0+ts+kw-half-2)
     float ccv = 0.f;                         // threads < CCN keep their value for the E3 publish
     if (tid < TSMAX + 6) {
@@ -808,8 +727,8 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
     }
     stamp(a, p.S - 1 - st, 4);
     // ---- gather E2: dq = sum of the partials
-    if (!gather_granules<(CG * A + CT - 1) / CT>(e2, CG * A, tag, gath, tid, a.status, 3)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
-    lds_barrier();
+    if (!ns_gather_granules<(CG * A + CT - 1) / CT, CT>(e2, CG * A, tag, gath, tid, a.status, 3)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     stamp(a, p.S - 1 - st, 5);
     if (st > 0) store_history(par ^ 1, tid);       // step s-1's history: loaded at the top of this step, landed long ago
@@ -820,7 +739,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       dq_s[tid] = s;
       if (tid / UPW == g) stf((T*)p.dq + rowS * A + tid, s);
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P6: dh of the own units through W_query, then the cell gradient: thread = (unit tid / 16, UL columns each)
     {
       const int j = tid >> 4, uq = tid & 15;
@@ -857,7 +776,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       }
     }
     if (st > 0) { o_dhc = h_dhc; o_c = h_c; o_cp = h_cp; }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, p.S - 1 - st, 6);
     // ---- P7: partial input gradients dga_own . Watt[k, own]^T for every input row k, published with the carry pieces
 #pragma unroll
@@ -865,19 +784,19 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       const int pi = tid + CT * jj, qr = pi / K;
       red[pi] = dot_regs<CPQ>(wxr[jj], dgs + qr * CPQ);          // red[qr * K + k], pi = qr * K + k
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < K) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) s += red[q * K + tid];
-      put_granule(e3 + (size_t)g * E3N + tid, tag, s);
+      ns_put_granule(e3 + (size_t)g * E3N + tid, tag, s);
     }
-    if (tid < CCN) put_granule(e3 + (size_t)g * E3N + K + tid, tag, ccv);
+    if (tid < CCN) ns_put_granule(e3 + (size_t)g * E3N + K + tid, tag, ccv);
     // in the shadow of exchange 3: the energy pass of step s-1 (history images of parity par ^ 1, filled behind E2)
     if (st > 0) energy_pass(par ? qs0 : qs1, par ? al0 : al1, lane, wave);
     stamp(a, p.S - 1 - st, 7);
-    if (!gather_granules<(CG * E3N + CT - 1) / CT>(e3, CG * E3N, tag, gath, tid, a.status, 4)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
-    lds_barrier();
+    if (!ns_gather_granules<(CG * E3N + CT - 1) / CT, CT>(e3, CG * E3N, tag, gath, tid, a.status, 4)) sc[2] = 1.f;        // the abort word: zero since the kernel's start
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     stamp(a, p.S - 1 - st, 8);
     // ---- P8: dp2 (masked), recurrent dh, carry and dcar for the step before
@@ -907,11 +826,11 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       }
       carry[tl] = s;
     }
-    lds_barrier();
+    ns_lds_barrier();
     stamp(a, p.S - 1 - st, 9);
     // ---- P9: dp1 = (dp2 . W2^T) masked: next dvec (every workgroup computes all of it)
     red[tid] = dot_regs<W2K>(w2r, dp2s + (tid / D1) * W2K);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < D1) {
       float s = 0.f;
 #pragma unroll
@@ -920,7 +839,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       dvec[tid] = s;
       if (tid / (D1 / CG) == g) stf((T*)p.df1 + rowS * D1 + tid, s);
     }
-    lds_barrier();
+    ns_lds_barrier();
   }
 }
 
@@ -957,37 +876,6 @@ struct DecArgs {
   u64* pub1; u64* pub2;                    // [2][N][D]
   float* h2hist;                           // [N][S + 1][D], slot s + 1
 };
-
-// PER granules per thread, all loads of a pass in flight together; at(i, src, dst) maps item i to its granule and its
-// LDS word.  Returns false on time-out / raised status.
-template <int PER, typename F>
-__device__ __forceinline__ bool dec_gather(int total, unsigned tag, int tid, int* status, int code, F at) {
-  const u64* src[PER];
-  float* dst[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int i = tid + j * CT;
-    src[j] = nullptr; dst[j] = nullptr;
-    if (i < total) at(i, src[j], dst[j]);
-  }
-  u64 v[PER];
-  unsigned spins = 0, clk0 = 0;
-  bool ok, good = true;
-  do {
-    ok = true;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) v[j] = src[j] ? __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((u64)tag << 32);
-#pragma unroll
-    for (int j = 0; j < PER; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
-    if (!ok && (++spins & 1023u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { good = false; ok = true; }
-      else if (ns_spin_timed_out(clk0)) { atomicExch(status, code); good = false; ok = true; }
-    }
-  } while (!ok);
-#pragma unroll
-  for (int j = 0; j < PER; ++j) if (dst[j]) *dst[j] = __uint_as_float((unsigned)v[j]);
-  return good;
-}
 
 // One decoder LSTM's workgroup w.  WHICH = 1: inputs h_att (A, registers) + context (through PM) + own h1; 2: h1 + own h2.
 // A workgroup owns UPW units = COLS = 4 UPW gate columns (column = gate * UPW + unit); thread (cg = tid & 15, ks = tid >> 4)
@@ -1061,23 +949,23 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
     // ---------------- phase a: the inputs of this step
     bool good;
     if (WHICH == 1) {
-      good = dec_gather<(NR * A + CT - 1) / CT>(N * A, tag, tid, d.att.status, 4, [&](int i, const u64*& src, float*& dst) {
+      good = ns_gather_mapped<(NR * A + CT - 1) / CT, CT>(N * A, tag, tid, d.att.status, 4, [&](int i, const u64*& src, float*& dst) {
         const int n = i / A, u = i % A;
         src = d.att.x2 + ((size_t)n * CG + u / UPWA) * X2N + A + u % UPWA;
         dst = xv + n * KX + u;
       });
-      good = dec_gather<(NR * 256 + CT - 1) / CT>(N * Tia, tag, tid, d.att.status, 4, [&](int i, const u64*& src, float*& dst) {
+      good = ns_gather_mapped<(NR * 256 + CT - 1) / CT, CT>(N * Tia, tag, tid, d.att.status, 4, [&](int i, const u64*& src, float*& dst) {
         src = d.att.alx + i;
         dst = al_s + i;
       }) && good;
     } else {
-      good = dec_gather<(NR * D + CT - 1) / CT>(N * D, tag, tid, d.att.status, 5, [&](int i, const u64*& src, float*& dst) {
+      good = ns_gather_mapped<(NR * D + CT - 1) / CT, CT>(N * D, tag, tid, d.att.status, 5, [&](int i, const u64*& src, float*& dst) {
         src = d.pub1 + par + i;
         dst = xv + i;
       });
     }
     if (!good) flag[0] = 1.f;
-    lds_barrier();
+    ns_lds_barrier();
     if (flag[0] != 0.f) return;
     for (int n = 0; n < N; ++n) {
       float acc[CPT];
@@ -1099,7 +987,7 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
       }
 #pragma unroll
       for (int j = 0; j < CPT; ++j) red[ks * RS + CPT * cg + j] = acc[j];
-      lds_barrier();
+      ns_lds_barrier();
       if (tid < COLS) {
         const int gate = tid / UPW, ul = tid % UPW;
         float s = (u0 + ul < D ? bias[gate * D + u0 + ul] : 0.f) + zr[n * COLS + tid];
@@ -1107,7 +995,7 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
         for (int q = 0; q < DEC_KS; ++q) s += red[q * RS + tid];
         zs[tid] = s;
       }
-      lds_barrier();
+      ns_lds_barrier();
       if (tid < UPW && u0 + tid < D) {
         const float gi = sigmoidf_(zs[tid]), gj = tanhf_(zs[UPW + tid]);
         const float gf = sigmoidf_(zs[2 * UPW + tid] + 1.0f), go = sigmoidf_(zs[3 * UPW + tid]);
@@ -1118,20 +1006,20 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
         const float h = go * tanhf_(c);
 #pragma unroll
         for (int q = 0; q < NR; ++q) cst[q] = n == q ? c : cst[q];
-        put_granule(mypub + par + (size_t)n * D + u0 + tid, tag, h);
+        ns_put_granule(mypub + par + (size_t)n * D + u0 + tid, tag, h);
         if (WHICH == 2) d.h2hist[((long)n * (d.S + 1) + st + 1) * D + u0 + tid] = h;
       }
       // red / zs are rewritten by the next row only behind the barrier that follows its partial sums
-      lds_barrier();
+      ns_lds_barrier();
     }
     // ---------------- phase b: everybody's h of this step -> the recurrent half of the next step (and the feedback)
     if (st + 1 < d.S) {
-      good = dec_gather<(NR * D + CT - 1) / CT>(N * D, tag, tid, d.att.status, 6, [&](int i, const u64*& src, float*& dst) {
+      good = ns_gather_mapped<(NR * D + CT - 1) / CT, CT>(N * D, tag, tid, d.att.status, 6, [&](int i, const u64*& src, float*& dst) {
         src = mypub + par + i;
         dst = hv + i;
       });
       if (!good) flag[0] = 1.f;
-      lds_barrier();
+      ns_lds_barrier();
       if (flag[0] != 0.f) return;
       for (int n = 0; n < N; ++n) {
         float acc[CPT];
@@ -1155,7 +1043,7 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
             red2[q * 64 + j] = s;
           }
         }
-        lds_barrier();
+        ns_lds_barrier();
         if (tid < COLS) {
           float s = 0.f;
 #pragma unroll
@@ -1166,9 +1054,9 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
           float s = d.bpf[f0 + j];
 #pragma unroll
           for (int q = 0; q < DEC_KS; ++q) s += red2[q * 64 + j];
-          put_granule(d.att.f1x + (size_t)n * D1 + f0 + j, tag + 1, s);
+          ns_put_granule(d.att.f1x + (size_t)n * D1 + f0 + j, tag + 1, s);
         }
-        lds_barrier();
+        ns_lds_barrier();
       }
     }
   }

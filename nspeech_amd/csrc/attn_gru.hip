@@ -13,8 +13,8 @@
 //                     * all of W_prenet2 (every workgroup computes the whole p2: cheaper than another exchange)
 //                     * memory positions [g ts, (g + 1) ts), ts = ceil(length / 8): keys and pv rows
 // A GRU step has TWO dependent products (the candidate needs r * h of EVERY unit), so the forward step takes three
-// exchanges inside the cluster where the LSTM cell of Tacotron-2 takes two (8-byte {step tag, fp32} granules written and
-// polled with relaxed agent-scope atomics; the data is its own flag, cdna guide G16):
+// exchanges inside the cluster where the LSTM cell of Tacotron-2 takes two ({step tag, fp32} granules: exchange.h; the
+// protocol is DESIGN.md, "The tagged-granule exchange"):
 //   X1: r * h(s-1) of the own units                                                -> every workgroup has r * h
 //   X2: partial queries h_own . Wq[own rows, :] (256 values) + the new h of the own units   -> q, h
 //   X3: partial next-prenet sums  sum_t w[t] pv[t, :] (256) + local softmax max / sum + the local weights
@@ -23,12 +23,11 @@
 // query gradients (E2), partial input gradients of the candidate kernel (E3a: they carry d(r * h)), then of the gate
 // kernel (E3b).  One buffer per exchange suffices: a workgroup publishes exchange X of step s+1 only after it has gathered
 // the last exchange of step s from every peer, and a peer publishes that only after it has gathered X of step s.
-// Every spin is bounded in wall-clock time; on a time-out the status word is raised and every workgroup of the cluster
-// leaves.  History is written in the layouts models/tacotron.py reads (the launch-per-step form stays as the fallback).
-#include "common.h"
+// On a time-out the status word is raised and every workgroup of the cluster leaves.  History is written in the
+// layouts models/tacotron.py reads (the launch-per-step form stays as the fallback).
+#include "exchange.h"
 #include <stdlib.h>
 
-typedef unsigned long long u64;
 namespace {
 constexpr int CG = 8;              // workgroups per utterance
 constexpr int CT = 512;            // threads per workgroup
@@ -68,83 +67,15 @@ struct TArgs {
   u64* f1x; u64* alx; const float* bpf; int nwd;
 };
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void put_granule(u64* g_, unsigned tag, float v) {
-  NS_GLOBAL u64* g = (NS_GLOBAL u64*)g_;
-  __hip_atomic_store(g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Every thread waits for its own granules (PER per thread, stride CT) and drops the values into LDS.  Returns false
-// when this thread gave up (a peer raised the status word, or the wall-clock bound passed).
-template <int PER>
-__device__ __forceinline__ bool gather_granules(const u64* src_, int total, unsigned tag, float* dst, int tid, int* status, int code) {
-  const NS_GLOBAL u64* src = (const NS_GLOBAL u64*)src_;
-  u64 v[PER];
-  unsigned spins = 0, clk0 = 0;
-  bool ok, gave_up = false;
-  do {
-    ok = true;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int i = tid + j * CT;
-      v[j] = i < total ? __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((u64)tag << 32);
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
-    if (!ok && (++spins & 1023u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ok = gave_up = true;
-      else if (ns_spin_timed_out(clk0)) { atomicExch(status, code); ok = gave_up = true; }
-    }
-  } while (!ok);
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int i = tid + j * CT;
-    if (i < total) dst[i] = __uint_as_float((unsigned)v[j]);
-  }
-  return !gave_up;
-}
-
-// sum_i w[i] * x[i], weights in registers, x in LDS (wave-uniform addresses); chunks fenced so that at most two chunks of
-// x are in flight (attn_cluster.hip: dot_regs)
-template <int NK>
-__device__ __forceinline__ float dot_regs(const float (&w)[NK], const float* x) {
-  static_assert(NK % 4 == 0, "chunking");
-  float s0 = 0.f, s1 = 0.f;
-  float4 cur = *(const float4*)x;
-#pragma unroll
-  for (int i = 0; i < NK; i += 4) {
-    float4 nxt = cur;
-    if (i + 4 < NK) nxt = *(const float4*)(x + i + 4);
-    s0 = fmaf(w[i], cur.x, s0); s1 = fmaf(w[i + 1], cur.y, s1);
-    s0 = fmaf(w[i + 2], cur.z, s0); s1 = fmaf(w[i + 3], cur.w, s1);
-    asm volatile("" : "+v"(s0), "+v"(s1) :: "memory");
-    cur = nxt;
-  }
-  return s0 + s1;
-}
-
 // The partial sums of one frame-term column from the nw decoder workgroups (stride D1), polled by its owner thread and
 // added in a fixed order.  Returns false on time-out / raised status.
 template <int NW>
-__device__ __forceinline__ bool poll_partials(const u64* src_, unsigned tag, float& out, int* status, int code) {
-  const NS_GLOBAL u64* src = (const NS_GLOBAL u64*)src_;
+__device__ __forceinline__ bool poll_partials(const u64* src, unsigned tag, float& out, int* status, int code) {
   u64 v[NW];
-  unsigned spins = 0, clk0 = 0;
-  for (;;) {
-    bool ok = true;
+  ns_spin sp;
+  if (!ns_poll_granules(v, tag, sp, status, code, [&](int j) { return ns_ld_granule(src + (size_t)j * D1); })) return false;
 #pragma unroll
-    for (int j = 0; j < NW; ++j) v[j] = __hip_atomic_load(src + (size_t)j * D1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int j = 0; j < NW; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
-    if (ok) break;
-    if ((++spins & 1023u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
-      if (ns_spin_timed_out(clk0)) { atomicExch(status, code); return false; }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NW; ++j) out += __uint_as_float((unsigned)v[j]);
+  for (int j = 0; j < NW; ++j) out += ns_granule_value(v[j]);
   return true;
 }
 
@@ -257,7 +188,7 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
 
     // ---- (1) p2 = relu(p1 . W2 + b2): every workgroup computes all of it
     red[tid] = dot_regs<P2K>(w2r, p1s + (tid / D2) * P2K);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < D2) {
       float s = b2c;
 #pragma unroll
@@ -269,11 +200,11 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
         stf((T*)p.xc + rowS * XA + tid, s);
       }
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- (2) r, u of the own units; r * h(s-1) goes out (X1); the candidate's prenet rows meanwhile
     red[tid] = hpart + dot_regs<GKP>(wgp, xs + (tid / GC) * GKP);
     const float cpart = dot_regs<CKP>(wcp, xs + (tid / UPW) * CKP);
-    lds_barrier();
+    ns_lds_barrier();
     float sv_r = 0.f, sv_u = 0.f, sv_rh = 0.f;
     if (tid < GC) {
       float z = gbias;
@@ -284,16 +215,16 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       if (tid < UPW) {
         sv_r = v;
         sv_rh = v * hloc[tid];
-        put_granule(x1 + (size_t)g * X1N + tid, tag, sv_rh);
+        ns_put_granule(x1 + (size_t)g * X1N + tid, tag, sv_rh);
       }
     }
     // ---- (3) gather X1: r * h of every unit (granule index = unit)
-    if (!gather_granules<1>(x1, CG * X1N, tag, gath, tid, a.status, 1)) sc[2] = 1.f;
-    lds_barrier();
+    if (!ns_gather_granules<1, CT>(x1, CG * X1N, tag, gath, tid, a.status, 1)) sc[2] = 1.f;
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     // ---- (4) candidate of the own units, the new h; h goes out with the partial queries (X2)
     red[tid] = cpart + dot_regs<CKH>(wch, gath + (tid / UPW) * CKH);
-    lds_barrier();
+    ns_lds_barrier();
     float sv_c = 0.f, sv_h = 0.f;
     if (tid < UPW) {
       float z = cbias;
@@ -303,9 +234,9 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       sv_u = rus[UPW + tid];
       sv_h = sv_u * hloc[tid] + (1.f - sv_u) * sv_c;
       hloc[tid] = sv_h;
-      put_granule(x2 + (size_t)g * X2N + A + tid, tag, sv_h);
+      ns_put_granule(x2 + (size_t)g * X2N + A + tid, tag, sv_h);
     }
-    lds_barrier();
+    ns_lds_barrier();
     {
       const int qu = tid % A, qq = tid / A;
       float s = 0.f;
@@ -313,11 +244,11 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       for (int i = 0; i < QK; ++i) s = fmaf(wq_s[(qq * QK + i) * A + qu], hloc[qq * QK + i], s);
       red[tid] = s;
     }
-    lds_barrier();
-    if (tid < A) put_granule(x2 + (size_t)g * X2N + tid, tag, red[tid] + red[A + tid]);
+    ns_lds_barrier();
+    if (tid < A) ns_put_granule(x2 + (size_t)g * X2N + tid, tag, red[tid] + red[A + tid]);
     // ---- (5) gather X2: q = sum of the partials (fixed order), h of every unit
-    if (!gather_granules<(CG * X2N + CT - 1) / CT>(x2, CG * X2N, tag, gath, tid, a.status, 2)) sc[2] = 1.f;
-    lds_barrier();
+    if (!ns_gather_granules<(CG * X2N + CT - 1) / CT, CT>(x2, CG * X2N, tag, gath, tid, a.status, 2)) sc[2] = 1.f;
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     if (tid < A) {
       float s = 0.f;
@@ -352,7 +283,7 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
           if (c == 0) ered[wave * TSMAX + rt * 16 + g4 * 4 + q] = e;
         }
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < UPW) {
       // this step's cell for the backward pass / the hoisted products: stored only now, behind the polls of this wave
       const int u = g * UPW + tid;
@@ -376,7 +307,7 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       if (lane < TSMAX) es[lane] = w;
       if (lane == 0) { sc[0] = m; sc[1] = l; }
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- (7) partial next-prenet sums over the own positions, published with the softmax pieces (X3)
     {
       const int c = tid % D1, th = tid / D1;
@@ -384,14 +315,14 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       for (int tl = th; tl < tn; tl += CXG) s = fmaf(es[tl], pv_s[tl * D1 + c], s);
       red[tid] = s;
     }
-    lds_barrier();
-    if (tid < D1) put_granule(x3 + (size_t)g * X3N + tid, tag, red[tid] + red[D1 + tid]);
-    else if (tid < D1 + 2) put_granule(x3 + (size_t)g * X3N + tid, tag, sc[tid - D1]);
-    else if (tid < D1 + 2 + TSMAX) put_granule(x3 + (size_t)g * X3N + tid, tag, es[tid - D1 - 2]);
+    ns_lds_barrier();
+    if (tid < D1) ns_put_granule(x3 + (size_t)g * X3N + tid, tag, red[tid] + red[D1 + tid]);
+    else if (tid < D1 + 2) ns_put_granule(x3 + (size_t)g * X3N + tid, tag, sc[tid - D1]);
+    else if (tid < D1 + 2 + TSMAX) ns_put_granule(x3 + (size_t)g * X3N + tid, tag, es[tid - D1 - 2]);
     // in the shadow of X3: the h rows of the NEXT step's gates (xs[D2 ..] = h(s) since (5))
     hpart = dot_regs<GKH>(wgh, xs + D2 + (tid / GC) * GKH);
-    if (!gather_granules<(CG * X3N + CT - 1) / CT>(x3, CG * X3N, tag, gath, tid, a.status, 3)) sc[2] = 1.f;
-    lds_barrier();
+    if (!ns_gather_granules<(CG * X3N + CT - 1) / CT, CT>(x3, CG * X3N, tag, gath, tid, a.status, 3)) sc[2] = 1.f;
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     float mall = -INFINITY;
 #pragma unroll
@@ -414,7 +345,7 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       if (mine) {
         p.align[rowS * p.Tia + t] = v;
         if (p.align_t) stf((T*)p.align_t + rowS * p.Tia + t, v);
-        if (INFER) put_granule(a.alx + (size_t)n * p.Tia + t, tag, v);      // the decoder workgroups wait for it
+        if (INFER) ns_put_granule(a.alx + (size_t)n * p.Tia + t, tag, v);      // the decoder workgroups wait for it
       }
     }
     if (tid < D1) {
@@ -431,7 +362,7 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       p1s[tid] = v;
       if (st + 1 < p.S && tid / (D1 / CG) == g) stf((T*)p.p1 + (rowS + 1) * D1 + tid, v);
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (INFER && sc[2] != 0.f) return;
   }
 }
@@ -598,7 +529,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
     const float* hpsb = csb + UPW; const float* dhcsb = hpsb + UPW;
 
     if (st > 0) load_history(st - 1, tid);   // lands by the middle of this step
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P2: dalign of the own positions: thread = (position tid / 16, 16 columns each)
     {
       const int tl = tid >> 4, cq = tid & 15;
@@ -615,16 +546,16 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
       s = row16_sum(s);
       if (cq == 0 && tl < TSMAX) dav[tl] = tl < tn ? da0s[tl] + s : 0.f;
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (wave == 7) {
       const float d = wave_sum(lane < tn ? acur[lane] * dav[lane] : 0.f);
-      if (lane == 0) put_granule(e1 + g, tag, d);
-      if (!gather_granules<1>(e1, CG, tag, gath, lane < CG ? lane : CG, a.status, 5)) sc[2] = 1.f;
+      if (lane == 0) ns_put_granule(e1 + g, tag, d);
+      if (!ns_gather_granules<1, CT>(e1, CG, tag, gath, lane < CG ? lane : CG, a.status, 5)) sc[2] = 1.f;
       float dd = lane < CG ? gath[lane] : 0.f;
       dd = wave_sum(dd);
       if (lane == 0) sc[0] = dd;
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < TSMAX) {
       float de = 0.f;
       if (tid < tn) {
@@ -633,7 +564,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
       }
       dev[tid] = de;
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P4: dq partials -> E2
     {
       const int c = lane & 15, g4 = lane >> 4;
@@ -646,11 +577,11 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
           for (int q = 0; q < 4; ++q) s = fmaf(dev[rt * 16 + g4 * 4 + q], g1v[ut * 8 + rt * 4 + q], s);
         s += __shfl_xor(s, 16, 64);
         s += __shfl_xor(s, 32, 64);
-        if (g4 == 0) put_granule(e2 + (size_t)g * A + wave * 32 + ut * 16 + c, tag, s);
+        if (g4 == 0) ns_put_granule(e2 + (size_t)g * A + wave * 32 + ut * 16 + c, tag, s);
       }
     }
-    if (!gather_granules<(CG * A + CT - 1) / CT>(e2, CG * A, tag, gath, tid, a.status, 3)) sc[2] = 1.f;
-    lds_barrier();
+    if (!ns_gather_granules<(CG * A + CT - 1) / CT, CT>(e2, CG * A, tag, gath, tid, a.status, 3)) sc[2] = 1.f;
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     if (st > 0) store_history((st & 1) ^ 1, tid);
     if (tid < A) {
@@ -660,7 +591,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
       dq_s[tid] = s;
       if (tid / UPW == g) stf((T*)p.dq + rowS * A + tid, s);
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P6: dh of the own units through W_query, the cell's first half: thread = (unit tid / 16, 16 columns each)
     {
       const int j = tid >> 4, uq = tid & 15;
@@ -688,22 +619,22 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
         stf((T*)p.dzg + rowS * 2 * A + A + u, dzu);
       }
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P7a: candidate kernel, partial input gradients over the own columns -> E3a
 #pragma unroll
     for (int jj = 0; jj < PPT; ++jj) {
       const int pi = tid + CT * jj, qr = pi / K;
       red[pi] = dot_regs<CPQ_C>(wcr[jj], dcs + qr * CPQ_C);
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < K) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) s += red[q * K + tid];
-      put_granule(e3a + (size_t)g * K + tid, tag, s);
+      ns_put_granule(e3a + (size_t)g * K + tid, tag, s);
     }
-    if (!gather_granules<(CG * K + CT - 1) / CT>(e3a, CG * K, tag, gath, tid, a.status, 4)) sc[2] = 1.f;
-    lds_barrier();
+    if (!ns_gather_granules<(CG * K + CT - 1) / CT, CT>(e3a, CG * K, tag, gath, tid, a.status, 4)) sc[2] = 1.f;
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     if (tid < D2) {
       float s = 0.f;
@@ -721,24 +652,24 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
       dird[j] += drh * r;
       stf((T*)p.dzg + rowS * 2 * A + u, dzr);
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P7b: gate kernel -> E3b
 #pragma unroll
     for (int jj = 0; jj < PPT; ++jj) {
       const int pi = tid + CT * jj, qr = pi / K;
       red[pi] = dot_regs<CPQ_G>(wgr[jj], dgs + qr * CPQ_G);
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < K) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) s += red[q * K + tid];
-      put_granule(e3b + (size_t)g * K + tid, tag, s);
+      ns_put_granule(e3b + (size_t)g * K + tid, tag, s);
     }
     // in the shadow of E3b: the energy pass of step s-1 (its history image was stored behind E2)
     if (st > 0) energy_pass(him + ((st & 1) ^ 1) * HIMG, lane, wave);
-    if (!gather_granules<(CG * K + CT - 1) / CT>(e3b, CG * K, tag, gath, tid, a.status, 6)) sc[2] = 1.f;
-    lds_barrier();
+    if (!ns_gather_granules<(CG * K + CT - 1) / CT, CT>(e3b, CG * K, tag, gath, tid, a.status, 6)) sc[2] = 1.f;
+    ns_lds_barrier();
     if (sc[2] != 0.f) return;
     if (tid < D2) {
       float s = dp2s[tid];
@@ -754,17 +685,17 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
       for (int q = 0; q < CG; ++q) s += gath[q * K + D2 + u];
       hrec[j] = s;
     }
-    lds_barrier();
+    ns_lds_barrier();
     // ---- P9: dp1 = (dp2 . W2^T) masked: the next dvec (every workgroup computes all of it)
     red[tid] = dot_regs<W2K>(w2r, dp2s + (tid / D1) * W2K);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < D1) {
       float s = red[tid] + red[D1 + tid];
       s = p1m[tid] > 0.f ? s : 0.f;
       dvec[tid] = s;
       if (tid / (D1 / CG) == g) stf((T*)p.df1 + rowS * D1 + tid, s);
     }
-    lds_barrier();
+    ns_lds_barrier();
   }
 }
 
@@ -822,37 +753,6 @@ struct DArgs {
   float* y2;                              // [N][S+1][DD]
   u64 *xa, *xb, *xc, *xd, *xe;            // [N][DD]; xc [N][2 DD]
 };
-
-// PER granules per thread, all loads of a pass in flight together; at(i, src, dsti) maps item i to its granule and LDS
-// word.  Returns false on time-out / raised status (attn_cluster.hip: dec_gather).
-template <int PER, typename F>
-__device__ __forceinline__ bool map_gather(int total, unsigned tag, float* dst, int tid, int* status, int code, F at) {
-  const NS_GLOBAL u64* src[PER];
-  int di[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int i = tid + j * CT;
-    src[j] = nullptr; di[j] = 0;
-    if (i < total) { const u64* s_; at(i, s_, di[j]); src[j] = (const NS_GLOBAL u64*)s_; }
-  }
-  u64 v[PER];
-  unsigned spins = 0, clk0 = 0;
-  bool ok, good = true;
-  do {
-    ok = true;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) v[j] = src[j] ? __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((u64)tag << 32);
-#pragma unroll
-    for (int j = 0; j < PER; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
-    if (!ok && (++spins & 1023u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { good = false; ok = true; }
-      else if (ns_spin_timed_out(clk0)) { atomicExch(status, code); good = false; ok = true; }
-    }
-  } while (!ok);
-#pragma unroll
-  for (int j = 0; j < PER; ++j) if (src[j]) dst[di[j]] = __uint_as_float((unsigned)v[j]);
-  return good;
-}
 
 template <typename T>
 __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w) {
@@ -915,41 +815,41 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
     const unsigned tag = (unsigned)(st + 1);
     const long slot = st + 1;
     // ---- D1: h_att(s), align(s) -> x1 of the own units
-    bool good = map_gather<(DNR * A + CT - 1) / CT>(N * A, tag, ha, tid, status, 5, [&](int i, const u64*& src, int& di) {
+    bool good = ns_gather_mapped<(DNR * A + CT - 1) / CT, CT>(N * A, tag, tid, status, 5, [&](int i, const u64*& src, float*& dst) {
       const int n = i / A, u = i % A;
       src = d.att.x2 + ((size_t)n * CG + u / UPW) * X2N + A + u % UPW;
-      di = i;
+      dst = ha + i;
     });
-    good = map_gather<(DNR * 256 + CT - 1) / CT>(N * Tia, tag, als, tid, status, 5, [&](int i, const u64*& src, int& di) {
+    good = ns_gather_mapped<(DNR * 256 + CT - 1) / CT, CT>(N * Tia, tag, tid, status, 5, [&](int i, const u64*& src, float*& dst) {
       src = d.att.alx + i;
-      di = (i / Tia) * 256 + i % Tia;
+      dst = als + (i / Tia) * 256 + i % Tia;
     }) && good;
     if (!good) flag[0] = 1.f;
-    lds_barrier();
+    ns_lds_barrier();
     if (flag[0] != 0.f) return;
     for (int n = 0; n < N; ++n) {
       float s = dot_regs<8>(wpr, ha + n * A + k16 * 8);
       for (int t = k16; t < Tia; t += 32) s = fmaf(als[n * 256 + t], PM[(n * 256 + t) * DU + c16], s);
       red[n * CT + tid] = s;
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < N * DU) {
       const int n = tid / DU, j = tid % DU;
       float s = bpv;
 #pragma unroll
       for (int q = 0; q < 32; ++q) s += red[n * CT + q * DU + j];
-      put_granule(d.xa + (size_t)n * DD + u0 + j, tag, s);
+      ns_put_granule(d.xa + (size_t)n * DD + u0 + j, tag, s);
     }
     // ---- D2: x1 of every unit -> GRU_1 gates of the own units, r * h1(s-1)
-    good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, x1f, tid, status, 6, [&](int i, const u64*& src, int& di) {
-      src = d.xa + i; di = i;
+    good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 6, [&](int i, const u64*& src, float*& dst) {
+      src = d.xa + i; dst = x1f + i;
     });
     if (!good) flag[0] = 1.f;
-    lds_barrier();
+    ns_lds_barrier();
     if (flag[0] != 0.f) return;
     for (int n = 0; n < N; ++n)
       red[n * CT + tid] = dot_regs<32>(g1r, k32 < 8 ? x1f + n * DD + k32 * 32 : yh1 + n * 2 * DD + DD + (k32 - 8) * 32);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < N * 2 * DU) {
       const int n = tid / (2 * DU), c = tid % (2 * DU);
       float z = bg1v;
@@ -957,18 +857,18 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       for (int q = 0; q < 16; ++q) z += red[n * CT + q * 2 * DU + c];
       const float v = sigmoidf_(z);
       rus[n * 2 * DU + c] = v;
-      if (c < DU) put_granule(d.xb + (size_t)n * DD + u0 + c, tag, v * yh1[n * 2 * DD + DD + u0 + c]);
+      if (c < DU) ns_put_granule(d.xb + (size_t)n * DD + u0 + c, tag, v * yh1[n * 2 * DD + DD + u0 + c]);
     }
     // ---- D3: r * h1 of every unit -> candidate, h1(s), y1 = x1 + h1 of the own units
-    good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, rhf, tid, status, 7, [&](int i, const u64*& src, int& di) {
-      src = d.xb + i; di = i;
+    good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 7, [&](int i, const u64*& src, float*& dst) {
+      src = d.xb + i; dst = rhf + i;
     });
     if (!good) flag[0] = 1.f;
-    lds_barrier();
+    ns_lds_barrier();
     if (flag[0] != 0.f) return;
     for (int n = 0; n < N; ++n)
       red[n * CT + tid] = dot_regs<16>(c1r, k16 < 16 ? x1f + n * DD + k16 * 16 : rhf + n * DD + (k16 - 16) * 16);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < N * DU) {
       const int n = tid / DU, j = tid % DU;
       float z = bc1v;
@@ -976,20 +876,20 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       for (int q = 0; q < 32; ++q) z += red[n * CT + q * DU + j];
       const float c = tanhf_(z), u = rus[n * 2 * DU + DU + j];
       const float h = u * yh1[n * 2 * DD + DD + u0 + j] + (1.f - u) * c;
-      put_granule(d.xc + (size_t)n * 2 * DD + u0 + j, tag, x1f[n * DD + u0 + j] + h);
-      put_granule(d.xc + (size_t)n * 2 * DD + DD + u0 + j, tag, h);
+      ns_put_granule(d.xc + (size_t)n * 2 * DD + u0 + j, tag, x1f[n * DD + u0 + j] + h);
+      ns_put_granule(d.xc + (size_t)n * 2 * DD + DD + u0 + j, tag, h);
     }
-    lds_barrier();                           // yh1's h1 half was read above; the gather below rewrites it
+    ns_lds_barrier();                           // yh1's h1 half was read above; the gather below rewrites it
     // ---- D4: y1 | h1 of every unit -> GRU_2 gates of the own units, r * h2(s-1)
-    good = map_gather<(DNR * 2 * DD + CT - 1) / CT>(N * 2 * DD, tag, yh1, tid, status, 8, [&](int i, const u64*& src, int& di) {
-      src = d.xc + i; di = i;
+    good = ns_gather_mapped<(DNR * 2 * DD + CT - 1) / CT, CT>(N * 2 * DD, tag, tid, status, 8, [&](int i, const u64*& src, float*& dst) {
+      src = d.xc + i; dst = yh1 + i;
     });
     if (!good) flag[0] = 1.f;
-    lds_barrier();
+    ns_lds_barrier();
     if (flag[0] != 0.f) return;
     for (int n = 0; n < N; ++n)
       red[n * CT + tid] = dot_regs<32>(g2r, k32 < 8 ? yh1 + n * 2 * DD + k32 * 32 : h2f + n * DD + (k32 - 8) * 32);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < N * 2 * DU) {
       const int n = tid / (2 * DU), c = tid % (2 * DU);
       float z = bg2v;
@@ -997,18 +897,18 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       for (int q = 0; q < 16; ++q) z += red[n * CT + q * 2 * DU + c];
       const float v = sigmoidf_(z);
       rus[n * 2 * DU + c] = v;
-      if (c < DU) put_granule(d.xd + (size_t)n * DD + u0 + c, tag, v * h2f[n * DD + u0 + c]);
+      if (c < DU) ns_put_granule(d.xd + (size_t)n * DD + u0 + c, tag, v * h2f[n * DD + u0 + c]);
     }
     // ---- D5: r * h2 of every unit -> candidate, h2(s), y2 = y1 + h2 of the own units; the feedback shares
-    good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, rhf, tid, status, 9, [&](int i, const u64*& src, int& di) {
-      src = d.xd + i; di = i;
+    good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 9, [&](int i, const u64*& src, float*& dst) {
+      src = d.xd + i; dst = rhf + i;
     });
     if (!good) flag[0] = 1.f;
-    lds_barrier();
+    ns_lds_barrier();
     if (flag[0] != 0.f) return;
     for (int n = 0; n < N; ++n)
       red[n * CT + tid] = dot_regs<16>(c2r, k16 < 16 ? yh1 + n * 2 * DD + k16 * 16 : rhf + n * DD + (k16 - 16) * 16);
-    lds_barrier();
+    ns_lds_barrier();
     if (tid < N * DU) {
       const int n = tid / DU, j = tid % DU;
       float z = bc2v;
@@ -1019,9 +919,9 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       const float y = yh1[n * 2 * DD + u0 + j] + h;
       y2s[n * DU + j] = y;
       d.y2[((long)n * S1 + slot) * DD + u0 + j] = y;
-      if (st + 1 < p.S) put_granule(d.xe + (size_t)n * DD + u0 + j, tag, h);
+      if (st + 1 < p.S) ns_put_granule(d.xe + (size_t)n * DD + u0 + j, tag, h);
     }
-    lds_barrier();
+    ns_lds_barrier();
     if (st + 1 < p.S) {
       // f1(s+1) share of the own rows: thread = (column tid & 255, rows 8 (tid >> 8) ..)
       for (int n = 0; n < N; ++n) {
@@ -1030,16 +930,16 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
         for (int i = 0; i < 8; ++i) s = fmaf(fpr[i], y2s[n * DU + (tid >> 8) * 8 + i], s);
         red[n * CT + tid] = s;
       }
-      lds_barrier();
+      ns_lds_barrier();
       if (tid < D1)
         for (int n = 0; n < N; ++n)
-          put_granule(d.att.f1x + ((size_t)n * DNW + w) * D1 + tid, tag + 1, red[n * CT + tid] + red[n * CT + D1 + tid]);
+          ns_put_granule(d.att.f1x + ((size_t)n * DNW + w) * D1 + tid, tag + 1, red[n * CT + tid] + red[n * CT + D1 + tid]);
       // ---- D6: h2(s) of every unit for the next step
-      good = map_gather<(DNR * DD + CT - 1) / CT>(N * DD, tag, h2f, tid, status, 10, [&](int i, const u64*& src, int& di) {
-        src = d.xe + i; di = i;
+      good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 10, [&](int i, const u64*& src, float*& dst) {
+        src = d.xe + i; dst = h2f + i;
       });
       if (!good) flag[0] = 1.f;
-      lds_barrier();
+      ns_lds_barrier();
       if (flag[0] != 0.f) return;
     }
   }

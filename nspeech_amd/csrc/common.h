@@ -183,6 +183,33 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return s;
 }
 
+// sum_i w[i] * x[i] with the weights in registers and x in LDS (wave-uniform addresses: broadcast reads).  The chunks
+// are fenced so that the compiler keeps at most two chunks of x in flight instead of hoisting every LDS read of the
+// product to its top (the weights already take most of the register file).
+template <int NK>
+__device__ __forceinline__ float dot_regs(const float (&w)[NK], const float* x) {
+  static_assert(NK % 4 == 0 || NK < 4, "chunking");
+  float s0 = 0.f, s1 = 0.f;
+  if constexpr (NK < 4) {
+#pragma unroll
+    for (int i = 0; i < NK; ++i) s0 = fmaf(w[i], x[i], s0);
+    return s0;
+  } else {
+    float4 cur = *(const float4*)x;
+#pragma unroll
+    for (int i = 0; i < NK; i += 4) {
+      float4 nxt = cur;
+      if (i + 4 < NK) nxt = *(const float4*)(x + i + 4);
+      s0 = fmaf(w[i], cur.x, s0); s1 = fmaf(w[i + 1], cur.y, s1);
+      s0 = fmaf(w[i + 2], cur.z, s0); s1 = fmaf(w[i + 3], cur.w, s1);
+      // the sums pass through the fence: this chunk's FMAs cannot sink below it, later reads cannot rise above it
+      asm volatile("" : "+v"(s0), "+v"(s1) :: "memory");
+      cur = nxt;
+    }
+    return s0 + s1;
+  }
+}
+
 // ---------------------------------------------------------------- split-bf16 helpers
 // fp32 value x = hi + lo (hi = bf16(x), lo = bf16(x - hi)); products hi*hi + hi*lo + lo*hi
 __device__ __forceinline__ void ldsplit8(const float* p, bool ok, bf16x8& hi, bf16x8& lo) {
@@ -215,28 +242,17 @@ __device__ __forceinline__ void ns_rows32_store(bf16_t* base, int nkc, int n, in
   base[(i16 + 1) * 8 + (k & 7)] = (bf16_t)(v - (float)h);
 }
 
-// ---------------------------------------------------------------- bounded spins of the persistent kernels
-// Every wait of a persistent kernel is bounded in WALL-CLOCK time, not in iterations: a workgroup that cannot be placed
-// because a foreign kernel (a collective's channel kernel, a weight-gradient product on the second stream) holds its CU
-// keeps its peers polling for as long as that kernel lives, and an iteration count says nothing about how long that is.
-// The clock (s_memrealtime, 100 MHz) is read once per 1024 polls; 32 bits of it wrap after 42 s, far beyond the bound.
-constexpr unsigned NS_SPIN_TICKS = 200000000u;      // 2 s
+// ---------------------------------------------------------------- LDS words shared between waves
+// (the persistent kernels' exchange between WORKGROUPS - granules, bounded spins, the LDS-only barrier - is exchange.h)
 // Volatile accesses to LDS words that another wave of the workgroup polls / raises.  Through a GENERIC pointer a volatile
 // access compiles to flat_load / flat_store ... sc0 sc1, and its s_waitcnt vmcnt(0) also waits for every vector-memory
 // load the wave has in flight (the sweep of lstm_wide, the weight prefetches of the WaveNet chain); with the LDS address
 // space spelled out it is a ds_read / ds_write that only touches lgkmcnt.
-#define NS_GLOBAL __attribute__((address_space(1)))      // a pointer known to be global memory (pointers out of by-value
-                                                        // argument structs are generic: flat_load / flat_store)
 template <typename T> __device__ __forceinline__ T ns_lds_peek(const T* p) {
   return *(const volatile __attribute__((address_space(3))) T*)p;
 }
 template <typename T> __device__ __forceinline__ void ns_lds_poke(T* p, T v) {
   *(volatile __attribute__((address_space(3))) T*)p = v;
-}
-__device__ __forceinline__ bool ns_spin_timed_out(unsigned& t0) {
-  const unsigned now = (unsigned)wall_clock64() | 1u;
-  if (t0 == 0u) { t0 = now; return false; }
-  return now - t0 > NS_SPIN_TICKS;
 }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }

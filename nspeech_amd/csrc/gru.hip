@@ -12,7 +12,7 @@
 //            r * h are bf16 (hi / lo) operand images in LDS, two LDS-only barriers per step;
 //   H = 256: (hi, lo) planes are 768 KB, more than a CU holds: a chain is a cluster of 4 workgroups with 64 units each
 //            (the same 48 K values per workgroup); r * h and h travel as {step tag, fp32} granules written and polled
-//            with relaxed agent-scope atomics (the data is its own flag, cdna guide G16), gathered by two poller waves.
+//            with relaxed agent-scope atomics ("The tagged-granule exchange"), gathered by two poller waves.
 //            A 16-unit block's K = 256 is split over two compute waves (the halves meet through LDS), which keeps the
 //            resident weights of every compute wave at 96 VGPRs in both shapes.
 // The product is taken transposed (weights = A operand, state = B operand): a lane's accumulators are 4 consecutive
@@ -24,7 +24,7 @@
 //
 // LDS hand-over audit (one image per operand, no double buffering needed):
 //   forward   himg   written in phase 2 of slot s (own block, G = 1) or by the pollers between Bp2(s) and B0(s+1); read in
-//                    phase 1 of slot s+1 behind B0(s+1); phase 1 reads of slot s are complete at B1(s) (wg_barrier waits
+//                    phase 1 of slot s+1 behind B0(s+1); phase 1 reads of slot s are complete at B1(s) (ns_lds_barrier waits
 //                    for lgkmcnt(0)), in front of any write of slot s.  A peer's h(s) granule can only exist once every
 //                    workgroup's r*h(s) is published, i.e. after all phase-1 reads of slot s everywhere.
 //             rhimg  written in phase 1 of slot s / by the pollers between B0(s) [Bp1(s)] and B1(s); read in phase 2 behind
@@ -35,11 +35,10 @@
 //   backward  dzcimg written in phase 1 of slot s (behind B2(s-1) in program order), read behind B1(s), reads complete at
 //                    B2(s); dzgimg written in phase 2 (behind B1(s)), read behind B2(s), reads complete at B1(s+1);
 //             st[b]  prefetchers write slot s+1 between B1(s) and B2(s); read in phase 1 of slot s+1 behind B2(s).
-#include "common.h"
+#include "exchange.h"
 #include <stdint.h>
 #include <stdlib.h>
 
-typedef unsigned long long u64;
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -97,7 +96,6 @@ template <int H_> struct GCfg {
 // (W + 8) * 2 bytes = 4 banks mod 64 keeps the 16 rows of a ds_read_b128 fragment read on different banks, and every offset
 // is (a lane's base) + (a compile-time constant) - the pollers' 32 - 64 image writes per gather carry no address arithmetic.
 __device__ __forceinline__ int swz(int row, int k, int W) { return row * (W + 8) + k; }
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 8 consecutive weights as an MFMA fragment: hi = bf16(w), lo = bf16(w - hi) (lo only for three passes)
 template <typename T, int NPL>
@@ -147,7 +145,7 @@ __device__ __forceinline__ void put_image(bf16_t* img, int plane_stride, int off
 // ONE 16-byte write-through store per lane and 1 KB of consecutive bytes per wave (with [row][unit] order a wave wrote
 // 64 scattered 8-byte pieces per instruction, two instructions per exchange: the store path, not the fabric, set the
 // publish time).  `slot` = (block * 2 + kh) * 64 + lane.
-typedef __attribute__((ext_vector_type(4))) unsigned gru_u32x4;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 __device__ __forceinline__ void publish2(u64* buf, int nslots, int slot, unsigned tag, const float (&v)[2]) {
   unsigned pay[2];
 #pragma unroll
@@ -158,7 +156,7 @@ __device__ __forceinline__ void publish2(u64* buf, int nslots, int slot, unsigne
   const uintptr_t base = (uintptr_t)buf;
   const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)base), bhi = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32));
   const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, nslots * 16, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b128((gru_u32x4){pay[0], tag, pay[1], tag}, rs, (unsigned)slot * 16u, 0, 16);      // aux 16 = sc1
+  __builtin_amdgcn_raw_buffer_store_b128((u32x4){pay[0], tag, pay[1], tag}, rs, (unsigned)slot * 16u, 0, 16);      // aux 16 = sc1
 }
 template <int NR> __device__ __forceinline__ void publish2(u64*, int, int, unsigned, const float (&)[NR]) {}      // (NR = 4: one workgroup per chain, nothing is published)
 
@@ -182,7 +180,9 @@ template <typename T, int NR> __device__ __forceinline__ void store_vals(T* p, c
 //            tags are checked), one 4-byte LDS write per plane;
 //   gather8  8-byte loads, one granule each, 2-byte LDS writes.
 // Poller pw takes the second half of the slots.  Returns false when the wave gave up (status raised / wall-clock bound).
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+// Both spell the give-up rule of exchange.h (ns_spin::give_up) out: through the shared function - in every form of the call
+// that was tried - gru_fwd_kernel<256, 3, float, false>, which lives at the SGPR limit, spills one more SGPR pair and takes
+// 143 VGPRs instead of 142 (profiles/exchange_header.txt).  Cadence, bound and status code are the shared ones.
 template <int W, int NPL, int ILD = W + 8>       // ILD: row stride of the image (a gather may fill a column range of a wider one)
 __device__ __forceinline__ bool gather(const u64* src_, unsigned tag, bf16_t* img, int pw, int lane, int* status) {
   constexpr int NLD = W / 16;                    // 16-byte loads per lane: (W / 16 blocks x 2 halves x 64 lanes) / 2 pollers / 64
@@ -201,7 +201,7 @@ __device__ __forceinline__ bool gather(const u64* src_, unsigned tag, bf16_t* im
     for (int j = 0; j < NLD; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)lane * 16u, j * 1024, 16);
 #pragma unroll
     for (int j = 0; j < NLD; ++j) ok = ok && v[j][1] == tag && v[j][3] == tag;
-    if (!ok && (++spins & 1023u) == 0) {
+    if (!ok && (++spins & 1023u) == 0) {         // ns_spin::give_up, spelled out: see above the two gathers
       if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ok = gave_up = true;
       else if (ns_spin_timed_out(clk0)) { atomicExch(status, 1); ok = gave_up = true; }
     }
@@ -219,7 +219,7 @@ __device__ __forceinline__ bool gather(const u64* src_, unsigned tag, bf16_t* im
 template <int W, int NPL, int ILD = W + 8>
 __device__ __forceinline__ bool gather8(const u64* src_, unsigned tag, bf16_t* img, int pw, int lane, int* status) {
   constexpr int PPG = W / 8;                     // granules per lane: 16 W / 128
-  const NS_GLOBAL char* src = (const NS_GLOBAL char*)((const NS_GLOBAL u64*)src_ + pw * PPG * 64);
+  const char* src = (const char*)(src_ + pw * PPG * 64);
   const unsigned lo8 = (unsigned)lane * 8u;
   // granule jj * 64 + l (jj = pw * PPG + j): row (l / 2) & 15, unit 16 (jj >> 2) + 8 (jj & 1) + 4 (l >> 5) + 2 ((jj >> 1) & 1) + (l & 1)
   unsigned short* dst = (unsigned short*)img + ((lane >> 1) & 15) * ILD + 4 * (lane >> 5) + (lane & 1) + 16 * ((pw * PPG) >> 2);
@@ -233,10 +233,10 @@ __device__ __forceinline__ bool gather8(const u64* src_, unsigned tag, bf16_t* i
     ok = true;
 #pragma unroll
     for (int j = 0; j < PPG; ++j)
-      v[j] = __hip_atomic_load((const NS_GLOBAL u64*)(src + j * 512 + lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      v[j] = ns_ld_granule((const u64*)(src + j * 512 + lo));
 #pragma unroll
-    for (int j = 0; j < PPG; ++j) ok = ok && ((unsigned)(v[j] >> 32) == tag);
-    if (!ok && (++spins & 1023u) == 0) {
+    for (int j = 0; j < PPG; ++j) ok = ok && ns_granule_tag(v[j]) == tag;
+    if (!ok && (++spins & 1023u) == 0) {         // ns_spin::give_up, spelled out: see above the two gathers
       if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ok = gave_up = true;
       else if (ns_spin_timed_out(clk0)) { atomicExch(status, 1); ok = gave_up = true; }
     }
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
     for (int s = 0; s < T_; ++s) {
       const int t = rev ? T_ - 1 - s : s, buf = s % C::NBUF;
       const unsigned rowi = (unsigned)(n * a.P + a.padl + t);
-      wg_barrier();                                        // B0: state image and stage of this slot are complete
+      ns_lds_barrier();                                        // B0: state image and stage of this slot are complete
       if (abortf[0]) return;
       GRU_STAMP(0);
       const float* xrow = xs + buf * XS_F + xoff;
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
         // the partner wave (the other half of K) gets the sums of ITS registers, this wave takes the partner's for its own
         const float4 give = kh ? make_float4(ar[0], ar[1], au[0], au[1]) : make_float4(ar[2], ar[3], au[2], au[3]);
         *(float4*)(pbuf + (wave * 64 + lane) * 4) = give;
-        wg_barrier();                                      // Bp1
+        ns_lds_barrier();                                      // Bp1
         const float4 take = *(const float4*)(pbuf + (((wave + NB) % C::GW) * 64 + lane) * 4);
         pr[0] = (kh ? ar[2] : ar[0]) + take.x; pr[1] = (kh ? ar[3] : ar[1]) + take.y;
         pu[0] = (kh ? au[2] : au[0]) + take.z; pu[1] = (kh ? au[3] : au[1]) + take.w;
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
         if (nvalid) store_vals<T, NR>(rhout + rowi * (unsigned)H + un, rhv);
       }
       GRU_STAMP(2);
-      wg_barrier();                                        // B1: r * h image complete
+      ns_lds_barrier();                                        // B1: r * h image complete
       if (abortf[0]) return;
       GRU_STAMP(3);
       f32x4 ac = {0.f, 0.f, 0.f, 0.f};
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
       if constexpr (KSPLIT == 2) {
         const float2 give = kh ? make_float2(ac[0], ac[1]) : make_float2(ac[2], ac[3]);
         *(float2*)(pbuf + (wave * 64 + lane) * 4) = give;
-        wg_barrier();                                      // Bp2
+        ns_lds_barrier();                                      // Bp2
         const float2 take = *(const float2*)(pbuf + (((wave + NB) % C::GW) * 64 + lane) * 4);
         pc[0] = (kh ? ac[2] : ac[0]) + take.x; pc[1] = (kh ? ac[3] : ac[1]) + take.y;
       } else {
@@ -438,14 +438,14 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
     if (T_ > 1) { issue(1); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NI) : "memory"); }
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     for (int s = 0; s < T_; ++s) {
-      wg_barrier();                                        // B0: slot s handed over
+      ns_lds_barrier();                                        // B0: slot s handed over
       if (abortf[0]) return;
       const bool more = s + 2 < T_ && !(a.dbg & 1);
       if (more) issue(s + 2);                              // its buffer was last read in slot s - 1
-      if (KSPLIT == 2) wg_barrier();                       // Bp1
-      wg_barrier();                                        // B1
+      if (KSPLIT == 2) ns_lds_barrier();                       // Bp1
+      ns_lds_barrier();                                        // B1
       if (abortf[0]) return;
-      if (KSPLIT == 2) wg_barrier();                       // Bp2
+      if (KSPLIT == 2) ns_lds_barrier();                       // Bp2
       if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NI) : "memory");     // slot s + 1 has landed
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -455,13 +455,13 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
       const int pw = wave - C::GW - 1;
       for (int s = 0; s < T_; ++s) {
         if (s > 0 && !gather_sel<H, NPL, H + 8, false>(a.dbg, xh, (unsigned)s, himg, pw, lane, a.status)) abortf[0] = 1;
-        wg_barrier();                                      // B0
+        ns_lds_barrier();                                      // B0
         if (abortf[0]) return;
-        if (KSPLIT == 2) wg_barrier();                     // Bp1: the own compute waves publish behind it
+        if (KSPLIT == 2) ns_lds_barrier();                     // Bp1: the own compute waves publish behind it
         if (!gather_sel<H, NPL, H + 8, false>(a.dbg, xr, (unsigned)(s + 1), rhimg, pw, lane, a.status)) abortf[0] = 1;
-        wg_barrier();                                      // B1
+        ns_lds_barrier();                                      // B1
         if (abortf[0]) return;
-        if (KSPLIT == 2) wg_barrier();                     // Bp2
+        if (KSPLIT == 2) ns_lds_barrier();                     // Bp2
       }
     }
   }
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
     const int hoff = sizeof(T) == 4 ? xoff : ((b * 2 + (q4 >> 1)) * 16 + col) * 8 + (q4 & 1) * 4 + mo;     // ... the h_prev section
     T* dzg = (T*)a.dzg[d];
     T* dzc = (T*)a.dzc[d];
-    wg_barrier();                                          // stage of the first slot
+    ns_lds_barrier();                                          // stage of the first slot
     for (int s = 0; s < T_; ++s) {
       const int t = rev ? s : T_ - 1 - s, buf = s % C::NBUF;      // the forward pass' steps, last first
       const int tp = rev ? t + 1 : t - 1;                  // the step whose output is this step's h_prev
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
         store_vals<T, NR>(dzc + rowi * (unsigned)H + un, dzcv);
         store_vals<T, NR>(dzg + rowi * (unsigned)(2 * H) + H + un, dzuv);
       }
-      wg_barrier();                                        // B1: dzc image complete
+      ns_lds_barrier();                                        // B1: dzc image complete
       if (abortf[0]) return;
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
       if constexpr (KSPLIT == 2) {
         const float2 give = kh ? make_float2(acc[0], acc[1]) : make_float2(acc[2], acc[3]);
         *(float2*)(pbuf + (wave * 64 + lane) * 2) = give;
-        wg_barrier();                                      // Bpa
+        ns_lds_barrier();                                      // Bpa
         const float2 take = *(const float2*)(pbuf + (((wave + NB) % C::GW) * 64 + lane) * 2);
         drh[0] = (kh ? acc[2] : acc[0]) + take.x; drh[1] = (kh ? acc[3] : acc[1]) + take.y;
       } else {
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
         publish2(xg_, 16 * H / 2, ((g * NB + b) * KSPLIT + kh) * 64 + lane, (unsigned)(s + 1), dzrv);
       }
       if (nvalid) store_vals<T, NR>(dzg + rowi * (unsigned)(2 * H) + un, dzrv);
-      wg_barrier();                                        // B2: dzg image complete (and the next slot's stage)
+      ns_lds_barrier();                                        // B2: dzg image complete (and the next slot's stage)
       if (abortf[0]) return;
       acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
       if constexpr (KSPLIT == 2) {
         const float2 give = kh ? make_float2(acc[0], acc[1]) : make_float2(acc[2], acc[3]);
         *(float2*)(pbuf + (wave * 64 + lane) * 2) = give;
-        wg_barrier();                                      // Bpb
+        ns_lds_barrier();                                      // Bpb
         const float2 take = *(const float2*)(pbuf + (((wave + NB) % C::GW) * 64 + lane) * 2);
         carry[0] = cn[0] + (kh ? acc[2] : acc[0]) + take.x;
         carry[1] = cn[1] + (kh ? acc[3] : acc[1]) + take.y;
@@ -659,34 +659,34 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
     issue(0);
     if (T_ > 1) { issue(1); wait_one_slot_left(); }
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    wg_barrier();
+    ns_lds_barrier();
     for (int s = 0; s < T_; ++s) {
       const bool more = s + 2 < T_;
       if (more) issue(s + 2);                              // its buffer was last read in phase 1 of slot s - 1
-      wg_barrier();                                        // B1
+      ns_lds_barrier();                                        // B1
       if (abortf[0]) return;
-      if (KSPLIT == 2) wg_barrier();                       // Bpa
+      if (KSPLIT == 2) ns_lds_barrier();                       // Bpa
       if (more) wait_one_slot_left(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // slot s + 1 has landed
-      wg_barrier();                                        // B2: hands slot s + 1 over
+      ns_lds_barrier();                                        // B2: hands slot s + 1 over
       if (abortf[0]) return;
-      if (KSPLIT == 2) wg_barrier();                       // Bpb
+      if (KSPLIT == 2) ns_lds_barrier();                       // Bpb
     }
   } else {
     // ================================================================ poller role (H = 256)
     if constexpr (G > 1) {
       const int pw = wave - C::GW - 2;
-      wg_barrier();
+      ns_lds_barrier();
       for (int s = 0; s < T_; ++s) {
         if (!gather_sel<H, NPL, H + 8, true>(a.dbg, xc_, (unsigned)(s + 1), dzcimg, pw, lane, a.status)) abortf[0] = 1;
-        wg_barrier();                                      // B1
+        ns_lds_barrier();                                      // B1
         if (abortf[0]) return;
-        if (KSPLIT == 2) wg_barrier();                     // Bpa: the own compute waves publish dzr / dzu behind it
+        if (KSPLIT == 2) ns_lds_barrier();                     // Bpa: the own compute waves publish dzr / dzu behind it
         // dzu went out in phase 1: this pass finds it at once, under the compute waves' first product; then dzr
         if (!gather_sel<H, NPL, 2 * H + 8, true>(a.dbg, xg_ + 16 * H, (unsigned)(s + 1), dzgimg + H, pw, lane, a.status)) abortf[0] = 1;
         if (!gather_sel<H, NPL, 2 * H + 8, true>(a.dbg, xg_, (unsigned)(s + 1), dzgimg, pw, lane, a.status)) abortf[0] = 1;
-        wg_barrier();                                      // B2
+        ns_lds_barrier();                                      // B2
         if (abortf[0]) return;
-        if (KSPLIT == 2) wg_barrier();                     // Bpb
+        if (KSPLIT == 2) ns_lds_barrier();                     // Bpb
       }
     }
   }

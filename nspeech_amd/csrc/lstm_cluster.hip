@@ -14,18 +14,18 @@
 // keeps its slice of W_h^T - 64 units x 4 gates x H - in REGISTERS as MFMA B fragments for the
 // whole sequence (8 waves x 8 units, 64 VGPRs per lane), and the cell state in registers too.
 // Per step the only inter-workgroup traffic is the new h slice (rows of the chain x 64 units), exchanged
-// through global memory as 8-byte {step tag, 2 x bf16} granules written and polled with relaxed
-// agent-scope atomics (sc1; no fences, data is its own flag), double-buffered by step parity.
+// through global memory as {step tag, 2 x bf16} granules (exchange.h; the protocol - granule, poll
+// cadence, bound, status word - is DESIGN.md, "The tagged-granule exchange"), double-buffered by step parity.
 // Measured exchange cost: ~1.3 us per step for 4 workgroups (vs ~6-8 us per dependent launch).
 //
 // Correctness of the 2-deep buffering: a workgroup publishes step s+2 into the slot of step s only
 // after it has gathered every peer's step s+1, which each peer published only after gathering step s.
-// Every spin is bounded; on timeout the kernel sets *status and every workgroup leaves.
-#include "common.h"
+// On a time-out (status 1 forward, 2 backward) every workgroup leaves; the single-role kernels read the status word
+// at the poll cadence too, so one expired wait ends the launch instead of costing every later step its own bound.
+#include "exchange.h"
 #include <stdlib.h>
 #include <stdint.h>
 
-typedef unsigned long long u64;
 constexpr int CW = 8;            // waves per workgroup
 constexpr int CTHREADS = CW * 64;
 
@@ -123,20 +123,11 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_fwd_kernel(LstmClusterA
       const int total = 16 * GPR;
       for (int i0 = tid; i0 < total; i0 += CTHREADS * 4) {
         u64 v[4];
-        unsigned spins = 0, clk0 = 0;
-        bool ok;
-        do {
-          ok = true;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int i = i0 + j * CTHREADS;
-            v[j] = i < total ? __hip_atomic_load(cur + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : ((u64)(unsigned)step << 32);
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) ok = ok && ((unsigned)(v[j] >> 32) == (unsigned)step);
-          if (!ok && (++spins & 1023u) == 0 && ns_spin_timed_out(clk0)) { atomicExch(a.status, 1); ok = true; }
-        } while (!ok);
+        ns_spin sp;
+        ns_poll_granules(v, (unsigned)step, sp, a.status, 1, [&](int j) {      // gave up: the status word is raised, read below
+          const int i = i0 + j * CTHREADS;
+          return i < total ? ns_ld_granule(cur + i) : ns_granule((unsigned)step, 0u);
+        });
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int i = i0 + j * CTHREADS;
@@ -183,8 +174,7 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_fwd_kernel(LstmClusterA
           const bf16_t b0 = (bf16_t)hv[r], b1 = (bf16_t)hp;
           const unsigned pay = (unsigned)(*(const unsigned short*)&b0) | ((unsigned)(*(const unsigned short*)&b1) << 16);
           const int row = g * 4 + r;
-          __hip_atomic_store(nxt + (size_t)row * GPR + (unit >> 1), ((u64)(unsigned)(step + 1) << 32) | pay,
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ns_put_granule(nxt + (size_t)row * GPR + (unit >> 1), ns_granule((unsigned)(step + 1), pay));
         }
       }
     }
@@ -274,20 +264,11 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_bwd_kernel(LstmClusterA
       const int total = 16 * GPR;
       for (int i0 = tid; i0 < total; i0 += CTHREADS * 8) {
         u64 v[8];
-        unsigned spins = 0, clk0 = 0;
-        bool okk;
-        do {
-          okk = true;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int i = i0 + j * CTHREADS;
-            v[j] = i < total ? __hip_atomic_load(cur + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : ((u64)(unsigned)bs << 32);
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) okk = okk && ((unsigned)(v[j] >> 32) == (unsigned)bs);
-          if (!okk && (++spins & 1023u) == 0 && ns_spin_timed_out(clk0)) { atomicExch(a.status, 2); okk = true; }
-        } while (!okk);
+        ns_spin sp;
+        ns_poll_granules(v, (unsigned)bs, sp, a.status, 2, [&](int j) {        // gave up: the status word is raised, read below
+          const int i = i0 + j * CTHREADS;
+          return i < total ? ns_ld_granule(cur + i) : ns_granule((unsigned)bs, 0u);
+        });
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int i = i0 + j * CTHREADS;
@@ -348,8 +329,7 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_bwd_kernel(LstmClusterA
       for (int j = 0; j < 4; ++j) {
         const bf16_t b0 = (bf16_t)dgv[0][j], b1 = (bf16_t)dgv[1][j];
         const unsigned pay = (unsigned)(*(const unsigned short*)&b0) | ((unsigned)(*(const unsigned short*)&b1) << 16);
-        __hip_atomic_store(nxt + (size_t)er * GPR + ((j * H + u0 + eu) >> 1), ((u64)(unsigned)(bs + 1) << 32) | pay,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ns_put_granule(nxt + (size_t)er * GPR + ((j * H + u0 + eu) >> 1), ns_granule((unsigned)(bs + 1), pay));
       }
     }
     if (ok) {
@@ -382,7 +362,7 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_bwd_kernel(LstmClusterA
 //
 // LDS hand-over audit (the class of the attention-backward race fixed in 844cc13 - an image filled by one role and
 // first read by another with no barrier in between).  Every image below is double-buffered by slot parity and handed
-// over by the ONE wg_barrier() per slot that every role joins (wg_barrier waits for lgkmcnt(0) first, so a role's LDS
+// over by the ONE ns_lds_barrier() per slot that every role joins (ns_lds_barrier waits for lgkmcnt(0) first, so a role's LDS
 // writes AND reads of the slot have completed when it arrives):
 //   forward   hs[s&1]   pollers fill it in front of barrier s, compute waves read it behind barrier s; the pollers'
 //                       next fill of the same image is for slot s+2, behind barrier s+1, which the compute waves join
@@ -391,7 +371,7 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_bwd_kernel(LstmClusterA
 //                       bf16 form: one interval earlier, see lstm_cluster2_fwd_kernel
 //             svs[s&1]  compute waves write it in slot s, the saver reads it behind barrier s+1 and joins barrier s+2
 //                       (after its reads returned) before the compute waves write that image again in slot s+2
-//             abortf    zeroed by wave 0 in front of its first wg_barrier, read by every role behind that barrier
+//             abortf    zeroed by wave 0 in front of its first ns_lds_barrier, read by every role behind that barrier
 //   backward  see lstm_cluster2p_bwd_kernel
 // The single-role kernels above use one image and __syncthreads() on both sides of every use.
 constexpr int XW = 4;
@@ -400,7 +380,6 @@ constexpr int FW_POLL = 2;               // poller waves (XW and XW + 3): half o
 constexpr int FW_WAVES = XW + 2 + FW_POLL;   // compute, poller, prefetcher, saver, second poller
 constexpr int XG_LD = 256 + 4;          // floats per row of the xg stage (pad: rows 4 apart hit different banks)
 
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
   const bf16_t b0 = (bf16_t)lo, b1 = (bf16_t)hi;
   return (unsigned)(*(const unsigned short*)&b0) | ((unsigned)(*(const unsigned short*)&b1) << 16);
@@ -484,14 +463,14 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
       else if constexpr (RPC == 8) return rep ? v[2 + r] : v[r];
       else return (rep & 2) ? ((rep & 1) ? v[3] : v[2]) : ((rep & 1) ? v[1] : v[0]);
     };
-    wg_barrier();                                      // xg of slot 0 and abortf are in place
+    ns_lds_barrier();                                      // xg of slot 0 and abortf are in place
     load_xg(0);
     // The slot loop of a compute role is a do-while (T >= 2 is checked on the host): with a loop guard in front the
     // compiler lays the slot out less well (backward 1.96 against 1.93 ms, forward 1.65 against 1.63 at batch 32, H 256, T 1000)
     int step = 0;
     do {
       const int t = d ? T - 1 - step : step, buf = step & 1;
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[buf]) return;
       const bool tr = (a.dbg & 16) && blockIdx.x == 0 && tid == 0 && step < 512;
       if (tr) a.trace[step * 8 + 0] = wall_clock64();
@@ -529,8 +508,8 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         if (step + 1 < T) {
           if (CS > 1) {
             u64* nxt = xb0 + (size_t)((step + 1) & 1) * CS * GPD + (size_t)wgc * GPD + (wave * 4 * RPC + g * RPC + r16) * 2;
-            __hip_atomic_store(nxt, ((u64)(unsigned)(step + 1) << 32) | hp.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(nxt + 1, ((u64)(unsigned)(step + 1) << 32) | hp.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ns_put_granule(nxt, ns_granule((unsigned)(step + 1), hp.x));
+            ns_put_granule(nxt + 1, ns_granule((unsigned)(step + 1), hp.y));
           }
           *(uint2*)(hs + (size_t)((step + 1) & 1) * 16 * H + swz_off(r16, u0 + wq, H)) = hp;   // the own block
         }
@@ -564,7 +543,7 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         if (step + 1 < T && holder) {
           if (CS > 1) {
             u64* nxt = xb0 + (size_t)((step + 1) & 1) * CS * GPD + (size_t)wgc * GPD + (wave * 4 * RPC + g * RPC + row) * 2 + pair;
-            __hip_atomic_store(nxt, ((u64)(unsigned)(step + 1) << 32) | hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ns_put_granule(nxt, ns_granule((unsigned)(step + 1), hp));
           }
           *(unsigned*)(hs + (size_t)((step + 1) & 1) * 16 * H + swz_off(row, u0 + wq + 2 * pair, H)) = hp;   // the own block
         }
@@ -585,20 +564,22 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
       }
       if (step + 1 < T) load_xg(step + 1);
     } while (++step < T);
-    wg_barrier();
+    ns_lds_barrier();
   } else if (wave == XW || wave == XW + 3) {
     // ================================================================ poller role: the peers' h blocks
     constexpr int NPG = (CS - 1) * GPD;                // granules to gather per slot
     constexpr int PPG = NPG / (FW_POLL * 64) > 0 ? NPG / (FW_POLL * 64) : 1;
     static_assert(CS == 1 || NPG == PPG * FW_POLL * 64, "poller coverage");
     const int j0 = (wave == XW ? 0 : 1) * PPG;
-    wg_barrier();
+    ns_lds_barrier();
     for (int step = 0; step < T; ++step) {
       const int buf = step & 1;
       const bool tr = (a.dbg & 16) && blockIdx.x == 0 && lane == 0 && wave == XW && step < 512;
       if (tr) a.trace[step * 8 + 4] = wall_clock64();
       if (step > 0 && CS > 1) {
         const u64* cur = xb0 + (size_t)(step & 1) * CS * GPD;   // published by the peers with tag = step
+        // (own loop, the give-up rule of exchange.h spelled out: through ns_poll_granules the kernel measured 22 us a
+        // launch slower - profiles/exchange_header.txt)
         u64 v[PPG];
         unsigned spins = 0, clk0 = 0;
         bool ok;
@@ -631,10 +612,10 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
           *(unsigned*)(dst + swz_off(lp % RPC, k, H)) = (unsigned)v[j];
         }
       }
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[buf]) return;
     }
-    wg_barrier();
+    ns_lds_barrier();
   } else if (wave == XW + 2) {
     // ================================================================ saver role (stores only)
     // Runs one slot behind the compute waves (slot s-1 is complete once barrier s has passed), so its store
@@ -664,13 +645,13 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
         }
       }
     };
-    wg_barrier();
+    ns_lds_barrier();
     for (int step = 0; step < T; ++step) {
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[step & 1]) return;
       if (step > 0) save(step - 1);
     }
-    wg_barrier();
+    ns_lds_barrier();
     save(T - 1);
   } else {
     // ================================================================ prefetcher role, one interval ahead:
@@ -695,16 +676,16 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
     pf_load(0);
     pf_store(0);
     if (T > 1) pf_load(1);
-    wg_barrier();
+    ns_lds_barrier();
     for (int step = 0; step < T; ++step) {
       if (step + 1 < T) {
         pf_store((step + 1) & 1);
         if (step + 2 < T) pf_load(step + 2);
       }
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[step & 1]) return;
     }
-    wg_barrier();
+    ns_lds_barrier();
   }
 }
 
@@ -748,7 +729,7 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
   u64* xb0 = a.xbuf + (size_t)(d * nch + rg) * 2 * GPC;                    // + parity * GPC
   const int u0 = wgc * X3_UPW;
   const int T = a.T;
-  if (tid < 2) abortf[tid] = 0;          // (audit) written by wave 0 in front of its first wg_barrier, read behind it
+  if (tid < 2) abortf[tid] = 0;          // (audit) written by wave 0 in front of its first ns_lds_barrier, read behind it
   if (RPC < 16) {
     // rows >= RPC of the operand images are MFMA padding: zeroed in front of every role's first barrier, never written
     for (int i = tid; i < 2 * 2 * 16 * H / 8; i += X3_WAVES * 64) ((uint4*)hsh)[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -785,7 +766,7 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     int step = 0;
     do {                                             // see lstm_cluster2_fwd_kernel
       const int t = d ? T - 1 - step : step, buf = step & 1;
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[buf]) return;
       // tile 0 = [i | j], tile 1 = [f | o]: column r16 -> gate 2*tile + (r16 >> 3), unit ul
       const float* xr = xgs + (size_t)buf * 16 * XG3_LD + (r16 >> 3) * X3_UPW + ul;
@@ -825,8 +806,7 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
         u64* nxt = xb0 + (size_t)((step + 1) & 1) * GPC + pub0;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          __hip_atomic_store(nxt + r, ((u64)(unsigned)(step + 1) << 32) | (u64)__float_as_uint(hv[r]), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+          ns_put_granule(nxt + r, ns_granule((unsigned)(step + 1), hv[r]));
       }
       // results for the backward pass / the consumers of h go to LDS; the saver wave writes them out
       if (cell_lane) {
@@ -843,7 +823,7 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
         }
       }
     } while (++step < T);
-    wg_barrier();
+    ns_lds_barrier();
   } else if (wave < X3W + X3_POLL) {
     // ================================================================ poller role: granule lane + 64 * jj of the chain
     // decodes as r = lane & 3, unit in wave = (lane >> 2) & 7, and with xi = 2 jj + (lane >> 5): g = xi % (RPC / 4),
@@ -855,20 +835,15 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
       if (step > 0) {
         const u64* cur = xb0 + (size_t)(step & 1) * GPC;
         u64 v[PPG];
-        unsigned spins = 0, clk0 = 0;
+        ns_spin sp;
         bool ok;
         do {
           ok = true;
 #pragma unroll
-          for (int j = 0; j < PPG; ++j) v[j] = __hip_atomic_load(cur + lane + (j0 + j) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          for (int j = 0; j < PPG; ++j) v[j] = ns_ld_granule(cur + lane + (j0 + j) * 64);
 #pragma unroll
-          for (int j = 0; j < PPG; ++j) ok = ok && ((unsigned)(v[j] >> 32) == (unsigned)step);
-          if (!ok) {
-            if ((++spins & 1023u) == 0) {
-              if (__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { abortf[buf] = 1; ok = true; }
-              else if (ns_spin_timed_out(clk0)) { atomicExch(a.status, 1); abortf[buf] = 1; ok = true; }
-            }
-          }
+          for (int j = 0; j < PPG; ++j) ok = ok && ns_granule_tag(v[j]) == (unsigned)step;
+          if (!ok && sp.give_up(a.status, 1)) { abortf[buf] = 1; ok = true; }
         } while (!ok);
         bf16_t* dh_ = hsh + (size_t)buf * 16 * H;
         bf16_t* dl_ = hsl + (size_t)buf * 16 * H;
@@ -884,10 +859,10 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
           dl_[so] = (bf16_t)(x - (float)hi);
         }
       }
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[buf]) return;
     }
-    wg_barrier();
+    ns_lds_barrier();
   } else if (wave == X3W + X3_POLL) {
     // ================================================================ saver role (stores only), one slot behind
     // per slot and row: h f32 8 chunks of 16 B, c 8, gates 16, h bf16 4 -> 9 per lane at 16 rows
@@ -921,11 +896,11 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
       }
     };
     for (int step = 0; step < T; ++step) {
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[step & 1]) return;
       if (step > 0) save(step - 1);
     }
-    wg_barrier();
+    ns_lds_barrier();
     save(T - 1);
   } else {
     // ================================================================ prefetcher role: RPC rows x 4 gates x 32 units = 32 RPC
@@ -951,14 +926,14 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
     pf_store(0);
     if (T > 1) pf_load(1);
     for (int step = 0; step < T; ++step) {
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[step & 1]) return;
       if (step + 1 < T) {
         pf_store((step + 1) & 1);
         if (step + 2 < T) pf_load(step + 2);
       }
     }
-    wg_barrier();
+    ns_lds_barrier();
   }
 }
 
@@ -995,7 +970,7 @@ constexpr int DGI_LD = 256 + 8;          // bf16 per row of the operand image (r
 // (audit, slot s = backward step s: stage[(s+1)&1] is stored between barrier(s-1) and barrier(s), last read in front of
 // barrier(s-1), next read behind barrier(s); dgi[s&1] is written in front of barrier(s), read by the product and - one
 // slot behind - the saver between barrier(s) and barrier(s+1), rewritten behind barrier(s+1); c0, stage[0] and abortf
-// are written in front of the one wg_barrier() every role passes ahead of slot 0, and read behind it).
+// are written in front of the one ns_lds_barrier() every role passes ahead of slot 0, and read behind it).
 // Slot timings of the forms that led here: profiles/r03_cluster_bwd_trace.txt.
 template <int HB, int RPC>
 __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmClusterArgs a) {
@@ -1021,7 +996,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
   u64* xb0 = a.xbuf + (size_t)(d * nch + rg) * 2 * CS * CS * GPD;
   const int u0 = wgc * 64;
   const int T = a.T;
-  if (tid == 0) abortf[0] = 0;           // (audit) by wave 0 in front of its first wg_barrier, read behind it
+  if (tid == 0) abortf[0] = 0;           // (audit) by wave 0 in front of its first ns_lds_barrier, read behind it
   if (RPC < 16 && blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
   auto t_of = [&](int step) { return d ? T - 1 - step : step; };
 
@@ -1085,7 +1060,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
         cpv[r] = cprev; gfv[r] = gf;
       }
     };
-    wg_barrier();                                      // stage 0, c0 and abortf are in place
+    ns_lds_barrier();                                      // stage 0, c0 and abortf are in place
     indep(0);
     int bs = 0;                                      // backward step index; forward step = T-1-bs
     do {                                             // see lstm_cluster2_fwd_kernel
@@ -1101,6 +1076,8 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
       f32x4 rec = ownp;
       if (bs > 0 && CS > 1) {
         const u64* cur = xb0 + (size_t)(bs & 1) * CS * CS * GPD + (size_t)wgc * CS * GPD + (g * OR / 2) * 64 + wu;
+        // (own loop, the give-up rule of exchange.h spelled out: through ns_poll_granules this kernel measured slower,
+        // as its own loop around ns_spin::give_up slower still - profiles/exchange_header.txt)
         u64 v[CS > 1 ? CS - 1 : 1][NV];
         unsigned spins = 0, clk0 = 0;
         bool ok;
@@ -1156,7 +1133,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
         *(uint2*)(di + row * DGI_LD + wu * 4) = pk;       // k = unit * 4 + gate
       }
       if (tr) a.trace[bs * 8 + 1] = wall_clock64();
-      wg_barrier();            // the operand image is complete (all four compute waves)
+      ns_lds_barrier();            // the operand image is complete (all four compute waves)
       if (abortf[0]) return;
       if (tr) a.trace[bs * 8 + 2] = wall_clock64();
       // ---- partial sums of dh from the own 256 gate columns; wave w: units 16 w .. 16 w + 16 of every workgroup
@@ -1188,12 +1165,10 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
             u64* dst = nxt + (size_t)(j * CS + wgc) * GPD + (g * 2) * 64 + wu;
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-              __hip_atomic_store(dst + h * 64, ((u64)(unsigned)(bs + 1) << 32) | pack_bf16(acc[j][2 * h], acc[j][2 * h + 1]),
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              ns_put_granule(dst + h * 64, ns_granule((unsigned)(bs + 1), pack_bf16(acc[j][2 * h], acc[j][2 * h + 1])));
           } else if (RPC == 8 || g < 2) {
             const unsigned pay = (RPC == 4 && g) ? pack_bf16(acc[j][2], acc[j][3]) : pack_bf16(acc[j][0], acc[j][1]);
-            __hip_atomic_store(nxt + (size_t)(j * CS + wgc) * GPD + g * 64 + wu, ((u64)(unsigned)(bs + 1) << 32) | pay,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ns_put_granule(nxt + (size_t)(j * CS + wgc) * GPD + g * 64 + wu, ns_granule((unsigned)(bs + 1), pay));
           }
         }
         if (tr) a.trace[bs * 8 + 7] = wall_clock64();
@@ -1230,10 +1205,10 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
         }
       }
     };
-    wg_barrier();
+    ns_lds_barrier();
     for (int bs = 0; bs < T; ++bs) {
       if (bs > 0) save(bs - 1);
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[0]) return;
     }
     save(T - 1);
@@ -1286,13 +1261,13 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
       pf_store(0);
       if (T > 1) pf_load(1);
     }
-    wg_barrier();
+    ns_lds_barrier();
     for (int bs = 0; bs < T; ++bs) {
       if (bs + 1 < T) {
         pf_store((bs + 1) & 1);
         if (bs + 2 < T) pf_load(bs + 2);
       }
-      wg_barrier();
+      ns_lds_barrier();
       if (abortf[0]) return;
     }
   }

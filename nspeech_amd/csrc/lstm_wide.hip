@@ -42,10 +42,11 @@
 // kernel and a 16-unit form of the partial-sum kernel (twice the write-through bytes, 4.97 us) stayed behind an
 // environment switch that no test set and were retired (profiles/wide_forms_retired.txt).
 //
-// Every spin is bounded; a timeout raises the status word and all waves of the workgroup leave together.  The grid
+// Every spin is bounded ("The tagged-granule exchange"; the forward sweep keeps its own loop with the same
+// bound); a timeout raises the status word and all waves of the workgroup leave together.  The grid
 // (row groups x unit blocks, one workgroup per CU) must be resident at once: ns_lstm_wide_supported() refuses shapes
 // that do not fit.
-#include "common.h"
+#include "exchange.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -398,9 +399,6 @@ __global__ __launch_bounds__(WTF) void lstm_wide_fwd_kernel(WideArgs a) {
 // Exchange area (in work): [row group][step parity][destination][source][128 items] of 8 bytes, zeroed per launch.
 constexpr int PSW = 8;                       // product waves
 constexpr int PST = PSW * 64 + 128;          // + two cell waves
-typedef unsigned long long ps_u64;
-// orders LDS only: __syncthreads() would also drain the vector-memory queue (the publish stores' acknowledgements)
-__device__ __forceinline__ void ps_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int UPB = 32;                      // units per workgroup
 // LANES: the operand image has 8 rows and an MFMA tile 16, so half of every product is padding.  With LANES the A
@@ -410,7 +408,7 @@ constexpr int UPB = 32;                      // units per workgroup
 // instructions per wave and step instead of 16, on a phase that is bound by instruction issue.  Same granules, same
 // addresses, same bits.  LANES = false is the form before that (NS_WIDE_LANES=0, read per call; the tests compare them).
 template <typename T, int NT, bool LANES>    // NT = destination tiles per product wave = H / 128
-__global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u64* xbuf) {
+__global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, u64* xbuf) {
   constexpr int TB = UPB / 16;               // 16-unit tiles per block
   constexpr int KO = 4 * UPB, KS = KO / 32;  // own gate columns, k-steps of the product
   constexpr int ITEMS = UPB * 4;             // (unit, row pair) items per (destination, source) block
@@ -428,7 +426,7 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
   const int H = p.H, K = 4 * H, NUB = H / UPB;
   const int rg = blockIdx.x / NUB, ub = blockIdx.x % NUB;
   const int n0 = rg * 8, u0 = ub * UPB;
-  ps_u64* xb0 = xbuf + (size_t)rg * 2 * NUB * NUB * ITEMS;
+  u64* xb0 = xbuf + (size_t)rg * 2 * NUB * NUB * ITEMS;
   if (tid == 0) abortf[0] = 0;
   for (int i = tid; i < 16 * LDW; i += PST) dgi[i] = (bf16_t)0.f;
   for (int i = tid; i < ITEMS * 2; i += PST) ownp[i] = 0.f;
@@ -459,9 +457,11 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
       wstamp(a, bs, 0);
       unsigned passes = 0;
       if (bs > 0) {
-        const ps_u64* cur = xb0 + ((size_t)(bs & 1) * NUB + ub) * NUB * ITEMS + lane;
+        const u64* cur = xb0 + ((size_t)(bs & 1) * NUB + ub) * NUB * ITEMS + lane;
         constexpr int NSRC = NT * 16 / UPB;            // sources per wave = NUB / PSW
-        ps_u64 v[NSRC][IPL];
+        // (own loop, the give-up rule of exchange.h spelled out: through ns_poll_granules, and as its own loop around
+        // ns_spin::give_up, the kernel measured slower in one of two sessions - profiles/exchange_header.txt)
+        u64 v[NSRC][IPL];
         unsigned spins = 0, clk0 = 0;
         bool ok;
         do {
@@ -471,8 +471,8 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
             const int src = wave + PSW * j;
 #pragma unroll
             for (int i = 0; i < IPL; ++i)
-              v[j][i] = src == ub ? ((ps_u64)(unsigned)bs << 32)
-                                  : __hip_atomic_load((const NS_GLOBAL ps_u64*)(cur + (size_t)src * ITEMS + 64 * i), __ATOMIC_RELAXED,
+              v[j][i] = src == ub ? ((u64)(unsigned)bs << 32)
+                                  : __hip_atomic_load((const NS_GLOBAL u64*)(cur + (size_t)src * ITEMS + 64 * i), __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_AGENT);
           }
 #pragma unroll
@@ -502,16 +502,16 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
         red[((wave * ITEMS) + lane + 64 * i) * 2] = s0[i];
         red[((wave * ITEMS) + lane + 64 * i) * 2 + 1] = s1[i];
       }
-      ps_barrier();                          // A: the partial sums are in LDS
+      ns_lds_barrier();                          // A: the partial sums are in LDS
       wstamp(a, bs, 2);
       if (abortf[0]) return;
-      ps_barrier();                          // B: the operand image of this step is complete
+      ns_lds_barrier();                          // B: the operand image of this step is complete
       wstamp(a, bs, 3);
       if (bs + 1 < p.T) {
         bf16x8 af[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) af[ks] = *(const bf16x8*)(dgi + (LANES ? (r16 & 7) : r16) * LDW + 32 * ks + 8 * g);
-        ps_u64* nxt = xb0 + (size_t)((bs + 1) & 1) * NUB * NUB * ITEMS;
+        u64* nxt = xb0 + (size_t)((bs + 1) & 1) * NUB * NUB * ITEMS;
         // four tiles at a time, k-step outermost: four independent accumulator chains keep the matrix pipe issuing
         // (one tile after the other is a chain of KS dependent MFMAs each), and the first group's stores go out under
         // the second group's products
@@ -532,10 +532,9 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
             // D: column r16 = unit of the destination tile, rows 4 g + q (rows 0 .. 7 are this workgroup's):
             // item = unit in the destination block + UPB * (row pair)
             const int tile = wave * NT + j0 + jj, dest = tile / TB, ui = (tile % TB) * 16 + r16;
-            const ps_u64 tg = (ps_u64)(unsigned)(bs + 1) << 32;
             auto granule = [&](float x0, float x1) {
               const bf16_t b0 = (bf16_t)x0, b1 = (bf16_t)x1;
-              return tg | (ps_u64)((unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16));
+              return ns_granule((unsigned)(bs + 1), (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16));
             };
             if constexpr (LANES) {
               // rows 4 g + q of D replicate rows 4 (g & 1) + q: this lane takes the pair q = 2 hf, 2 hf + 1 (selects, no
@@ -546,17 +545,16 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
               if (dest == ub) {
                 ownp[item * 2] = x0; ownp[item * 2 + 1] = x1;
               } else {
-                __hip_atomic_store((NS_GLOBAL ps_u64*)(nxt + ((size_t)dest * NUB + ub) * ITEMS + item), granule(x0, x1), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+                ns_put_granule(nxt + ((size_t)dest * NUB + ub) * ITEMS + item, granule(x0, x1));
               }
             } else if (g < 2) {
               if (dest == ub) {
                 ownp[(ui + UPB * (2 * g)) * 2] = acc[jj][0]; ownp[(ui + UPB * (2 * g)) * 2 + 1] = acc[jj][1];
                 ownp[(ui + UPB * (2 * g + 1)) * 2] = acc[jj][2]; ownp[(ui + UPB * (2 * g + 1)) * 2 + 1] = acc[jj][3];
               } else {
-                NS_GLOBAL ps_u64* dst = (NS_GLOBAL ps_u64*)(nxt + ((size_t)dest * NUB + ub) * ITEMS + ui + 2 * UPB * g);
-                __hip_atomic_store(dst, granule(acc[jj][0], acc[jj][1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(dst + UPB, granule(acc[jj][2], acc[jj][3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                u64* dst = nxt + ((size_t)dest * NUB + ub) * ITEMS + ui + 2 * UPB * g;
+                ns_put_granule(dst, granule(acc[jj][0], acc[jj][1]));
+                ns_put_granule(dst + UPB, granule(acc[jj][2], acc[jj][3]));
               }
             }
           }
@@ -596,7 +594,7 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
   load_ops(p.T - 1);
   for (int t = p.T - 1; t >= 0; --t) {
     if (a.trace && blockIdx.x == 0 && e == 0 && p.T - 1 - t < 256) a.trace[(p.T - 1 - t) * 8 + 6] = wall_clock64();      // a cell wave reaches A
-    ps_barrier();                            // A
+    ns_lds_barrier();                            // A
     if (abortf[0]) return;
     float dgv[TB][4];
 #pragma unroll
@@ -628,7 +626,7 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, ps_u6
 #pragma unroll
       for (int j = 0; j < 4; ++j) dgi[er * LDW + j * UPB + eu + 16 * c] = (bf16_t)dgv[c][j];
     }
-    ps_barrier();                            // B
+    ns_lds_barrier();                            // B
     // ---- what only later kernels read: the gate gradients (bf16 copy and, for fp32 storage, fp32), next operands
     if (eok) {
       const long rowi = (long)en * p.P + p.padl + t;
@@ -681,7 +679,7 @@ bool wide_shape_ok(const ns_lstm_seq_params* p, int backward) {
 // the backward kernel's exchange area: [8-row group][step parity][destination][source][UPB * 4 items] granules
 size_t ps_exchange_bytes(const ns_lstm_seq_params* p) {
   const size_t nb = p->H / UPB;
-  return (size_t)((p->N + 7) / 8) * 2 * nb * nb * (UPB * 4) * sizeof(ps_u64);
+  return (size_t)((p->N + 7) / 8) * 2 * nb * nb * (UPB * 4) * sizeof(u64);
 }
 }  // namespace
 
@@ -754,7 +752,7 @@ extern "C" int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stre
 }
 
 // The instantiations of the backward kernel, [all-lane publish off, on][storage type bf16, fp32][H / 128 = 2, 4, 8]
-typedef void (*wide_bwd_kernel_t)(WideArgs, ps_u64*);
+typedef void (*wide_bwd_kernel_t)(WideArgs, u64*);
 #define NS_WIDE_BWD_FORMS(T_, L_) {lstm_wide_bwd_ps_kernel<T_, 2, L_>, lstm_wide_bwd_ps_kernel<T_, 4, L_>, lstm_wide_bwd_ps_kernel<T_, 8, L_>}
 static const wide_bwd_kernel_t wide_bwd_forms[2][2][3] = {{NS_WIDE_BWD_FORMS(bf16_t, false), NS_WIDE_BWD_FORMS(float, false)},
                                                           {NS_WIDE_BWD_FORMS(bf16_t, true), NS_WIDE_BWD_FORMS(float, true)}};
@@ -772,7 +770,7 @@ extern "C" int ns_lstm_wide_bwd(const ns_lstm_seq_params* p, void* work, ns_stre
   a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
   int rc = ns_zero_async(work, 256, s);
   if (rc) return rc;
-  ps_u64* xbuf = (ps_u64*)(((uintptr_t)work + 256 + WIDE_TRACE_BYTES + 15) & ~(uintptr_t)15);
+  u64* xbuf = (u64*)(((uintptr_t)work + 256 + WIDE_TRACE_BYTES + 15) & ~(uintptr_t)15);
   rc = ns_zero_async(xbuf, ps_exchange_bytes(p), s);
   if (rc) return rc;
   const int grid = (p->N + 7) / 8 * (p->H / UPB);      // 8-row groups x unit blocks, one workgroup per CU

@@ -9,7 +9,7 @@
 //   ns_wavenet_softmax    float64 softmax of logit rows (predict_proba)                  (:436-453)
 //   ns_wavenet_softmax_ce mean softmax cross-entropy against integer targets    (:479-502) and d/dlogits
 //   ns_wavenet_generate   incremental sample-by-sample generation (persistent)  (generate_wavenet.py:56-142)
-#include "common.h"
+#include "exchange.h"
 
 // ------------------------------------------------------------------ input layer
 // x0[n,t,:] = W[0][ids[n,t-1]] + W[1][ids[n,t]]  for 1 <= t < T   (row t = 0 is written as zero)
@@ -647,25 +647,15 @@ constexpr int MF_AHEAD = 2;
 // vectors in a fixed order.  Two hand-offs per sample.  The tag is the index of the drawn sample (1, 2, ...), so a
 // granule is its own flag and nothing is ever reset; one buffer per array is enough: h0 of sample e + 1 is published
 // only after every partial logit of sample e has come back.
-typedef unsigned long long wn_u64;
 constexpr int WN_S = 512, WN_Q = 256, WN_XW = WN_S + NS_WN_HELPERS * WN_Q;       // granules per waveform
-__device__ __forceinline__ wn_u64 wn_pack(unsigned tag, float v) { return ((wn_u64)tag << 32) | (wn_u64)__float_as_uint(v); }
-__device__ __forceinline__ void wn_put(wn_u64* p, unsigned tag, float v) {
-  __hip_atomic_store((NS_GLOBAL wn_u64*)p, wn_pack(tag, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// polls one granule until it carries `tag`; false = gave up (status raised, or `ticks` of the 100 MHz clock went by)
-__device__ __forceinline__ bool wn_get(const wn_u64* p, unsigned tag, float& v, int* status, unsigned ticks) {
-  unsigned spins = 0, t0 = 0;
-  for (;;) {
-    const wn_u64 g = __hip_atomic_load((const NS_GLOBAL wn_u64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned)(g >> 32) == tag) { v = __uint_as_float((unsigned)g); return true; }
-    if ((++spins & 255u) == 0) {
-      if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
-      const unsigned now = (unsigned)wall_clock64() | 1u;
-      if (t0 == 0u) t0 = now;
-      else if (now - t0 > ticks) { atomicExch(status, 1); return false; }
-    }
-  }
+// polls one granule until it carries `tag`, every 256 polls for giving up; false = gave up (status raised, or `ticks` of
+// the 100 MHz clock went by)
+__device__ __forceinline__ bool wn_get(const u64* p, unsigned tag, float& v, int* status, unsigned ticks) {
+  u64 g[1];
+  ns_spin sp;
+  if (!ns_poll_granules<256>(g, tag, sp, status, 1, [&](int) { return ns_ld_granule(p); }, ticks)) return false;
+  v = ns_granule_value(g[0]);
+  return true;
 }
 
 // helper h of waveform b = block b * NS_WN_HELPERS + h.  512 threads.  post1: thread (n = tid % 128, kq = tid / 128) keeps
@@ -678,8 +668,8 @@ __global__ __launch_bounds__(512) void wn_post_helper_kernel(ns_wavenet_generate
   __shared__ int abortf;
   const int tid = threadIdx.x, b = blockIdx.x / NS_WN_HELPERS, h = blockIdx.x % NS_WN_HELPERS;
   int* status = (int*)p.post_x;
-  wn_u64* x = (wn_u64*)((char*)p.post_x + 256) + (size_t)b * WN_XW;
-  wn_u64 *xh0 = x, *xlg = x + WN_S + h * WN_Q;
+  u64* x = (u64*)((char*)p.post_x + 256) + (size_t)b * WN_XW;
+  u64 *xh0 = x, *xlg = x + WN_S + h * WN_Q;
   const bf16_t* wb = (const bf16_t*)p.weights;
   const int n1 = tid & 127, kq = tid >> 7, q2 = tid & 255, kh = tid >> 8;
   unsigned w1[64], w2[32];
@@ -730,11 +720,11 @@ __global__ __launch_bounds__(512) void wn_post_helper_kernel(ns_wavenet_generate
       part[tid] = acc;
     }
     __syncthreads();
-    if (tid < 256) wn_put(xlg + tid, (unsigned)e, part[tid] + part[256 + tid]);
+    if (tid < 256) ns_put_granule(xlg + tid, (unsigned)e, part[tid] + part[256 + tid]);
     __syncthreads();                        // part, hv and h1v are free for the next sample
   }
 }
-extern "C" size_t ns_wavenet_post_bytes(int B) { return 256 + (size_t)(B > 0 ? B : 0) * WN_XW * sizeof(wn_u64); }
+extern "C" size_t ns_wavenet_post_bytes(int B) { return 256 + (size_t)(B > 0 ? B : 0) * WN_XW * sizeof(u64); }
 
 struct GenMf { uint4 fg[8]; uint4 de[2]; float4 r0, r1; };
 
@@ -811,9 +801,9 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
         __syncthreads();
         if (p.post_x) {        // engine 3: the helpers of this waveform hold post1 / post2 in registers
           int* status = (int*)p.post_x;
-          wn_u64* x = (wn_u64*)((char*)p.post_x + 256) + (size_t)b * WN_XW;
+          u64* x = (u64*)((char*)p.post_x + 256) + (size_t)b * WN_XW;
           const unsigned e = (unsigned)(t + 2 - p.n_seed);       // index of the sample being drawn
-          wn_put(x + tid, e, h0[tid]);                           // (S == GEN_THREADS == 512)
+          ns_put_granule(x + tid, e, h0[tid]);                           // (S == GEN_THREADS == 512)
           {   // thread (q = tid % 256, pair = tid / 256) takes helpers 2 pair and 2 pair + 1: the four partial vectors add up
               // as (h0 + h1) + (h2 + h3), always in that order
             const int q = tid & 255, pr = tid >> 8;
