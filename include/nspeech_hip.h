@@ -138,6 +138,11 @@ size_t ns_gemm_splitk_counters(int M, int N);
 /* name of the kernel the calling thread's last ns_gemm call launched (e.g. "gemm_mfma_f32_kernel<0, 1, 3>"): lets a
  * caller attribute its own event timings to the names a profiler reports. */
 const char* ns_gemm_last_kernel(void);
+/* K loop of the calling thread's last ns_gemm / ns_gemm_group launch: "dma" = operand tiles loaded straight into LDS (the
+ * bf16 products with both operands k-slow on the 128-tile kernel, and the grouped launch when every bf16 product of it
+ * qualifies), "staged" = through registers.  NS_GEMM_DMA = 0 in the environment, read per call, keeps every product on
+ * the staged loop; the results are bit-identical. */
+const char* ns_gemm_last_loop(void);
 
 
 /* ------------------------------------------------------------------ element-wise / reductions */

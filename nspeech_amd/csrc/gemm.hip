@@ -307,6 +307,8 @@ __device__ __forceinline__ int col_img_off_unit(int k, int unit) {  // 8-B unit 
 }
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+typedef __attribute__((address_space(1))) const void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ bf16x8 frag_row(const char* img, int row, int chunk) {
   return *(const bf16x8*)(img + row_img_off(row, chunk));
@@ -533,6 +535,8 @@ __device__ __forceinline__ void x256_quadrant(const ns_gemm_params& p, f32x4 (&a
 // workgroup, so three workgroups share a CU where BK = 64 allows two.
 // TM = 64 (k-contiguous A, vector epilogue only): 64 x 128 tiles, the four waves side by side (64 x 32 each), for
 // products whose 128-row tiles would leave a third of the CUs without a workgroup (M ~ 5 000 rows: 164 tiles).
+// Both operands k-slow (the weight gradients): the host launches gemm_mfma_dma_body below instead - this tiling with a
+// direct-to-LDS K loop - and keeps this body for NS_GEMM_DMA = 0 and for operands beyond 31-bit byte offsets.
 // The body takes its work item - output tile wgid, k slice ksl - from the caller: the kernel below reads it off blockIdx,
 // a grouped launch (gemm_group_kernel) off its item table.  p is the (batch-shifted) product of this workgroup.
 template <int AMODE, int BMODE, bool VEC, int BK = GBK, int TM = GBM>
@@ -642,6 +646,162 @@ __global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_kernel(ns_gem
   gemm_mfma_body<AMODE, BMODE, VEC, BK, TM>(p, wgid, ksl);
 }
 
+// ---- the k-slow x k-slow 128-tile product (the weight gradients) with a direct-to-LDS K loop.  Same tiling, work items,
+// images, fragment reads, MFMA order and epilogues as gemm_mfma_body<1, 1, VEC, BK, 128>, so every accumulator sees the
+// same operands in the same order and the results are bit-identical; what changes is how a tile reaches its images:
+//  - buffer_load_dwordx4 ... lds, no stage registers and no stage stores.  One wave-instruction writes 1 KB = four k-rows
+//    of an image, lane-linear, so the image's swizzle sits on the SOURCE address: lane l of the piece that covers rows
+//    kr .. kr + 3 holds row kr + (l >> 4), slot l & 15, and fetches chunk (l & 15) ^ (col_swz(row) << 1).  The pieces of
+//    one lane are 16 rows apart, which leaves col_swz alone: one chunk index per lane for the whole loop.
+//  - out-of-range elements (k >= K in the last K-tile, columns past M / N) are lanes whose offset is moved past the
+//    descriptor's range (the operand's extent): the load writes zeros.  The predicate is per lane because the rows of an
+//    overlapping im2col view run into each other, so a linear range alone cannot tell row K from row K - 1.
+//  - a ring of NST tile buffers: tile t + NST - 1 is issued behind the barrier of tile t into the buffer tile t - 1 has
+//    just left, and the wait in front of that barrier leaves the NST - 2 newer tiles in flight.  One barrier per tile:
+//    it publishes tile t (every wave has waited for its own pieces) and retires tile t - 1 (a wave's fragment reads are
+//    complete before the products that consume them issue, in front of the barrier).
+// The host sends a product here when both operand extents fit 31-bit byte offsets (gemm_dma_ok); NS_GEMM_DMA = 0 keeps
+// the register-staged loop above.
+// Measured alone on MI355X, staged -> direct, fixed-order split-K (profiles/wgrad_dma.txt): 2560 x 512 x 32124 split 6
+// 129 -> 97 us, 1024 x 4096 x 6432 split 2 87 -> 71, 768 x 4096 x 6432 83 -> 67, 2560 x 512 x 5244 49 -> 43.  BK = 64 runs
+// two buffers (64 KB, two workgroups per CU as before; a third buffer leaves one workgroup per CU: 130 us on the first
+// shape), BK = 32 three (48 KB, three workgroups per CU).  Registers do not change (194 against 195 VGPRs at BK = 64: the
+// fixed-order gather's 2 x 16 float4 are the peak, not the stage registers).
+// The loads are inline assembly: the compiler counts a direct-to-LDS load it knows of as a pending LDS write and waits
+// vmcnt(0) in front of the next fragment read, which would put every tile's load time back into the loop.  These it does
+// not count, so the loop's own counted waits are the only ones (and must drain them all before the epilogue's loads).
+typedef unsigned int dma_rsrc __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ dma_rsrc dma_descriptor(const void* base, long bytes) {      // raw buffer, no stride: range = bytes
+  const uintptr_t b = (uintptr_t)base;
+  // (readfirstlane: the words are uniform, but the asm operand needs the compiler to know it)
+  return (dma_rsrc){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b),
+                    (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xffffu)),
+                    (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
+}
+__device__ __forceinline__ void dma_load16(const dma_rsrc& rs, unsigned lds, unsigned voff) {   // lds: wave-uniform; lane l lands at lds + 16 l
+  unsigned keep;                             // m0 is the compiler's: saved and put back
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane((int)lds)), "v"(voff), "s"(rs) : "memory");
+}
+template <bool VEC, int BK, int NST>
+__device__ __forceinline__ void gemm_mfma_dma_body(const ns_gemm_params& p, const int wgid, const int ksl) {
+  constexpr int IMG = BK * 256;                 // bytes per operand image
+  constexpr int LPI = BK / 16;                  // 1 KB pieces per wave and image
+  constexpr int LPT = 2 * LPI;                  // ... and K-tile
+  static_assert(NST == 2 || NST == 3, "two or three tile buffers");
+  static_assert(NST * 2 * IMG * (BK == 64 ? 2 : 3) <= 160 * 1024, "the workgroups of a CU share 160 KB");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // [stage][A IMG | B IMG]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int tiles_n = (p.N + GBN - 1) / GBN;
+  const int tm = wgid / tiles_n, tn = wgid % tiles_n;
+  const int m0 = tm * GBM, n0 = tn * GBN;
+
+  const int nk = (p.K + BK - 1) / BK;
+  const int per = (nk + p.split_k - 1) / p.split_k;
+  const int kt0 = ksl * per, kt1 = min(nk, kt0 + per);
+  const int nt = kt1 - kt0;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // descriptors over the operands' extents; lanes outside them, and lanes sent to OUT, load zeros
+  constexpr unsigned OUT = 0x80000000u;
+  const long b_rows = p.b_seg_len > 0 ? (long)(p.K / p.b_seg_len - 1) * p.b_seg_stride + (long)(p.b_seg_len - 1) * p.ldb
+                                      : (long)(p.K - 1) * p.ldb;
+  const dma_rsrc ra = dma_descriptor(p.A, ((long)(p.K - 1) * p.lda + p.M) * 2);
+  const dma_rsrc rb = dma_descriptor(p.B, (b_rows + p.N) * 2);
+  const int kr = tid >> 4;                                   // this lane's k-row in the first piece; piece i: + 16 i
+  const int ch = (tid & 15) ^ (col_swz(kr) << 1);            // ... and its 16-byte chunk of that row
+  const unsigned lda2 = (unsigned)p.lda * 2u, ldb2 = (unsigned)p.ldb * 2u;
+  const unsigned a_lane = m0 + ch * 8 < p.M ? (unsigned)kr * lda2 + (unsigned)(m0 + ch * 8) * 2u : OUT;
+  const unsigned b_lane = n0 + ch * 8 < p.N ? (unsigned)kr * ldb2 + (unsigned)(n0 + ch * 8) * 2u : OUT;
+  const unsigned lpiece = (unsigned)(uintptr_t)(lptr_t)smem + wave * 1024;     // LDS byte address of this wave's first piece
+
+  auto issue = [&](int t, int buf) {                         // tile kt0 + t into ring buffer buf
+    const int k0 = (kt0 + t) * BK;
+    const unsigned a_tile = (unsigned)k0 * lda2;
+    unsigned b_tile = (unsigned)k0 * ldb2;
+    if (p.b_seg_len > 0) {
+      const int s = k0 / p.b_seg_len;
+      b_tile = (unsigned)(((long)s * p.b_seg_stride + (long)(k0 - s * p.b_seg_len) * p.ldb) * 2);
+    }
+    const unsigned dst = lpiece + buf * 2 * IMG;
+    if (k0 + BK <= p.K) {
+#pragma unroll
+      for (int i = 0; i < LPI; ++i)
+        dma_load16(ra, dst + i * 4096, a_lane + a_tile + (unsigned)(16 * i) * lda2);
+#pragma unroll
+      for (int i = 0; i < LPI; ++i)
+        dma_load16(rb, dst + IMG + i * 4096, b_lane + b_tile + (unsigned)(16 * i) * ldb2);
+    } else {                                                 // the ragged last K-tile: rows k >= K are zeros
+#pragma unroll
+      for (int i = 0; i < LPI; ++i) {
+        const bool in = k0 + 16 * i + kr < p.K;
+        dma_load16(ra, dst + i * 4096, in ? a_lane + a_tile + (unsigned)(16 * i) * lda2 : OUT);
+      }
+#pragma unroll
+      for (int i = 0; i < LPI; ++i) {
+        const bool in = k0 + 16 * i + kr < p.K;
+        dma_load16(rb, dst + IMG + i * 4096, in ? b_lane + b_tile + (unsigned)(16 * i) * ldb2 : OUT);
+      }
+    }
+  };
+
+#pragma unroll
+  for (int t = 0; t < NST - 1; ++t)
+    if (t < nt) issue(t, t);
+
+  int cur = 0;                                               // ring buffer of tile t
+  for (int t = 0; t < nt; ++t) {
+    // tile t has landed: everything but the (up to NST - 2) newer tiles
+    const int ahead = min(NST - 2, nt - 1 - t);
+    if (NST >= 3 && ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (t + NST - 1 < nt) issue(t + NST - 1, cur == 0 ? NST - 1 : cur - 1);
+    const char* imgA = smem + cur * 2 * IMG;
+    const char* imgB = imgA + IMG;
+#pragma unroll
+    for (int ks = 0; ks < BK / 32; ++ks) {
+      bf16x8 af[4], bfr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = frag_col(imgA, ks * 32, wm * 64 + i * 16, lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bfr[j] = frag_col(imgB, ks * 32, wn * 64 + j * 16, lane);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = VEC ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0)
+                          : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    }
+    cur = cur == NST - 1 ? 0 : cur + 1;
+  }
+
+  bool add_bias = ksl == 0;
+  if (p.splitk_work && p.split_k > 1) {           // deterministic split-K: the last slice of the tile sums and stores
+    if (!splitk_gather_acc<4>(p, acc, wgid, ksl, tid)) return;
+    add_bias = true;
+  }
+  if constexpr (VEC) x256_quadrant(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
+  else mfma_epilogue(p, acc, m0, n0, wm, wn, lane, add_bias);
+}
+template <bool VEC, int BK, int NST>
+__global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_dma_kernel(ns_gemm_params p) {
+  const int nwg = ((p.M + GBM - 1) / GBM) * ((p.N + GBN - 1) / GBN);
+  int wgid, ksl;                                 // output tile, k slice
+  xcd_work_item(p, nwg, wgid, ksl);
+  batch_shift(p, blockIdx.z);
+  gemm_mfma_dma_body<VEC, BK, NST>(p, wgid, ksl);
+}
+
 // ------------------------------------------------------------------ 256 x 256 tiles, 8 phases per two K-tiles
 // Both operands k-contiguous bf16 (a_mode 0, b_mode 0), K % 64 == 0.  One workgroup per CU: 8 waves as 2 (M) x 4 (N),
 // 128 x 64 outputs per wave held as acc[A half][4][B half][2].  LDS = 2 buffers x {A0 A1 B0 B1} half-tiles of
@@ -672,9 +832,6 @@ __global__ __launch_bounds__(256, BK == 64 ? 2 : 3) void gemm_mfma_kernel(ns_gem
 // gradient 32124 x 512 x 2560 1044 (rounds 2 - 4, same box: 1082 / 1157 / 988; 128^2 kernel: 662 / - / 610);
 // three-segment product at 4096^3 434 algorithmic = 1302 issued (round 4: 383; in-kernel split: 239).
 constexpr int XHALF = 16384, XBUF = 65536;
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <int NSEG>
 __global__ __launch_bounds__(512, 1) void gemm_x256_kernel(ns_gemm_params p) {
@@ -1180,6 +1337,22 @@ static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // its per-kernel averages can be read against the rocprofv3 kernel statistics)
 static thread_local const char* g_last_kernel = "";
 extern "C" const char* ns_gemm_last_kernel(void) { return g_last_kernel; }
+static thread_local const char* g_last_loop = "staged";
+extern "C" const char* ns_gemm_last_loop(void) { return g_last_loop; }
+
+// the direct-to-LDS K loop (gemm_mfma_dma_body) for a product the 128-tile bf16 kernel takes with both operands k-slow:
+// its buffer descriptors address an operand by 31-bit byte offsets from its base.  NS_GEMM_DMA = 0, read per call, keeps
+// the register-staged loop (A/B runs; tests/test_gemm_dma_gpu.py compares the two bit for bit).
+static bool gemm_dma_ok(const ns_gemm_params& p) {
+  const char* e = getenv("NS_GEMM_DMA");
+  if (e && atoi(e) == 0) return false;
+  if (p.a_mode != 1 || p.b_mode != 1 || p.K < 1 || p.lda < 0 || p.ldb < 0 || p.b_seg_stride < 0) return false;
+  const double a_bytes = ((double)(p.K - 1) * (double)p.lda + p.M) * 2.0;
+  const double b_bytes = p.b_seg_len > 0 ? ((double)(p.K / p.b_seg_len - 1) * (double)p.b_seg_stride +
+                                            (double)(p.b_seg_len - 1) * (double)p.ldb + p.N) * 2.0
+                                         : ((double)(p.K - 1) * (double)p.ldb + p.N) * 2.0;
+  return a_bytes < 2147483648.0 && b_bytes < 2147483648.0;
+}
 
 // the 256-tile kernel: large k-contiguous bf16 products whose tiles fill the chip
 // the vector epilogue (x256_quadrant): 16-byte (fp32) / 8-byte (bf16) accesses of C and of every per-element epilogue
@@ -1314,7 +1487,8 @@ static gemm_form gemm_classify(const ns_gemm_params& p) {
     const bool vec = vec_epilogue_ok(p);
     // 64-row tiles when the 128-row ones leave CUs without a workgroup (<= 192 tiles) and A is k-contiguous
     const bool half = vec && p.a_mode == 0 && half_tiles_wanted(p, tiles);
-    static const int bk32_env = [] { const char* e = getenv("NS_GEMM_BK32"); return e ? atoi(e) : -1; }();
+    const char* const bk32_e = getenv("NS_GEMM_BK32");       // read per call, as NS_GEMM_DMA: one process can run both forms
+    const int bk32_env = bk32_e ? atoi(bk32_e) : -1;
     // BK = 32 (four workgroups per CU instead of two) pays when a launch has more workgroups than the 512 the BK = 64
     // form keeps resident: 1280 workgroups 202 -> 169 us, 640: 73 -> 52 us; at <= 512 (what the models' split-K rule
     // asks for) it is slower alone (84 -> 99 us) and no faster beside another stream's kernels
@@ -1345,6 +1519,7 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
   if (p.M == 0 || p.N == 0) return NS_OK;
   if (int rc = gemm_normalize(p)) return rc;
   const gemm_form form = gemm_classify(p);
+  g_last_loop = "staged";
   // (pre-split operands never come here: this kernel reads A and B only, and the check below refuses them)
   if (form.kind == GF_SKINNY) {
     // enough workgroups to spread the weight stream over the chip
@@ -1410,7 +1585,33 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     g_last_kernel = "gemm_mfma_kernel<0, " #BM_ ", true, 64, 64>";                                \
     hipLaunchKernelGGL((gemm_mfma_kernel<0, BM_, true, 64, 64>), grid, dim3(256), lds, stream, p);    \
   } while (0)
-    if (half) {
+#define LAUNCH_DMA(BK_, NST_)                                                                                  \
+  do {                                                                                                         \
+    static bool attr_set = false;                                                                              \
+    constexpr int lds_ = NST_ * BK_ * 512;                                                                     \
+    if (!attr_set) {                                                                                           \
+      (void)hipFuncSetAttribute((const void*)gemm_mfma_dma_kernel<false, BK_, NST_>,                           \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                             \
+      (void)hipFuncSetAttribute((const void*)gemm_mfma_dma_kernel<true, BK_, NST_>,                            \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                             \
+      attr_set = true;                                                                                         \
+    }                                                                                                          \
+    if (vec) hipLaunchKernelGGL((gemm_mfma_dma_kernel<true, BK_, NST_>), grid, dim3(256), lds_, stream, p);    \
+    else hipLaunchKernelGGL((gemm_mfma_dma_kernel<false, BK_, NST_>), grid, dim3(256), lds_, stream, p);       \
+  } while (0)
+    if (!half && p.a_mode == 1 && p.b_mode == 1 && gemm_dma_ok(p)) {
+      // (the names stay those of the staged kernels: callers group their timings by tile form, ns_gemm_last_loop tells the loop)
+      g_last_loop = "dma";
+      // buffers per ring, measured (profiles/wgrad_dma.txt): BK = 64 two - a third costs the second workgroup of a CU;
+      // BK = 32 three - three workgroups per CU still fit
+      if (form.bk32) {
+        g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 32, 128>" : "gemm_mfma_kernel<1, 1, false, 32, 128>";
+        LAUNCH_DMA(32, 3);
+      } else {
+        g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 64, 128>" : "gemm_mfma_kernel<1, 1, false, 64, 128>";
+        LAUNCH_DMA(64, 2);
+      }
+    } else if (half) {
       if (p.b_mode == 0) LAUNCH_MFMA_HALF(0); else LAUNCH_MFMA_HALF(1);
     } else if (form.bk32) {
       g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 32, 128>" : "gemm_mfma_kernel<1, 1, false, 32, 128>";
@@ -1420,6 +1621,7 @@ static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
     else if (p.a_mode == 0 && p.b_mode == 1) LAUNCH_MFMA(0, 1);
     else if (p.a_mode == 1 && p.b_mode == 0) LAUNCH_MFMA(1, 0);
     else LAUNCH_MFMA(1, 1);
+#undef LAUNCH_DMA
 #undef LAUNCH_MFMA_HALF
 #undef LAUNCH_MFMA
     NS_CHECK_LAUNCH("gemm_mfma");
@@ -1517,7 +1719,7 @@ static_assert(sizeof(ns_gemm_group_item) == 112, "ns_gemm_group_item: layout of 
 static_assert(sizeof(gemm_group_args) <= 4096, "the item table must fit the kernel argument block");
 extern "C" size_t ns_gemm_group_arg_bytes(void) { return sizeof(gemm_group_args); }
 
-__device__ __forceinline__ ns_gemm_params group_product(const ns_gemm_group_item& it) {
+__host__ __device__ __forceinline__ ns_gemm_params group_product(const ns_gemm_group_item& it) {
   ns_gemm_params p = {};
   p.dtype = it.dtype;
   p.M = it.M; p.N = it.N; p.K = it.K;
@@ -1534,6 +1736,7 @@ __device__ __forceinline__ ns_gemm_params group_product(const ns_gemm_group_item
   return p;
 }
 
+template <bool DMA>      // the K loop of the bf16 products: gemm_mfma_dma_body (two buffers) or gemm_mfma_body
 __global__ __launch_bounds__(256, 2) void gemm_group_kernel(const gemm_group_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x;
@@ -1557,8 +1760,10 @@ __global__ __launch_bounds__(256, 2) void gemm_group_kernel(const gemm_group_arg
   const int tiles = ((it.M + GBM - 1) / GBM) * ((it.N + GBN - 1) / GBN);
   int tile, ksl;
   xcd_group_item(it.split_k, tiles, local, tile, ksl);
-  if (it.kind == 0) gemm_mfma_body<1, 1, false, GBK, GBM>(p, tile, ksl);
-  else gemm_mfma_f32_body<1, 1, 1, false, GBM>(p, tile, ksl);
+  if (it.kind == 0) {
+    if constexpr (DMA) gemm_mfma_dma_body<false, GBK, 2>(p, tile, ksl);
+    else gemm_mfma_body<1, 1, false, GBK, GBM>(p, tile, ksl);
+  } else gemm_mfma_f32_body<1, 1, 1, false, GBM>(p, tile, ksl);
 }
 
 namespace {
@@ -1703,15 +1908,18 @@ extern "C" int ns_gemm_group(const ns_gemm_params* products, int n_products, con
   int rc = gemm_group_build(products, n_products, sums, n_sums, e, &n);
   static bool attr_set = false;
   if (rc == NS_OK && !attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)gemm_group_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)gemm_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     attr_set = true;
   }
   for (int first = 0; rc == NS_OK && first < n;) {
     const int end = group_launch_end(e, n, first);
     gemm_group_args a;
     int k = 0, total = 0;
+    bool dma = true;          // one loop per launch: the direct-to-LDS one when every bf16 product of the launch can take it
     for (int i = first; i < end; ++i) {
       if (e[i].it.nwg <= 0) continue;
+      if (e[i].it.kind == 0) dma = dma && gemm_dma_ok(group_product(e[i].it));
       a.wg0[k] = e[i].it.wg0;
       a.item[k++] = e[i].it;
       total = e[i].it.wg0 + e[i].it.nwg;
@@ -1719,7 +1927,9 @@ extern "C" int ns_gemm_group(const ns_gemm_params* products, int n_products, con
     for (int i = k; i < NS_GEMM_GROUP_MAX; ++i) { a.wg0[i] = INT_MAX; a.item[i] = ns_gemm_group_item{}; }
     if (k > 0) {
       g_last_kernel = "gemm_group_kernel";
-      hipLaunchKernelGGL(gemm_group_kernel, dim3(total), dim3(256), 65536, (hipStream_t)stream_, a);
+      g_last_loop = dma ? "dma" : "staged";
+      if (dma) hipLaunchKernelGGL(gemm_group_kernel<true>, dim3(total), dim3(256), 65536, (hipStream_t)stream_, a);
+      else hipLaunchKernelGGL(gemm_group_kernel<false>, dim3(total), dim3(256), 65536, (hipStream_t)stream_, a);
       if (hipGetLastError() != hipSuccess) { ns_set_error("gemm_group: launch failed"); rc = NS_ERR_LAUNCH; }
     }
     first = end;
