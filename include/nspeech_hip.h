@@ -414,8 +414,10 @@ typedef struct {
   uint32_t zoneout_seed_cell, zoneout_seed_output;
   /* LSTMBlockCell's cell_clip attribute: > 0 clips the new cell state to [-cell_clip, cell_clip] in every forward form
    * (the clipped state is what c holds); TF's gradient kernel applies no mask for clipped values, so the backward forms
-   * are unchanged.  0 (the default) = no clipping = the reference's cells as this build reads them (modules.py:41-42,
-   * tacotron2.py:69-70 pass no cell_clip; hparam lstm_cell_clip). */
+   * are unchanged - except that with zoneout, where they rebuild c' from the saved gates (c holds the zoned state), they
+   * clip it as the forward pass did: h' was o tanh of the clipped value.  0 (the default) = no clipping = the
+   * reference's cells as this build reads them (modules.py:41-42, tacotron2.py:69-70 pass no cell_clip; hparam
+   * lstm_cell_clip). */
   float cell_clip;
   /* ns_lstm_wide_fwd, dtype NS_F32 with f32_passes 3: with h_bf16 AND h_lo_bf16 the call writes the pre-split planes
    * hi = bf16(h) into h_bf16 and lo = bf16(h - hi) here (both with leading dimension ld_h_bf16, rows as h; pad rows

@@ -396,14 +396,14 @@ __global__ __launch_bounds__(LTHREADS) void lstm_bwd_step_kernel(LstmBwdStepPair
   float c = pc, dcin = pdc, dckeep = 0.f;
   if (a.zmode) {
     // h[t] = m_h ? h[t-1] : h'[t]: the gradient of a kept unit passes to step t-1 untouched; c[t] likewise, and the
-    // saved c is the ZONED state, so tanh needs the plain cell's c' = f c[t-1] + i j again
+    // saved c is the ZONED state, so tanh needs the plain cell's c' = clip(f c[t-1] + i j) again: h' was o tanh(c')
     dh += pdhc;
     const bool mh = ns_zone_keep(a.zseed_h, (uint32_t)a.t, (uint32_t)n, (uint32_t)u, a.zthr_h);
     const bool mc = ns_zone_keep(a.zseed_c, (uint32_t)a.t, (uint32_t)n, (uint32_t)u, a.zthr_c);
     a.dh_carry[ci] = mh ? dh : 0.f;
     if (mh) dh = 0.f;
     if (mc) { dckeep = dcin; dcin = 0.f; }
-    c = gf * cp + gi * gj;
+    c = ns_cell_clip(gf * cp + gi * gj, a.cell_clip);
   }
   const float tc = tanhf_(c);
   const float d_o = dh * tc * go * (1.f - go);
@@ -506,6 +506,7 @@ static void fill_bwd(LstmBwdStep<T>& a, const ns_lstm_seq_params& p, int step, f
     a.zthr_c = p.zoneout_thr_cell; a.zthr_h = p.zoneout_thr_output;
     a.zseed_c = p.zoneout_seed_cell; a.zseed_h = p.zoneout_seed_output;
     a.dh_carry = dc_carry + (long)p.N * H;
+    a.cell_clip = p.cell_clip;
   }
 }
 

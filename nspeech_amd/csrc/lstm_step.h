@@ -49,6 +49,7 @@ struct LstmBwdStep {
   // zoneout masks of the forward pass (zmode 1): dh_carry [N,H] in/out carries dh through units that kept h
   int zmode; uint32_t zthr_c, zthr_h, zseed_c, zseed_h;
   float* dh_carry;
+  float cell_clip;                         // the forward pass's clip (zmode 1 only: c' is rebuilt from the saved gates)
 };
 template <typename T>
 struct LstmBwdStepPair { LstmBwdStep<T> s[2]; int n; };

@@ -613,7 +613,7 @@ __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, u64* 
         dhc[c] = mh ? dh : 0.f;
         if (mh) dh = 0.f;
         if (mc) { dckeep = dcin; dcin = 0.f; }
-        cc = gf * pcp[c] + gi * gj;
+        cc = ns_cell_clip(gf * pcp[c] + gi * gj, p.cell_clip);      // the forward kernel's c': h' was o tanh of the clipped value
       }
       const float tc = tanhf_(cc);
       const float dc = dh * go * (1.f - tc * tc) + dcin;

@@ -1,6 +1,7 @@
 """The persistent whole-sequence BiLSTM kernels (cluster of workgroups, register-resident W_h,
 tagged-granule exchange) against the one-launch-per-step kernels on the same bf16 inputs,
-forward and backward, with per-row lengths, partial row groups and repeated launches."""
+forward and backward, with per-row lengths, partial row groups and repeated launches.
+The step kernels compared against here are held to float64 in test_lstm_contract_gpu.py (as are the cluster kernels)."""
 import pytest
 import torch
 

@@ -2,7 +2,8 @@
 sentinel-filled history arrays themselves) against the one-launch-per-step kernels on the same operands,
 forward and backward: bf16 storage, and fp32 storage in the `mixed` arrangement (forward three split-bf16 passes over
 pre-split weights, backward one bf16 pass over bf16 copies).  Partial row groups, per-row lengths, repeated launches,
-the status word."""
+the status word.
+The step kernels compared against here are held to float64 in test_lstm_contract_gpu.py (as are the wide kernels)."""
 import pytest
 import torch
 
