@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Synthesis from a checkpoint, the reference's eval.py surface (eval.py:23-27,62-76): flags --checkpoint --model
 --hparams --gpu --speaker; one `eval-<step>-<i>.wav` per test sentence next to the checkpoint.  The checkpoint may be
-this build's `model.ckpt-<step>` file or a TensorFlow checkpoint prefix (nspeech_amd/utils/tf_bundle.py)."""
+this build's `model.ckpt-<step>` file or a TensorFlow checkpoint prefix (nspeech_amd/utils/tf_bundle.py).
+--batch-size B > 1 writes the same files from Synthesizer.synthesize_batch on B sentences at a time."""
 import argparse
 import os
 import re
@@ -30,9 +31,17 @@ def output_stem(checkpoint_path):
     return os.path.join(os.path.dirname(checkpoint_path), "eval-%d" % int(step.group(1)) if step else "eval")
 
 
-def synthesize_all(checkpoint, model_name, speaker, precision):
+def synthesize_all(checkpoint, model_name, speaker, precision, batch_size=1):
     synth = Synthesizer(hparams_mod.get_hparams(), dtype=precision).load(checkpoint, model_name)
     stem = output_stem(checkpoint)
+    if batch_size > 1:      # synthesize_batch on chunks of batch_size sentences: the same files, from padded batches
+        for start in range(0, len(TEST_SENTENCES), batch_size):
+            chunk = TEST_SENTENCES[start:start + batch_size]
+            targets = ["%s-%d.wav" % (stem, start + i) for i in range(len(chunk))]
+            print("Synthesizing: %s" % " ".join(targets))
+            for target, (wav, _, _) in zip(targets, synth.synthesize_batch(chunk, speaker)):
+                audio.save_wav(wav, target)
+        return
     for index, sentence in enumerate(TEST_SENTENCES):
         target = "%s-%d.wav" % (stem, index)
         print("Synthesizing: %s" % target)
@@ -48,7 +57,9 @@ if __name__ == "__main__":
     cli.add_argument("--gpu", default="0")
     cli.add_argument("--speaker", type=int, default=0)
     cli.add_argument("--precision", default="mixed", choices=["mixed", "bf16", "bf16x3", "fp32"])
+    cli.add_argument("--batch-size", type=int, default=1,
+                     help="sentences per Synthesizer.synthesize_batch call; 1: one synthesize call per sentence")
     opts = cli.parse_args()
     os.environ.setdefault("HIP_VISIBLE_DEVICES", opts.gpu)
     hparams_mod.load(opts.model).parse(opts.hparams)
-    synthesize_all(opts.checkpoint, opts.model, opts.speaker, opts.precision)
+    synthesize_all(opts.checkpoint, opts.model, opts.speaker, opts.precision, opts.batch_size)

@@ -1055,6 +1055,25 @@ int ns_audio_pointwise(const ns_audio_pointwise_params* p, ns_stream_t stream);
 typedef struct { const float* x; float* y; int64_t n; float coef; int inverse; } ns_preemphasis_params;
 int ns_preemphasis(const ns_preemphasis_params* p, ns_stream_t stream);
 
+/* The tail of synthesis for N clips in ONE launch: audio.inv_preemphasis of every row, then audio.find_endpoint on
+ * the filtered row.  One workgroup per row, a grid of N, nothing shared between workgroups.
+ * Row i of y = ns_preemphasis(inverse = 1) of row i of x, bit for bit (the same device function).
+ * end[i] = x + hop for the smallest x in hop, 2 hop, ... below L - window with max(y[i][x : x + window]) < threshold,
+ * L when there is none - find_endpoint's rule as it stands: the maximum, not its absolute value; a strict comparison
+ * made in double, (double)max < threshold; a window that holds a NaN is never silent; the window at 0 is never tested;
+ * window need not be a multiple of hop.  No sample at or beyond L of a row is read or written.
+ * A null pointer, N < 0, L < 0, ld < L, window < 1 or hop < 1: NS_ERR_BAD_ARG.  N == 0 or L == 0 succeeds without a
+ * launch of the filter (L == 0: end[i] = 0, through ns_zero where N is even and end 16-byte aligned, as ns_zero asks). */
+typedef struct {
+  const float* x; float* y;      /* [N] rows of L samples, row stride ld >= L (elements); y == x allowed */
+  int N; int64_t L, ld;
+  float coef;                    /* y[n] = x[n] + coef * y[n-1], zero initial state per row */
+  int64_t window, hop;           /* find_endpoint's window_length and hop_length, both >= 1 */
+  double threshold;              /* 10^(threshold_db / 20), as a double */
+  int64_t* end;                  /* [N] */
+} ns_wave_finish_params;
+int ns_wave_finish(const ns_wave_finish_params* p, ns_stream_t stream);
+
 /* ---------------------------------------------------------------- utterance front end (frontend.hip)
  * ns_resample: resampy's 'kaiser_best' band-limited interpolation as audio.resample restates it (utils/audio.py),
  * one launch per waveform, float64 arithmetic in the order of audio._resample_reference: per output sample the left

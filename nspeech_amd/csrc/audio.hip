@@ -778,27 +778,25 @@ extern "C" int ns_audio_pointwise(const ns_audio_pointwise_params* p, ns_stream_
 // ------------------------------------------------------------------ pre-emphasis FIR / IIR
 // inverse: y[n] = x[n] + c*y[n-1].  One workgroup walks the signal in 2048-sample tiles; inside a
 // tile each thread owns 8 consecutive samples and the (decay, partial) pairs are combined with a
-// Hillis-Steele scan of the affine maps, carry handed from tile to tile.
-__global__ __launch_bounds__(256) void preemph_kernel(ns_preemphasis_params p) {
-  if (!p.inverse) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += (long)gridDim.x * blockDim.x)
-      p.y[i] = p.x[i] - (i > 0 ? p.coef * p.x[i - 1] : 0.f);
-    return;
-  }
+// Hillis-Steele scan of the affine maps, carry handed from tile to tile.  The walk is a function of its own, called
+// by all 256 threads of a workgroup: preemph_kernel runs it over the one signal, wave_finish_kernel over its row, and
+// both get the same bits.  A thread reads its 8 samples of a tile before it writes them: y == x is allowed.  Ends
+// behind a __syncthreads(): what the workgroup reads of y afterwards is what was written here.
+__device__ __forceinline__ void inv_preemph_row(const float* x, float* y, const long n, const float coef) {
   __shared__ float sa[256], sb[256];
   __shared__ float carry;
   const int tid = threadIdx.x;
   if (tid == 0) carry = 0.f;
   float c8 = 1.f;
-  for (int i = 0; i < 8; ++i) c8 *= p.coef;
-  for (long base = 0; base < p.n; base += 2048) {
+  for (int i = 0; i < 8; ++i) c8 *= coef;
+  for (long base = 0; base < n; base += 2048) {
     float loc[8];
     float acc = 0.f;
     const long i0 = base + (long)tid * 8;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float xv = (i0 + j < p.n) ? p.x[i0 + j] : 0.f;
-      acc = xv + p.coef * acc;
+      const float xv = (i0 + j < n) ? x[i0 + j] : 0.f;
+      acc = xv + coef * acc;
       loc[j] = acc;
     }
     // affine map of this chunk: out = A*in + B with A = c^8, B = acc
@@ -819,16 +817,25 @@ __global__ __launch_bounds__(256) void preemph_kernel(ns_preemphasis_params p) {
     const float cin = carry;
     float inS = cin;
     if (tid > 0) inS = sa[tid - 1] * cin + sb[tid - 1];
-    float pw = p.coef;
+    float pw = coef;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      if (i0 + j < p.n) p.y[i0 + j] = loc[j] + pw * inS;
-      pw *= p.coef;
+      if (i0 + j < n) y[i0 + j] = loc[j] + pw * inS;
+      pw *= coef;
     }
     __syncthreads();
     if (tid == 255) carry = sa[255] * cin + sb[255];
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(256) void preemph_kernel(ns_preemphasis_params p) {
+  if (!p.inverse) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += (long)gridDim.x * blockDim.x)
+      p.y[i] = p.x[i] - (i > 0 ? p.coef * p.x[i - 1] : 0.f);
+    return;
+  }
+  inv_preemph_row(p.x, p.y, p.n, p.coef);
 }
 
 extern "C" int ns_preemphasis(const ns_preemphasis_params* p, ns_stream_t s) {
@@ -837,5 +844,63 @@ extern "C" int ns_preemphasis(const ns_preemphasis_params* p, ns_stream_t s) {
   const int grid = p->inverse ? 1 : (int)min((long)1024, (long)((p->n + 255) / 256));
   hipLaunchKernelGGL(preemph_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, *p);
   NS_CHECK_LAUNCH("preemphasis");
+  return NS_OK;
+}
+
+// ------------------------------------------------------------------ inv_preemphasis + find_endpoint of N clips
+// One workgroup per row and nothing between workgroups.  The row goes through inv_preemph_row; behind its last
+// barrier the same workgroup reads y back (its own stores, from L2) and looks for the first silent window of
+// audio.find_endpoint: window k starts at x = (k + 1) hop (the one at 0 is never tested), x + window < L, silent when
+// max(y[x : x + window]) < threshold with the comparison in double and a NaN in the window making it loud (np.max
+// returns the NaN, fmaxf would drop it).  Wave w takes the windows k = w, w + 4, ... in rising order and stops at its
+// first silent one, so the smallest over the four waves is the row's; a sample is read window / hop times, a 10 s
+// clip's 0.8 MB four times.  Every index is 64-bit and below L - 1.
+__global__ __launch_bounds__(256) void wave_finish_kernel(ns_wave_finish_params p) {
+  const long row = blockIdx.x;
+  float* y = p.y + row * p.ld;
+  inv_preemph_row(p.x + row * p.ld, y, p.L, p.coef);
+  __shared__ long first[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long nwin = p.L > p.window ? (p.L - p.window - 1) / p.hop : 0;      // the x = hop, 2 hop, ... below L - window
+  long found = p.L;
+  for (long k = wave; k < nwin; k += 4) {
+    const long x = (k + 1) * p.hop;
+    const float* w = y + x;
+    float m = -INFINITY;
+    int nan = 0;
+    long j = lane;
+    for (; j + 192 < p.window; j += 256) {       // four loads in flight per lane
+      const float v0 = w[j], v1 = w[j + 64], v2 = w[j + 128], v3 = w[j + 192];
+      nan |= (v0 != v0) | (v1 != v1) | (v2 != v2) | (v3 != v3);
+      m = fmaxf(fmaxf(m, v0), fmaxf(fmaxf(v1, v2), v3));
+    }
+    for (; j < p.window; j += 64) {
+      const float v = w[j];
+      nan |= v != v;
+      m = fmaxf(m, v);
+    }
+    m = wave_max(m);
+    if (!__any(nan) && (double)m < p.threshold) { found = x + p.hop; break; }
+  }
+  if (lane == 0) first[wave] = found;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long e = first[0];
+    for (int i = 1; i < 4; ++i) e = first[i] < e ? first[i] : e;
+    p.end[row] = e;
+  }
+}
+
+extern "C" int ns_wave_finish(const ns_wave_finish_params* p, ns_stream_t s) {
+  NS_CHECK_ARG(p && p->x && p->y && p->end, "ns_wave_finish: null");
+  NS_CHECK_ARG(p->N >= 0 && p->L >= 0 && p->ld >= p->L, "ns_wave_finish: N < 0, L < 0 or ld < L");
+  NS_CHECK_ARG(p->window >= 1 && p->hop >= 1, "ns_wave_finish: window and hop must be >= 1");
+  if (p->N == 0) return NS_OK;
+  // L == 0: end[i] = 0.  ns_zero clears 16 bytes at a time; an odd N or an end that is only 8-byte aligned takes the
+  // kernel, which walks no sample and writes end[i] = L
+  if (p->L == 0 && (p->N & 1) == 0 && (((uintptr_t)p->end) & 15) == 0)
+    return ns_zero(p->end, sizeof(int64_t) * (size_t)p->N, s);
+  hipLaunchKernelGGL(wave_finish_kernel, dim3(p->N), dim3(256), 0, (hipStream_t)s, *p);
+  NS_CHECK_LAUNCH("wave_finish");
   return NS_OK;
 }

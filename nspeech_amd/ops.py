@@ -402,6 +402,16 @@ def zero(t):
     L.check(L.lib().ns_zero(C.c_void_p(ptr(t)), C.c_size_t(nbytes), C.c_void_p(stream())), "ns_zero")
 
 
+def wave_finish(x, y, N, L_, ld, coef, window, hop, threshold, end, x_off=0, y_off=0):
+    """ns_wave_finish: rows of y (fp32, stride ld; y may be x) = inv_preemphasis of the rows of x, end int64 [N] =
+    find_endpoint of every filtered row for (window, hop, threshold), one launch (include/nspeech_hip.h)."""
+    assert x.dtype == torch.float32 and y.dtype == torch.float32 and end.dtype == torch.int64
+    p = L.struct("ns_wave_finish_params")
+    _fill(p, x=ptr(x, x_off), y=ptr(y, y_off), N=int(N), L=int(L_), ld=int(ld), coef=float(coef), window=int(window),
+          hop=int(hop), threshold=float(threshold), end=ptr(end))
+    L.call("ns_wave_finish", p, stream())
+
+
 def streams_concurrent(a, b):
     """True when launches on torch streams a and b can run side by side (ns_streams_concurrent: they do not share a
     hardware queue).  Synchronises both."""

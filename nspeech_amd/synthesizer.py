@@ -5,7 +5,10 @@ inv_preemphasis and find_endpoint, exactly the reference's order (synthesizer.py
 
 load_vocoder(checkpoint_path, wavenet_hparams) + synthesize(text, vocoder="wavenet") vocode the mel output through a
 WaveNet trained on mel local conditions (train_wavenet.py --hparams lc_channels=<num_mels>) instead: one mel row per hop
-samples, a seed of receptive-field silence in front of row 0, T * hop samples drawn by the incremental generator."""
+samples, a seed of receptive-field silence in front of row 0, T * hop samples drawn by the incremental generator.
+
+synthesize_batch(texts, speaker_ids) is the same for many texts: one model pass per 32 of them, one Griffin-Lim call
+(or one WaveNet generate) per pass and one audio.finish_waves for the inv_preemphasis / find_endpoint tail."""
 import numpy as np
 import torch
 
@@ -13,6 +16,24 @@ from . import hparams as hparams_mod
 from .models import create_model
 from .utils import audio
 from .utils.text import text_to_sequence
+
+
+MAX_BATCH = 32      # texts per model pass: the rows one packed decode step takes (ns_rows32)
+
+
+def pad_text_batch(seqs):
+    """Symbol-id sequences of different lengths -> (inputs int32 [N, T_max] padded with id 0 as the feeder's _pad does,
+    lengths int32 [N])."""
+    lengths = np.asarray([len(s) for s in seqs], dtype=np.int32)
+    inputs = np.zeros((len(seqs), int(lengths.max()) if len(seqs) else 0), dtype=np.int32)
+    for i, s in enumerate(seqs):
+        inputs[i, :len(s)] = np.asarray(s, dtype=np.int32)
+    return inputs, lengths
+
+
+def batch_chunks(n, size=MAX_BATCH):
+    """[(start, stop)] of the consecutive chunks of at most `size` that cover range(n), in order."""
+    return [(s, min(n, s + size)) for s in range(0, n, size)]
 
 
 class Synthesizer(object):
@@ -62,16 +83,24 @@ class Synthesizer(object):
         hparams_mod.set_hparams(mine)
         return self
 
-    def _wavenet_vocode(self, mel, seed=0, global_conditions=None):
-        """mel float [T, num_mels] -> float32 [T * hop] in [-1, 1]: row r conditions samples r * hop .. r * hop + hop - 1;
-        the seed - receptive-field copies of mu_law_encode(0) - stands at t0 = -rf and takes row 0.  No inv_preemphasis:
-        the WaveNet feeder's waveforms are not pre-emphasised."""
+    def _wavenet_vocode_batch(self, mels, seed=0, global_conditions=None):
+        """mels float [B, T, num_mels] -> float32 [B, T * hop] in [-1, 1], ONE generate call: row r of a mel conditions
+        samples r * hop .. r * hop + hop - 1; the seed - receptive-field copies of mu_law_encode(0) - stands at t0 = -rf
+        and takes row 0.  Waveform i draws from np.random.default_rng(seed + i).random(T * hop), so B = 1 is the stream
+        generate(seed=seed) draws itself.  No inv_preemphasis: the WaveNet feeder's waveforms are not pre-emphasised."""
         from .models.wavenet import mu_law_decode, mu_law_encode
         v, hop = self.vocoder, self._vocoder_hop
+        mels = np.asarray(mels, np.float32)
+        B, n = mels.shape[0], mels.shape[1] * hop
         silence = int(mu_law_encode(np.zeros(1, np.float32), v.Q)[0])
-        ids = v.generate(np.full((1, v.rf), silence, np.int32), len(mel) * hop, seed=seed, global_conditions=global_conditions,
-                         local_conditions=np.asarray(mel, np.float32)[None], hold=hop, t0=-v.rf)
-        return mu_law_decode(ids[0, v.rf:].cpu().numpy(), v.Q)
+        uniforms = np.stack([np.random.default_rng(seed + i).random(n) for i in range(B)])
+        ids = v.generate(np.full((B, v.rf), silence, np.int32), n, uniforms=uniforms, global_conditions=global_conditions,
+                         local_conditions=mels, hold=hop, t0=-v.rf)
+        return mu_law_decode(ids[:, v.rf:].cpu().numpy(), v.Q)
+
+    def _wavenet_vocode(self, mel, seed=0, global_conditions=None):
+        """mel float [T, num_mels] -> float32 [T * hop]: _wavenet_vocode_batch of the one mel."""
+        return self._wavenet_vocode_batch(np.asarray(mel, np.float32)[None], seed=seed, global_conditions=global_conditions)[0]
 
     def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0):
         """vocoder="wavenet" (after load_vocoder): the mel output through the WaveNet; seed: of the draws' random stream
@@ -101,3 +130,55 @@ class Synthesizer(object):
         wav = audio.inv_preemphasis(wav.cpu().numpy())
         wav = wav[:audio.find_endpoint(wav)]
         return wav, mel, lin
+
+    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0):
+        """synthesize for a list of texts: [(wav, mel, lin)] in the order of `texts`, every entry with the shapes and
+        dtypes synthesize returns.  speaker_ids: one int for all, or one id per text.  More than MAX_BATCH texts run as
+        consecutive chunks of at most MAX_BATCH in the given order (never sorted: see below); [] returns [].
+        Per chunk: ONE model pass on the padded texts, then
+          griffin_lim: one griffin_lim_gpu on linear_outputs [N, T, F], one audio.finish_waves (inv_preemphasis and
+            find_endpoint of all N on the device), one copy to the host each of the waves, the ends, the mels and the
+            linears, check_status() behind them as in synthesize, wav[i] = y[i, :ends[i]];
+          wavenet: one generate for the chunk, text i of the LIST drawing from np.random.default_rng(seed + i); mu-law
+            decoding and find_endpoint per row on the host, no pre-emphasis.
+        Row i is the row of a PADDED batch: the encoder's convolutions read the padding behind a shorter text, as the
+        reference's graph would, and other kernels run at N > 2 than at N = 1 (model.last_paths["decode"]).  So entry i
+        is close to synthesize(texts[i]), not bit-equal to it - and depends on which texts share its chunk.  The WaveNet
+        rows of different batch sizes are not promised bit-equal either: the condition products are dispatched by
+        shape."""
+        if vocoder not in ("griffin_lim", "wavenet"):
+            raise ValueError("vocoder %r: 'griffin_lim' or 'wavenet'" % (vocoder,))
+        texts = list(texts)
+        if np.ndim(speaker_ids) == 0:
+            speakers = np.full(len(texts), int(speaker_ids), dtype=np.int32)
+        else:
+            speakers = np.asarray(speaker_ids, dtype=np.int32).reshape(-1)
+            if len(speakers) != len(texts):
+                raise ValueError("%d speaker_ids for %d texts" % (len(speakers), len(texts)))
+        if not texts:
+            return []
+        if vocoder == "wavenet" and self.vocoder is None:
+            raise ValueError("vocoder='wavenet' needs load_vocoder(checkpoint_path, hparams) first")
+        cleaner_names = [x.strip() for x in self.hparams.cleaners.split(",")]
+        seqs = [text_to_sequence(t, cleaner_names) for t in texts]
+        m = self.model
+        out = []
+        for start, stop in batch_chunks(len(seqs)):
+            inputs, lengths = pad_text_batch(seqs[start:stop])
+            spk = speakers[start:stop]
+            m.initialize(inputs, lengths, spk)
+            if vocoder == "wavenet":
+                mels = m.mel_outputs.float().cpu().numpy()
+                lins = m.linear_outputs.float().cpu().numpy()
+                m.check_status()            # (as in synthesize: invalid outputs are never vocoded)
+                full = self._wavenet_vocode_batch(mels, seed=seed + start, global_conditions=spk if self.vocoder.gc else None)
+                wavs = [w[:audio.find_endpoint(w)] for w in full]
+            else:
+                y, ends = audio.finish_waves(audio.griffin_lim_gpu(m.linear_outputs))
+                y, ends = y.cpu().numpy(), ends.cpu().numpy()
+                mels = m.mel_outputs.float().cpu().numpy()
+                lins = m.linear_outputs.float().cpu().numpy()
+                m.check_status()            # after the host copies, before anything is handed out
+                wavs = [y[i, :int(ends[i])] for i in range(stop - start)]
+            out.extend((wavs[i], mels[i], lins[i]) for i in range(stop - start))
+        return out

@@ -576,3 +576,31 @@ def find_endpoint(wav, threshold_db=-40, min_silence_sec=0.8):
         if np.max(wav[x:x + window_length]) < threshold:
             return x + hop_length
     return len(wav)
+
+
+def finish_waves(wavs, threshold_db=-40, min_silence_sec=0.8):
+    """inv_preemphasis and find_endpoint of N clips in ONE launch (ns_wave_finish): wavs float32 [L] or [N, L], a CUDA
+    tensor (no host trip) or an array (one upload).  Returns (y, ends) on the device: y float32 [N, L], row i
+    inv_preemphasis(wavs[i]) bit for bit, and ends int64 [N], ends[i] = find_endpoint(y[i], threshold_db,
+    min_silence_sec); the caller cuts y[i, :ends[i]].  The coefficient, the window and the hop come from the current
+    hparams exactly as those two functions form them."""
+    hp = get_hparams()
+    dev = _dev()
+    if torch.is_tensor(wavs):
+        x = wavs.to(dev, torch.float32)
+    else:
+        x = torch.as_tensor(np.ascontiguousarray(wavs, dtype=np.float32)).to(dev)
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    assert x.dim() == 2, "finish_waves takes [L] or [N, L]"
+    x = x.contiguous()              # x and y share one row stride: L
+    N, Lw = x.shape
+    window_length = int(hp.sample_rate * min_silence_sec)
+    hop_length = int(window_length / 4)
+    threshold = float(np.power(10.0, threshold_db * 0.05))
+    y = torch.empty((N, Lw), dtype=torch.float32, device=dev)
+    ends = torch.zeros(N, dtype=torch.int64, device=dev)
+    if N > 0 and Lw > 0:            # (an empty clip has no device address to hand over: its end is 0)
+        with torch.cuda.device(dev):
+            ops.wave_finish(x, y, N, Lw, Lw, float(hp.preemphasis), window_length, hop_length, threshold, ends)
+    return y, ends
