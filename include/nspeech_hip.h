@@ -704,7 +704,8 @@ int ns_highway(const ns_highway_params* p, ns_stream_t stream);
  *   p1 = relu(F1[s] + ctx[s-1].W1c)       (F1 = frame part of prenet dense_1 + bias, hoisted)
  *   p2 = relu(p1.W2 + b2)
  *   (c,h) = LSTM([p2, h[s-1]].Watt + b)
- *   e[t] = sum_u v[u] tanh(keys[t,u] + (h.Wq)[u] + sum_k align[s-1][t+k-kw/2] Wcl[k,u])
+ *   e[t] = sum_u v[u] tanh(keys[t,u] + (h.Wq)[u] + sum_k align[s-1][t+k-(kw-1)/2] Wcl[k,u])   (zero outside [0, T_in):
+ *          conv1d 'same' pads (kw-1)/2 on the left, so an even kw has the longer side on the right)
  *   align[s] = softmax over t < length;  ctx[s] = sum_t align[s][t] values[t]
  * where Wcl = location_conv . location_layer folded into one [kw, A] filter.
  * In training (teacher forcing, helpers.py:73-77) this chain does not depend on the two

@@ -434,7 +434,8 @@ struct BCfg : Cfg<A_, D1_, D2_> {
   static constexpr int CPQ = B::GC / NQ;                 // gate columns per group (32 | 4)
   static constexpr int PPT = 3;                          // (row, group) pairs per thread: NQ * K = 3 * CT
   static constexpr int W2H = CT / B::D1, W2K = B::D2 / W2H;       // dp1 product: halves, k per thread
-  static constexpr int CCN = TSMAX + 8;                  // carry contributions (ts + 6 used) + dcar
+  static constexpr int CCN = TSMAX + 8;                  // carry contributions of a slice: ts + kw - 1 used, at most TSMAX + KWMAX - 1 = 39; the last granule carries 0
+  static_assert(CCN >= TSMAX + KWMAX - 1, "the carry window of a full slice under the widest filter");
   static constexpr int E3N = B::K + CCN;                 // granules per workgroup, exchange 3
   static constexpr int EMAX = E3N > B::A ? E3N : B::A;
   static constexpr int UL = B::A / 16;                   // query columns per lane in the dhq product
@@ -717,8 +718,10 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
     ns_lds_barrier();
     // ---- P5: this workgroup's contributions to the carry of step s-1 (positions t0-half .. t0+ts+kw-half-2)
     float ccv = 0.f;                         // threads < CCN keep their value for the E3 publish
-    if (tid < TSMAX + 6) {
-      // carry[t'] += G[t' - k + half][k]; local: t' = t0 - half + tid  ->  G row (tid - k)
+    if (tid < TSMAX + KWMAX - 1) {
+      // carry[t'] += G[t' - k + half][k]; local: t' = t0 - half + tid  ->  G row (tid - k).  Row TSMAX - 1 with tap
+      // KWMAX - 1 lands on tid = TSMAX + KWMAX - 2 (the bound was TSMAX + 6, one short of it: with kw = 8 and a full
+      // slice of 32 positions the last tap of the slice's last position never reached the next slice's carry)
 #pragma unroll
       for (int k = 0; k < KWMAX; ++k) {
         const int row = tid - k;
@@ -821,7 +824,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
 #pragma unroll
         for (int q = 0; q < CG; ++q) {
           const int j = tp - q * ts + half;            // index into workgroup q's contributions (its t0 - half ...)
-          if (j >= 0 && j < TSMAX + 6) s += gath[q * E3N + K + j];
+          if (j >= 0 && j < TSMAX + KWMAX - 1) s += gath[q * E3N + K + j];
         }
       }
       carry[tl] = s;
