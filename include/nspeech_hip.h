@@ -834,10 +834,15 @@ int ns_taco1_attn_cluster_bwd(const ns_taco1_attn_params* p, void* work, ns_stre
  * att: as for ns_taco1_attn_cluster_fwd with S = decoder steps and pv = values.W1[M:]; f1 slot 1 must hold the <GO>
  * frame's term (= b1), later slots are not read; xa carries the speaker projection in every slot when Dsp > 0.
  * Writes att.align / p1 / xa / xc / hc[:, :, :A] / ru / cc / q (/ align_t) as the teacher-forced call does, and y2.
- * Shapes: A = D1 = D = 256, D2 = 128, any E, T_in <= 256, N <= 2, any Dsp; 8 N + 16 workgroups must fit the device
- * (one per CU).  The caller owns `work` (ns_taco1_decode_work_bytes()); the call re-initialises it.  work[0] (int) is
- * the status word: non-zero after the call completes = an exchange timed out and the outputs are invalid (1-3: the
- * attention's exchanges, 4: its frame-term poll, 5-10: the decoder workgroups' six exchanges). */
+ * Shapes: A = D1 = D = 256, D2 = 128, any E, T_in <= 256, any N >= 1, any Dsp.  The rows run in groups of two: a group is
+ * the attention clusters of its rows plus 16 decoder workgroups of its own (32 workgroups, 24 for a single row), one per CU,
+ * and a launch holds at most ns_taco1_decode_max_rows() = 2 * (CUs / 32) rows (16 on 256 CUs).  A call with more rows
+ * issues ceil(N / max_rows) launches on `stream` over balanced consecutive row ranges (N = 20: 10 + 10); N <= 2 is the one
+ * launch of 8 N + 16 workgroups.  The caller owns `work` (ns_taco1_decode_work_bytes(), which scales with N); the call
+ * clears it once, ahead of its first launch, and allocates nothing.  work[0] (int) is the status word, shared by every
+ * group and every launch of the call and cleared by none of them: non-zero after the call completes = an exchange timed out
+ * and the outputs are invalid (1-3: the attention's exchanges, 4: its frame-term poll, 5-10: the decoder workgroups' six
+ * exchanges).  A group that times out ends alone: no group waits on another. */
 typedef struct {
   ns_taco1_attn_params att;
   int D;
@@ -850,6 +855,7 @@ typedef struct {
   const float* wpf; const float* bpf;      /* folded feedback [D, D1], [D1] */
   float* y2;                               /* fp32 [N, S+1, D] out: y2 of step s in slot s+1 */
 } ns_taco1_decode_params;
+int ns_taco1_decode_max_rows(void);   /* rows per launch on the current device (256 CUs assumed without one) */
 int ns_taco1_decode_supported(const ns_taco1_decode_params* p);
 size_t ns_taco1_decode_work_bytes(const ns_taco1_decode_params* p);
 int ns_taco1_decode(const ns_taco1_decode_params* p, void* work, ns_stream_t stream);

@@ -54,8 +54,8 @@ constexpr int W2H = CT / D1, W2K = D2 / W2H;             // dp1 product: 2 halve
 // free-running synthesis: decoder workgroups (see "free-running synthesis" below)
 constexpr int DD = 256;                                  // decoder width D
 constexpr int DU = 16;                                   // decoder units per decoder workgroup
-constexpr int DNW = DD / DU;                             // decoder workgroups per launch: 16
-constexpr int DNR = 2;                                   // utterances per launch
+constexpr int DNW = DD / DU;                             // decoder workgroups per group: 16
+constexpr int DNR = 2;                                   // utterances per group of decoder workgroups
 static_assert(NQ * K == PPT * CT && P2K == 64 && GKP + GKH == 48 && CKP + CKH == 24, "shape");
 
 struct TArgs {
@@ -713,9 +713,18 @@ size_t bwd_granules(int N) { return (size_t)N * CG * (1 + A + 2 * K); }
 // Synthesis (tacotron.py:80-86 with TacoTestHelper, helpers.py:7-38): the frame fed to step s+1 is the last frame
 // predicted at step s, so nothing can be hoisted out of the time loop and the launch-per-step form needs ~28 dependent
 // launches per decoder step.  Here the whole loop is ONE launch with two roles, selected by blockIdx:
-//   workgroups [0, 8N)        the attention clusters of attn_fwd_body<INFER> above
-//   the next DNW = 16         decoder workgroups, DU = 16 units of D = 256 each, for BOTH decoder GRUs and the
-//                             attention projection (N <= 2 utterances per workgroup)
+//   workgroups [0, 8 nr)      the attention clusters of attn_fwd_body<INFER> above, one per row of the launch
+//   the next 16 G             decoder workgroups: G = ceil(nr / 2) GROUPS of DNW = 16, DU = 16 units of D = 256 each,
+//                             for BOTH decoder GRUs and the attention projection; group g serves the (at most DNR = 2)
+//                             rows n0 + 2 g, n0 + 2 g + 1 of the call - a tail group has one row
+// A launch takes the rows [n0, n0 + nr) of the call, nr <= ns_taco1_decode_max_rows() = 2 * (CUs / 32): every workgroup
+// of the grid (8 nr + 16 G, 256 for 16 rows) must be resident at once, one per CU.  ns_taco1_decode splits a larger N
+// into balanced consecutive launches on one stream.  The groups are independent: every exchange array is indexed by the
+// row's number in the CALL (x1..x3, f1x, alx, xa..xe, the history), a group reads and writes its own rows' granules only,
+// and no group waits on another.  All groups and launches of a call share the status word: a time-out raises it (codes
+// below) and ends the group whose wait ran out; another group leaves early only if one of its own waits stalls long
+// enough to read the word (ns_spin: every 1024 polls), otherwise it finishes - the call's outputs are invalid either way.
+// Nothing clears the word between the launches of a call.
 // A decoder workgroup keeps, as fp32 in registers, the columns of its own units: W_proj[h rows] (8 per thread), GRU_1 and
 // GRU_2 gates (2 x 32) and candidates (2 x 16), and the rows of the folded feedback wpf that its y2 units multiply (8):
 // 112 weights per thread, matrix-VECTOR products as exact fp32 FMAs.  The context never forms in the loop: the projected
@@ -743,23 +752,42 @@ size_t bwd_granules(int N) { return (size_t)N * CG * (1 + A + 2 * K); }
 // after D3's reduction); h2f by the D6 gather, read in D4 / D5 of the next step; red / rus / y2s are reduction
 // scratch, each rewritten only behind the barrier that follows its readers.  Status codes: 1-3 the attention's three
 // gathers, 4 its frame-term poll, 5-10 the decoder phases D1-D6.
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, both dtypes): 229 VGPRs, 0 AGPRs, no scratch, 115 328 bytes of
-// dynamic LDS (the attention role's image; the decoder role needs 82 KB), one workgroup per CU.  Measured on one MI355X
-// (profiles/taco1_decode.txt): 300 steps at T_in = 160 in 5.22 ms (N = 1, 17.4 us per step) / 5.68 ms (N = 2).
+// The audit for the grouped form: LDS is per workgroup and a decoder workgroup belongs to one group, so every LDS image
+// above holds the group's rows only, indexed by the row's place in the GROUP (0 or 1), and the hand-overs are the ones
+// listed; the global arrays are entered at the group's first row (dec_role's x2 / alx / f1x / xa..xe / y2 / val), so the
+// one-buffer argument above holds per group - its readers and writers are the group's 16 workgroups and its rows'
+// clusters, as they were the launch's.  Two launches of a call touch disjoint rows of every array but the status word.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, both dtypes): 229 VGPRs, 0 AGPRs, 106 SGPRs, no scratch,
+// 115 328 bytes of dynamic LDS (the attention role's image; the decoder role needs 82 KB), one workgroup per CU - as
+// before the groups.  Measured on one MI355X (profiles/taco1_decode.txt), 300 steps at T_in = 160, the decoder section of
+// initialize(): 5.24 ms (N = 1, 17.5 us per step) / 5.77 ms (N = 2) / 5.81 ms (N = 4) / 6.02 ms (N = 16, one launch of
+// 256 workgroups, 20.1 us per step) / 11.89 ms (N = 32, two launches).  Groups of four rows (dec_role templated on the
+// rows per group, 243 VGPRs, 103 KB LDS) lost: 7.51 / 7.67 / 15.17 ms at N = 4 / 16 / 32.
 struct DArgs {
   TArgs att;
   const void* values;                     // (dtype) [N*Pi, E]
   const float *wp, *bp, *wg1, *bg1, *wc1, *bc1, *wg2, *bg2, *wc2, *bc2, *wpf;
   float* y2;                              // [N][S+1][DD]
   u64 *xa, *xb, *xc, *xd, *xe;            // [N][DD]; xc [N][2 DD]
+  int n0, nr;                             // the rows of the call that this launch serves: [n0, n0 + nr)
 };
 
 template <typename T>
-__device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w) {
+__device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w, const int nb, const int N) {
   const ns_taco1_attn_params& p = d.att.p;
-  const int tid = threadIdx.x, N = p.N, Tia = p.Tia, u0 = w * DU;
+  const int tid = threadIdx.x, Tia = p.Tia, u0 = w * DU;
   const long S1 = p.S + 1;
   int* status = d.att.status;
+  // the group's rows are nb .. nb + N (N <= DNR) of the call: every global array starts at row nb, LDS is group-local
+  const u64* x2 = d.att.x2 + (size_t)nb * CG * X2N;
+  const u64* alx = d.att.alx + (size_t)nb * Tia;
+  u64* f1x = d.att.f1x + (size_t)nb * DNW * D1;
+  u64* xa = d.xa + (size_t)nb * DD;
+  u64* xb = d.xb + (size_t)nb * DD;
+  u64* xc = d.xc + (size_t)nb * 2 * DD;
+  u64* xd = d.xd + (size_t)nb * DD;
+  u64* xe = d.xe + (size_t)nb * DD;
+  float* y2 = d.y2 + (long)nb * S1 * DD;
   float* ha = sm;                          // [DNR][A]      h_att(s)
   float* als = ha + DNR * A;               // [DNR][256]    align(s)
   float* x1f = als + DNR * 256;            // [DNR][DD]     x1(s) of every unit
@@ -794,7 +822,7 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
   const float bg1v = d.bg1[gcol], bg2v = d.bg2[gcol];
   // ---- LDS images: PM = memory . W_proj[ctx rows] (own columns), zero states
   {
-    const T* val = (const T*)d.values;
+    const T* val = (const T*)d.values + (long)nb * p.Pi * p.E;
     for (int o = tid; o < N * 256 * DU; o += CT) {
       const int j = o % DU, t = (o / DU) % 256, n = o / (DU * 256);
       float s = 0.f;
@@ -817,11 +845,11 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
     // ---- D1: h_att(s), align(s) -> x1 of the own units
     bool good = ns_gather_mapped<(DNR * A + CT - 1) / CT, CT>(N * A, tag, tid, status, 5, [&](int i, const u64*& src, float*& dst) {
       const int n = i / A, u = i % A;
-      src = d.att.x2 + ((size_t)n * CG + u / UPW) * X2N + A + u % UPW;
+      src = x2 + ((size_t)n * CG + u / UPW) * X2N + A + u % UPW;
       dst = ha + i;
     });
     good = ns_gather_mapped<(DNR * 256 + CT - 1) / CT, CT>(N * Tia, tag, tid, status, 5, [&](int i, const u64*& src, float*& dst) {
-      src = d.att.alx + i;
+      src = alx + i;
       dst = als + (i / Tia) * 256 + i % Tia;
     }) && good;
     if (!good) flag[0] = 1.f;
@@ -838,11 +866,11 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       float s = bpv;
 #pragma unroll
       for (int q = 0; q < 32; ++q) s += red[n * CT + q * DU + j];
-      ns_put_granule(d.xa + (size_t)n * DD + u0 + j, tag, s);
+      ns_put_granule(xa + (size_t)n * DD + u0 + j, tag, s);
     }
     // ---- D2: x1 of every unit -> GRU_1 gates of the own units, r * h1(s-1)
     good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 6, [&](int i, const u64*& src, float*& dst) {
-      src = d.xa + i; dst = x1f + i;
+      src = xa + i; dst = x1f + i;
     });
     if (!good) flag[0] = 1.f;
     ns_lds_barrier();
@@ -857,11 +885,11 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       for (int q = 0; q < 16; ++q) z += red[n * CT + q * 2 * DU + c];
       const float v = sigmoidf_(z);
       rus[n * 2 * DU + c] = v;
-      if (c < DU) ns_put_granule(d.xb + (size_t)n * DD + u0 + c, tag, v * yh1[n * 2 * DD + DD + u0 + c]);
+      if (c < DU) ns_put_granule(xb + (size_t)n * DD + u0 + c, tag, v * yh1[n * 2 * DD + DD + u0 + c]);
     }
     // ---- D3: r * h1 of every unit -> candidate, h1(s), y1 = x1 + h1 of the own units
     good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 7, [&](int i, const u64*& src, float*& dst) {
-      src = d.xb + i; dst = rhf + i;
+      src = xb + i; dst = rhf + i;
     });
     if (!good) flag[0] = 1.f;
     ns_lds_barrier();
@@ -876,13 +904,13 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       for (int q = 0; q < 32; ++q) z += red[n * CT + q * DU + j];
       const float c = tanhf_(z), u = rus[n * 2 * DU + DU + j];
       const float h = u * yh1[n * 2 * DD + DD + u0 + j] + (1.f - u) * c;
-      ns_put_granule(d.xc + (size_t)n * 2 * DD + u0 + j, tag, x1f[n * DD + u0 + j] + h);
-      ns_put_granule(d.xc + (size_t)n * 2 * DD + DD + u0 + j, tag, h);
+      ns_put_granule(xc + (size_t)n * 2 * DD + u0 + j, tag, x1f[n * DD + u0 + j] + h);
+      ns_put_granule(xc + (size_t)n * 2 * DD + DD + u0 + j, tag, h);
     }
     ns_lds_barrier();                           // yh1's h1 half was read above; the gather below rewrites it
     // ---- D4: y1 | h1 of every unit -> GRU_2 gates of the own units, r * h2(s-1)
     good = ns_gather_mapped<(DNR * 2 * DD + CT - 1) / CT, CT>(N * 2 * DD, tag, tid, status, 8, [&](int i, const u64*& src, float*& dst) {
-      src = d.xc + i; dst = yh1 + i;
+      src = xc + i; dst = yh1 + i;
     });
     if (!good) flag[0] = 1.f;
     ns_lds_barrier();
@@ -897,11 +925,11 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       for (int q = 0; q < 16; ++q) z += red[n * CT + q * 2 * DU + c];
       const float v = sigmoidf_(z);
       rus[n * 2 * DU + c] = v;
-      if (c < DU) ns_put_granule(d.xd + (size_t)n * DD + u0 + c, tag, v * h2f[n * DD + u0 + c]);
+      if (c < DU) ns_put_granule(xd + (size_t)n * DD + u0 + c, tag, v * h2f[n * DD + u0 + c]);
     }
     // ---- D5: r * h2 of every unit -> candidate, h2(s), y2 = y1 + h2 of the own units; the feedback shares
     good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 9, [&](int i, const u64*& src, float*& dst) {
-      src = d.xd + i; dst = rhf + i;
+      src = xd + i; dst = rhf + i;
     });
     if (!good) flag[0] = 1.f;
     ns_lds_barrier();
@@ -918,8 +946,8 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       const float h = u * h2f[n * DD + u0 + j] + (1.f - u) * c;
       const float y = yh1[n * 2 * DD + u0 + j] + h;
       y2s[n * DU + j] = y;
-      d.y2[((long)n * S1 + slot) * DD + u0 + j] = y;
-      if (st + 1 < p.S) ns_put_granule(d.xe + (size_t)n * DD + u0 + j, tag, h);
+      y2[((long)n * S1 + slot) * DD + u0 + j] = y;
+      if (st + 1 < p.S) ns_put_granule(xe + (size_t)n * DD + u0 + j, tag, h);
     }
     ns_lds_barrier();
     if (st + 1 < p.S) {
@@ -933,10 +961,10 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
       ns_lds_barrier();
       if (tid < D1)
         for (int n = 0; n < N; ++n)
-          ns_put_granule(d.att.f1x + ((size_t)n * DNW + w) * D1 + tid, tag + 1, red[n * CT + tid] + red[n * CT + D1 + tid]);
+          ns_put_granule(f1x + ((size_t)n * DNW + w) * D1 + tid, tag + 1, red[n * CT + tid] + red[n * CT + D1 + tid]);
       // ---- D6: h2(s) of every unit for the next step
       good = ns_gather_mapped<(DNR * DD + CT - 1) / CT, CT>(N * DD, tag, tid, status, 10, [&](int i, const u64*& src, float*& dst) {
-        src = d.xe + i; dst = h2f + i;
+        src = xe + i; dst = h2f + i;
       });
       if (!good) flag[0] = 1.f;
       ns_lds_barrier();
@@ -948,9 +976,13 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w)
 template <typename T>
 __global__ __launch_bounds__(CT) void taco1_decode_kernel(DArgs d) {
   extern __shared__ __attribute__((aligned(16))) float sm_dec[];
-  const int na = d.att.p.N * CG;
-  if ((int)blockIdx.x < na) attn_fwd_body<T, true>(d.att, sm_dec, blockIdx.x);
-  else dec_role<T>(d, sm_dec, blockIdx.x - na);
+  const int na = d.nr * CG;
+  if ((int)blockIdx.x < na) {
+    attn_fwd_body<T, true>(d.att, sm_dec, d.n0 * CG + (int)blockIdx.x);
+  } else {
+    const int b = (int)blockIdx.x - na, nb = d.n0 + (b / DNW) * DNR;
+    dec_role<T>(d, sm_dec, b % DNW, nb, min(DNR, d.n0 + d.nr - nb));
+  }
 }
 
 constexpr size_t DEC_LDS = sizeof(float) * (DNR * A + DNR * 256 + DNR * DD * 2 + DNR * 2 * DD + DNR * DD + DNR * CT +
@@ -962,13 +994,19 @@ size_t decode_granules(int N) {
 }
 }  // namespace
 
-extern "C" int ns_taco1_attn_cluster_supported(const ns_taco1_attn_params* p) {
+// Everything ns_taco1_attn_cluster_supported asks but the residency of the launch (ns_taco1_decode splits its rows).
+static int taco1_attn_shape_ok(const ns_taco1_attn_params* p) {
   if (!p) return 0;
   if (!(p->A == A && p->D1 == D1 && p->D2 == D2 && p->E > 0 && p->Ti >= 1 && p->Ti <= 256 && p->Tia >= p->Ti && p->S >= 1 && p->N >= 1 && p->Dsp >= 0)) return 0;
   if (!(p->dtype == NS_F32 || p->dtype == NS_BF16)) return 0;
   if (!p->keys || !p->pv || !p->f1 || !p->w2 || !p->wg || !p->wc || !p->wq || !p->b2 || !p->bg || !p->bc || !p->v) return 0;
   if (!p->p1 || !p->xa || !p->xc || !p->hc || !p->ru || !p->cc || !p->q || !p->align) return 0;
   if ((long)p->N * (p->S + 1) * (long)(p->A + p->E) >= (1L << 31)) return 0;
+  return 1;
+}
+
+extern "C" int ns_taco1_attn_cluster_supported(const ns_taco1_attn_params* p) {
+  if (!taco1_attn_shape_ok(p)) return 0;
   return p->N * CG <= ns_device_cus();      // every workgroup of the launch must be resident at once, one per CU
 }
 
@@ -1025,15 +1063,27 @@ extern "C" int ns_taco1_attn_cluster_bwd(const ns_taco1_attn_params* p, void* wo
 }
 
 // ------------------------------------------------------------------ free-running synthesis, C ABI
+// Rows per launch: a group of DNR rows takes DNR * CG + DNW = 32 workgroups, one per CU.
+extern "C" int ns_taco1_decode_max_rows(void) { return DNR * (ns_device_cus() / (DNR * CG + DNW)); }
+
+// The call's N rows as balanced consecutive launches of at most max_rows each (20 rows at 16 per launch: 10 + 10).  A
+// device below 32 CUs has max_rows = 0 and still takes the one launch of N <= 2 if that fits.
+static int decode_launches(int N) {
+  const int cap = ns_taco1_decode_max_rows();
+  return cap > 0 ? (N + cap - 1) / cap : 1;
+}
+static int decode_grid(int nr) { return nr * CG + DNW * ((nr + DNR - 1) / DNR); }
+
 extern "C" int ns_taco1_decode_supported(const ns_taco1_decode_params* q) {
   if (!q) return 0;
   const ns_taco1_attn_params* p = &q->att;
-  if (!ns_taco1_attn_cluster_supported(p)) return 0;
-  if (q->D != DD || p->N > DNR || p->Tia > 256 || p->E < 1) return 0;
+  if (!taco1_attn_shape_ok(p)) return 0;
+  if (q->D != DD || p->Tia > 256 || p->E < 1) return 0;
   if (!q->values || !q->w_proj || !q->b_proj || !q->wg_1 || !q->bg_1 || !q->wc_1 || !q->bc_1 || !q->wg_2 || !q->bg_2 ||
       !q->wc_2 || !q->bc_2 || !q->wpf || !q->bpf || !q->y2)
     return 0;
-  return p->N * CG + DNW <= ns_device_cus();     // every workgroup of the launch resident at once, one per CU
+  const int nl = decode_launches(p->N);
+  return decode_grid((p->N + nl - 1) / nl) <= ns_device_cus();     // every workgroup of a launch resident at once, one per CU
 }
 
 extern "C" size_t ns_taco1_decode_work_bytes(const ns_taco1_decode_params* q) {
@@ -1045,7 +1095,7 @@ extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_s
   hipStream_t s = (hipStream_t)s_;
   NS_CHECK_ARG(q && work, "ns_taco1_decode: null");
   NS_CHECK_ARG(ns_taco1_decode_supported(q), "ns_taco1_decode: unsupported shape (needs A = D1 = D = 256, D2 = 128, "
-               "T_in <= 256, N <= 2, 8 N + 16 workgroups resident) or a null operand");
+               "T_in <= 256, N >= 1, 32 workgroups resident per two rows of a launch: ns_taco1_decode_max_rows) or a null operand");
   const ns_taco1_attn_params* p = &q->att;
   DArgs d = {};
   d.att.p = *p;
@@ -1064,6 +1114,7 @@ extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_s
   d.wg1 = q->wg_1; d.bg1 = q->bg_1; d.wc1 = q->wc_1; d.bc1 = q->bc_1;
   d.wg2 = q->wg_2; d.bg2 = q->bg_2; d.wc2 = q->wc_2; d.bc2 = q->bc_2;
   d.wpf = q->wpf; d.y2 = q->y2;
+  // the whole work area once, status word included: the launches below share that word and none of them clears it
   { const int zrc = ns_zero_async(work, (256 + decode_granules(p->N) * sizeof(u64) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   static bool attr = false;
   if (!attr) {
@@ -1071,9 +1122,15 @@ extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_s
     (void)hipFuncSetAttribute((const void*)taco1_decode_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  const dim3 grid((unsigned)(p->N * CG + DNW)), block(CT);
-  if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_decode_kernel<bf16_t>, grid, block, DECODE_LDS, s, d);
-  else hipLaunchKernelGGL(taco1_decode_kernel<float>, grid, block, DECODE_LDS, s, d);
-  NS_CHECK_LAUNCH("ns_taco1_decode");
+  const int nl = decode_launches(p->N);
+  for (int l = 0; l < nl; ++l) {
+    // rows [N l / nl, N (l + 1) / nl): consecutive, sizes differ by at most one
+    d.n0 = (int)((long)p->N * l / nl);
+    d.nr = (int)((long)p->N * (l + 1) / nl) - d.n0;
+    const dim3 grid((unsigned)decode_grid(d.nr)), block(CT);
+    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_decode_kernel<bf16_t>, grid, block, DECODE_LDS, s, d);
+    else hipLaunchKernelGGL(taco1_decode_kernel<float>, grid, block, DECODE_LDS, s, d);
+    NS_CHECK_LAUNCH("ns_taco1_decode");
+  }
   return NS_OK;
 }

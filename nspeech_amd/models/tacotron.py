@@ -667,9 +667,10 @@ class Tacotron(Tacotron2):
                           out2_sn=out2_sn)
 
     def _decode_persistent(self, N, Ti, Pi, Tia, S, enc, keys, spk_dec):
-        """The free-running decoder loop as ONE launch (ns_taco1_decode): attention clusters + register-resident
-        projection / decoder GRUs + folded frame feedback.  Returns (dec, al, S1) in the [N, S+1, X] slot layout, or
-        None when the shape is not covered (other widths, T_in > 256, more than two utterances)."""
+        """The free-running decoder loop as ONE launch per ns_taco1_decode_max_rows() utterances (ns_taco1_decode splits
+        a larger batch itself): attention clusters + register-resident projection / decoder GRUs + folded frame
+        feedback.  Returns (dec, al, S1) in the [N, S+1, X] slot layout, or None when the shape is not covered (other
+        widths, T_in > 256)."""
         import ctypes as C
         from .. import _lib as L
         hp = self._hparams
@@ -781,8 +782,9 @@ class Tacotron(Tacotron2):
         Tia = _round_up(Ti, 8)
         keys_t = buf("keys_t", N * A * Tia, torch.float32)
         ops.keys_transpose(keys, keys_t, N, Ti, Tia, Pi, self.padl, A)
-        # The whole free-running loop as ONE persistent launch (csrc/attn_gru.hip "free-running synthesis") where the shape
-        # allows; otherwise one decoder step = ~28 dependent launches from here.  last_paths["decode"] says which ran.
+        # The whole free-running loop as ONE persistent launch per 16 utterances (csrc/attn_gru.hip "free-running
+        # synthesis") where the widths and T_in allow, at every batch size; otherwise one decoder step = ~28 dependent
+        # launches from here.  last_paths["decode"] says which ran.
         done = None
         if getattr(self, "use_decode_kernel", True):
             done = self._decode_persistent(N, Ti, Pi, Tia, S, enc, keys, spk_dec)
