@@ -9,6 +9,7 @@
 // accumulate in registers; quantities that are sums over t (dq, dv, dWcl) are computed by a
 // second sweep with one unit per lane over the original [T_in][A] layout.
 #include "common.h"
+#include "carve.h"
 #include "lstm_step.h"
 
 constexpr int MAXKW = 8;
@@ -165,14 +166,22 @@ __global__ __launch_bounds__(ATHREADS) void attn_energy_kernel(AttnStep<T> a) {
 }
 
 constexpr int CCH = 128;   // context columns per workgroup
-// LDS (floats): al[Tia] | red[32] | cpart[4][CCH]
+template <typename O = int>
+struct CtxLds {                              // dynamic LDS of attn_context_kernel
+  O Tia;
+  CarveT<O> c = {};
+  O al = c.template take<float>(Tia);           // [Tia] softmaxed alignments
+  O red = c.template take<float>(32);            // block reductions
+  O cpart = c.template take<float>(4 * CCH);     // [4][CCH] per-wave partial contexts
+  O bytes = c.off;
+};
 template <typename T>
 __global__ __launch_bounds__(256) void attn_context_kernel(AttnStep<T> a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int Ti = a.Ti, Tia = a.Tia;
-  float* al = sm;
-  float* red = al + Tia;
-  float* cpart = red + 32;
+  const CtxLds<> lay{Tia};
+  float* al = carve_at<float>(sm, lay.al); float* red = carve_at<float>(sm, lay.red);
+  float* cpart = carve_at<float>(sm, lay.cpart);
   const int n = blockIdx.y;
   const bool second = a.pv && (int)blockIdx.x >= a.nch;
   const int ch = second ? blockIdx.x - a.nch : blockIdx.x;
@@ -402,13 +411,21 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_energy_kernel(AttnBwdStep<T
 }
 
 // (3) dq[u] = sum_t dpre[t,u];  grid (unit chunks of 64, N), lane = unit, wave = time slice
+template <typename O = int>
+struct DqLds {                               // dynamic LDS of attn_bwd_dq_kernel
+  O Ti, Tia;
+  CarveT<O> c = {};
+  O ap = c.template take<float>(Ti + 2 * PADK);  // [Ti + 2 PADK] previous alignments inside a zero margin
+  O de = c.template take<float>(Tia);            // [Tia] energy gradients, zero past the length
+  O part = c.template take<float>(AW * 64);      // [AW][64] per-wave partial sums
+  O bytes = c.off;
+};
 template <typename T>
 __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_kernel(AttnBwdStep<T> a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];   // ap[Ti+2P] | de[Tia] | part[AW][64]
+  extern __shared__ __attribute__((aligned(16))) float sm[];
   const int Ti = a.Ti, A = a.A, Tia = a.Tia;
-  float* ap = sm;
-  float* de = ap + Ti + 2 * PADK;
-  float* part = de + Tia;
+  const DqLds<> lay{Ti, Tia};
+  float* ap = carve_at<float>(sm, lay.ap); float* de = carve_at<float>(sm, lay.de); float* part = carve_at<float>(sm, lay.part);
   const int n = blockIdx.y, uw = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, ts = tid >> 6;
   const int L = min(a.lengths ? a.lengths[n] : Ti, Ti);
@@ -702,11 +719,6 @@ static int check_attn(const ns_taco2_attn_params* p, const char* who) {
   return NS_OK;
 }
 
-static size_t ctx_lds(const ns_taco2_attn_params& p) { return sizeof(float) * ((size_t)p.Tia + 32 + 4 * CCH); }
-static size_t dq_lds(const ns_taco2_attn_params& p) {
-  return sizeof(float) * ((size_t)p.Ti + 2 * PADK + p.Tia + AW * 64);
-}
-
 // projected-memory form, step 0: p1[slot 1] = relu(f1[slot 1]) (the context before the first step is zero)
 template <typename T>
 __global__ void attn_p1_init_kernel(const float* f1, T* p1, int N, long S1, int D1) {
@@ -737,7 +749,7 @@ static int attn_fwd_t(const ns_taco2_attn_params& p, hipStream_t s) {
   const long S1 = p.S + 1, A = p.A, E = p.E, D1 = p.D1, D2 = p.D2;
   const long Dsp = p.Dsp, XA = D2 + Dsp + A, HC = A + E;
   const int dt = p.dtype;
-  const size_t lds = ctx_lds(p);
+  const size_t lds = CtxLds<size_t>{(size_t)p.Tia}.bytes;
   NS_CHECK_ARG(lds <= 64 * 1024, "ns_taco2_attn_fwd: T_in too long for LDS (%zu bytes)", lds);
   NS_CHECK_ARG(p.work != nullptr, "ns_taco2_attn_fwd: work buffer missing");
   float* e_raw = p.work + (size_t)p.N * p.E;
@@ -932,7 +944,7 @@ static int attn_bwd_t(const ns_taco2_attn_params& p, hipStream_t s) {
   float* dhq = gk + (size_t)p.N * p.Tia * MAXKW;
   float* dc_carry = dhq + (size_t)p.N * A;
   float* dkeys_t = dc_carry + (size_t)p.N * A;
-  const size_t lds = dq_lds(p);
+  const size_t lds = DqLds<size_t>{(size_t)p.Ti, (size_t)p.Tia}.bytes;
   NS_CHECK_ARG(lds <= 64 * 1024 && sizeof(float) * p.E <= 64 * 1024,
                "ns_taco2_attn_bwd: T_in / memory depth too large for LDS");
   T* xa = (T*)p.xa; T* p1 = (T*)p.p1;
@@ -1048,7 +1060,7 @@ extern "C" int ns_attention_step(const ns_attention_step_params* p, ns_stream_t 
                "ns_attention_step: null");
   NS_CHECK_ARG(p->A % 8 == 0 && p->A <= 256 && p->E % 8 == 0 && p->kw >= 1 && p->kw <= MAXKW && p->Tia >= p->Ti,
                "ns_attention_step: unsupported shape");
-  const size_t lds = sizeof(float) * ((size_t)p->Tia + 32 + 4 * CCH);
+  const size_t lds = CtxLds<size_t>{(size_t)p->Tia}.bytes;
   NS_CHECK_ARG(lds <= 64 * 1024, "ns_attention_step: T_in too long for LDS");
   NS_CHECK_ARG(!p->pv || (p->pv_out && p->E2 > 0 && p->E2 % 8 == 0), "ns_attention_step: pv needs pv_out and E2 %% 8 == 0");
   NS_CHECK_ARG(!p->ctx_rows || (p->N <= 32 && p->ctx_rows_col >= 0 && p->ctx_rows_col + p->E <= ((p->ctx_rows_K + 31) / 32) * 32),
@@ -1097,7 +1109,7 @@ extern "C" int ns_attention_step_bwd(const ns_attention_step_bwd_params* p, ns_s
                    p->dq_out && p->de_out && p->dctx_out && p->wcl && p->v, "ns_attention_step_bwd: null");
   NS_CHECK_ARG(p->A % 8 == 0 && p->A <= 256 && p->E % 8 == 0 && p->kw >= 1 && p->kw <= MAXKW && p->Tia >= p->Ti,
                "ns_attention_step_bwd: unsupported shape");
-  const size_t lds = sizeof(float) * ((size_t)p->Ti + 2 * PADK + p->Tia + AW * 64);
+  const size_t lds = DqLds<size_t>{(size_t)p->Ti, (size_t)p->Tia}.bytes;
   NS_CHECK_ARG(lds <= 64 * 1024 && sizeof(float) * p->E <= 64 * 1024, "ns_attention_step_bwd: too large for LDS");
   auto run = [&](auto tag) -> int {
     using T = decltype(tag);

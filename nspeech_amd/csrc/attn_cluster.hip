@@ -23,6 +23,7 @@
 // All history the backward pass and the hoisted products read (p1, xa, hc, ca, ga, q, align, align_t) is written in
 // the layouts of ns_taco2_attn_fwd, which stays as the fallback for shapes this kernel does not cover.
 #include "exchange.h"
+#include "carve.h"
 #include <stdlib.h>
 
 int ns_attn_contexts_after_loop(const ns_taco2_attn_params& p, hipStream_t s);     // attn.hip
@@ -75,26 +76,38 @@ template <typename T> __device__ __forceinline__ float ldw(const T* p, long i) {
 // The forward recurrence of one workgroup (bid = utterance * CG + member).  INFER = free-running decode: the frame term
 // of the next step is not hoisted (it depends on this step's output through the two decoder LSTMs) but polled from
 // a.f1x, and the alignment is published to a.alx for the workgroups that run the first decoder LSTM.
+template <typename C>
+struct FwdLds {                            // dynamic LDS of attn_fwd_body<*, C, *> (the forward kernel, the decode kernel's clusters)
+  LdsCarve c = {};
+  int xs = c.take<float>(C::K);            // [K]      LSTM input: p2 | h(s-1)
+  int p1s = c.take<float>(C::D1);          // [D1]     prenet layer 1 of the current step
+  int red = c.take<float>(CT);             // [CT]     partial sums across the k / t groups of a product
+  int qs = c.take<float>(C::A);            // [A]      query
+  int al = c.take<float>(256 + 2 * APAD);  // [APAD + 256 + APAD] alignment of the previous step, zero margins
+  int es = c.take<float>(TSMAX);           // [TSMAX]  local unnormalised softmax weights
+  int ered = c.take<float>((CT / 64) * TSMAX);       // [CT/64][TSMAX] per-wave energy sums
+  int hloc = c.take<float>(C::UPW);        // [UPW] new h of this workgroup's units
+  int sc = c.take<float>(16);              // [16]     [0] local max, [1] local sum, [2] abort flag
+  int gath = c.take<float>(CG * C::XMAX);  // [CG][XMAX]
+  int keys_s = c.take<float>(TSMAX * (C::A + KPAD)); // [TSMAX][A + KPAD]
+  int pv_s = c.take<float>(TSMAX * C::D1); // [TSMAX][D1]
+  int wq_s = c.take<float>(C::UPW * C::A); // [UPW][A]  W_query rows of the own units
+  int cst_s = c.take<float>((KWMAX + 1) * (C::A + KPAD));     // [KWMAX + 1][A + KPAD]  folded location filter, attention_v
+  int bytes = c.off;
+};
 template <typename T, typename C, bool INFER>
 __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const int bid) {
   constexpr int A = C::A, D1 = C::D1, D2 = C::D2, UPW = C::UPW, GC = C::GC, K = C::K;
   constexpr int GG = C::GG, GK = C::GK, P2G = C::P2G, P2K = C::P2K, QG = C::QG, QK = C::QK, CXG = C::CXG;
   constexpr int X2N = C::X2N, X3N = C::X3N;
   const ns_taco2_attn_params& p = a.p;
-  float* xs = sm;                          // [K]      LSTM input: p2 | h(s-1)
-  float* p1s = xs + K;                     // [D1]     prenet layer 1 of the current step
-  float* red = p1s + D1;                   // [CT]     partial sums across the k / t groups of a product
-  float* qs = red + CT;                    // [A]      query
-  float* al = qs + A;                      // [APAD + 256 + APAD] alignment of the previous step, zero margins
-  float* es = al + 256 + 2 * APAD;         // [TSMAX]  local unnormalised softmax weights
-  float* ered = es + TSMAX;                // [CT/64][TSMAX] per-wave energy sums
-  float* hloc = ered + (CT / 64) * TSMAX;  // [UPW] new h of this workgroup's units
-  float* sc = hloc + UPW;                  // [16]     [0] local max, [1] local sum, [2] abort flag
-  float* gath = sc + 16;                   // [CG][XMAX]
-  float* keys_s = gath + CG * C::XMAX;     // [TSMAX][A + KPAD]
-  float* pv_s = keys_s + TSMAX * (A + KPAD);        // [TSMAX][D1]
-  float* wq_s = pv_s + TSMAX * D1;         // [UPW][A]  W_query rows of the own units
-  float* cst_s = wq_s + UPW * A;           // [KWMAX + 1][A]  folded location filter, attention_v
+  constexpr FwdLds<C> lay;
+  float* xs = carve_at<float>(sm, lay.xs); float* p1s = carve_at<float>(sm, lay.p1s); float* red = carve_at<float>(sm, lay.red);
+  float* qs = carve_at<float>(sm, lay.qs); float* al = carve_at<float>(sm, lay.al); float* es = carve_at<float>(sm, lay.es);
+  float* ered = carve_at<float>(sm, lay.ered); float* hloc = carve_at<float>(sm, lay.hloc);
+  float* sc = carve_at<float>(sm, lay.sc); float* gath = carve_at<float>(sm, lay.gath);
+  float* keys_s = carve_at<float>(sm, lay.keys_s); float* pv_s = carve_at<float>(sm, lay.pv_s);
+  float* wq_s = carve_at<float>(sm, lay.wq_s); float* cst_s = carve_at<float>(sm, lay.cst_s);
 
   const int tid_ = threadIdx.x;
   const int n = bid / CG, g = bid % CG;
@@ -442,46 +455,68 @@ struct BCfg : Cfg<A_, D1_, D2_> {
   static_assert(NQ * B::K == PPT * CT && B::GC % NQ == 0 && B::D2 % W2H == 0 && B::A % 32 == 0 && B::D1 == 256, "shape");
 };
 
+template <typename C>
+struct BwdLds {                            // dynamic LDS of attn_cluster_bwd_kernel<*, C>
+  LdsCarve c = {};
+  int dvec = c.take<float>(C::D1);         // [D1]  dp1 of the step after (the vector dotted with the pv rows)
+  int dp2s = c.take<float>(C::D2);         // [D2]
+  int dgs = c.take<float>(C::GC);          // [GC]  gate gradients of the own units, (gate, unit)
+  int red = c.take<float>(C::NQ * C::K);   // [NQ * K] partial sums
+  // the per-step history images exist twice (parity of the step): the next step's are filled in the middle of this
+  // one, when its loads have long landed - at the top of a step they would wait behind the write-through stores
+  // that end the step before (one vmcnt queue: 1.1 us per step)
+  int qs0 = c.take<float>(C::A);           // [A]
+  int al0 = c.take<float>(256 + 2 * APAD); // [APAD + 256 + APAD] alignment of step s-1
+  int acur0 = c.take<float>(TSMAX);        // [TSMAX] alignment of step s, own positions
+  int da0s0 = c.take<float>(TSMAX);        // [TSMAX]
+  int dav = c.take<float>(TSMAX);          // [TSMAX] dalign
+  int dev = c.take<float>(TSMAX);          // [TSMAX] energy gradients
+  int carry = c.take<float>(TSMAX);        // [TSMAX] location-filter carry for the own positions
+  int Gs = c.take<float>(TSMAX * 8);       // [TSMAX][8]
+  int zred = c.take<float>(8 * TSMAX * 8); // [8 waves][TSMAX][8]
+  int hrec = c.take<float>(C::UPW);        // [UPW] recurrent part of dh for the own units
+  int dq_s = c.take<float>(C::A);          // [A]
+  int p1m0 = c.take<float>(C::D1);         // [D1] p1 of this step (ReLU mask)
+  int p2m0 = c.take<float>(C::D2);         // [D2]
+  int gts0 = c.take<float>(C::GC);         // [GC] saved gates of the own units
+  int sc = c.take<float>(48);              // [48]  [0] dot, [1] dcar, [2] abort, [4..] block_sum scratch
+  int gath = c.take<float>(CG * C::EMAX);  // [CG][EMAX]
+  int keys_s = c.take<float>(TSMAX * (C::A + KPAD)); // [TSMAX][A + KPAD]
+  int pv_s = c.take<float>(TSMAX * C::D1); // [TSMAX][D1]
+  int wq_s = c.take<float>(C::UPW * C::A); // [UPW][A]
+  int cst_s = c.take<float>((KWMAX + 1) * (C::A + KPAD));     // [KWMAX + 1][A + KPAD]
+  int qs1 = c.take<float>(C::A);           // the second set of history images, as the first
+  int al1 = c.take<float>(256 + 2 * APAD);
+  int acur1 = c.take<float>(TSMAX);
+  int da0s1 = c.take<float>(TSMAX);
+  int p1m1 = c.take<float>(C::D1);
+  int p2m1 = c.take<float>(C::D2);
+  int gts1 = c.take<float>(C::GC);
+  int bytes = c.off;
+};
 template <typename T, typename C>
 __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
   constexpr int A = C::A, D1 = C::D1, D2 = C::D2, UPW = C::UPW, GC = C::GC, K = C::K;
   constexpr int NQ = C::NQ, CPQ = C::CPQ, PPT = C::PPT, W2H = C::W2H, W2K = C::W2K, CCN = C::CCN, E3N = C::E3N, UL = C::UL;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const ns_taco2_attn_params& p = a.p;
-  float* dvec = sm;                        // [D1]  dp1 of the step after (the vector dotted with the pv rows)
-  float* dp2s = dvec + D1;                 // [D2]
-  float* dgs = dp2s + D2;                  // [GC]  gate gradients of the own units, (gate, unit)
-  float* red = dgs + GC;                   // [NQ * K] partial sums
-  // the per-step history images exist twice (parity of the step): the next step's are filled in the middle of this
-  // one, when its loads have long landed - at the top of a step they would wait behind the write-through stores
-  // that end the step before (one vmcnt queue: 1.1 us per step)
-  float* qs0 = red + NQ * K;               // [A]
-  float* al0 = qs0 + A;                    // [APAD + 256 + APAD] alignment of step s-1
-  float* acur0 = al0 + 256 + 2 * APAD;     // [TSMAX] alignment of step s, own positions
-  float* da0s0 = acur0 + TSMAX;            // [TSMAX]
-  float* dav = da0s0 + TSMAX;              // [TSMAX] dalign
-  float* dev = dav + TSMAX;                // [TSMAX] energy gradients
-  float* carry = dev + TSMAX;              // [TSMAX] location-filter carry for the own positions
-  float* Gs = carry + TSMAX;               // [TSMAX][8]
-  float* zred = Gs + TSMAX * 8;            // [8 waves][TSMAX][8]
-  float* hrec = zred + 8 * TSMAX * 8;      // [UPW] recurrent part of dh for the own units
-  float* dq_s = hrec + UPW;                // [A]
-  float* p1m0 = dq_s + A;                  // [D1] p1 of this step (ReLU mask)
-  float* p2m0 = p1m0 + D1;                 // [D2]
-  float* gts0 = p2m0 + D2;                 // [GC] saved gates of the own units
-  float* sc = gts0 + GC;                   // [16]  [0] dot, [1] dcar, [2] abort, [4..] block_sum scratch
-  float* gath = sc + 48;                   // [CG][EMAX]
-  float* keys_s = gath + CG * C::EMAX;     // [TSMAX][A + KPAD]
-  float* pv_s = keys_s + TSMAX * (A + KPAD);        // [TSMAX][D1]
-  float* wq_s = pv_s + TSMAX * D1;         // [UPW][A]
-  float* cst_s = wq_s + UPW * A;           // [KWMAX + 1][A + KPAD]
-  float* qs1 = cst_s + (KWMAX + 1) * (A + KPAD);
-  float* al1 = qs1 + A;
-  float* acur1 = al1 + 256 + 2 * APAD;
-  float* da0s1 = acur1 + TSMAX;
-  float* p1m1 = da0s1 + TSMAX;
-  float* p2m1 = p1m1 + D1;
-  float* gts1 = p2m1 + D2;                 // ... + GC
+  constexpr BwdLds<C> lay;
+  float* dvec = carve_at<float>(sm, lay.dvec); float* dp2s = carve_at<float>(sm, lay.dp2s);
+  float* dgs = carve_at<float>(sm, lay.dgs); float* red = carve_at<float>(sm, lay.red);
+  float* qs0 = carve_at<float>(sm, lay.qs0); float* al0 = carve_at<float>(sm, lay.al0);
+  float* acur0 = carve_at<float>(sm, lay.acur0); float* da0s0 = carve_at<float>(sm, lay.da0s0);
+  float* dav = carve_at<float>(sm, lay.dav); float* dev = carve_at<float>(sm, lay.dev);
+  float* carry = carve_at<float>(sm, lay.carry); float* Gs = carve_at<float>(sm, lay.Gs);
+  float* zred = carve_at<float>(sm, lay.zred); float* hrec = carve_at<float>(sm, lay.hrec);
+  float* dq_s = carve_at<float>(sm, lay.dq_s); float* p1m0 = carve_at<float>(sm, lay.p1m0);
+  float* p2m0 = carve_at<float>(sm, lay.p2m0); float* gts0 = carve_at<float>(sm, lay.gts0);
+  float* sc = carve_at<float>(sm, lay.sc); float* gath = carve_at<float>(sm, lay.gath);
+  float* keys_s = carve_at<float>(sm, lay.keys_s); float* pv_s = carve_at<float>(sm, lay.pv_s);
+  float* wq_s = carve_at<float>(sm, lay.wq_s); float* cst_s = carve_at<float>(sm, lay.cst_s);
+  float* qs1 = carve_at<float>(sm, lay.qs1); float* al1 = carve_at<float>(sm, lay.al1);
+  float* acur1 = carve_at<float>(sm, lay.acur1); float* da0s1 = carve_at<float>(sm, lay.da0s1);
+  float* p1m1 = carve_at<float>(sm, lay.p1m1); float* p2m1 = carve_at<float>(sm, lay.p2m1);
+  float* gts1 = carve_at<float>(sm, lay.gts1);
 
   const int tid_ = threadIdx.x;
   const int n = blockIdx.x / CG, g = blockIdx.x % CG;
@@ -883,6 +918,25 @@ struct DecArgs {
 // One decoder LSTM's workgroup w.  WHICH = 1: inputs h_att (A, registers) + context (through PM) + own h1; 2: h1 + own h2.
 // A workgroup owns UPW units = COLS = 4 UPW gate columns (column = gate * UPW + unit); thread (cg = tid & 15, ks = tid >> 4)
 // holds the CPT = COLS / 16 columns CPT cg .. of the k slice ks of each input.
+template <typename C, int D, int NR, int WHICH>
+struct DecRoleLds {                        // dynamic LDS of dec_lstm_role<*, C, *, D, NR, WHICH> with NW workgroups in its LSTM
+  static constexpr int UPW = WHICH == 1 ? DEC_UPW1 : DEC_UPW2, COLS = 4 * UPW, RS = COLS + 1, KX = WHICH == 1 ? C::A : D;
+  int Tia, NW;
+  int FPW = (C::D1 + NW - 1) / NW;                      // feedback columns per workgroup (LSTM 2)
+  LdsCarve c = {};
+  int xv = c.take<float>(NR * KX);                      // [NR][KX]   gathered input of the x part
+  int hv = c.take<float>(NR * D);                       // [NR][D]    gathered own h of the previous step
+  int red = c.take<float>(DEC_KS * RS);                 // [32][COLS + 1] partial sums over the k slices
+  int zr = c.take<float>(NR * COLS);                    // [NR][COLS] recurrent half, computed a phase ahead
+  int zs = c.take<float>(COLS);                         // [COLS]     gate pre-activations of the row in work
+  int flag = c.take<float>(4);                          // [4]        [0] abort
+  // what follows differs by role (the one a role lacks takes nothing)
+  int al_s = c.take<float>(WHICH == 1 ? NR * Tia : 0);            // 1: [NR][Tia]
+  int PM = c.take<float>(WHICH == 1 ? NR * Tia * COLS : 0);       // 1: [NR][Tia][COLS]
+  int wpf_s = c.take<float>(WHICH == 2 ? FPW * D : 0);            // 2: [FPW][D]
+  int red2 = c.take<float>(WHICH == 2 ? DEC_KS * 64 : 0);         // 2: [32][64]
+  int bytes = c.off;
+};
 template <typename T, typename C, int E, int D, int NR, int WHICH>
 __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const int w) {
   constexpr int A = C::A, D1 = C::D1, X2N = C::X2N, UPWA = C::UPW;
@@ -893,19 +947,12 @@ __device__ __forceinline__ void dec_lstm_role(const DecArgs& d, float* sm, const
   const int tid = threadIdx.x, cg = tid & 15, ks = tid >> 4;
   const int N = d.N, Tia = p.Tia, u0 = w * UPW;
   const int NW = WHICH == 1 ? d.NW1 : d.NW2;
-  const int FPW = (D1 + NW - 1) / NW, f0 = w * FPW, fn = max(0, min(D1, f0 + FPW) - f0);      // own feedback columns (LSTM 2)
-  // ---- LDS
-  float* xv = sm;                               // [NR][KX]   gathered input of the x part
-  float* hv = xv + NR * KX;                     // [NR][D]    gathered own h of the previous step
-  float* red = hv + NR * D;                     // [32][COLS + 1] partial sums over the k slices
-  float* zr = red + DEC_KS * RS;                // [NR][COLS] recurrent half, computed a phase ahead
-  float* zs = zr + NR * COLS;                   // [COLS]     gate pre-activations of the row in work
-  float* flag = zs + COLS;                      // [4]        [0] abort
-  float* xtra = flag + 4;                       // WHICH 1: al_s [NR][Tia], PM [NR][Tia][COLS]; 2: wpf_s [FPW][D], red2 [32][64]
-  float* al_s = xtra;
-  float* PM = al_s + NR * Tia;
-  float* wpf_s = xtra;
-  float* red2 = wpf_s + (size_t)FPW * D;
+  const DecRoleLds<C, D, NR, WHICH> lay{Tia, NW};
+  const int FPW = lay.FPW, f0 = w * FPW, fn = max(0, min(D1, f0 + FPW) - f0);      // own feedback columns (LSTM 2)
+  float* xv = carve_at<float>(sm, lay.xv); float* hv = carve_at<float>(sm, lay.hv); float* red = carve_at<float>(sm, lay.red);
+  float* zr = carve_at<float>(sm, lay.zr); float* zs = carve_at<float>(sm, lay.zs); float* flag = carve_at<float>(sm, lay.flag);
+  float* al_s = carve_at<float>(sm, lay.al_s); float* PM = carve_at<float>(sm, lay.PM);
+  float* wpf_s = carve_at<float>(sm, lay.wpf_s); float* red2 = carve_at<float>(sm, lay.red2);
   // ---- resident weights
   const float* W = WHICH == 1 ? d.w1 : d.w2;
   const float* bias = WHICH == 1 ? d.b1 : d.b2;
@@ -1075,20 +1122,62 @@ __global__ __launch_bounds__(CT) void taco2_decode_kernel(DecArgs d) {
   else dec_lstm_role<T, C, E, D, NR, 2>(d, sm_dec, b - na - d.NW1);
 }
 
-template <typename C, int E, int D, int NR>
-size_t dec_lds_bytes(int Tia, int NW2) {
-  const int FPW = (C::D1 + NW2 - 1) / NW2;
-  constexpr int C1 = 4 * DEC_UPW1, C2 = 4 * DEC_UPW2;
-  const size_t l1 = (size_t)NR * (C::A + D) + DEC_KS * (C1 + 1) + NR * C1 + C1 + 4 + (size_t)NR * Tia * (1 + C1);
-  const size_t l2 = (size_t)NR * (D + D) + DEC_KS * (C2 + 1) + NR * C2 + C2 + 4 + (size_t)FPW * D + DEC_KS * 64;
-  return sizeof(float) * (l1 > l2 ? l1 : l2);
-}
 
+// Work areas: the status word in a block of its own, then one granule array per exchange, [N] utterances each.
 template <typename C>
-size_t fwd_lds_bytes() {
-  return sizeof(float) * (C::K + C::D1 + CT + C::A + 256 + 2 * APAD + TSMAX + (CT / 64) * TSMAX + C::UPW + 16 +
-                          CG * C::XMAX + TSMAX * (C::A + KPAD) + TSMAX * C::D1 + C::UPW * C::A + (KWMAX + 1) * (C::A + KPAD));
-}
+struct FwdWork {                           // ns_taco2_attn_cluster_fwd, and the head of ns_taco2_decode's
+  size_t N;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);
+  size_t x2 = c.take<u64>(N * CG * C::X2N);          // [N][CG][X2N]
+  size_t x3 = c.take<u64>(N * CG * C::X3N);          // [N][CG][X3N]
+  size_t used = c.off;
+};
+template <typename C>
+struct BwdWork {                           // ns_taco2_attn_cluster_bwd
+  size_t N;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);
+  size_t x2 = c.take<u64>(N * CG * C::A);            // [N][CG][A]    dq partials (E2)
+  size_t x3 = c.take<u64>(N * CG * C::E3N);          // [N][CG][E3N]  input gradients and carry contributions (E3)
+  size_t x1 = c.take<u64>(N * CG);                   // [N][CG]       dot-product shares (E1)
+  size_t used = c.off;
+};
+template <typename C, int D>
+struct DecWork {                           // ns_taco2_decode: the forward form's arrays, then the decoder's
+  size_t N;
+  FwdWork<C> att{N};
+  WorkCarve c{att.used};
+  size_t f1x = c.take<u64>(N * C::D1);               // [N][D1]   the next step's frame term
+  size_t alx = c.take<u64>(N * 256);                 // [N][256]  the alignment
+  size_t pub1 = c.take<u64>(2 * N * D);              // [2][N][D] h of LSTM 1, by step parity
+  size_t pub2 = c.take<u64>(2 * N * D);              // [2][N][D] h of LSTM 2
+  size_t used = c.off;
+};
+// What callers allocate is ABI and larger than any form uses: per workgroup the forward form exchanges X2N + X3N = 578
+// granules and the backward form A + E3N + 1 = 681 at A = 256 (fewer at A = 64); the size stayed when the exchanges shrank.
+constexpr size_t ABI_GRANULES_PER_WG = 2 * (256 + 32 + 2 + TSMAX) + 1024;
+struct AbiWork {                           // ns_taco2_attn_cluster_work_bytes
+  size_t N;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);
+  size_t xch = c.take<u64>(N * CG * ABI_GRANULES_PER_WG);       // every form's exchange arrays
+  size_t trace = c.take<char>(TRACE_BYTES);                      // NS_ATTN_TRACE timestamps
+  size_t bytes = c.off;
+};
+struct DecAbiWork {                        // ns_taco2_decode_work_bytes: the attention's area, the decoder's arrays, a spare block
+  size_t N, D1, D;
+  AbiWork att{N};
+  WorkCarve c{att.bytes};
+  size_t dec = c.take<u64>(N * (D1 + 256) + 4 * N * D);         // f1x, alx, pub1, pub2 (DecWork places them from the front)
+  size_t spare = c.take<char>(256);
+  size_t bytes = c.off;
+};
+// every form stays in front of the trace area: all sizes are 256 + N * (a constant), so N = 1 decides
+static_assert(FwdWork<Cfg<256, 256, 128>>{1}.used <= AbiWork{1}.trace && BwdWork<BCfg<256, 256, 128>>{1}.used <= AbiWork{1}.trace &&
+              BwdWork<BCfg<64, 256, 128>>{1}.used <= AbiWork{1}.trace, "a form outgrew the work area");
+static_assert(DecWork<Cfg<256, 256, 128>, 1024>{1}.used <= DecAbiWork{1, 256, 1024}.bytes &&
+              DecWork<Cfg<64, 256, 128>, 64>{1}.used <= DecAbiWork{1, 256, 64}.bytes, "the decode form outgrew the work area");
 
 bool cluster_shape_ok(const ns_taco2_attn_params* p) {
   if (!p || !p->pv || p->D1 != 256 || p->D2 != 128) return false;
@@ -1105,22 +1194,21 @@ extern "C" int ns_taco2_attn_cluster_supported(const ns_taco2_attn_params* p) { 
 
 extern "C" size_t ns_taco2_attn_cluster_work_bytes(const ns_taco2_attn_params* p) {
   if (!p) return 0;
-  // status block + the two exchange buffers (sized for the widest instantiation)
-  return 256 + sizeof(u64) * (size_t)p->N * CG * (size_t)(2 * (256 + 32 + 2 + TSMAX) + 1024) + TRACE_BYTES;
+  return AbiWork{(size_t)p->N}.bytes;
 }
 
 template <typename T, typename C>
 static int launch_fwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) {
   ACArgs a;
   a.p = *p;
-  a.status = (int*)work;
-  a.x2 = (u64*)((char*)work + 256);
-  a.x3 = a.x2 + (size_t)p->N * CG * C::X2N;
+  const FwdWork<C> wl{(size_t)p->N};
+  a.status = carve_at<int>(work, wl.status);
+  a.x2 = carve_at<u64>(work, wl.x2);
+  a.x3 = carve_at<u64>(work, wl.x3);
   a.x1 = nullptr;
-  const size_t xbytes = sizeof(u64) * (size_t)p->N * CG * (C::X2N + C::X3N);
-  a.trace = getenv("NS_ATTN_TRACE") ? (long long*)((char*)work + ns_taco2_attn_cluster_work_bytes(p) - TRACE_BYTES) : nullptr;
-  { const int zrc = ns_zero_async(work, ((256 + xbytes) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
-  const size_t lds = fwd_lds_bytes<C>();
+  a.trace = getenv("NS_ATTN_TRACE") ? carve_at<long long>(work, AbiWork{(size_t)p->N}.trace) : nullptr;
+  { const int zrc = ns_zero_async(work, (wl.used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  constexpr size_t lds = FwdLds<C>().bytes;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)attn_cluster_fwd_kernel<T, C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1177,26 +1265,19 @@ extern "C" int ns_taco2_attn_cluster_fwd(const ns_taco2_attn_params* p, void* wo
   return launch_fwd<float, Cfg<64, 256, 128>>(p, work, s);
 }
 
-template <typename C>
-static size_t bwd_lds_bytes() {
-  return sizeof(float) * (C::D1 + C::D2 + C::GC + C::NQ * C::K + C::A + 256 + 2 * APAD + 5 * TSMAX + TSMAX * 8 + 8 * TSMAX * 8 +
-                          C::UPW + C::A + C::D1 + C::D2 + C::GC + 48 + CG * C::EMAX + TSMAX * (C::A + KPAD) + TSMAX * C::D1 +
-                          C::UPW * C::A + (KWMAX + 1) * (C::A + KPAD) +
-                          C::A + 256 + 2 * APAD + 2 * TSMAX + C::D1 + C::D2 + C::GC);      // second set of history images
-}
 
 template <typename T, typename C>
 static int launch_bwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) {
   ACArgs a;
   a.p = *p;
-  a.status = (int*)work;
-  a.x2 = (u64*)((char*)work + 256);
-  a.x3 = a.x2 + (size_t)p->N * CG * C::A;
-  a.x1 = a.x3 + (size_t)p->N * CG * C::E3N;
-  const size_t xbytes = sizeof(u64) * (size_t)p->N * CG * (C::A + C::E3N + 1);
-  a.trace = getenv("NS_ATTN_TRACE") ? (long long*)((char*)work + ns_taco2_attn_cluster_work_bytes(p) - TRACE_BYTES) : nullptr;
-  { const int zrc = ns_zero_async(work, ((256 + xbytes) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
-  const size_t lds = bwd_lds_bytes<C>();
+  const BwdWork<C> wl{(size_t)p->N};
+  a.status = carve_at<int>(work, wl.status);
+  a.x2 = carve_at<u64>(work, wl.x2);
+  a.x3 = carve_at<u64>(work, wl.x3);
+  a.x1 = carve_at<u64>(work, wl.x1);
+  a.trace = getenv("NS_ATTN_TRACE") ? carve_at<long long>(work, AbiWork{(size_t)p->N}.trace) : nullptr;
+  { const int zrc = ns_zero_async(work, (wl.used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  constexpr size_t lds = BwdLds<C>().bytes;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)attn_cluster_bwd_kernel<T, C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1264,7 +1345,8 @@ extern "C" int ns_taco2_decode_supported(const ns_taco2_decode_params* q) { retu
 extern "C" size_t ns_taco2_decode_work_bytes(const ns_taco2_decode_params* q) {
   if (!q) return 0;
   const ns_taco2_attn_params* p = &q->att;
-  return ns_taco2_attn_cluster_work_bytes(p) + sizeof(u64) * ((size_t)p->N * (p->D1 + 256) + 4 * (size_t)p->N * q->D) + 256;
+  const DecAbiWork wl{(size_t)p->N, (size_t)p->D1, (size_t)q->D};
+  return wl.bytes;
 }
 
 template <typename T, typename C, int E, int D>
@@ -1272,27 +1354,27 @@ static int launch_decode(const ns_taco2_decode_params* q, void* work, hipStream_
   const ns_taco2_attn_params* p = &q->att;
   DecArgs d;
   d.att.p = *p;
-  d.att.status = (int*)work;
-  d.att.x2 = (u64*)((char*)work + 256);
-  d.att.x3 = d.att.x2 + (size_t)p->N * CG * C::X2N;
+  const DecWork<C, D> wl{(size_t)p->N};
+  d.att.status = carve_at<int>(work, wl.att.status);
+  d.att.x2 = carve_at<u64>(work, wl.att.x2);
+  d.att.x3 = carve_at<u64>(work, wl.att.x3);
   d.att.x1 = nullptr;
-  d.att.f1x = d.att.x3 + (size_t)p->N * CG * C::X3N;
-  d.att.alx = d.att.f1x + (size_t)p->N * C::D1;
-  d.pub1 = d.att.alx + (size_t)p->N * 256;
-  d.pub2 = d.pub1 + 2 * (size_t)p->N * D;
-  const size_t xbytes = (size_t)((char*)(d.pub2 + 2 * (size_t)p->N * D) - (char*)work);
+  d.att.f1x = carve_at<u64>(work, wl.f1x);
+  d.att.alx = carve_at<u64>(work, wl.alx);
+  d.pub1 = carve_at<u64>(work, wl.pub1);
+  d.pub2 = carve_at<u64>(work, wl.pub2);
   d.att.trace = nullptr;
   d.N = p->N; d.S = p->S; d.E = E; d.D = D;
   d.NW1 = (D + DEC_UPW1 - 1) / DEC_UPW1; d.NW2 = (D + DEC_UPW2 - 1) / DEC_UPW2;
   d.w1 = q->w_l1; d.b1 = q->b_l1; d.w2 = q->w_l2; d.b2 = q->b_l2; d.wpf = q->wpf; d.bpf = q->bpf;
   d.h2hist = q->h2;
-  { const int zrc = ns_zero_async(work, (xbytes + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  { const int zrc = ns_zero_async(work, (wl.used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   const int grid = p->N * CG + d.NW1 + d.NW2;
 #define NS_LAUNCH_DEC(NR_)                                                                                           \
   do {                                                                                                               \
-    size_t lds = dec_lds_bytes<C, E, D, NR_>(p->Tia, d.NW2);                                                         \
-    const size_t la = fwd_lds_bytes<C>();                                                                            \
-    if (la > lds) lds = la;                                                                                          \
+    /* the three roles overlay one region */                                                                         \
+    const int l1 = DecRoleLds<C, D, NR_, 1>{p->Tia, d.NW1}.bytes, l2 = DecRoleLds<C, D, NR_, 2>{p->Tia, d.NW2}.bytes; \
+    const size_t lds = max_of(max_of(l1, l2), FwdLds<C>().bytes);                                                    \
     NS_CHECK_ARG(lds <= 160 * 1024, "ns_taco2_decode: %zu bytes of LDS needed", lds);                                \
     static bool attr = false;                                                                                        \
     if (!attr) {                                                                                                     \

@@ -26,6 +26,7 @@
 // On a time-out the status word is raised and every workgroup of the cluster leaves.  History is written in the
 // layouts models/tacotron.py reads (the launch-per-step form stays as the fallback).
 #include "exchange.h"
+#include "carve.h"
 #include <stdlib.h>
 
 namespace {
@@ -83,22 +84,33 @@ __device__ __forceinline__ bool poll_partials(const u64* src, unsigned tag, floa
 // One workgroup of an utterance's cluster (bid = utterance * CG + member).  INFER = free-running synthesis: the frame
 // term of the next step is not hoisted (it depends on this step's output through the decoder GRUs) but polled from
 // a.f1x, and the alignment is published to a.alx for the decoder workgroups (attn_cluster.hip: attn_fwd_body<INFER>).
+struct FwdLds {                            // dynamic LDS of attn_fwd_body (the forward kernel, the decode kernel's clusters)
+  LdsCarve c = {};
+  int xs = c.take<float>(K);               // [K]      p2 | h(s-1)
+  int p1s = c.take<float>(D1);             // [D1]     prenet layer 1 of the current step
+  int red = c.take<float>(CT);             // [CT]     partial sums across the k / t groups of a product
+  int rus = c.take<float>(GC);             // [GC]     r | u of the own units
+  int hloc = c.take<float>(UPW);           // [UPW]    h of the own units
+  int es = c.take<float>(TSMAX);           // [TSMAX]  local unnormalised softmax weights
+  int ered = c.take<float>(8 * TSMAX);     // [8][TSMAX] per-wave energy sums
+  int sc = c.take<float>(16);              // [16]     [0] local max, [1] local sum, [2] abort flag
+  int gath = c.take<float>(CG * XMAX);     // [CG][XMAX]
+  int vs = c.take<float>(A);               // [A]      attention_v
+  int keys_s = c.take<float>(TSMAX * (A + KPAD));   // [TSMAX][A + KPAD]
+  int pv_s = c.take<float>(TSMAX * D1);    // [TSMAX][D1]
+  int wq_s = c.take<float>(UPW * A);       // [UPW][A]  W_query rows of the own units
+  int bytes = c.off;
+};
 template <typename T, bool INFER>
 __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const int bid) {
   const ns_taco1_attn_params& p = a.p;
-  float* xs = sm;                          // [K]      p2 | h(s-1)
-  float* p1s = xs + K;                     // [D1]     prenet layer 1 of the current step
-  float* red = p1s + D1;                   // [CT]     partial sums across the k / t groups of a product
-  float* rus = red + CT;                   // [GC]     r | u of the own units
-  float* hloc = rus + GC;                  // [UPW]    h of the own units
-  float* es = hloc + UPW;                  // [TSMAX]  local unnormalised softmax weights
-  float* ered = es + TSMAX;                // [8][TSMAX] per-wave energy sums
-  float* sc = ered + 8 * TSMAX;            // [16]     [0] local max, [1] local sum, [2] abort flag
-  float* gath = sc + 16;                   // [CG][XMAX]
-  float* vs = gath + CG * XMAX;            // [A]      attention_v
-  float* keys_s = vs + A;                  // [TSMAX][A + KPAD]
-  float* pv_s = keys_s + TSMAX * (A + KPAD);      // [TSMAX][D1]
-  float* wq_s = pv_s + TSMAX * D1;         // [UPW][A]  W_query rows of the own units
+  constexpr FwdLds lay;
+  float* xs = carve_at<float>(sm, lay.xs); float* p1s = carve_at<float>(sm, lay.p1s); float* red = carve_at<float>(sm, lay.red);
+  float* rus = carve_at<float>(sm, lay.rus); float* hloc = carve_at<float>(sm, lay.hloc);
+  float* es = carve_at<float>(sm, lay.es); float* ered = carve_at<float>(sm, lay.ered); float* sc = carve_at<float>(sm, lay.sc);
+  float* gath = carve_at<float>(sm, lay.gath); float* vs = carve_at<float>(sm, lay.vs);
+  float* keys_s = carve_at<float>(sm, lay.keys_s); float* pv_s = carve_at<float>(sm, lay.pv_s);
+  float* wq_s = carve_at<float>(sm, lay.wq_s);
 
   const int tid_ = threadIdx.x;
   const int n = bid / CG, g = bid % CG;
@@ -385,29 +397,43 @@ __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
 //       rows < 128: dp2 (first part); rows 128 + own units: d(r h_prev) -> dzr = . h_prev r (1-r), direct += . r
 //   P7b the same for the gate kernel over the own [dzr | dzu] columns -> E3b: dp2 (second part), hrec = direct + h rows
 //   P9  dp1 = (dp2 . W2^T) masked = the next dvec
+struct BwdLds {                            // dynamic LDS of taco1_attn_bwd_kernel
+  // per-step history images, twice (parity of the step): the next step's are filled in the middle of this one
+  static constexpr int HIMG = A + D1 + D2 + 2 * TSMAX + GC + 3 * UPW;
+  LdsCarve c = {};
+  int dvec = c.take<float>(D1);            // [D1]
+  int dp2s = c.take<float>(D2);            // [D2]
+  int dcs = c.take<float>(UPW);            // [UPW]  dzc of the own units
+  int dgs = c.take<float>(GC);             // [GC]   dzr | dzu of the own units
+  int red = c.take<float>(NQ * K);         // [NQ * K]
+  int dav = c.take<float>(TSMAX);          // [TSMAX] dalign
+  int dev = c.take<float>(TSMAX);          // [TSMAX] energy gradients
+  int hrec = c.take<float>(UPW);           // [UPW]
+  int dird = c.take<float>(UPW);           // [UPW]  direct part of the gradient wrt h_prev
+  int dq_s = c.take<float>(A);             // [A]
+  int sc = c.take<float>(16);              // [16]  [0] dot, [2] abort
+  int gath = c.take<float>(CG * K);        // [CG][K]
+  int vs = c.take<float>(A);               // [A]
+  int keys_s = c.take<float>(TSMAX * (A + KPAD));   // [TSMAX][A + KPAD]
+  int pv_s = c.take<float>(TSMAX * D1);    // [TSMAX][D1]
+  int wq_s = c.take<float>(UPW * A);       // [UPW][A]
+  int him = c.take<float>(2 * HIMG);       // [2][HIMG]: qs | p1m | p2m | acur | da0s | rus | cs | hps | dhcs
+  int bytes = c.off;
+};
 template <typename T>
 __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const ns_taco1_attn_params& p = a.p;
-  float* dvec = sm;                        // [D1]
-  float* dp2s = dvec + D1;                 // [D2]
-  float* dcs = dp2s + D2;                  // [UPW]  dzc of the own units
-  float* dgs = dcs + UPW;                  // [GC]   dzr | dzu of the own units
-  float* red = dgs + GC;                   // [NQ * K]
-  float* dav = red + NQ * K;               // [TSMAX] dalign
-  float* dev = dav + TSMAX;                // [TSMAX] energy gradients
-  float* hrec = dev + TSMAX;               // [UPW]
-  float* dird = hrec + UPW;                // [UPW]  direct part of the gradient wrt h_prev
-  float* dq_s = dird + UPW;                // [A]
-  float* sc = dq_s + A;                    // [16]  [0] dot, [2] abort
-  float* gath = sc + 16;                   // [CG][K]
-  float* vs = gath + CG * K;               // [A]
-  float* keys_s = vs + A;                  // [TSMAX][A + KPAD]
-  float* pv_s = keys_s + TSMAX * (A + KPAD);      // [TSMAX][D1]
-  float* wq_s = pv_s + TSMAX * D1;         // [UPW][A]
-  // per-step history images, twice (parity of the step): the next step's are filled in the middle of this one
-  constexpr int HIMG = A + D1 + D2 + 2 * TSMAX + GC + 3 * UPW;
-  float* him = wq_s + UPW * A;             // [2][HIMG]: qs | p1m | p2m | acur | da0s | rus | cs | hps | dhcs
+  constexpr BwdLds lay;
+  constexpr int HIMG = BwdLds::HIMG;
+  float* dvec = carve_at<float>(sm, lay.dvec); float* dp2s = carve_at<float>(sm, lay.dp2s);
+  float* dcs = carve_at<float>(sm, lay.dcs); float* dgs = carve_at<float>(sm, lay.dgs);
+  float* red = carve_at<float>(sm, lay.red); float* dav = carve_at<float>(sm, lay.dav);
+  float* dev = carve_at<float>(sm, lay.dev); float* hrec = carve_at<float>(sm, lay.hrec);
+  float* dird = carve_at<float>(sm, lay.dird); float* dq_s = carve_at<float>(sm, lay.dq_s);
+  float* sc = carve_at<float>(sm, lay.sc); float* gath = carve_at<float>(sm, lay.gath); float* vs = carve_at<float>(sm, lay.vs);
+  float* keys_s = carve_at<float>(sm, lay.keys_s); float* pv_s = carve_at<float>(sm, lay.pv_s);
+  float* wq_s = carve_at<float>(sm, lay.wq_s); float* him = carve_at<float>(sm, lay.him);
 
   const int tid_ = threadIdx.x;
   const int n = blockIdx.x / CG, g = blockIdx.x % CG;
@@ -699,15 +725,29 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
   }
 }
 
-constexpr size_t FWD_LDS = sizeof(float) * (K + D1 + CT + GC + UPW + TSMAX + 8 * TSMAX + 16 + CG * XMAX + A + TSMAX * (A + KPAD) +
-                                             TSMAX * D1 + UPW * A);
-constexpr size_t BWD_LDS = sizeof(float) * (D1 + D2 + UPW + GC + NQ * K + 2 * TSMAX + 2 * UPW + A + 16 + CG * K + A +
-                                             TSMAX * (A + KPAD) + TSMAX * D1 + UPW * A +
-                                             2 * (A + D1 + D2 + 2 * TSMAX + GC + 3 * UPW));
-static_assert(FWD_LDS <= 160 * 1024 && BWD_LDS <= 160 * 1024, "LDS");
+static_assert(FwdLds().bytes <= 160 * 1024 && BwdLds().bytes <= 160 * 1024, "LDS");
 
-size_t fwd_granules(int N) { return (size_t)N * CG * (X1N + X2N + X3N); }
-size_t bwd_granules(int N) { return (size_t)N * CG * (1 + A + 2 * K); }
+
+// work areas: the status word in a block of its own, then one granule array per exchange, [N] rows each
+struct FwdWork {                           // ns_taco1_attn_cluster_fwd, and the head of ns_taco1_decode's
+  size_t N;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);
+  size_t x1 = c.take<u64>(N * CG * X1N);   // [N][CG][X1N]
+  size_t x2 = c.take<u64>(N * CG * X2N);   // [N][CG][X2N]
+  size_t x3 = c.take<u64>(N * CG * X3N);   // [N][CG][X3N]
+  size_t bytes = c.off;
+};
+struct BwdWork {                           // ns_taco1_attn_cluster_bwd
+  size_t N;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);
+  size_t e1 = c.take<u64>(N * CG);         // [N][CG]      softmax-backward dot-product shares
+  size_t e2 = c.take<u64>(N * CG * A);     // [N][CG][A]   dq partials
+  size_t e3a = c.take<u64>(N * CG * K);    // [N][CG][K]   input gradients of the candidate kernel
+  size_t e3b = c.take<u64>(N * CG * K);    // [N][CG][K]   input gradients of the gate kernel
+  size_t bytes = c.off;
+};
 
 // ===================================================================================== free-running synthesis
 // Synthesis (tacotron.py:80-86 with TacoTestHelper, helpers.py:7-38): the frame fed to step s+1 is the last frame
@@ -772,6 +812,21 @@ struct DArgs {
   int n0, nr;                             // the rows of the call that this launch serves: [n0, n0 + nr)
 };
 
+struct DecLds {                            // dynamic LDS of dec_role (the decode kernel's decoder workgroups)
+  LdsCarve c = {};
+  int ha = c.take<float>(DNR * A);         // [DNR][A]      h_att(s)
+  int als = c.take<float>(DNR * 256);      // [DNR][256]    align(s)
+  int x1f = c.take<float>(DNR * DD);       // [DNR][DD]     x1(s) of every unit
+  int rhf = c.take<float>(DNR * DD);       // [DNR][DD]     r * h(s-1) of every unit (GRU_1, then GRU_2)
+  int yh1 = c.take<float>(DNR * 2 * DD);   // [DNR][2 DD]   y1(s) | h1(s)
+  int h2f = c.take<float>(DNR * DD);       // [DNR][DD]     h2(s-1)
+  int red = c.take<float>(DNR * CT);       // [DNR][CT]     partial sums over the k groups
+  int rus = c.take<float>(DNR * 2 * DU);   // [DNR][2 DU]   r | u of the own units
+  int y2s = c.take<float>(DNR * DU);       // [DNR][DU]     y2 of the own units
+  int flag = c.take<float>(4);             // [4]           [0] abort
+  int PM = c.take<float>(DNR * 256 * DU);  // [DNR][256][DU] projected memory of the own columns
+  int bytes = c.off;
+};
 template <typename T>
 __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w, const int nb, const int N) {
   const ns_taco1_attn_params& p = d.att.p;
@@ -788,17 +843,12 @@ __device__ __forceinline__ void dec_role(const DArgs& d, float* sm, const int w,
   u64* xd = d.xd + (size_t)nb * DD;
   u64* xe = d.xe + (size_t)nb * DD;
   float* y2 = d.y2 + (long)nb * S1 * DD;
-  float* ha = sm;                          // [DNR][A]      h_att(s)
-  float* als = ha + DNR * A;               // [DNR][256]    align(s)
-  float* x1f = als + DNR * 256;            // [DNR][DD]     x1(s) of every unit
-  float* rhf = x1f + DNR * DD;             // [DNR][DD]     r * h(s-1) of every unit (GRU_1, then GRU_2)
-  float* yh1 = rhf + DNR * DD;             // [DNR][2 DD]   y1(s) | h1(s)
-  float* h2f = yh1 + DNR * 2 * DD;         // [DNR][DD]     h2(s-1)
-  float* red = h2f + DNR * DD;             // [DNR][CT]     partial sums over the k groups
-  float* rus = red + DNR * CT;             // [DNR][2 DU]   r | u of the own units
-  float* y2s = rus + DNR * 2 * DU;         // [DNR][DU]     y2 of the own units
-  float* flag = y2s + DNR * DU;            // [4]           [0] abort
-  float* PM = flag + 4;                    // [DNR][256][DU] projected memory of the own columns
+  constexpr DecLds lay;
+  float* ha = carve_at<float>(sm, lay.ha); float* als = carve_at<float>(sm, lay.als); float* x1f = carve_at<float>(sm, lay.x1f);
+  float* rhf = carve_at<float>(sm, lay.rhf); float* yh1 = carve_at<float>(sm, lay.yh1);
+  float* h2f = carve_at<float>(sm, lay.h2f); float* red = carve_at<float>(sm, lay.red);
+  float* rus = carve_at<float>(sm, lay.rus); float* y2s = carve_at<float>(sm, lay.y2s);
+  float* flag = carve_at<float>(sm, lay.flag); float* PM = carve_at<float>(sm, lay.PM);
 
   // ---- resident weights: 16 columns x 32 k groups (c16, k16) or 32 columns x 16 k groups (c32, k32)
   const int c16 = tid & 15, k16 = tid >> 4, c32 = tid & 31, k32 = tid >> 5;
@@ -985,13 +1035,21 @@ __global__ __launch_bounds__(CT) void taco1_decode_kernel(DArgs d) {
   }
 }
 
-constexpr size_t DEC_LDS = sizeof(float) * (DNR * A + DNR * 256 + DNR * DD * 2 + DNR * 2 * DD + DNR * DD + DNR * CT +
-                                            DNR * 2 * DU + DNR * DU + 4 + DNR * 256 * DU);
-constexpr size_t DECODE_LDS = DEC_LDS > FWD_LDS ? DEC_LDS : FWD_LDS;
+constexpr size_t DECODE_LDS = max_of(DecLds().bytes, FwdLds().bytes);      // the two roles overlay one region
 static_assert(DECODE_LDS <= 160 * 1024 && D1 == 256 && DD == 256, "LDS / shapes");
-size_t decode_granules(int N) {
-  return fwd_granules(N) + (size_t)N * DNW * D1 + (size_t)N * 256 + (size_t)N * DD * 6;
-}
+struct DecWork {                           // ns_taco1_decode: the forward form's arrays, then the decoder's
+  size_t N;
+  FwdWork att{N};
+  WorkCarve c{att.bytes};
+  size_t f1x = c.take<u64>(N * DNW * D1);  // [N][DNW][D1] partial sums of the next step's frame term
+  size_t alx = c.take<u64>(N * 256);       // [N][256]     align(s)
+  size_t xa = c.take<u64>(N * DD);         // [N][DD]      x1
+  size_t xb = c.take<u64>(N * DD);         // [N][DD]      r * h1
+  size_t xc = c.take<u64>(N * 2 * DD);     // [N][2 DD]    y1 | h1
+  size_t xd = c.take<u64>(N * DD);         // [N][DD]      r * h2
+  size_t xe = c.take<u64>(N * DD);         // [N][DD]      h2
+  size_t bytes = c.off;
+};
 }  // namespace
 
 // Everything ns_taco1_attn_cluster_supported asks but the residency of the launch (ns_taco1_decode splits its rows).
@@ -1012,8 +1070,7 @@ extern "C" int ns_taco1_attn_cluster_supported(const ns_taco1_attn_params* p) {
 
 extern "C" size_t ns_taco1_attn_cluster_work_bytes(const ns_taco1_attn_params* p) {
   if (!p) return 0;
-  const size_t f = fwd_granules(p->N), b = bwd_granules(p->N);
-  return 256 + (f > b ? f : b) * sizeof(u64);
+  return max_of(FwdWork{(size_t)p->N}.bytes, BwdWork{(size_t)p->N}.bytes);
 }
 
 static int taco1_run(const ns_taco1_attn_params* p, void* work, hipStream_t s, int backward) {
@@ -1023,18 +1080,19 @@ static int taco1_run(const ns_taco1_attn_params* p, void* work, hipStream_t s, i
   if (backward) NS_CHECK_ARG(p->dhc && p->da0 && p->df1 && p->dp2 && p->dzg && p->dzc && p->dq && p->de, "%s: null backward operand", name);
   TArgs a = {};
   a.p = *p;
-  a.status = (int*)work;
-  u64* x = (u64*)((char*)work + 256);
-  const size_t N = (size_t)p->N;
-  size_t gran;
+  size_t used;
   if (!backward) {
-    a.x1 = x; a.x2 = a.x1 + N * CG * X1N; a.x3 = a.x2 + N * CG * X2N; a.x4 = nullptr;
-    gran = fwd_granules(p->N);
+    const FwdWork wl{(size_t)p->N};
+    a.status = carve_at<int>(work, wl.status);
+    a.x1 = carve_at<u64>(work, wl.x1); a.x2 = carve_at<u64>(work, wl.x2); a.x3 = carve_at<u64>(work, wl.x3); a.x4 = nullptr;
+    used = wl.bytes;
   } else {
-    a.x1 = x; a.x2 = a.x1 + N * CG; a.x3 = a.x2 + N * CG * A; a.x4 = a.x3 + N * CG * K;
-    gran = bwd_granules(p->N);
+    const BwdWork wl{(size_t)p->N};
+    a.status = carve_at<int>(work, wl.status);
+    a.x1 = carve_at<u64>(work, wl.e1); a.x2 = carve_at<u64>(work, wl.e2); a.x3 = carve_at<u64>(work, wl.e3a); a.x4 = carve_at<u64>(work, wl.e3b);
+    used = wl.bytes;
   }
-  { const int zrc = ns_zero_async(work, (256 + gran * sizeof(u64) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  { const int zrc = ns_zero_async(work, (used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)taco1_attn_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1045,11 +1103,11 @@ static int taco1_run(const ns_taco1_attn_params* p, void* work, hipStream_t s, i
   }
   const dim3 grid((unsigned)(p->N * CG)), block(CT);
   if (!backward) {
-    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_fwd_kernel<bf16_t>, grid, block, FWD_LDS, s, a);
-    else hipLaunchKernelGGL(taco1_attn_fwd_kernel<float>, grid, block, FWD_LDS, s, a);
+    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_fwd_kernel<bf16_t>, grid, block, FwdLds().bytes, s, a);
+    else hipLaunchKernelGGL(taco1_attn_fwd_kernel<float>, grid, block, FwdLds().bytes, s, a);
   } else {
-    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_bwd_kernel<bf16_t>, grid, block, BWD_LDS, s, a);
-    else hipLaunchKernelGGL(taco1_attn_bwd_kernel<float>, grid, block, BWD_LDS, s, a);
+    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_bwd_kernel<bf16_t>, grid, block, BwdLds().bytes, s, a);
+    else hipLaunchKernelGGL(taco1_attn_bwd_kernel<float>, grid, block, BwdLds().bytes, s, a);
   }
   NS_CHECK_LAUNCH(name);
   return NS_OK;
@@ -1088,7 +1146,7 @@ extern "C" int ns_taco1_decode_supported(const ns_taco1_decode_params* q) {
 
 extern "C" size_t ns_taco1_decode_work_bytes(const ns_taco1_decode_params* q) {
   if (!q) return 0;
-  return 256 + decode_granules(q->att.N) * sizeof(u64);
+  return DecWork{(size_t)q->att.N}.bytes;
 }
 
 extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_stream_t s_) {
@@ -1099,23 +1157,23 @@ extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_s
   const ns_taco1_attn_params* p = &q->att;
   DArgs d = {};
   d.att.p = *p;
-  d.att.status = (int*)work;
-  const size_t N = (size_t)p->N;
-  u64* x = (u64*)((char*)work + 256);
-  d.att.x1 = x; d.att.x2 = d.att.x1 + N * CG * X1N; d.att.x3 = d.att.x2 + N * CG * X2N; d.att.x4 = nullptr;
-  d.att.f1x = d.att.x3 + N * CG * X3N;
-  d.att.alx = d.att.f1x + N * DNW * D1;
+  const DecWork wl{(size_t)p->N};
+  d.att.status = carve_at<int>(work, wl.att.status);
+  d.att.x1 = carve_at<u64>(work, wl.att.x1); d.att.x2 = carve_at<u64>(work, wl.att.x2); d.att.x3 = carve_at<u64>(work, wl.att.x3);
+  d.att.x4 = nullptr;
+  d.att.f1x = carve_at<u64>(work, wl.f1x);
+  d.att.alx = carve_at<u64>(work, wl.alx);
   d.att.bpf = q->bpf;
   d.att.nwd = DNW;
-  d.xa = d.att.alx + N * 256;
-  d.xb = d.xa + N * DD; d.xc = d.xb + N * DD; d.xd = d.xc + 2 * N * DD; d.xe = d.xd + N * DD;
+  d.xa = carve_at<u64>(work, wl.xa); d.xb = carve_at<u64>(work, wl.xb); d.xc = carve_at<u64>(work, wl.xc);
+  d.xd = carve_at<u64>(work, wl.xd); d.xe = carve_at<u64>(work, wl.xe);
   d.values = q->values;
   d.wp = q->w_proj; d.bp = q->b_proj;
   d.wg1 = q->wg_1; d.bg1 = q->bg_1; d.wc1 = q->wc_1; d.bc1 = q->bc_1;
   d.wg2 = q->wg_2; d.bg2 = q->bg_2; d.wc2 = q->wc_2; d.bc2 = q->bc_2;
   d.wpf = q->wpf; d.y2 = q->y2;
   // the whole work area once, status word included: the launches below share that word and none of them clears it
-  { const int zrc = ns_zero_async(work, (256 + decode_granules(p->N) * sizeof(u64) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  { const int zrc = ns_zero_async(work, (wl.bytes + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)taco1_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -36,6 +36,7 @@
 //                    B2(s); dzgimg written in phase 2 (behind B1(s)), read behind B2(s), reads complete at B1(s+1);
 //             st[b]  prefetchers write slot s+1 between B1(s) and B2(s); read in phase 1 of slot s+1 behind B2(s).
 #include "exchange.h"
+#include "carve.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -262,17 +263,29 @@ __device__ __forceinline__ bool gather_sel(int dbg, const u64* src, unsigned tag
 }
 
 // ===================================================================================================== forward
+template <int H, int P>
+struct GruFwdLds {                                    // dynamic LDS of gru_fwd_kernel<H, P, *>
+  using C = GCfg<H>;
+  static constexpr int NPL = P == 3 ? 2 : 1, PS = 16 * (H + 8);
+  LdsCarve c = {};
+  int himg = c.take<bf16_t>(NPL * PS);                // [NPL][16][H] the state, swizzled
+  int rhimg = c.take<bf16_t>(NPL * PS);               // [NPL][16][H] r * h
+  int xs = c.take<float>(C::NBUF * C::XS_F);          // [NBUF][XS_F] stage, filled by LDS-DMA
+  int pbuf = c.take<float>(C::KSPLIT == 2 ? C::GW * 64 * 4 : 0);   // [C::GW][64][4] (K split)
+  int abortf = c.take<int>(4);                        // the abort flag in a 16-byte slot
+  int bytes = c.off;
+};
 template <int H, int P, typename T, bool TRACE = false>
 __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs a) {
   using C = GCfg<H>;
   constexpr int G = C::G, U = C::U, NB = C::NB, KSPLIT = C::KSPLIT, KSW = C::KSW, NR = C::NR, XS_F = C::XS_F, SECF = C::SECF;
   constexpr int NPL = P == 3 ? 2 : 1, PS = 16 * (H + 8);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* himg = (bf16_t*)smem;                       // [NPL][16][H] the state, swizzled
-  bf16_t* rhimg = himg + NPL * PS;                    // [NPL][16][H] r * h
-  float* xs = (float*)(rhimg + NPL * PS);             // [NBUF][XS_F] stage, filled by LDS-DMA
-  float* pbuf = xs + C::NBUF * XS_F;                  // [C::GW][64][4] (K split)
-  int* abortf = (int*)(pbuf + (KSPLIT == 2 ? C::GW * 64 * 4 : 0));
+  constexpr GruFwdLds<H, P> lay;
+  static_assert(carve_aligned(lay.xs, 16), "the LDS-DMA stage takes 16-byte writes");
+  bf16_t* himg = carve_at<bf16_t>(smem, lay.himg); bf16_t* rhimg = carve_at<bf16_t>(smem, lay.rhimg);
+  float* xs = carve_at<float>(smem, lay.xs); float* pbuf = carve_at<float>(smem, lay.pbuf);
+  int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int chain = blockIdx.x / G, g = blockIdx.x % G;
@@ -475,18 +488,32 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
 //   carry' += [dzr | dzu] . Wg_h^T
 // Two dependent products again; the weights are rows of the ORIGINAL kernels (A[row = unit k][j] = W[k][j]).
 template <int H, int P, typename T>
+struct GruBwdLds {                                    // dynamic LDS of gru_bwd_kernel<H, P, T>
+  using C = GCfg<H>;
+  // backward slot: r | u | c | dh sections (fp32) + h_prev in the history's own type (bf16: half a section)
+  static constexpr int HPF = sizeof(T) == 4 ? C::SECF : C::SECF / 2, ST_F = 4 * C::SECF + HPF;
+  static constexpr int NPL = P == 3 ? 2 : 1, PSC = 16 * (H + 8), PSG = 16 * (2 * H + 8);
+  LdsCarve c = {};
+  int dzcimg = c.take<bf16_t>(NPL * PSC);             // [NPL][16][H]
+  int dzgimg = c.take<bf16_t>(NPL * PSG);             // [NPL][16][2H]
+  int st = c.take<float>(C::NBUF * ST_F);             // [NBUF][ST_F] stage, filled by LDS-DMA
+  int pbuf = c.take<float>(C::KSPLIT == 2 ? C::GW * 64 * 2 : 0);   // [C::GW][64][2] (K split)
+  int abortf = c.take<int>(4);                        // the abort flag in a 16-byte slot
+  int bytes = c.off;
+};
+template <int H, int P, typename T>
 __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs a) {
   using C = GCfg<H>;
+  using Lds = GruBwdLds<H, P, T>;
   constexpr int G = C::G, U = C::U, NB = C::NB, KSPLIT = C::KSPLIT, KSW = C::KSW, NR = C::NR, SECF = C::SECF;
-  // backward slot: r | u | c | dh sections (fp32) + h_prev in the history's own type (bf16: half a section)
-  constexpr int HPF = sizeof(T) == 4 ? SECF : SECF / 2, ST_F = 4 * SECF + HPF, NI = ST_F / 256, NIW = NI / 2;
+  constexpr int HPF = Lds::HPF, ST_F = Lds::ST_F, NI = ST_F / 256, NIW = NI / 2;
   constexpr int NPL = P == 3 ? 2 : 1, PSC = 16 * (H + 8), PSG = 16 * (2 * H + 8);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* dzcimg = (bf16_t*)smem;                     // [NPL][16][H]
-  bf16_t* dzgimg = dzcimg + NPL * PSC;                // [NPL][16][2H]
-  float* st = (float*)(dzgimg + NPL * PSG);           // [NBUF][ST_F] stage, filled by LDS-DMA
-  float* pbuf = st + C::NBUF * ST_F;                  // [C::GW][64][2] (K split)
-  int* abortf = (int*)(pbuf + (KSPLIT == 2 ? C::GW * 64 * 2 : 0));
+  constexpr Lds lay;
+  static_assert(carve_aligned(lay.st, 16), "the LDS-DMA stage takes 16-byte writes");
+  bf16_t* dzcimg = carve_at<bf16_t>(smem, lay.dzcimg); bf16_t* dzgimg = carve_at<bf16_t>(smem, lay.dzgimg);
+  float* st = carve_at<float>(smem, lay.st); float* pbuf = carve_at<float>(smem, lay.pbuf);
+  int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int chain = blockIdx.x / G, g = blockIdx.x % G;
@@ -693,17 +720,6 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-template <int H> size_t fwd_lds(int P) {
-  using C = GCfg<H>;
-  const int npl = P == 3 ? 2 : 1;
-  return (size_t)2 * npl * 16 * (H + 8) * 2 + sizeof(float) * C::NBUF * C::XS_F + (C::KSPLIT == 2 ? sizeof(float) * C::GW * 64 * 4 : 0) + 16;
-}
-template <int H> size_t bwd_lds(int P, bool bf16_hist) {
-  using C = GCfg<H>;
-  const int npl = P == 3 ? 2 : 1;
-  const size_t st_f = 4 * C::SECF + (bf16_hist ? C::SECF / 2 : C::SECF);
-  return (size_t)npl * 16 * (3 * H + 16) * 2 + sizeof(float) * C::NBUF * st_f + (C::KSPLIT == 2 ? sizeof(float) * C::GW * 64 * 2 : 0) + 16;
-}
 
 int passes_of(const ns_gru_seq_params* p) { return p->dtype == NS_BF16 ? 1 : p->f32_passes; }
 
@@ -736,10 +752,19 @@ bool one_ok(const ns_gru_seq_params* p, int backward) {
   return true;
 }
 
-size_t xbytes(const ns_gru_seq_params* p, int ndir) {
-  const size_t chains = (size_t)ndir * ((p->N + 15) / 16);
-  return p->H == 256 ? chains * 3 * 16 * (size_t)p->H * sizeof(u64) : 0;
-}
+struct GruWork {                                      // work area of ns_gru_seq_fwd / _bwd for ndir directions
+  size_t N, H, ndir;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);                  // the status word in a block of its own
+  // per chain [3][16][H] granules, H = 256 only (one workgroup per chain exchanges nothing): r * h | h forward,
+  // dzc | dzr | dzu backward - the forward form is sized like the backward one
+  size_t xbuf = c.take<u64>(H == 256 ? ndir * ((N + 15) / 16) * 3 * 16 * H : 0);
+  size_t used = c.off;                                // what a launch clears
+  size_t trace = c.take<long long>(16 * 8);           // NS_GRU_TRACE sums
+  size_t bytes = c.off;
+};
+// one direction's launch leaves the trace area where two directions' has it: the ABI size is the two-direction one
+GruWork work_abi(const ns_gru_seq_params* p) { return GruWork{(size_t)p->N, (size_t)p->H, 2}; }
 void fill(GruArgs& a, const ns_gru_seq_params* p0, const ns_gru_seq_params* p1, void* work) {
   const ns_gru_seq_params* pp[2] = {p0, p1 ? p1 : p0};
   a.N = p0->N; a.T = p0->T; a.P = p0->P; a.padl = p0->padl; a.ndir = p1 ? 2 : 1; a.nrg = (p0->N + 15) / 16;
@@ -753,10 +778,11 @@ void fill(GruArgs& a, const ns_gru_seq_params* p0, const ns_gru_seq_params* p1, 
     a.h[d] = p->h; a.ru[d] = p->ru; a.c[d] = p->c; a.rh[d] = p->rh; a.h_init[d] = p->h_init;
     a.dh[d] = p->dh; a.dzg[d] = p->dzg; a.dzc[d] = p->dzc; a.dh_init[d] = p->dh_init;
   }
-  a.status = (int*)work;
-  a.xbuf = (u64*)((char*)work + 256);
+  const GruWork wl = work_abi(p0);
+  a.status = carve_at<int>(work, wl.status);
+  a.xbuf = carve_at<u64>(work, wl.xbuf);
   const char* tr = getenv("NS_GRU_TRACE");
-  a.trace = (tr && atoi(tr)) ? (long long*)((char*)work + 256 + xbytes(p0, 2)) : nullptr;
+  a.trace = (tr && atoi(tr)) ? carve_at<long long>(work, wl.trace) : nullptr;
   const char* dbg = getenv("NS_GRU_DBG");
   a.dbg = dbg ? atoi(dbg) : 0;
 }
@@ -771,12 +797,13 @@ extern "C" int ns_gru_seq_supported(const ns_gru_seq_params* p0, const ns_gru_se
 
 extern "C" size_t ns_gru_seq_work_bytes(const ns_gru_seq_params* p) {
   if (!p) return 0;
-  return 256 + xbytes(p, 2) + 16 * 8 * sizeof(long long);      // status, exchange buffers, NS_GRU_TRACE sums
+  return work_abi(p).bytes;
 }
 
 template <int H, int P, typename T>
 static void launch_fwd(const GruArgs& a, hipStream_t s) {
   using C = GCfg<H>;
+  constexpr size_t lds = GruFwdLds<H, P>().bytes;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)gru_fwd_kernel<H, P, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -785,21 +812,22 @@ static void launch_fwd(const GruArgs& a, hipStream_t s) {
   if (a.trace) {       // diagnostic instantiation with in-kernel stamps (never the production path)
     if constexpr (P == 3) {
       (void)hipFuncSetAttribute((const void*)gru_fwd_kernel<H, P, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((gru_fwd_kernel<H, P, T, true>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::FW_WAVES * 64), fwd_lds<H>(P), s, a);
+      hipLaunchKernelGGL((gru_fwd_kernel<H, P, T, true>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::FW_WAVES * 64), lds, s, a);
       return;
     }
   }
-  hipLaunchKernelGGL((gru_fwd_kernel<H, P, T>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::FW_WAVES * 64), fwd_lds<H>(P), s, a);
+  hipLaunchKernelGGL((gru_fwd_kernel<H, P, T>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::FW_WAVES * 64), lds, s, a);
 }
 template <int H, int P, typename T>
 static void launch_bwd(const GruArgs& a, hipStream_t s) {
   using C = GCfg<H>;
+  constexpr size_t lds = GruBwdLds<H, P, T>().bytes;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)gru_bwd_kernel<H, P, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL((gru_bwd_kernel<H, P, T>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::BW_WAVES * 64), bwd_lds<H>(P, sizeof(T) == 2), s, a);
+  hipLaunchKernelGGL((gru_bwd_kernel<H, P, T>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::BW_WAVES * 64), lds, s, a);
 }
 
 static int gru_seq_run(const ns_gru_seq_params* p0, const ns_gru_seq_params* p1, void* work, hipStream_t s, int backward) {
@@ -809,7 +837,7 @@ static int gru_seq_run(const ns_gru_seq_params* p0, const ns_gru_seq_params* p1,
                "16-byte aligned operand rows and two directions of equal shape", name);
   GruArgs a = {};
   fill(a, p0, p1, work);
-  { const int zrc = ns_zero_async(work, (256 + xbytes(p0, a.ndir) + 15) & ~(size_t)15, s); if (zrc) return zrc; }
+  { const int zrc = ns_zero_async(work, (GruWork{(size_t)p0->N, (size_t)p0->H, (size_t)a.ndir}.used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   const int P = passes_of(p0);
 #define NS_GRU_LAUNCH(FN) \
   do { \

@@ -23,6 +23,7 @@
 // On a time-out (status 1 forward, 2 backward) every workgroup leaves; the single-role kernels read the status word
 // at the poll cadence too, so one expired wait ends the launch instead of costing every later step its own bound.
 #include "exchange.h"
+#include "carve.h"
 #include <stdlib.h>
 #include <stdint.h>
 
@@ -202,11 +203,18 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_fwd_kernel(LstmClusterA
 // dh[t] = dh_out[t] + dgates[next].Wh^T ; this workgroup owns 64 units (rows of Wh [H,4H]); the
 // contraction runs over all 4H gate gradients of the next step, gathered from the cluster.
 // Wave w holds the K-slice [w*4H/8, (w+1)*4H/8) of the 4 unit tiles in registers.
+struct ClusterBwdLds {                                         // dynamic LDS of lstm_cluster_bwd_kernel
+  int H;
+  LdsCarve c = {};
+  int dgs = c.take<bf16_t>(16 * 4 * H);                        // [16][4H] swizzled gathered gate grads
+  int red = c.take<float>(CW * 16 * 65);                       // [CW][16][65]
+  int bytes = c.off;
+};
 __global__ __launch_bounds__(CTHREADS) void lstm_cluster_bwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int CS = a.CS, H = a.H, K = 4 * a.H;
-  bf16_t* dgs = (bf16_t*)smem;                                 // [16][4H] swizzled gathered gate grads
-  float* red = (float*)(smem + (size_t)16 * K * 2);            // [CW][16][65]
+  const ClusterBwdLds lay{H};
+  bf16_t* dgs = carve_at<bf16_t>(smem, lay.dgs); float* red = carve_at<float>(smem, lay.red);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nrg = (a.N + 15) / 16;
   const int chain = blockIdx.x / CS, wgc = blockIdx.x % CS;
@@ -402,18 +410,29 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
 // waves (own block, in slot s-1 behind barrier(s-1)) in front of barrier(s), read behind it, refilled behind
 // barrier(s+1); xgs[(s+1)&1] is stored between barrier(s-1) and barrier(s), read between barrier(s) and barrier(s+1);
 // svs as above.
+struct Cluster2FwdLds {                                         // dynamic LDS of lstm_cluster2_fwd_kernel<H / 64, RPC>
+  int H, RPC;
+  // a slot's results for the saver wave: h bf16 [rows][64], c f32 [rows][64], gates bf16 [rows][4][64]  (2 + 4 + 8 KB at 16 rows)
+  static constexpr int sv_bytes(int rows) { return rows * 64 * 2 + rows * 64 * 4 + rows * 4 * 64 * 2; }
+  LdsCarve c = {};
+  int hs = c.take<bf16_t>(2 * 16 * H);                          // [2][16][H] swizzled
+  int xgs = c.take<float>(2 * 16 * XG_LD);                      // [2][16][XG_LD]: row, gate * 64 + unit
+  int svs = c.take<char>(2 * sv_bytes(RPC));                    // [2][SV_BYTES]
+  int abortf = c.take<int>(8);                                  // [3] in a 32-byte slot
+  int slack = c.take<char>(2 * (sv_bytes(16) - sv_bytes(RPC))); // unused: the narrow forms ask for the 16-row size
+  int bytes = c.off;
+};
 template <int HB, int RPC>
 __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int H = HB * 64, KS = H / 32, CS = HB;
   static_assert(RPC == 16 || RPC == 8 || RPC == 4, "rows per chain");
   constexpr int GPD = XW * (4 * RPC) * 2;                       // granules per source workgroup and slot: [wave][g][row][2]
-  bf16_t* hs = (bf16_t*)smem;                                   // [2][16][H] swizzled
-  float* xgs = (float*)(smem + (size_t)2 * 16 * H * 2);         // [2][16][XG_LD]: row, gate * 64 + unit
-  // this slot's results for the saver wave: h bf16 [RPC][64], c f32 [RPC][64], gates bf16 [RPC][4][64]  (2 + 4 + 8 KB at 16 rows)
+  constexpr Cluster2FwdLds lay{H, RPC};
   constexpr int SV_H = RPC * 64 * 2, SV_C = RPC * 64 * 4, SV_G = RPC * 4 * 64 * 2, SV_BYTES = SV_H + SV_C + SV_G;
-  char* svs = (char*)(xgs + 2 * 16 * XG_LD);                    // [2][SV_BYTES]
-  int* abortf = (int*)(svs + 2 * SV_BYTES);                     // [2]
+  static_assert(SV_BYTES == Cluster2FwdLds::sv_bytes(RPC), "the saver image");
+  bf16_t* hs = carve_at<bf16_t>(smem, lay.hs); float* xgs = carve_at<float>(smem, lay.xgs);
+  char* svs = carve_at<char>(smem, lay.svs); int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nch = (a.N + RPC - 1) / RPC;                        // chains per direction
@@ -704,6 +723,19 @@ constexpr int X3W = 4, X3_POLL = 2, X3_UPW = 32;
 constexpr int X3_WAVES = X3W + X3_POLL + 2;          // compute, pollers, prefetcher, saver: 8 waves, two per SIMD
 constexpr int XG3_LD = 4 * X3_UPW + 4;
 
+struct Cluster3FwdLds {                                           // dynamic LDS of lstm_cluster3_fwd_kernel<H / 64, RPC>
+  int H, RPC;
+  // a slot's results for the saver: h f32 [rows][32], c f32 [rows][32], gates bf16 [rows][4][32], h bf16 [rows][32]  (9216 at 16 rows)
+  static constexpr int sv_bytes(int rows) { return rows * 32 * 4 + rows * 32 * 4 + rows * 4 * 32 * 2 + rows * 32 * 2; }
+  LdsCarve c = {};
+  int hsh = c.take<bf16_t>(2 * 16 * H);                           // [2][16][H] swizzled, high parts
+  int hsl = c.take<bf16_t>(2 * 16 * H);                           // [2][16][H] low parts
+  int xgs = c.take<float>(2 * 16 * XG3_LD);                       // [2][16][XG3_LD]: row, gate * 32 + unit
+  int svs = c.take<char>(2 * sv_bytes(RPC));                      // [2][SV_BYTES]
+  int abortf = c.take<int>(8);                                    // [2] in a 32-byte slot
+  int slack = c.take<char>(2 * (sv_bytes(16) - sv_bytes(RPC)));   // unused: the narrow forms ask for the 16-row size
+  int bytes = c.off;
+};
 template <int HB, int RPC>               // HB = H / 64, RPC = batch rows per chain
 __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -712,14 +744,13 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
   constexpr int CS = H / X3_UPW;                                   // workgroups per chain
   constexpr int PPG = GPC / (X3_POLL * 64);                        // granules per poller lane (H / 8)
   static_assert(GPC % (X3_POLL * 64) == 0, "poller coverage");
-  bf16_t* hsh = (bf16_t*)smem;                                    // [2][16][H] swizzled, high parts
-  bf16_t* hsl = hsh + 2 * 16 * H;                                 // [2][16][H] low parts
-  float* xgs = (float*)(hsl + 2 * 16 * H);                        // [2][16][XG3_LD]: row, gate * 32 + unit
-  // this slot's results for the saver: h f32 [RPC][32], c f32 [RPC][32], gates bf16 [RPC][4][32], h bf16 [RPC][32]
+  constexpr Cluster3FwdLds lay{H, RPC};
   constexpr int SV_H = RPC * 32 * 4, SV_C = RPC * 32 * 4, SV_G = RPC * 4 * 32 * 2, SV_HB = RPC * 32 * 2;
-  constexpr int SV_BYTES = SV_H + SV_C + SV_G + SV_HB;           // 9216 at 16 rows
-  char* svs = (char*)(xgs + 2 * 16 * XG3_LD);                     // [2][SV_BYTES]
-  int* abortf = (int*)(svs + 2 * SV_BYTES);                       // [2]
+  constexpr int SV_BYTES = SV_H + SV_C + SV_G + SV_HB;
+  static_assert(SV_BYTES == Cluster3FwdLds::sv_bytes(RPC), "the saver image");
+  bf16_t* hsh = carve_at<bf16_t>(smem, lay.hsh); bf16_t* hsl = carve_at<bf16_t>(smem, lay.hsl);
+  float* xgs = carve_at<float>(smem, lay.xgs); char* svs = carve_at<char>(smem, lay.svs);
+  int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nch = (a.N + RPC - 1) / RPC;                          // chains per direction
@@ -972,20 +1003,28 @@ constexpr int DGI_LD = 256 + 8;          // bf16 per row of the operand image (r
 // slot behind - the saver between barrier(s) and barrier(s+1), rewritten behind barrier(s+1); c0, stage[0] and abortf
 // are written in front of the one ns_lds_barrier() every role passes ahead of slot 0, and read behind it).
 // Slot timings of the forms that led here: profiles/r03_cluster_bwd_trace.txt.
+struct Cluster2pBwdLds {                                              // dynamic LDS of lstm_cluster2p_bwd_kernel (every H, every RPC)
+  static constexpr int OPS_G = 16 * 4 * 64 * 2, OPS_F = 16 * 64 * 4;  // 8192, 4096
+  static constexpr int OPS_STAGE = OPS_G + 2 * OPS_F;                 // 16384
+  LdsCarve c = {};
+  int dgi = c.take<bf16_t>(2 * 16 * DGI_LD);                          // [2][16][DGI_LD] this slot's gate gradients (row, gate*64 + unit)
+  // The operand stage keeps the row-major layout of the global arrays (a transposing prefetcher store was measured:
+  // 96 scattered LDS writes per lane, slower than the compute lanes' scalar reads of this layout)
+  int ops = c.take<char>(2 * OPS_STAGE);                              // [2] stages of {gates bf16 [16][4][64], dh f32 [16][64], cprev f32 [16][64]}
+  int c0 = c.take<float>(16 * 64);                                    // [16][64] cell state at the first processed step
+  int abortf = c.take<int>(8);                                        // [1] in a 32-byte slot
+  int bytes = c.off;
+};
 template <int HB, int RPC>
 __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmClusterArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int H = HB * 64, K4 = 4 * H, CS = HB;
   static_assert(RPC == 16 || RPC == 8 || RPC == 4, "rows per chain");
   constexpr int GPD = RPC * 32;                                       // granules per (destination, source) block
-  bf16_t* dgi = (bf16_t*)smem;                                        // [2][16][DGI_LD] this slot's gate gradients (row, gate*64 + unit)
-  // The operand stage keeps the row-major layout of the global arrays (a transposing prefetcher store was measured:
-  // 96 scattered LDS writes per lane, slower than the compute lanes' scalar reads of this layout)
-  char* ops = (char*)(dgi + 2 * 16 * DGI_LD);                         // [2] stages of {gates bf16 [16][4][64], dh f32 [16][64], cprev f32 [16][64]}
-  constexpr int OPS_G = 16 * 4 * 64 * 2, OPS_F = 16 * 64 * 4;         // 8192, 4096
-  constexpr int OPS_STAGE = OPS_G + 2 * OPS_F;                        // 16384
-  float* c0 = (float*)(ops + 2 * OPS_STAGE);                          // [16][64] cell state at the first processed step
-  int* abortf = (int*)(c0 + 16 * 64);                                 // [1]
+  constexpr Cluster2pBwdLds lay;
+  constexpr int OPS_G = Cluster2pBwdLds::OPS_G, OPS_F = Cluster2pBwdLds::OPS_F, OPS_STAGE = Cluster2pBwdLds::OPS_STAGE;
+  bf16_t* dgi = carve_at<bf16_t>(smem, lay.dgi); char* ops = carve_at<char>(smem, lay.ops);
+  float* c0 = carve_at<float>(smem, lay.c0); int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nch = (a.N + RPC - 1) / RPC;                              // chains per direction
@@ -1274,9 +1313,21 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
 }
 
 // ------------------------------------------------------------------ C ABI
-// `work`: status word at 0, row-count word at 4, exchange granules at XBUF_OFF, the debug trace behind them.
+// `work`: status word at 0, row-count word at 4, the exchange granules, the debug trace behind them.
 constexpr size_t RESERVED_BYTES = 4096;          // unused; keeps the exchange and trace offsets where callers and tools expect them
-constexpr size_t XBUF_OFF = 256 + RESERVED_BYTES;
+constexpr size_t SPARE_ROW_GROUPS = 1;           // per direction, used by nothing; kept because the size is ABI
+struct ClusterWork {
+  size_t N, H;
+  size_t chains = 2 * ((N + 15) / 16 + SPARE_ROW_GROUPS);          // 16-row groups of both directions
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);               // the status and row-count words in a block of their own
+  size_t reserved = c.take<char>(RESERVED_BYTES);
+  // per chain [2][16][2H] granules: the single-role backward kernel's payload, the largest of the forms (the launchers
+  // compute what theirs uses; the narrow forms need no more than the 16-row sizing: chain_slots_ok, role_split_ok)
+  size_t xbuf = c.take<u64>(chains * 2 * 16 * (4 * H / 2));
+  size_t trace = c.take<long long>(512 * 8);       // NS_CLUSTER_DBG bit 16 timestamps
+  size_t bytes = c.off;
+};
 constexpr int MAX_CHAIN_SLOTS = 128;             // 16-row chain slots of the role-split forms, the spare one per direction included: N <= 1008
 static bool chain_slots_ok(int N) { return 2 * ((N + 15) / 16 + 1) <= MAX_CHAIN_SLOTS; }
 
@@ -1312,10 +1363,7 @@ extern "C" int ns_lstm_cluster_supported(const ns_lstm_seq_params* p0, const ns_
 
 extern "C" size_t ns_lstm_cluster_work_bytes(const ns_lstm_seq_params* p) {
   if (!p) return 0;
-  const size_t chains = 2 * (size_t)((p->N + 15) / 16 + 1);   // one spare row group per direction, never used (kept: the size is ABI)
-  // exchange buffers for the larger (backward) payload + status word + debug trace (the fp32 forward form's granules,
-  // one per unit, are half of that)
-  return chains * 2 * 16 * (size_t)(4 * p->H / 2) * sizeof(u64) + XBUF_OFF + 512 * 8 * sizeof(long long);
+  return ClusterWork{(size_t)p->N, (size_t)p->H}.bytes;
 }
 
 static void fill(LstmClusterArgs& a, const ns_lstm_seq_params* p0, const ns_lstm_seq_params* p1, void* work) {
@@ -1331,17 +1379,18 @@ static void fill(LstmClusterArgs& a, const ns_lstm_seq_params* p0, const ns_lstm
     a.hf[d] = (float*)pp[d]->h; a.hb[d] = (bf16_t*)pp[d]->h_bf16;
   }
   a.ld_hb = p0->ld_h_bf16;
-  a.status = (int*)work;
-  a.xbuf = (u64*)((char*)work + XBUF_OFF);
+  const ClusterWork wl{(size_t)a.N, (size_t)a.H};
+  a.status = carve_at<int>(work, wl.status);
+  a.xbuf = carve_at<u64>(work, wl.xbuf);
   const char* dbg = getenv("NS_CLUSTER_DBG");
   a.dbg = dbg ? atoi(dbg) : 0;
-  const size_t chains = 2 * (size_t)((a.N + 15) / 16 + 1);
-  a.trace = (long long*)((char*)work + XBUF_OFF + chains * 2 * 16 * (size_t)(4 * a.H / 2) * sizeof(u64));
+  a.trace = carve_at<long long>(work, wl.trace);
 }
 
 // Every launch zeroes the status and row-count words and the exchange granules it will use (tag 0 = nothing published).
 static int zero_work(void* work, size_t xbytes, hipStream_t s) {
-  return ns_zero_async(work, ((XBUF_OFF + xbytes) + 15) & ~(size_t)15, s);
+  constexpr size_t xbuf = ClusterWork{0, 0}.xbuf;  // (the offset depends on neither N nor H)
+  return ns_zero_async(work, ((xbuf + xbytes) + 15) & ~(size_t)15, s);
 }
 
 // The role-split kernels cover H <= 256 with 16-byte aligned operand rows; everything else the cluster path accepts
@@ -1413,7 +1462,7 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
     const int RPC = cluster_rows(a.N, a.H / X3_UPW), nch = (a.N + RPC - 1) / RPC;   // chains per direction
     const size_t xbytes = 2 * (size_t)nch * 2 * RPC * (size_t)a.H * sizeof(u64);
     { const int zrc = zero_work(work, xbytes, s); if (zrc) return zrc; }
-    const size_t lds3 = (size_t)2 * 2 * 16 * a.H * 2 + sizeof(float) * 2 * 16 * XG3_LD + 2 * 9216 + 32;
+    const size_t lds3 = Cluster3FwdLds{a.H, RPC}.bytes;
     static bool attr3 = false;
     if (!attr3) {
       for (const auto& widths : cluster3_fwd_forms)
@@ -1433,7 +1482,7 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
   const size_t xbytes = 2 * (size_t)nch * 2 * RPC * (size_t)(a.H / 2) * sizeof(u64);
   { const int zrc = zero_work(work, xbytes, s); if (zrc) return zrc; }
   if (split) {
-    const size_t lds2 = (size_t)2 * 16 * a.H * 2 + sizeof(float) * 2 * 16 * XG_LD + 2 * (2048 + 4096 + 8192) + 32;
+    const size_t lds2 = Cluster2FwdLds{a.H, RPC}.bytes;
     hipLaunchKernelGGL(role_split_form(cluster2_fwd_forms, a.H, RPC), dim3((unsigned)(2 * nch * a.CS)), dim3(FW_WAVES * 64),
                        lds2, s, a);
     NS_CHECK_LAUNCH("lstm_cluster2_fwd");
@@ -1460,7 +1509,7 @@ extern "C" int ns_lstm_cluster_bwd(const ns_lstm_seq_params* p0, const ns_lstm_s
   const size_t xbytes = 2 * (size_t)nch * 2 * (psum ? (size_t)a.CS * a.CS * RPC * 32 : 16 * (size_t)(4 * a.H / 2)) * sizeof(u64);
   { const int zrc = zero_work(work, xbytes, s); if (zrc) return zrc; }
   if (psum) {
-    const size_t ldsp = (size_t)2 * 16 * DGI_LD * 2 + 2 * 16384 + sizeof(float) * 16 * 64 + 32;
+    const size_t ldsp = Cluster2pBwdLds().bytes;
     hipLaunchKernelGGL(role_split_form(cluster2p_bwd_forms, a.H, RPC), dim3((unsigned)(2 * nch * a.CS)), dim3(BP_WAVES * 64),
                        ldsp, s, a);
     NS_CHECK_LAUNCH("lstm_cluster2p_bwd");
@@ -1471,7 +1520,7 @@ extern "C" int ns_lstm_cluster_bwd(const ns_lstm_seq_params* p0, const ns_lstm_s
     (void)hipFuncSetAttribute((const void*)lstm_cluster_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  const size_t lds = (size_t)16 * 4 * a.H * 2 + sizeof(float) * CW * 16 * 65;
+  const size_t lds = ClusterBwdLds{a.H}.bytes;
   hipLaunchKernelGGL(lstm_cluster_bwd_kernel, dim3((unsigned)(2 * nch * a.CS)), dim3(CTHREADS), lds, s, a);
   NS_CHECK_LAUNCH("lstm_cluster_bwd");
   return NS_OK;

@@ -47,6 +47,7 @@
 // (row groups x unit blocks, one workgroup per CU) must be resident at once: ns_lstm_wide_supported() refuses shapes
 // that do not fit.
 #include "exchange.h"
+#include "carve.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -407,20 +408,32 @@ constexpr int UPB = 32;                      // units per workgroup
 // one granule per tile (group g: row pair 2 (g & 1) + (g >> 1)) instead of groups 0 and 1 two each - 8 store
 // instructions per wave and step instead of 16, on a phase that is bound by instruction issue.  Same granules, same
 // addresses, same bits.  LANES = false is the form before that (NS_WIDE_LANES=0, read per call; the tests compare them).
+struct WideBwdLds {                          // dynamic LDS of lstm_wide_bwd_ps_kernel<*, NT, *>
+  int NT;
+  static constexpr int ITEMS = UPB * 4;      // (unit, row pair) items per (destination, source) block
+  static constexpr int LDW = 4 * UPB + 8;    // bf16 per row of the operand image
+  LdsCarve c = {};
+  int dgi = c.take<bf16_t>(16 * LDW);        // [16][LDW] the operand image, rows 8 .. 15 stay zero (LANES: unread)
+  int red = c.take<float>(PSW * ITEMS * 2);  // [PSW][ITEMS][2] the polled sums
+  int ownp = c.take<float>(ITEMS * 2);       // [ITEMS][2] the own block
+  int abortf = c.take<int>(4);               // [4] the abort flag
+  int wl = c.take<bf16x8>(PSW * NT * 64);    // [PSW * NT tiles][64 lanes] the last k-step's weight fragments
+  int bytes = c.off;
+};
 template <typename T, int NT, bool LANES>    // NT = destination tiles per product wave = H / 128
 __global__ __launch_bounds__(PST) void lstm_wide_bwd_ps_kernel(WideArgs a, u64* xbuf) {
   constexpr int TB = UPB / 16;               // 16-unit tiles per block
   constexpr int KO = 4 * UPB, KS = KO / 32;  // own gate columns, k-steps of the product
-  constexpr int ITEMS = UPB * 4;             // (unit, row pair) items per (destination, source) block
+  constexpr int ITEMS = WideBwdLds::ITEMS;
   constexpr int IPL = ITEMS / 64;            // items per polling lane
-  constexpr int LDW = KO + 8;                // bf16 per row of the operand image
+  constexpr int LDW = WideBwdLds::LDW;
   constexpr int KSR = KS - 1;                // k-steps of the weights kept in registers (the last one: LDS)
   extern __shared__ __attribute__((aligned(16))) char ps_smem[];
-  bf16_t* dgi = (bf16_t*)ps_smem;                               // [16][LDW], rows 8 .. 15 stay zero (LANES: unread)
-  float* red = (float*)(dgi + 16 * LDW);                        // [PSW][ITEMS][2]
-  float* ownp = red + PSW * ITEMS * 2;                          // [ITEMS][2]
-  int* abortf = (int*)(ownp + ITEMS * 2);                       // [4]
-  bf16x8* wl = (bf16x8*)(abortf + 4);                           // [PSW * NT tiles][64 lanes] the last k-step's fragments
+  constexpr WideBwdLds lay{NT};
+  static_assert(carve_aligned(lay.wl, 16), "the fragments are read as 16-byte vectors");
+  bf16_t* dgi = carve_at<bf16_t>(ps_smem, lay.dgi); float* red = carve_at<float>(ps_smem, lay.red);
+  float* ownp = carve_at<float>(ps_smem, lay.ownp); int* abortf = carve_at<int>(ps_smem, lay.abortf);
+  bf16x8* wl = carve_at<bf16x8>(ps_smem, lay.wl);
   const ns_lstm_seq_params& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = p.H, K = 4 * H, NUB = H / UPB;
@@ -684,20 +697,29 @@ size_t ps_exchange_bytes(const ns_lstm_seq_params* p) {
 }  // namespace
 
 extern "C" int ns_lstm_wide_supported(const ns_lstm_seq_params* p, int backward) { return wide_shape_ok(p, backward) ? 1 : 0; }
-// work: status word (256 bytes reserved), the NS_WIDE_TRACE timestamps, the 16-byte-aligned exchange area of the
-// backward kernel for every shape ns_lstm_wide_bwd can take (the call is not told the direction)
-static size_t wide_work_base(const ns_lstm_seq_params* p) {
+// The work area.  The call is not told the direction, so the one layout holds what either takes.  Two arrays are placed
+// by the ADDRESS, not the offset: xbuf at the next 16-byte boundary from its offset, xch at the next 256-byte one
+// (wide_at), and the slack in front of each pays for that.
+struct WideWork {
+  size_t xbuf_bytes, xch_bytes;
+  WorkCarve c = {};
+  size_t status = c.take<char>(256);                 // the status word in a block of its own: what a launch clears
+  size_t trace = c.take<char>(WIDE_TRACE_BYTES);     // the NS_WIDE_TRACE timestamps
+  size_t xbuf = c.take<char>(xbuf_bytes);            // the backward kernel's exchange area (ps_exchange_bytes), cleared per launch
+  size_t xbuf_slack = c.take<char>(64);              // room for xbuf's rounding (15 bytes would do)
+  size_t xch_slack = c.take<char>(xch_bytes ? 256 : 0);   // room for xch's rounding
+  size_t xch = c.take<char>(xch_bytes);              // the split forward form's exchange array: [N * P][H] (hi, lo) pairs
+  size_t bytes = c.off;
+};
+static WideWork wide_work(const ns_lstm_seq_params* p) {
+  // the exchange area for every shape ns_lstm_wide_bwd can take; the pairs with both planes given (the split forward form)
   const bool bwd_fits = (p->H == 256 || p->H == 512 || p->H == 1024) && (p->N + 15) / 16 * (p->H / 16) <= ns_device_cus();
-  return 256 + WIDE_TRACE_BYTES + (bwd_fits ? ps_exchange_bytes(p) : 0) + 64;
+  return WideWork{bwd_fits ? ps_exchange_bytes(p) : 0, (p->h_bf16 && p->h_lo_bf16) ? (size_t)p->N * p->P * p->H * 4 : 0};
 }
-// the split forward form's exchange array: behind everything else, at the next 256-byte boundary of the address
-static void* wide_xch(const ns_lstm_seq_params* p, void* work) {
-  return (void*)(((uintptr_t)work + wide_work_base(p) + 255) & ~(uintptr_t)255);
-}
+static void* wide_at(void* work, size_t off, uintptr_t align) { return (void*)(((uintptr_t)work + off + align - 1) & ~(align - 1)); }
 extern "C" size_t ns_lstm_wide_work_bytes(const ns_lstm_seq_params* p) {
   if (!p) return 0;
-  // with both planes given (the split forward form): + [N * P][H] (hi, lo) pairs
-  return wide_work_base(p) + ((p->h_bf16 && p->h_lo_bf16) ? 256 + (size_t)p->N * p->P * p->H * 4 : 0);
+  return wide_work(p).bytes;
 }
 
 template <typename T, int PASSES, bool SPLIT>
@@ -730,10 +752,11 @@ extern "C" int ns_lstm_wide_fwd(const ns_lstm_seq_params* p, void* work, ns_stre
     NS_CHECK_ARG((double)p->N * p->P * p->H * 4 < 2.0e9, "ns_lstm_wide_fwd: exchange array beyond a buffer resource");
   }
   WideArgs a;
-  a.p = *p; a.status = (int*)work; a.nub = p->H / 8;
-  a.xch = split ? wide_xch(p, work) : nullptr;
-  a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
-  int rc = ns_zero_async(work, 256, s);
+  const WideWork wl = wide_work(p);
+  a.p = *p; a.status = carve_at<int>(work, wl.status); a.nub = p->H / 8;
+  a.xch = split ? wide_at(work, wl.xch_slack, 256) : nullptr;
+  a.trace = getenv("NS_WIDE_TRACE") ? carve_at<long long>(work, wl.trace) : nullptr;
+  int rc = ns_zero_async(work, wl.trace, s);
   if (rc) return rc;
   const int grid = ((p->N + 15) / 16) * a.nub;
   if (p->dtype == NS_BF16) {
@@ -766,17 +789,17 @@ extern "C" int ns_lstm_wide_bwd(const ns_lstm_seq_params* p, void* work, ns_stre
   NS_CHECK_ARG(wide_shape_ok(p, 1), "ns_lstm_wide_bwd: unsupported (needs H in {256, 512, 1024}, row groups x H/16 <= 256, "
                "bf16, or fp32 with wh_bf16 + dgates_bf16 and f32_passes 1)");
   WideArgs a;
-  a.p = *p; a.status = (int*)work; a.nub = 0; a.xch = nullptr;
-  a.trace = getenv("NS_WIDE_TRACE") ? (long long*)((char*)work + 256) : nullptr;
-  int rc = ns_zero_async(work, 256, s);
+  const WideWork wl = wide_work(p);
+  a.p = *p; a.status = carve_at<int>(work, wl.status); a.nub = 0; a.xch = nullptr;
+  a.trace = getenv("NS_WIDE_TRACE") ? carve_at<long long>(work, wl.trace) : nullptr;
+  int rc = ns_zero_async(work, wl.trace, s);
   if (rc) return rc;
-  u64* xbuf = (u64*)(((uintptr_t)work + 256 + WIDE_TRACE_BYTES + 15) & ~(uintptr_t)15);
+  u64* xbuf = (u64*)wide_at(work, wl.xbuf, 16);
   rc = ns_zero_async(xbuf, ps_exchange_bytes(p), s);
   if (rc) return rc;
   const int grid = (p->N + 7) / 8 * (p->H / UPB);      // 8-row groups x unit blocks, one workgroup per CU
-  const int nt = p->H / 128, items = UPB * 4;
-  // the operand image, the polled sums + the own block, the abort flag, the last k-step's weight fragments
-  const size_t ldsb = (size_t)16 * (4 * UPB + 8) * 2 + sizeof(float) * (PSW * items * 2 + items * 2) + 16 + (size_t)PSW * nt * 64 * 16;
+  const int nt = p->H / 128;
+  const size_t ldsb = WideBwdLds{nt}.bytes;
   static bool attr = false;
   if (!attr) {
     for (const auto& lanes : wide_bwd_forms)

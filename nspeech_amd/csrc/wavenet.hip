@@ -10,6 +10,7 @@
 //   ns_wavenet_softmax_ce mean softmax cross-entropy against integer targets    (:479-502) and d/dlogits
 //   ns_wavenet_generate   incremental sample-by-sample generation (persistent)  (generate_wavenet.py:56-142)
 #include "exchange.h"
+#include "carve.h"
 
 // ------------------------------------------------------------------ input layer
 // x0[n,t,:] = W[0][ids[n,t-1]] + W[1][ids[n,t]]  for 1 <= t < T   (row t = 0 is written as zero)
@@ -309,18 +310,28 @@ __device__ __forceinline__ void gen_load(GenLayerW<W>& w, const ns_wavenet_gener
   }
 }
 
+struct GenLds {                                   // dynamic LDS of wn_generate_kernel
+  int R, Dc, S, Q;
+  LdsCarve c = {};
+  int xin = c.take<float>(2 * R);              // [2R]: x[t-d] | x[t]
+  int z = c.take<float>(2 * Dc);               // [2Dc]
+  int out = c.take<float>(Dc);                 // [Dc]
+  int part = c.take<float>(GEN_THREADS);       // [GEN_THREADS] partial sums of the layer products
+  int h0 = c.take<float>(S);                   // [S] relu(skip sum)
+  int h1 = c.take<float>(S);                   // [S]
+  int lg = c.take<float>((Q + 1) & ~1);        // [Q], rounded up to an even count
+  int ex = c.take<double>(Q);                  // [Q]; 8-byte aligned when Dc is even (the launcher checks)
+  int bytes = c.off;
+};
 template <typename W>
 __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p) {
   extern __shared__ float gsm[];
   const int R = p.R, Dc = p.Dc, S = p.S, Q = p.Q;
-  float* xin = gsm;                       // [2R]: x[t-d] | x[t]
-  float* z = xin + 2 * R;                 // [2Dc]
-  float* out = z + 2 * Dc;                // [Dc]
-  float* part = out + Dc;                 // [GEN_THREADS] partial sums of the layer products
-  float* h0 = part + GEN_THREADS;         // [S] relu(skip sum)
-  float* h1 = h0 + S;                     // [S]
-  float* lg = h1 + S;                     // [Q]
-  double* ex = (double*)(lg + ((Q + 1) & ~1));   // [Q]
+  const GenLds lay{R, Dc, S, Q};
+  float* xin = carve_at<float>(gsm, lay.xin); float* z = carve_at<float>(gsm, lay.z);
+  float* out = carve_at<float>(gsm, lay.out); float* part = carve_at<float>(gsm, lay.part);
+  float* h0 = carve_at<float>(gsm, lay.h0); float* h1 = carve_at<float>(gsm, lay.h1); float* lg = carve_at<float>(gsm, lay.lg);
+  double* ex = carve_at<double>(gsm, lay.ex);
   const int tid = threadIdx.x, b = blockIdx.x;
   const W* wb = (const W*)p.weights;
   int* ids = p.ids + (long)b * p.total;
@@ -519,17 +530,27 @@ __device__ __forceinline__ void gen_matvec8(const bf16_t* Wm, int K, int N, cons
   __syncthreads();
 }
 
+struct FastLds {                                  // dynamic LDS of wn_generate_fast_kernel<C>
+  int L, C, S, Q;
+  LdsCarve c = {};
+  int outs = c.take<float>(L * C);     // [L][C] gated outputs of this sample (skip path)
+  int h0 = c.take<float>(S);                   // [S]
+  int h1 = c.take<float>(S);                   // [S]
+  int lg = c.take<float>((Q + 1) & ~1);        // [Q], rounded up to an even count
+  int red = c.take<float>(16);                 // [16]
+  int part = c.take<float>(GEN_THREADS * 8);   // [GEN_THREADS * 8]: K-split partial sums of the big products
+  int ex = c.take<double>(Q);                  // [Q]; 8-byte aligned when L * C is even (the launcher checks)
+  int bytes = c.off;
+};
 template <int C>
 __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p) {
   extern __shared__ float gsm[];
   const int S = p.S, Q = p.Q, L = p.L;
-  float* outs = gsm;                       // [L][C] gated outputs of this sample (skip path)
-  float* h0 = outs + L * C;                // [S]
-  float* h1 = h0 + S;                      // [S]
-  float* lg = h1 + S;                      // [Q]
-  float* red = lg + ((Q + 1) & ~1);        // [16]
-  float* part = red + 16;                  // [GEN_THREADS * 8]: K-split partial sums of the big products
-  double* ex = (double*)(part + GEN_THREADS * 8);   // [Q]
+  const FastLds lay{L, C, S, Q};
+  float* outs = carve_at<float>(gsm, lay.outs); float* h0 = carve_at<float>(gsm, lay.h0);
+  float* h1 = carve_at<float>(gsm, lay.h1); float* lg = carve_at<float>(gsm, lay.lg);
+  float* red = carve_at<float>(gsm, lay.red); float* part = carve_at<float>(gsm, lay.part);
+  double* ex = carve_at<double>(gsm, lay.ex);
   __shared__ int dil[128];
   __shared__ long qoff[128];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
@@ -748,20 +769,31 @@ __device__ __forceinline__ bf16x8 mf_bits(uint4 w) {
 // 16 g + s read their channel's three values ahead of the layer's products: the two condition terms join zf / zg behind
 // the DPP gather, the dense bias goes back to lane 16 g on the row shifts that bring the gated outputs back.  COND =
 // false compiles to the kernel as it was.
+template <typename O = int>
+struct ChainLds {                                 // dynamic LDS of wn_generate_mfma_kernel<cond> (R = 32 channels)
+  O L, R, S, Q, cond;
+  CarveT<O> c = {};
+  O outs = c.template take<float>(L * R);         // [L][R] gated outputs of this sample
+  O xg = c.template take<float>(32);              // [32] operand gather line of the chain wave
+  O h0 = c.template take<float>(S);               // [S]
+  O h1 = c.template take<float>(S);               // [S]
+  O lg = c.template take<float>((Q + 1) & ~(O)1); // [Q], rounded up to an even count
+  O red = c.template take<float>(16);             // [16]
+  O part = c.template take<float>(GEN_THREADS * 8);   // [GEN_THREADS * 8]
+  O ex = c.template take<double>(Q);              // [Q]
+  O ctab = c.template take<float>(cond ? L * 96 : 0);   // COND: [L][3 * 32]
+  O bytes = c.off;
+};
 template <bool COND>
 __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p) {
   extern __shared__ float gsm[];
   constexpr int C = 32;
   const int S = p.S, Q = p.Q, L = p.L;
-  float* outs = gsm;                       // [L][C] gated outputs of this sample
-  float* xg = outs + L * C;                // [C] operand gather line of the chain wave
-  float* h0 = xg + C;                      // [S]
-  float* h1 = h0 + S;                      // [S]
-  float* lg = h1 + S;                      // [Q]
-  float* red = lg + ((Q + 1) & ~1);        // [16]
-  float* part = red + 16;                  // [GEN_THREADS * 8]
-  double* ex = (double*)(part + GEN_THREADS * 8);   // [Q]
-  float* ctab = (float*)(ex + Q);          // COND: [L][3 C]
+  const ChainLds<> lay{L, C, S, Q, COND};
+  float* outs = carve_at<float>(gsm, lay.outs); float* xg = carve_at<float>(gsm, lay.xg);
+  float* h0 = carve_at<float>(gsm, lay.h0); float* h1 = carve_at<float>(gsm, lay.h1); float* lg = carve_at<float>(gsm, lay.lg);
+  float* red = carve_at<float>(gsm, lay.red); float* part = carve_at<float>(gsm, lay.part);
+  double* ex = carve_at<double>(gsm, lay.ex); float* ctab = carve_at<float>(gsm, lay.ctab);
   __shared__ int dil[128];
   __shared__ long qoff[128];
   __shared__ int chain_pos;
@@ -1084,13 +1116,9 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   }
 }
 
-static size_t wn_chain_lds_bytes(int L, int R, int S, int Q, int cond) {
-  const size_t lds2 = sizeof(float) * ((size_t)L * R + 2 * S + ((Q + 1) & ~1) + 16 + GEN_THREADS * 8) + sizeof(double) * Q;
-  return lds2 + sizeof(float) * 32 + (cond ? sizeof(float) * (size_t)L * 96 : 0);      // + the gather line, + ctab [L][3 * 32]
-}
 constexpr size_t WN_CHAIN_LDS_MAX = 60 * 1024;
 extern "C" int ns_wavenet_chain_fits(int L, int R, int S, int Q, int cond) {
-  return L > 0 && R > 0 && S > 0 && Q > 0 && wn_chain_lds_bytes(L, R, S, Q, cond) <= WN_CHAIN_LDS_MAX;
+  return L > 0 && R > 0 && S > 0 && Q > 0 && ChainLds<size_t>{(size_t)L, (size_t)R, (size_t)S, (size_t)Q, (size_t)cond}.bytes <= WN_CHAIN_LDS_MAX;
 }
 
 extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t s) {
@@ -1099,7 +1127,8 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
   NS_CHECK_ARG(GEN_THREADS % (2 * p->Dc) == 0 && GEN_THREADS % p->R == 0 && 2 * p->R * 2 * p->Dc <= GEN_FG * GEN_THREADS &&
                    p->Dc * p->R <= GEN_DE * GEN_THREADS && p->Dc <= GEN_SK && p->S <= GEN_THREADS && p->Q <= 1024,
                "ns_wavenet_generate: channel counts outside the kernel's register plan");
-  const size_t lds = sizeof(float) * (2 * p->R + 3 * p->Dc + GEN_THREADS + 2 * p->S + ((p->Q + 1) & ~1)) + sizeof(double) * p->Q;
+  const GenLds gl{p->R, p->Dc, p->S, p->Q};
+  const size_t lds = (size_t)gl.bytes;
   NS_CHECK_ARG(lds <= 60 * 1024, "ns_wavenet_generate: state does not fit in LDS");
   const bool full = p->cond || p->dense_bias || p->skip_bias || p->post1_bias || p->post2_bias;
   NS_CHECK_ARG(!full || (!p->fgT && !p->deT) || p->engine == 2,
@@ -1116,8 +1145,9 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
     NS_CHECK_ARG(p->w_dtype == NS_BF16 && p->R == p->Dc && (p->R == 32 || p->R == 16) && p->S % 8 == 0 && p->Q % 8 == 0 && p->S / 8 <= GEN_THREADS &&
                      GEN_THREADS % (p->S / 8) == 0 && GEN_THREADS % (p->Q / 8) == 0,
                  "ns_wavenet_generate: the single-wave chain needs bf16 weights and R == Dc in {16, 32}");
-    const size_t lds2 = sizeof(float) * ((size_t)p->L * p->R + 2 * p->S + ((p->Q + 1) & ~1) + 16 + GEN_THREADS * 8) + sizeof(double) * p->Q;
-    NS_CHECK_ARG(lds2 <= 60 * 1024 && ((size_t)p->L * p->R) % 2 == 0, "ns_wavenet_generate: state does not fit in LDS");
+    const FastLds fl{p->L, p->R, p->S, p->Q};
+    const size_t lds2 = (size_t)fl.bytes;
+    NS_CHECK_ARG(lds2 <= 60 * 1024 && carve_aligned(fl.ex, sizeof(double)), "ns_wavenet_generate: state does not fit in LDS");
     NS_CHECK_ARG(p->engine == 3 || !p->post_x, "ns_wavenet_generate: post_x belongs to engine 3");
     if (p->engine == 2 || p->engine == 3) {
       NS_CHECK_ARG(p->R == 32 && p->S / 8 <= 64 && p->S * 7 <= GEN_THREADS * 8, "ns_wavenet_generate: the MFMA chain needs R == Dc == 32, S <= 512");
@@ -1138,9 +1168,9 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
         hipLaunchKernelGGL(wn_post_helper_kernel, dim3(p->B * NS_WN_HELPERS), dim3(512), 0, (hipStream_t)p->helper_stream, *p);
         NS_CHECK_LAUNCH("wavenet_post_helper");
       }
-      const size_t lds3 = wn_chain_lds_bytes(p->L, p->R, p->S, p->Q, 0);
+      const size_t lds3 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 0}.bytes;
       if (full) {                            // + the condition row and the dense biases
-        const size_t lds4 = wn_chain_lds_bytes(p->L, p->R, p->S, p->Q, 1);
+        const size_t lds4 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 1}.bytes;
         NS_CHECK_ARG(lds4 <= WN_CHAIN_LDS_MAX, "ns_wavenet_generate: state and condition row do not fit in LDS (ns_wavenet_chain_fits)");
         hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p);
         NS_CHECK_LAUNCH("wavenet_generate_mfma_cond");
@@ -1155,6 +1185,8 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
     NS_CHECK_LAUNCH("wavenet_generate_fast");
     return NS_OK;
   }
+  NS_CHECK_ARG(carve_aligned(gl.ex, sizeof(double)),
+               "ns_wavenet_generate: the per-layer kernel needs an even Dc (its float64 row follows 3 Dc floats in LDS)");
   if (p->w_dtype == NS_BF16) hipLaunchKernelGGL(wn_generate_kernel<bf16_t>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p);
   else hipLaunchKernelGGL(wn_generate_kernel<float>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p);
   NS_CHECK_LAUNCH("wavenet_generate");

@@ -58,6 +58,13 @@ def test_the_valu_chain_still_takes_no_condition():
     assert rc == ERR_ARG and "conditions / biases" in msg
 
 
+def test_the_per_layer_kernel_refuses_an_odd_dc():
+    # Dc = 1 passes every divisibility check (512 % (2 Dc) == 0), but the kernel's float64 row follows 3 Dc floats in LDS:
+    # an odd Dc leaves it 4 bytes off an 8-byte boundary
+    rc, msg = _refused(_params(Dc=1, R=32))
+    assert rc == ERR_ARG and "even Dc" in msg
+
+
 def test_chain_fits_follows_the_layer_count():
     lib = _lib.lib()
     # shipped widths: 50 layers fit with and without a condition row; 74 only without (L * 384 bytes more)
