@@ -135,14 +135,26 @@ int ns_gemm(const ns_gemm_params* p, ns_stream_t stream);
 size_t ns_gemm_stat_part_floats(int M, int N);
 size_t ns_gemm_splitk_work_bytes(int M, int N, int split_k);
 size_t ns_gemm_splitk_counters(int M, int N);
-/* name of the kernel the calling thread's last ns_gemm call launched (e.g. "gemm_mfma_f32_kernel<0, 1, 3>"): lets a
- * caller attribute its own event timings to the names a profiler reports. */
+/* name of the kernel the calling thread's last ns_gemm call launched, with every template argument as a profiler prints
+ * it (e.g. "gemm_mfma_f32_kernel<0, 1, 3, true, 128>", "gemm_x256_kernel<1>", "gemm_generic_kernel"): lets a caller
+ * attribute its own event timings to the names a profiler reports.  A product on the direct-to-LDS loop reports the name
+ * of the staged kernel of the same tile form; ns_gemm_last_loop tells the two apart. */
 const char* ns_gemm_last_kernel(void);
 /* K loop of the calling thread's last ns_gemm / ns_gemm_group launch: "dma" = operand tiles loaded straight into LDS (the
  * bf16 products with both operands k-slow on the 128-tile kernel, and the grouped launch when every bf16 product of it
  * qualifies), "staged" = through registers.  NS_GEMM_DMA = 0 in the environment, read per call, keeps every product on
  * the staged loop; the results are bit-identical. */
 const char* ns_gemm_last_loop(void);
+/* What ns_gemm would launch for *p, without launching: the host part alone (version 103).  The same checks, defaults and
+ * kernel choice as ns_gemm - the two share the code - with the same return codes and error texts; no operand is
+ * dereferenced and no device is needed, so made-up addresses of the right alignment serve.  kernel / loop: what
+ * ns_gemm_last_kernel / ns_gemm_last_loop report after the launch (static strings); an empty product (M or N = 0)
+ * gives NS_OK and kernel = NULL.  The environment switches are read as ns_gemm reads them. */
+typedef struct {
+  const char* kernel; const char* loop;
+  int grid_x, grid_y, grid_z, block, lds_bytes, stat_slots;
+} ns_gemm_plan_info;
+int ns_gemm_plan(const ns_gemm_params* p, ns_gemm_plan_info* out);
 
 
 /* ------------------------------------------------------------------ element-wise / reductions */

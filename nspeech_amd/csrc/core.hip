@@ -23,7 +23,7 @@ int ns_device_cus() {
   return cached[dev];
 }
 
-extern "C" int ns_version(void) { return 102; }
+extern "C" int ns_version(void) { return 103; }
 extern "C" const char* ns_device_arch(void) { return "gfx950"; }
 extern "C" const char* ns_last_error(void) { return g_err; }
 

@@ -1357,13 +1357,16 @@ static bool gemm_dma_ok(const ns_gemm_params& p) {
 // the 256-tile kernel: large k-contiguous bf16 products whose tiles fill the chip
 // the vector epilogue (x256_quadrant): 16-byte (fp32) / 8-byte (bf16) accesses of C and of every per-element epilogue
 // operand, four consecutive columns per lane, plain stores
-static bool vec_epilogue_ok(const ns_gemm_params& p) {
+static bool vec_operands_aligned(const ns_gemm_params& p) {
   auto al = [](const void* q, long ld, bool bf16) { return !q || ((((uintptr_t)q) & (bf16 ? 7 : 15)) == 0 && ld % 4 == 0); };
-  if (p.accumulate == 2 || p.split_k != 1 || p.N % 4 != 0) return false;
-  if (p.batch > 1 && p.batch_stride_c % 4 != 0) return false;
   return al(p.C, p.ldc, p.c_dtype == NS_BF16) && al(p.addend, p.ld_add, p.addend_dtype == NS_BF16) &&
          al(p.gate, p.ld_gate, p.dtype == NS_BF16) && al(p.stat_z, p.ld_stat_z, p.stat_z_dtype == NS_BF16) &&
          al(p.bias, 4, false) && al(p.stat_mean, 4, false) && al(p.stat_istd, 4, false) && al(p.stat_part, 4, false);
+}
+static bool vec_epilogue_ok(const ns_gemm_params& p) {
+  if (p.accumulate == 2 || p.split_k != 1 || p.N % 4 != 0) return false;
+  if (p.batch > 1 && p.batch_stride_c % 4 != 0) return false;
+  return vec_operands_aligned(p);
 }
 // 64 x 128 tiles instead of 128 x 128: when the 128-row tiling leaves CUs idle and halving the tile height adds workgroups
 static bool half_tiles_wanted(const ns_gemm_params& p, int tiles128) {
@@ -1377,12 +1380,7 @@ static bool x256_ok(const ns_gemm_params& p) {
   if (p.K % 64 != 0 || p.K < 128 || p.M < 1024 || p.N % 128 != 0) return false;
   if ((p.A_lo != nullptr) != (p.B_lo != nullptr)) return false;
   if (p.A_lo && (!aligned16(p.A_lo) || !aligned16(p.B_lo))) return false;
-  {   // the vector epilogue: 16-byte (fp32) / 8-byte (bf16) accesses of C and of every per-element epilogue operand
-    auto al = [](const void* q, long ld, bool bf16) { return !q || ((((uintptr_t)q) & (bf16 ? 7 : 15)) == 0 && ld % 4 == 0); };
-    if (!al(p.C, p.ldc, p.c_dtype == NS_BF16) || !al(p.addend, p.ld_add, p.addend_dtype == NS_BF16) ||
-        !al(p.gate, p.ld_gate, true) || !al(p.stat_z, p.ld_stat_z, p.stat_z_dtype == NS_BF16) || !al(p.bias, 4, false) ||
-        !al(p.stat_mean, 4, false) || !al(p.stat_istd, 4, false) || !al(p.stat_part, 4, false)) return false;
-  }
+  if (!vec_operands_aligned(p)) return false;      // (the gate is bf16 here, as A is; accumulate is not looked at)
   if ((double)p.M * (double)p.lda * 2.0 >= 4.0e9 || (double)p.N * (double)p.ldb * 2.0 >= 4.0e9) return false;
   if (getenv("NS_GEMM_NO256")) return false;
   // at least ~3/4 of the CUs busy, or the 128-tile kernel's finer grain wins
@@ -1393,8 +1391,6 @@ extern "C" size_t ns_gemm_stat_part_floats(int M, int N) {
   if (M <= 0 || N <= 0) return 0;
   return (size_t)2 * 4 * ceil_div(M, 256) * (size_t)N;     // the 256-tile kernel has the most slots per row
 }
-
-static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream);
 
 // the fixed-order second stage on its own (ns_bn_bwd's fallback reduction and its bias-gradient partials use it too)
 int ns_stats_finalize(const float* part, int slots, int N, float* s1, float* s2, hipStream_t stream) {
@@ -1410,33 +1406,6 @@ extern "C" size_t ns_gemm_splitk_work_bytes(int M, int N, int split_k) {
   return (size_t)split_k * ((size_t)ceil_div(M, 128) * 128) * ((size_t)ceil_div(N, 128) * 128) * sizeof(float);
 }
 extern "C" size_t ns_gemm_splitk_counters(int M, int N) { return (size_t)ceil_div(M, 64) * ceil_div(N, 64); }
-
-extern "C" int ns_gemm(const ns_gemm_params* pp, ns_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  NS_CHECK_ARG(pp != nullptr, "ns_gemm: null params");
-  ns_gemm_params p = *pp;
-  NS_CHECK_ARG(!p.col_sumsq || p.col_sum, "ns_gemm: col_sumsq needs col_sum");
-  NS_CHECK_ARG(!p.col_sum || p.stat_part, "ns_gemm: col_sum needs the stat_part scratch (ns_gemm_stat_part_floats)");
-  NS_CHECK_ARG(!p.stat_z || (p.col_sum && p.col_sumsq && p.stat_mean && p.stat_istd && p.accumulate != 2 && p.split_k <= 1),
-               "ns_gemm: stat_z needs col_sum, col_sumsq, stat_mean, stat_istd and a non-atomic store");
-  const ns_gemm_bn_params bn = p.bn;
-  if (bn.mean_out) {
-    NS_CHECK_ARG(p.col_sum && p.col_sumsq && !p.stat_z, "ns_gemm: bn needs col_sum and col_sumsq, and no stat_z");
-    NS_CHECK_ARG(bn.istd_out && (bn.training ? bn.count > 0 && !bn.moving_mean == !bn.moving_var
-                                             : bn.moving_mean && bn.moving_var),
-                 "ns_gemm: bn needs istd_out and, in training, count > 0 / otherwise the moving statistics");
-    NS_CHECK_ARG(p.M > 0 && p.N > 0, "ns_gemm: bn on an empty product");
-  }
-  p.bn = ns_gemm_bn_params{};      // the product kernels take the block by value and have no use for this part
-  if (!p.col_sum) p.stat_part = nullptr;
-  p.stat_slots = 0;
-  int rc = gemm_dispatch(p, stream);
-  if (rc || !p.stat_part || p.M == 0 || p.N == 0) return rc;
-  hipLaunchKernelGGL(gemm_stats_finalize_kernel, dim3(ceil_div(p.N, 32)), dim3(1024), 0, stream, p.stat_part, p.stat_slots,
-                     p.N, p.col_sum, p.col_sumsq, bn);
-  NS_CHECK_LAUNCH("gemm_stats_finalize");
-  return NS_OK;
-}
 
 // argument checks and defaults of a non-empty product (ns_gemm and every product of ns_gemm_group)
 static int gemm_normalize(ns_gemm_params& p) {
@@ -1464,11 +1433,74 @@ static int gemm_normalize(ns_gemm_params& p) {
   return NS_OK;
 }
 
-// Which kernel form a (normalised) product takes.  gemm_dispatch launches by it and the grouped launch's plan asks it
-// too, so the two cannot drift: a group item is a product this function sends to one of the two forms the group carries.
-enum { GF_SKINNY, GF_X256, GF_PRESPLIT_REFUSED, GF_MFMA, GF_SKINNY_F32, GF_F32, GF_GENERIC };
-struct gemm_form { int kind; bool vec, half, bk32; };
-static gemm_form gemm_classify(const ns_gemm_params& p) {
+// The kernel forms: every instantiation ns_gemm can launch, once.  gemm_classify picks an entry by its key and
+// gemm_dispatch launches what the entry says; the name is spelled from the template arguments of the same line.  A new
+// form is one line here and its condition in gemm_classify.
+typedef void (*gemm_kernel_fn)(ns_gemm_params);
+enum { GF_SKINNY, GF_X256, GF_MFMA, GF_MFMA_DMA, GF_SKINNY_F32, GF_F32, GF_GENERIC };
+struct gemm_entry {
+  int key;                                  // form_key(family, template arguments)
+  gemm_kernel_fn fn;
+  const char* name; const char* loop;       // ns_gemm_last_kernel, ns_gemm_last_loop
+  const char* family;                       // the launch check's error text
+  int block, lds;                           // threads per workgroup, dynamic LDS bytes
+};
+constexpr int form_key(int kind, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0) {
+  return ((((kind * 4 + a) * 4 + b) * 4 + c) * 128 + d) * 256 + e;
+}
+#define F_SKINNY(NT) {form_key(GF_SKINNY, NT), gemm_skinny_kernel<NT>, "gemm_skinny_kernel<" #NT ">", "staged", "gemm_skinny", SKW * 64, 0}
+#define F_X256(NSEG) {form_key(GF_X256, NSEG), gemm_x256_kernel<NSEG>, "gemm_x256_kernel<" #NSEG ">", "staged", "gemm_x256", 512, 2 * XBUF}
+#define F_MFMA(AM, BM_, VEC, BK, TM) {form_key(GF_MFMA, AM, BM_, VEC, BK, TM), gemm_mfma_kernel<AM, BM_, VEC, BK, TM>, \
+    "gemm_mfma_kernel<" #AM ", " #BM_ ", " #VEC ", " #BK ", " #TM ">", "staged", "gemm_mfma", 256, BK * 1024}
+// (the direct-to-LDS kernels report the staged kernel's name: callers group their timings by tile form, the loop tells them apart)
+#define F_DMA(VEC, BK, NST) {form_key(GF_MFMA_DMA, 1, 1, VEC, BK, 128), gemm_mfma_dma_kernel<VEC, BK, NST>, \
+    "gemm_mfma_kernel<1, 1, " #VEC ", " #BK ", 128>", "dma", "gemm_mfma", 256, NST * BK * 512}
+#define F_SKINNY_F32(PS, MT, NC) {form_key(GF_SKINNY_F32, PS, MT), gemm_skinny_f32_kernel<PS, MT, NC>, \
+    "gemm_skinny_f32_kernel<" #PS ", " #MT ", " #NC ">", "staged", "gemm_skinny_f32", SKW * 64, 0}
+#define F_F32(AM, BM_, PS, VEC, TM) {form_key(GF_F32, AM, BM_, VEC, PS, TM), gemm_mfma_f32_kernel<AM, BM_, PS, VEC, TM>, \
+    "gemm_mfma_f32_kernel<" #AM ", " #BM_ ", " #PS ", " #VEC ", " #TM ">", "staged", "gemm_mfma_f32", 256, 65536}
+#define F_F32_PASSES(PS) F_F32(0, 0, PS, true, 64), F_F32(0, 1, PS, true, 64),                                                            \
+    F_F32(0, 0, PS, false, 128), F_F32(0, 0, PS, true, 128), F_F32(0, 1, PS, false, 128), F_F32(0, 1, PS, true, 128),                     \
+    F_F32(1, 0, PS, false, 128), F_F32(1, 0, PS, true, 128), F_F32(1, 1, PS, false, 128), F_F32(1, 1, PS, true, 128)
+#define F_GENERIC(T, DT) {form_key(GF_GENERIC, DT), gemm_generic_kernel<T>, "gemm_generic_kernel", "staged", "gemm_generic", 256, 0}
+// (the lines stand in the order in which the kernels have always been instantiated: it is their order in the code object)
+static const gemm_entry GEMM_FORMS[] = {
+  F_SKINNY(2), F_SKINNY(1),
+  F_X256(1), F_X256(3), F_X256(2),
+  // buffers per ring, measured (profiles/wgrad_dma.txt): BK = 64 two - a third costs the second workgroup of a CU;
+  // BK = 32 three - three workgroups per CU still fit
+  F_DMA(false, 32, 3), F_DMA(true, 32, 3), F_DMA(false, 64, 2), F_DMA(true, 64, 2),
+  F_MFMA(0, 0, true, 64, 64), F_MFMA(0, 1, true, 64, 64),            // the half-height tiles
+  F_MFMA(1, 1, true, 32, 128), F_MFMA(1, 1, false, 32, 128),
+  F_MFMA(0, 0, false, 64, 128), F_MFMA(0, 0, true, 64, 128), F_MFMA(0, 1, false, 64, 128), F_MFMA(0, 1, true, 64, 128),
+  F_MFMA(1, 0, false, 64, 128), F_MFMA(1, 0, true, 64, 128), F_MFMA(1, 1, false, 64, 128), F_MFMA(1, 1, true, 64, 128),
+  F_SKINNY_F32(3, 1, 8), F_SKINNY_F32(1, 1, 8), F_SKINNY_F32(3, 2, 16), F_SKINNY_F32(1, 2, 16),
+  F_F32_PASSES(3), F_F32_PASSES(1),
+  F_GENERIC(float, NS_F32), F_GENERIC(bf16_t, NS_BF16),
+};
+#undef F_SKINNY
+#undef F_X256
+#undef F_MFMA
+#undef F_DMA
+#undef F_SKINNY_F32
+#undef F_F32
+#undef F_F32_PASSES
+#undef F_GENERIC
+static const gemm_entry* gemm_form(int key) {
+  for (const gemm_entry& e : GEMM_FORMS)
+    if (e.key == key) return &e;
+  fprintf(stderr, "ns_gemm: no kernel form with key %d\n", key);      // a condition of gemm_classify without its table line
+  abort();
+}
+
+// What a (normalised) product runs on: the single decision.  gemm_dispatch launches by it, ns_gemm_plan reports it and
+// the grouped launch's plan asks it too, so the three cannot drift.  entry == nullptr: pre-split operands on a shape the
+// 256-tile kernel does not take.
+struct gemm_plan { const gemm_entry* entry; dim3 grid; int stat_slots; };
+static gemm_plan gemm_classify(const ns_gemm_params& p) {
+  // the a_mode / b_mode ladder of the 128-tile kernels (0 0, 0 1, 1 0, anything else 1 1)
+  const int modes = p.a_mode == 0 && p.b_mode == 0 ? 0 : p.a_mode == 0 && p.b_mode == 1 ? 1 : p.a_mode == 1 && p.b_mode == 0 ? 2 : 3;
+  const int am = modes >> 1, bm = modes & 1;
   bool fast = (p.dtype == NS_BF16) && aligned16(p.A) && aligned16(p.B) && (p.lda % 8 == 0) &&
               (p.ldb % 8 == 0) && (p.b_seg_stride % 8 == 0) && (p.batch_stride_a % 8 == 0) &&
               (p.batch_stride_b % 8 == 0);
@@ -1478,12 +1510,26 @@ static gemm_form gemm_classify(const ns_gemm_params& p) {
     if (p.b_mode == 0) fast = fast && (p.K % 8 == 0); else fast = fast && (p.N % 8 == 0);
     if (p.b_seg_len > 0) fast = fast && (p.b_seg_len % GBK == 0);
   }
+  // (pre-split operands never reach the skinny kernel: it reads A and B only, and they are refused below)
   if (fast && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 &&
-      !p.col_sum && p.batch == 1 && !p.A_lo && !p.B_lo) return {GF_SKINNY, false, false, false};
-  if (fast && p.batch == 1 && x256_ok(p)) return {GF_X256, false, false, false};
-  if (p.A_lo || p.B_lo) return {GF_PRESPLIT_REFUSED, false, false, false};
+      !p.col_sum && p.batch == 1 && !p.A_lo && !p.B_lo) {
+    // enough workgroups to spread the weight stream over the chip
+    if (p.N >= 32 * 128) return {gemm_form(form_key(GF_SKINNY, 2)), dim3(ceil_div(p.N, 32)), 0};
+    return {gemm_form(form_key(GF_SKINNY, 1)), dim3(ceil_div(p.N, 16)), 0};
+  }
+  if (fast && p.batch == 1 && x256_ok(p)) {
+    const bool two = p.A_lo && p.f32_passes == 2;
+    return {gemm_form(form_key(GF_X256, two ? 2 : p.A_lo ? 3 : 1)), dim3(ceil_div(p.M, 256) * ceil_div(p.N, 256)),
+            4 * ceil_div(p.M, 256)};
+  }
+  if (p.A_lo || p.B_lo) return {nullptr, dim3(), 0};
+  // the 128-tile kernels' grid and statistics slots; 64-row tiles when `half`
+  const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
+  auto tiled = [&](int key, bool half) {
+    return gemm_plan{gemm_form(key), dim3(half ? ceil_div(p.M, 64) * ceil_div(p.N, GBN) : tiles, p.split_k, p.batch),
+                     half ? ceil_div(p.M, 64) : 2 * ceil_div(p.M, GBM)};
+  };
   if (fast) {
-    const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
     const bool vec = vec_epilogue_ok(p);
     // 64-row tiles when the 128-row ones leave CUs without a workgroup (<= 192 tiles) and A is k-contiguous
     const bool half = vec && p.a_mode == 0 && half_tiles_wanted(p, tiles);
@@ -1495,213 +1541,104 @@ static gemm_form gemm_classify(const ns_gemm_params& p) {
     // (profiles/r03_gemm_128_ablation.txt).  NS_GEMM_BK32 = 0 / 1 forces it off / on.
     const bool bk32w = bk32_env >= 0 ? bk32_env != 0 : (long)tiles * p.split_k * p.batch >= 600;
     const bool bk32 = !half && p.a_mode == 1 && p.b_mode == 1 && bk32w && (p.b_seg_len == 0 || p.b_seg_len % 32 == 0);
-    return {GF_MFMA, vec, half, bk32};
+    if (!half && p.a_mode == 1 && p.b_mode == 1 && gemm_dma_ok(p))
+      return tiled(form_key(GF_MFMA_DMA, 1, 1, vec, bk32 ? 32 : 64, 128), false);
+    if (half) return tiled(form_key(GF_MFMA, 0, p.b_mode == 0 ? 0 : 1, true, 64, 64), true);
+    if (bk32) return tiled(form_key(GF_MFMA, 1, 1, vec, 32, 128), false);
+    return tiled(form_key(GF_MFMA, am, bm, vec, 64, 128), false);
   }
   if (p.dtype == NS_F32 && p.f32_passes > 0) {
+    const int passes = p.f32_passes >= 3 ? 3 : 1;
     bool ok = aligned16(p.A) && aligned16(p.B) && (p.lda % 4 == 0) && (p.ldb % 4 == 0) && (p.b_seg_stride % 4 == 0) &&
               (p.batch_stride_a % 4 == 0) && (p.batch_stride_b % 4 == 0);
     if (p.a_mode == 0) ok = ok && (p.K % 4 == 0); else ok = ok && (p.M % 4 == 0);
     if (p.b_mode == 0) ok = ok && (p.K % 4 == 0); else ok = ok && (p.N % 4 == 0);
     if (p.b_seg_len > 0) ok = ok && (p.b_seg_len % FBK == 0);
     if (ok && p.M <= 32 && p.a_mode == 0 && p.b_mode == 0 && p.b_seg_len == 0 && p.split_k == 1 && !p.col_sum &&
-        p.K % 8 == 0 && p.lda % 4 == 0 && p.batch == 1) return {GF_SKINNY_F32, false, false, false};
+        p.K % 8 == 0 && p.lda % 4 == 0 && p.batch == 1) {
+      if (ceil_div(p.N, 16) <= 64)      // few column tiles: 16 rows x 8 columns per workgroup
+        return {gemm_form(form_key(GF_SKINNY_F32, passes, 1)), dim3(ceil_div(p.N, 8), ceil_div(p.M, 16)), 0};
+      return {gemm_form(form_key(GF_SKINNY_F32, passes, 2)), dim3(ceil_div(p.N, 16)), 0};
+    }
     if (ok) {
-      const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
       const bool vec = vec_epilogue_ok(p);
-      return {GF_F32, vec, vec && p.a_mode == 0 && half_tiles_wanted(p, tiles), false};
+      if (vec && p.a_mode == 0 && half_tiles_wanted(p, tiles))
+        return tiled(form_key(GF_F32, 0, p.b_mode == 0 ? 0 : 1, true, passes, 64), true);
+      return tiled(form_key(GF_F32, am, bm, vec, passes, 128), false);
     }
   }
-  return {GF_GENERIC, false, false, false};
+  return {gemm_form(form_key(GF_GENERIC, p.dtype == NS_F32 ? NS_F32 : NS_BF16)),
+          dim3(ceil_div(p.N, 64), ceil_div(p.M, 64), p.split_k * p.batch), ceil_div(p.M, 64)};
 }
 
-static int gemm_dispatch(ns_gemm_params& p, hipStream_t stream) {
+// ns_gemm up to its launch, and all of ns_gemm_plan: checks, defaults and the plan (entry == nullptr: an empty product).
+// `bn` gets the statistics tail, which the product kernels have no use for.
+static int gemm_prepare(const ns_gemm_params* pp, ns_gemm_params& p, ns_gemm_bn_params& bn, gemm_plan& plan) {
+  NS_CHECK_ARG(pp != nullptr, "ns_gemm: null params");
+  p = *pp;
+  NS_CHECK_ARG(!p.col_sumsq || p.col_sum, "ns_gemm: col_sumsq needs col_sum");
+  NS_CHECK_ARG(!p.col_sum || p.stat_part, "ns_gemm: col_sum needs the stat_part scratch (ns_gemm_stat_part_floats)");
+  NS_CHECK_ARG(!p.stat_z || (p.col_sum && p.col_sumsq && p.stat_mean && p.stat_istd && p.accumulate != 2 && p.split_k <= 1),
+               "ns_gemm: stat_z needs col_sum, col_sumsq, stat_mean, stat_istd and a non-atomic store");
+  bn = p.bn;
+  if (bn.mean_out) {
+    NS_CHECK_ARG(p.col_sum && p.col_sumsq && !p.stat_z, "ns_gemm: bn needs col_sum and col_sumsq, and no stat_z");
+    NS_CHECK_ARG(bn.istd_out && (bn.training ? bn.count > 0 && !bn.moving_mean == !bn.moving_var
+                                             : bn.moving_mean && bn.moving_var),
+                 "ns_gemm: bn needs istd_out and, in training, count > 0 / otherwise the moving statistics");
+    NS_CHECK_ARG(p.M > 0 && p.N > 0, "ns_gemm: bn on an empty product");
+  }
+  p.bn = ns_gemm_bn_params{};      // the product kernels take the block by value
+  if (!p.col_sum) p.stat_part = nullptr;
+  p.stat_slots = 0;
+  plan = gemm_plan{nullptr, dim3(), 0};
   NS_CHECK_ARG(p.M >= 0 && p.N >= 0 && p.K >= 0, "ns_gemm: negative dims");
   if (p.M == 0 || p.N == 0) return NS_OK;
   if (int rc = gemm_normalize(p)) return rc;
-  const gemm_form form = gemm_classify(p);
-  g_last_loop = "staged";
-  // (pre-split operands never come here: this kernel reads A and B only, and the check below refuses them)
-  if (form.kind == GF_SKINNY) {
-    // enough workgroups to spread the weight stream over the chip
-    g_last_kernel = p.N >= 32 * 128 ? "gemm_skinny_kernel<2>" : "gemm_skinny_kernel<1>";
-    if (p.N >= 32 * 128) hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3(ceil_div(p.N, 32)), dim3(SKW * 64), 0, stream, p);
-    else hipLaunchKernelGGL(gemm_skinny_kernel<1>, dim3(ceil_div(p.N, 16)), dim3(SKW * 64), 0, stream, p);
-    NS_CHECK_LAUNCH("gemm_skinny");
-    return NS_OK;
-  }
-  if (form.kind == GF_X256) {
-    const int tiles = ceil_div(p.M, 256) * ceil_div(p.N, 256);
-    const size_t lds = 2 * XBUF;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_x256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)gemm_x256_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)gemm_x256_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    p.stat_slots = 4 * ceil_div(p.M, 256);
-    const bool two = p.A_lo && p.f32_passes == 2;
-    g_last_kernel = p.A_lo ? (two ? "gemm_x256_kernel<2>" : "gemm_x256_kernel<3>") : "gemm_x256_kernel<1>";
-    if (two) hipLaunchKernelGGL(gemm_x256_kernel<2>, dim3(tiles), dim3(512), lds, stream, p);
-    else if (p.A_lo) hipLaunchKernelGGL(gemm_x256_kernel<3>, dim3(tiles), dim3(512), lds, stream, p);
-    else hipLaunchKernelGGL(gemm_x256_kernel<1>, dim3(tiles), dim3(512), lds, stream, p);
-    NS_CHECK_LAUNCH("gemm_x256");
-    return NS_OK;
-  }
-  NS_CHECK_ARG(form.kind != GF_PRESPLIT_REFUSED, "ns_gemm: pre-split operands (A_lo / B_lo) need the 256-tile path "
+  plan = gemm_classify(p);
+  NS_CHECK_ARG(plan.entry, "ns_gemm: pre-split operands (A_lo / B_lo) need the 256-tile path "
                "(bf16, a_mode 0, b_mode 0, K %% 64 == 0, M >= 1024, N %% 128 == 0, >= 96 tiles, no split_k)");
-  if (form.kind == GF_MFMA) {
-    const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
-    dim3 grid(tiles, p.split_k, p.batch);
-    const size_t lds = 65536;
-    p.stat_slots = 2 * ceil_div(p.M, GBM);
-    const bool vec = form.vec, half = form.half;
-    if (half) {
-      grid.x = ceil_div(p.M, 64) * ceil_div(p.N, GBN);
-      p.stat_slots = ceil_div(p.M, 64);
-    }
-#define LAUNCH_MFMA(AM, BM_)                                                                      \
-  do {                                                                                            \
-    static bool attr_set = false;                                                                 \
-    if (!attr_set) {                                                                              \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<AM, BM_, false>,                        \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<AM, BM_, true>,                         \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-      attr_set = true;                                                                            \
-    }                                                                                             \
-    g_last_kernel = vec ? "gemm_mfma_kernel<" #AM ", " #BM_ ", true, 64, 128>" : "gemm_mfma_kernel<" #AM ", " #BM_ ", false, 64, 128>";  \
-    if (vec) hipLaunchKernelGGL((gemm_mfma_kernel<AM, BM_, true>), grid, dim3(256), lds, stream, p);  \
-    else hipLaunchKernelGGL((gemm_mfma_kernel<AM, BM_, false>), grid, dim3(256), lds, stream, p);     \
-  } while (0)
-#define LAUNCH_MFMA_HALF(BM_)                                                                     \
-  do {                                                                                            \
-    static bool attr_set = false;                                                                 \
-    if (!attr_set) {                                                                              \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<0, BM_, true, 64, 64>,                  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-      attr_set = true;                                                                            \
-    }                                                                                             \
-    g_last_kernel = "gemm_mfma_kernel<0, " #BM_ ", true, 64, 64>";                                \
-    hipLaunchKernelGGL((gemm_mfma_kernel<0, BM_, true, 64, 64>), grid, dim3(256), lds, stream, p);    \
-  } while (0)
-#define LAUNCH_DMA(BK_, NST_)                                                                                  \
-  do {                                                                                                         \
-    static bool attr_set = false;                                                                              \
-    constexpr int lds_ = NST_ * BK_ * 512;                                                                     \
-    if (!attr_set) {                                                                                           \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_dma_kernel<false, BK_, NST_>,                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                             \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_dma_kernel<true, BK_, NST_>,                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                             \
-      attr_set = true;                                                                                         \
-    }                                                                                                          \
-    if (vec) hipLaunchKernelGGL((gemm_mfma_dma_kernel<true, BK_, NST_>), grid, dim3(256), lds_, stream, p);    \
-    else hipLaunchKernelGGL((gemm_mfma_dma_kernel<false, BK_, NST_>), grid, dim3(256), lds_, stream, p);       \
-  } while (0)
-    if (!half && p.a_mode == 1 && p.b_mode == 1 && gemm_dma_ok(p)) {
-      // (the names stay those of the staged kernels: callers group their timings by tile form, ns_gemm_last_loop tells the loop)
-      g_last_loop = "dma";
-      // buffers per ring, measured (profiles/wgrad_dma.txt): BK = 64 two - a third costs the second workgroup of a CU;
-      // BK = 32 three - three workgroups per CU still fit
-      if (form.bk32) {
-        g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 32, 128>" : "gemm_mfma_kernel<1, 1, false, 32, 128>";
-        LAUNCH_DMA(32, 3);
-      } else {
-        g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 64, 128>" : "gemm_mfma_kernel<1, 1, false, 64, 128>";
-        LAUNCH_DMA(64, 2);
-      }
-    } else if (half) {
-      if (p.b_mode == 0) LAUNCH_MFMA_HALF(0); else LAUNCH_MFMA_HALF(1);
-    } else if (form.bk32) {
-      g_last_kernel = vec ? "gemm_mfma_kernel<1, 1, true, 32, 128>" : "gemm_mfma_kernel<1, 1, false, 32, 128>";
-      if (vec) hipLaunchKernelGGL((gemm_mfma_kernel<1, 1, true, 32>), grid, dim3(256), 32768, stream, p);
-      else hipLaunchKernelGGL((gemm_mfma_kernel<1, 1, false, 32>), grid, dim3(256), 32768, stream, p);
-    } else if (p.a_mode == 0 && p.b_mode == 0) LAUNCH_MFMA(0, 0);
-    else if (p.a_mode == 0 && p.b_mode == 1) LAUNCH_MFMA(0, 1);
-    else if (p.a_mode == 1 && p.b_mode == 0) LAUNCH_MFMA(1, 0);
-    else LAUNCH_MFMA(1, 1);
-#undef LAUNCH_DMA
-#undef LAUNCH_MFMA_HALF
-#undef LAUNCH_MFMA
-    NS_CHECK_LAUNCH("gemm_mfma");
-    return NS_OK;
-  }
-  if (form.kind == GF_SKINNY_F32 || form.kind == GF_F32) {
-    const bool three = p.f32_passes >= 3;
-    if (form.kind == GF_SKINNY_F32) {
-      if (ceil_div(p.N, 16) <= 64) {      // few column tiles: 16 rows x 8 columns per workgroup
-        g_last_kernel = three ? "gemm_skinny_f32_kernel<3, 1, 8>" : "gemm_skinny_f32_kernel<1, 1, 8>";
-        const dim3 grid(ceil_div(p.N, 8), ceil_div(p.M, 16));
-        if (three) hipLaunchKernelGGL((gemm_skinny_f32_kernel<3, 1, 8>), grid, dim3(SKW * 64), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_skinny_f32_kernel<1, 1, 8>), grid, dim3(SKW * 64), 0, stream, p);
-      } else {
-        g_last_kernel = three ? "gemm_skinny_f32_kernel<3, 2, 16>" : "gemm_skinny_f32_kernel<1, 2, 16>";
-        if (three) hipLaunchKernelGGL((gemm_skinny_f32_kernel<3, 2, 16>), dim3(ceil_div(p.N, 16)), dim3(SKW * 64), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_skinny_f32_kernel<1, 2, 16>), dim3(ceil_div(p.N, 16)), dim3(SKW * 64), 0, stream, p);
-      }
-      NS_CHECK_LAUNCH("gemm_skinny_f32");
-      return NS_OK;
-    }
-    {
-      const int tiles = ceil_div(p.M, GBM) * ceil_div(p.N, GBN);
-      dim3 grid(tiles, p.split_k, p.batch);
-      const size_t lds = 65536;
-      p.stat_slots = 2 * ceil_div(p.M, GBM);
-      const bool vec = form.vec, half = form.half;
-      if (half) {
-        grid.x = ceil_div(p.M, 64) * ceil_div(p.N, GBN);
-        p.stat_slots = ceil_div(p.M, 64);
-      }
-#define LAUNCH_F32(AM, BM_, PS)                                                                     \
-  do {                                                                                              \
-    static bool attr_set = false;                                                                   \
-    if (!attr_set) {                                                                                \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_f32_kernel<AM, BM_, PS, false>,              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_f32_kernel<AM, BM_, PS, true>,               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-      attr_set = true;                                                                              \
-    }                                                                                               \
-    g_last_kernel = vec ? "gemm_mfma_f32_kernel<" #AM ", " #BM_ ", " #PS ", true, 128>"             \
-                        : "gemm_mfma_f32_kernel<" #AM ", " #BM_ ", " #PS ", false, 128>";           \
-    if (vec) hipLaunchKernelGGL((gemm_mfma_f32_kernel<AM, BM_, PS, true>), grid, dim3(256), lds, stream, p);   \
-    else hipLaunchKernelGGL((gemm_mfma_f32_kernel<AM, BM_, PS, false>), grid, dim3(256), lds, stream, p);      \
-  } while (0)
-#define LAUNCH_F32_HALF(BM_, PS)                                                                    \
-  do {                                                                                              \
-    static bool attr_set = false;                                                                   \
-    if (!attr_set) {                                                                                \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_f32_kernel<0, BM_, PS, true, 64>,            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-      attr_set = true;                                                                              \
-    }                                                                                               \
-    g_last_kernel = "gemm_mfma_f32_kernel<0, " #BM_ ", " #PS ", true, 64>";                         \
-    hipLaunchKernelGGL((gemm_mfma_f32_kernel<0, BM_, PS, true, 64>), grid, dim3(256), lds, stream, p);         \
-  } while (0)
-#define LAUNCH_F32_MODES(PS)                                                   \
-  do {                                                                         \
-    if (half && p.b_mode == 0) LAUNCH_F32_HALF(0, PS);                         \
-    else if (half) LAUNCH_F32_HALF(1, PS);                                     \
-    else if (p.a_mode == 0 && p.b_mode == 0) LAUNCH_F32(0, 0, PS);             \
-    else if (p.a_mode == 0 && p.b_mode == 1) LAUNCH_F32(0, 1, PS);             \
-    else if (p.a_mode == 1 && p.b_mode == 0) LAUNCH_F32(1, 0, PS);             \
-    else LAUNCH_F32(1, 1, PS);                                                 \
-  } while (0)
-      if (three) LAUNCH_F32_MODES(3); else LAUNCH_F32_MODES(1);
-#undef LAUNCH_F32_HALF
-#undef LAUNCH_F32_MODES
-#undef LAUNCH_F32
-      NS_CHECK_LAUNCH("gemm_mfma_f32");
-      return NS_OK;
-    }
-  }
-  dim3 grid(ceil_div(p.N, 64), ceil_div(p.M, 64), p.split_k * p.batch);
-  p.stat_slots = ceil_div(p.M, 64);
-  g_last_kernel = "gemm_generic_kernel";
-  if (p.dtype == NS_F32) hipLaunchKernelGGL(gemm_generic_kernel<float>, grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(gemm_generic_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
-  NS_CHECK_LAUNCH("gemm_generic");
+  p.stat_slots = plan.stat_slots;
+  return NS_OK;
+}
+
+static void gemm_allow_lds();      // (below the grouped kernels, which it covers too)
+
+static int gemm_dispatch(ns_gemm_params& p, const gemm_plan& plan, hipStream_t stream) {
+  const gemm_entry& e = *plan.entry;
+  gemm_allow_lds();
+  g_last_kernel = e.name;
+  g_last_loop = e.loop;
+  hipLaunchKernelGGL(e.fn, plan.grid, dim3(e.block), e.lds, stream, p);
+  NS_CHECK_LAUNCH(e.family);
+  return NS_OK;
+}
+
+extern "C" int ns_gemm(const ns_gemm_params* pp, ns_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ns_gemm_params p;
+  ns_gemm_bn_params bn;
+  gemm_plan plan;
+  if (int rc = gemm_prepare(pp, p, bn, plan)) return rc;
+  if (!plan.entry) return NS_OK;
+  if (int rc = gemm_dispatch(p, plan, stream)) return rc;
+  if (!p.stat_part) return NS_OK;
+  hipLaunchKernelGGL(gemm_stats_finalize_kernel, dim3(ceil_div(p.N, 32)), dim3(1024), 0, stream, p.stat_part, p.stat_slots,
+                     p.N, p.col_sum, p.col_sumsq, bn);
+  NS_CHECK_LAUNCH("gemm_stats_finalize");
+  return NS_OK;
+}
+
+extern "C" int ns_gemm_plan(const ns_gemm_params* pp, ns_gemm_plan_info* out) {
+  NS_CHECK_ARG(out != nullptr, "ns_gemm_plan: null out");
+  *out = ns_gemm_plan_info{};
+  ns_gemm_params p;
+  ns_gemm_bn_params bn;
+  gemm_plan plan;
+  if (int rc = gemm_prepare(pp, p, bn, plan)) return rc;
+  if (!plan.entry) return NS_OK;
+  const gemm_entry& e = *plan.entry;
+  *out = ns_gemm_plan_info{e.name, e.loop, (int)plan.grid.x, (int)plan.grid.y, (int)plan.grid.z, e.block, e.lds, plan.stat_slots};
   return NS_OK;
 }
 
@@ -1766,6 +1703,18 @@ __global__ __launch_bounds__(256, 2) void gemm_group_kernel(const gemm_group_arg
   } else gemm_mfma_f32_body<1, 1, 1, false, GBM>(p, tile, ksl);
 }
 
+// the dynamic-LDS allowance of every kernel form and of the two grouped kernels, once per process (any thread may be first)
+static void gemm_allow_lds() {
+  static const bool once = [] {
+    for (const gemm_entry& e : GEMM_FORMS)
+      if (e.lds > 0) (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, e.lds);
+    (void)hipFuncSetAttribute((const void*)gemm_group_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void*)gemm_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    return true;
+  }();
+  (void)once;
+}
+
 namespace {
 struct group_entry {
   ns_gemm_group_item it;
@@ -1795,9 +1744,10 @@ static int gemm_group_build(const ns_gemm_params* products, int n_products, cons
       NS_CHECK_ARG(!p.bias && p.act == NS_ACT_NONE && !p.gate && !p.addend && !p.col_sum && !p.col_sumsq && !p.stat_z &&
                    p.row_period <= 0 && !p.A_lo && !p.B_lo && !p.bn.mean_out,
                    "ns_gemm_group: product %d carries an epilogue operand the item table has no field for", i);
-      const gemm_form f = gemm_classify(p);
-      const bool k0 = f.kind == GF_MFMA && !f.vec && !f.half && !f.bk32;
-      const bool k1 = f.kind == GF_F32 && !f.vec && !f.half && p.f32_passes == 1;
+      // the two product forms the group carries, the bf16 one on either K loop (the launch picks the loop for all its items)
+      const gemm_entry* const f = gemm_classify(p).entry;
+      const bool k0 = f == gemm_form(form_key(GF_MFMA, 1, 1, false, 64, 128)) || f == gemm_form(form_key(GF_MFMA_DMA, 1, 1, false, 64, 128));
+      const bool k1 = f == gemm_form(form_key(GF_F32, 1, 1, false, 1, 128));
       NS_CHECK_ARG((k0 || k1) && p.a_mode == 1 && p.b_mode == 1,
                    "ns_gemm_group: product %d is not one ns_gemm runs on gemm_mfma_kernel<1, 1, false, 64, 128> or "
                    "gemm_mfma_f32_kernel<1, 1, 1, false, 128>", i);
@@ -1906,12 +1856,7 @@ extern "C" int ns_gemm_group(const ns_gemm_params* products, int n_products, con
   group_entry* e = new group_entry[n_products + n_sums];
   int n = 0;
   int rc = gemm_group_build(products, n_products, sums, n_sums, e, &n);
-  static bool attr_set = false;
-  if (rc == NS_OK && !attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_group_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)gemm_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    attr_set = true;
-  }
+  if (rc == NS_OK) gemm_allow_lds();
   for (int first = 0; rc == NS_OK && first < n;) {
     const int end = group_launch_end(e, n, first);
     gemm_group_args a;

@@ -191,3 +191,48 @@ def test_grouped_launch_of_two_items_is_bit_equal(dev, monkeypatch):
     for n, a, b in zip(names, out["dma"], out["staged"]):
         assert torch.equal(a, b), n
         assert torch.equal(a, _run(dev, monkeypatch, n, "dma", True, False)), n     # and to the item launched alone
+
+
+# (form of tests/test_gemm_epilogue_gpu.py at its smallest shape: dtype, M, N, K, a_mode, b_mode, f32_passes, element offset of A)
+PLANNED = {
+    "skinny": (bf, 17, 72, 104, 0, 0, 0, 0),
+    "generic": (bf, 70, 67, 45, 0, 0, 0, 3),
+    "half_tiles": (bf, 130, 136, 72, 0, 0, 0, 0),
+    "dma": (bf, 136, 136, 100, 1, 1, 0, 0),
+    "three_passes": (f32, 136, 136, 100, 1, 0, 3, 0),
+}
+
+
+@pytest.mark.parametrize("name", list(PLANNED))
+def test_the_launch_is_what_the_plan_said(dev, monkeypatch, name):
+    """ns_gemm_plan and ns_gemm on one block: the query names the kernel and the loop that the launch then reports"""
+    L, lib = _lib()
+    monkeypatch.delenv("NS_GEMM_DMA", raising=False)
+    monkeypatch.delenv("NS_GEMM_BK32", raising=False)
+    dtype, M, N, K, a_mode, b_mode, passes, a_off = PLANNED[name]
+    g = torch.Generator().manual_seed(7)
+    A = (torch.rand(a_off + M * K, generator=g) - 0.5).to(dtype).to(dev)
+    B = (torch.rand(K * N, generator=g) - 0.5).to(dtype).to(dev)
+    Cm = torch.zeros(M * N, dtype=f32, device=dev)
+    p = L.struct("ns_gemm_params")
+    p.dtype, p.M, p.N, p.K = (L.NS_BF16 if dtype == bf else L.NS_F32), M, N, K
+    p.A, p.lda, p.a_mode = A.data_ptr() + a_off * A.element_size(), (K if a_mode == 0 else M), a_mode
+    p.B, p.ldb, p.b_mode = B.data_ptr(), (K if b_mode == 0 else N), b_mode
+    p.C, p.ldc, p.c_dtype = Cm.data_ptr(), N, L.NS_F32
+    p.alpha, p.f32_passes = 1.0, passes
+    info = L.struct("ns_gemm_plan_info")
+    L.check(lib.ns_gemm_plan(ctypes.byref(p), ctypes.byref(info)), "ns_gemm_plan")
+    said = (ctypes.cast(info.kernel, ctypes.c_char_p).value, ctypes.cast(info.loop, ctypes.c_char_p).value)
+    L.check(lib.ns_gemm(ctypes.byref(p), _stream()), "ns_gemm")
+    torch.cuda.synchronize()
+    assert (lib.ns_gemm_last_kernel(), lib.ns_gemm_last_loop()) == said
+    want = {"skinny": b"gemm_skinny_kernel<1>", "generic": b"gemm_generic_kernel", "half_tiles": b"gemm_mfma_kernel<0, 0, true, 64, 64>",
+            "dma": b"gemm_mfma_kernel<1, 1, true, 64, 128>", "three_passes": b"gemm_mfma_f32_kernel<1, 0, 3, true, 128>"}[name]
+    assert said == (want, b"dma" if name == "dma" else b"staged")
+    a = A[a_off:].double().cpu().reshape((M, K) if a_mode == 0 else (K, M))
+    b = B.double().cpu().reshape((N, K) if b_mode == 0 else (K, N))
+    ref = (a if a_mode == 0 else a.t()) @ (b.t() if b_mode == 0 else b)
+    # the bounds of tests/test_gemm_epilogue_gpu.py: exact products 2 (K + 4) u mag, three passes 3e-5 max|A| max|B| sqrt(K)
+    acc = 3e-5 * a.abs().max() * b.abs().max() * K ** 0.5 if passes == 3 else 2.0 * (K + 4) * U * (
+        (a.abs() if a_mode == 0 else a.abs().t()) @ (b.abs().t() if b_mode == 0 else b.abs()))
+    assert bool(((Cm.double().cpu().reshape(M, N) - ref).abs() <= acc + 2.0 ** -23 * ref.abs()).all())
