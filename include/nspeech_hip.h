@@ -48,6 +48,17 @@ const char* ns_last_error(void);
 int ns_occupy(int blocks, int threads, int lds_bytes, int heavy, double usec, int* started, ns_stream_t stream);
 int ns_wait_counter(const int* counter, int target, double timeout_usec, ns_stream_t stream);
 
+/* Placement of the persistent kernels' clusters (csrc/exchange.h; no reference counterpart).  A launch of `clusters`
+ * clusters of `members` workgroups has ns_cluster_grid_query() workgroups; grid index b is member *member of cluster
+ * *cluster and ns_cluster_place_query() returns 1, or the index is padding and it returns 0.  placed != 0: all members
+ * of a cluster share b % 8 (one XCD under round-robin dispatch) and the grid is padded to 8 * members * ceil(clusters / 8);
+ * placed == 0: b / members, b % members, no padding.  Pure host code.
+ * ns_cluster_probe: launches such a grid; the workgroup of (cluster, member) writes the id of the XCD it runs on (0 - 7,
+ * the hardware's id register) into xcc[cluster * members + member] (device int [clusters * members]). */
+int ns_cluster_grid_query(int clusters, int members, int placed);
+int ns_cluster_place_query(int b, int clusters, int members, int placed, int* cluster, int* member);
+int ns_cluster_probe(int clusters, int members, int placed, int* xcc, ns_stream_t stream);
+
 /* ------------------------------------------------------------------ GEMM / conv1d
  * C[M,N] (=|+=) act( alpha * A·B + bias + addend ), fp32 accumulate; then the gate (0 where gate <= 0) and the row mask
  * (0 in masked rows) are applied to that value, and the result is stored or added to C (alpha = 0 is read as 1).

@@ -61,11 +61,14 @@ struct ACArgs {
   u64* x1;                   // backward: [N][CG] dot-product shares
   int* status;
   long long* trace;          // NS_ATTN_TRACE=1: [step][16] timestamps (100 MHz) of workgroup 0, else null
+  int xcd;                   // the forward / backward kernels: an utterance's cluster shares an XCD (ns_cluster_place;
+                             // NS_CLUSTER_XCD, family "attn"); the decode kernel deals its own roles and ignores it
   // free-running decode (taco2_decode_kernel): the next step's frame term f1 arrives as granules from the decoder-LSTM
   // workgroups ([N][D1], tag = consuming step + 1) and the alignment goes out to them ([N][Tia], tag = step + 1)
   u64* f1x; u64* alx;
 };
 constexpr size_t TRACE_BYTES = 256 * 16 * sizeof(long long);
+// (grid index 0 is cluster 0, member 0 under either placement, and the first attention workgroup of the decode kernel)
 __device__ __forceinline__ void stamp(const ACArgs& a, int st, int k) {
   if (a.trace && blockIdx.x == 0 && threadIdx.x == 0 && st < 256) a.trace[st * 16 + k] = wall_clock64();
 }
@@ -423,7 +426,9 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
 template <typename T, typename C>
 __global__ __launch_bounds__(CT) void attn_cluster_fwd_kernel(ACArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm_attn_fwd[];
-  attn_fwd_body<T, C, false>(a, sm_attn_fwd, blockIdx.x);
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, a.p.N, CG, a.xcd != 0);
+  if (!slot.active) return;                                 // padding of a placed grid (exchange.h)
+  attn_fwd_body<T, C, false>(a, sm_attn_fwd, slot.cluster * CG + slot.member);
 }
 
 // ===================================================================================== backward
@@ -519,7 +524,9 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
   float* gts1 = carve_at<float>(sm, lay.gts1);
 
   const int tid_ = threadIdx.x;
-  const int n = blockIdx.x / CG, g = blockIdx.x % CG;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, p.N, CG, a.xcd != 0);
+  if (!slot.active) return;                                 // padding of a placed grid (exchange.h)
+  const int n = slot.cluster, g = slot.member;
   const long S1 = p.S + 1;
   const int Dsp = p.Dsp, HC = A + p.E;
   const int XA = D2 + Dsp + A;
@@ -1206,6 +1213,7 @@ static int launch_fwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
   a.x2 = carve_at<u64>(work, wl.x2);
   a.x3 = carve_at<u64>(work, wl.x3);
   a.x1 = nullptr;
+  a.xcd = ns_cluster_placed("attn") ? 1 : 0;
   a.trace = getenv("NS_ATTN_TRACE") ? carve_at<long long>(work, AbiWork{(size_t)p->N}.trace) : nullptr;
   { const int zrc = ns_zero_async(work, (wl.used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   constexpr size_t lds = FwdLds<C>().bytes;
@@ -1236,7 +1244,7 @@ static int launch_fwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
     b.p.align_t = p->align_t ? (char*)p->align_t + (long)n0 * S1 * p->Tia * esz : nullptr;
     b.x2 = a.x2 + (size_t)n0 * CG * C::X2N;
     b.x3 = a.x3 + (size_t)n0 * CG * C::X3N;
-    hipLaunchKernelGGL((attn_cluster_fwd_kernel<T, C>), dim3(nn * CG), dim3(CT), lds, s, b);
+    hipLaunchKernelGGL((attn_cluster_fwd_kernel<T, C>), dim3(ns_cluster_grid(nn, CG, b.xcd != 0)), dim3(CT), lds, s, b);
   }
   NS_CHECK_LAUNCH("attn_cluster_fwd");
   // the transposed keys the per-step forward leaves behind for either backward path (hoisted sums over the steps)
@@ -1275,6 +1283,7 @@ static int launch_bwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
   a.x2 = carve_at<u64>(work, wl.x2);
   a.x3 = carve_at<u64>(work, wl.x3);
   a.x1 = carve_at<u64>(work, wl.x1);
+  a.xcd = ns_cluster_placed("attn") ? 1 : 0;
   a.trace = getenv("NS_ATTN_TRACE") ? carve_at<long long>(work, AbiWork{(size_t)p->N}.trace) : nullptr;
   { const int zrc = ns_zero_async(work, (wl.used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   constexpr size_t lds = BwdLds<C>().bytes;
@@ -1307,7 +1316,7 @@ static int launch_bwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
     b.x2 = a.x2 + (size_t)n0 * CG * C::A;
     b.x3 = a.x3 + (size_t)n0 * CG * C::E3N;
     b.x1 = a.x1 + (size_t)n0 * CG;
-    hipLaunchKernelGGL((attn_cluster_bwd_kernel<T, C>), dim3(b.p.N * CG), dim3(CT), lds, s, b);
+    hipLaunchKernelGGL((attn_cluster_bwd_kernel<T, C>), dim3(ns_cluster_grid(b.p.N, CG, b.xcd != 0)), dim3(CT), lds, s, b);
   }
   NS_CHECK_LAUNCH("attn_cluster_bwd");
   return ns_attn_bwd_post<T>(*p, s);       // keys_t: written by either forward

@@ -63,6 +63,8 @@ struct TArgs {
   ns_taco1_attn_params p;
   u64* x1; u64* x2; u64* x3; u64* x4;       // fwd: [N][CG][X1N | X2N | X3N]; bwd: E1 [N][CG], E2 [N][CG][A], E3a / E3b [N][CG][K]
   int* status;
+  int xcd;                   // the forward / backward kernels: an utterance's cluster shares an XCD (ns_cluster_place;
+                             // NS_CLUSTER_XCD, family "taco1attn"); the decode kernel deals its own roles and ignores it
   // free-running synthesis (taco1_decode_kernel): the next step's frame term arrives as nwd partial sums per column
   // ([N][nwd][D1] granules, plus bpf), the alignment goes out as [N][Tia] granules
   u64* f1x; u64* alx; const float* bpf; int nwd;
@@ -382,7 +384,9 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
 template <typename T>
 __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  attn_fwd_body<T, false>(a, sm, blockIdx.x);
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, a.p.N, CG, a.xcd != 0);
+  if (!slot.active) return;                                 // padding of a placed grid (exchange.h)
+  attn_fwd_body<T, false>(a, sm, slot.cluster * CG + slot.member);
 }
 
 // ===================================================================================== backward
@@ -436,7 +440,9 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
   float* wq_s = carve_at<float>(sm, lay.wq_s); float* him = carve_at<float>(sm, lay.him);
 
   const int tid_ = threadIdx.x;
-  const int n = blockIdx.x / CG, g = blockIdx.x % CG;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, p.N, CG, a.xcd != 0);
+  if (!slot.active) return;                                 // padding of a placed grid (exchange.h)
+  const int n = slot.cluster, g = slot.member;
   const long S1 = p.S + 1;
   const int HC = A + p.E;
   const int Dsp = p.Dsp, XA = D2 + Dsp + A;                // the loop's K rows skip the speaker rows of both kernels (see the forward kernel)
@@ -1101,7 +1107,8 @@ static int taco1_run(const ns_taco1_attn_params* p, void* work, hipStream_t s, i
     (void)hipFuncSetAttribute((const void*)taco1_attn_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  const dim3 grid((unsigned)(p->N * CG)), block(CT);
+  a.xcd = ns_cluster_placed("taco1attn") ? 1 : 0;
+  const dim3 grid((unsigned)ns_cluster_grid(p->N, CG, a.xcd != 0)), block(CT);
   if (!backward) {
     if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_fwd_kernel<bf16_t>, grid, block, FwdLds().bytes, s, a);
     else hipLaunchKernelGGL(taco1_attn_fwd_kernel<float>, grid, block, FwdLds().bytes, s, a);

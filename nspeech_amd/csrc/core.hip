@@ -1,6 +1,7 @@
 // Library-wide state: thread-local error string, version, architecture tag.
-#include "common.h"
+#include "exchange.h"
 #include <stdarg.h>
+#include <stdlib.h>
 
 static thread_local char g_err[512] = "";
 
@@ -21,6 +22,53 @@ int ns_device_cus() {
     cached[dev] = n;
   }
   return cached[dev];
+}
+
+// ---------------------------------------------------------------- cluster placement (exchange.h)
+// The families whose launches place a cluster on one XCD by default: those that measured faster placed than linear in
+// every alternated run (profiles/cluster_xcd.txt); "bilstmf32", the fp32-state BiLSTM forward, measured slower and is not.
+static const char* const kPlacedByDefault[] = {"bilstm", "attn", "gru", "taco1attn"};
+bool ns_cluster_placed(const char* family) {
+  const char* e = getenv("NS_CLUSTER_XCD");
+  if (!e || !*e) {
+    for (const char* f : kPlacedByDefault) if (!strcmp(f, family)) return true;
+    return false;
+  }
+  if (!strcmp(e, "0")) return false;
+  if (!strcmp(e, "1")) return true;
+  const size_t n = strlen(family);
+  for (const char* p = e; *p;) {                   // a comma list of the families that stay linear
+    const char* q = strchr(p, ',');
+    const size_t len = q ? (size_t)(q - p) : strlen(p);
+    if (len == n && !strncmp(p, family, n)) return false;
+    p += len + (q ? 1 : 0);
+  }
+  return true;
+}
+extern "C" int ns_cluster_grid_query(int clusters, int members, int placed) {
+  NS_CHECK_ARG(clusters >= 0 && members >= 1, "ns_cluster_grid_query: clusters >= 0, members >= 1");
+  return ns_cluster_grid(clusters, members, placed != 0);
+}
+extern "C" int ns_cluster_place_query(int b, int clusters, int members, int placed, int* cluster, int* member) {
+  NS_CHECK_ARG(b >= 0 && clusters >= 0 && members >= 1 && cluster && member, "ns_cluster_place_query: bad argument");
+  const ns_cluster_slot w = ns_cluster_place(b, clusters, members, placed != 0);
+  *cluster = w.cluster; *member = w.member;
+  return w.active ? 1 : 0;
+}
+// Every active workgroup of a cluster launch reports the XCD it runs on (the hardware's id register), at its logical index.
+__global__ void ns_cluster_probe_kernel(int clusters, int members, int placed, int* xcc) {
+  const ns_cluster_slot w = ns_cluster_place(blockIdx.x, clusters, members, placed != 0);
+  if (!w.active) return;
+  int id;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
+  if (threadIdx.x == 0) xcc[w.cluster * members + w.member] = id & 15;
+}
+extern "C" int ns_cluster_probe(int clusters, int members, int placed, int* xcc, ns_stream_t stream) {
+  NS_CHECK_ARG(clusters >= 1 && members >= 1 && xcc, "ns_cluster_probe: clusters >= 1, members >= 1, xcc");
+  hipLaunchKernelGGL(ns_cluster_probe_kernel, dim3((unsigned)ns_cluster_grid(clusters, members, placed != 0)), dim3(64), 0,
+                     (hipStream_t)stream, clusters, members, placed, xcc);
+  NS_CHECK_LAUNCH("ns_cluster_probe");
+  return NS_OK;
 }
 
 extern "C" int ns_version(void) { return 103; }

@@ -13,6 +13,36 @@ typedef unsigned long long u64;
 // through global memory is either tag-polled (the exchanges) or read by later kernels.
 __device__ __forceinline__ void ns_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// ---------------------------------------------------------------- cluster placement
+// Which (cluster, member) the workgroup of grid index b is, in a launch of `clusters` independent clusters of `members`
+// workgroups that exchange with each other.  The hardware deals consecutive grid indices to the 8 XCDs in turn (gemm.hip,
+// xcd_work_item), so the linear map b / members, b % members spreads the members of a cluster over as many XCDs as
+// there are; a hand-off inside one XCD is the shorter one (profiles/r05_ring_bench.txt, profiles/cluster_xcd.txt).  The
+// placed map gives all members of a cluster one residue b % 8: XCD x holds clusters x, x + 8, .. in slots of `members`
+// indices each.  clusters % 8 != 0 pads the grid: an index whose cluster does not exist is inactive and its workgroup
+// returns before its first barrier, poll, LDS write or global write.  Index 0 is cluster 0, member 0 in both maps.
+// Only which CU runs which role moves: work areas, exchange buffers and history are indexed by the logical ids.
+constexpr int NS_XCDS = 8;
+struct ns_cluster_slot { int cluster, member; bool active; };
+__host__ __device__ __forceinline__ int ns_cluster_grid(int clusters, int members, bool placed = true) {
+  return placed ? NS_XCDS * members * ((clusters + NS_XCDS - 1) / NS_XCDS) : clusters * members;
+}
+__host__ __device__ __forceinline__ ns_cluster_slot ns_cluster_place(int b, int clusters, int members, bool placed = true) {
+  // (unsigned: a signed b / 8 costs the kernels sign fix-ups and, in one backward form, its register allocation)
+  const unsigned ub = (unsigned)b, um = (unsigned)members;
+  const int cluster = (int)(placed ? (ub & 7u) + 8u * ((ub >> 3) / um) : ub / um);
+  const int member = (int)(placed ? (ub >> 3) % um : ub % um);
+  return {cluster, member, cluster < clusters};
+}
+// Measured and not taken (profiles/cluster_xcd.txt): the fp32-state BiLSTM forward, whose H / 32 members all poll the whole
+// chain's granules, is slower on one XCD ("bilstmf32" below stays linear by default), and so are lstm_wide's chip-wide
+// row groups kept to 8 / (row groups) XCDs each.
+// core.hip: whether the launches of `family` place their clusters - "bilstm" (lstm_cluster2_fwd, lstm_cluster2p_bwd and
+// the single-role kernels), "bilstmf32" (lstm_cluster3_fwd), "attn", "gru", "taco1attn".  NS_CLUSTER_XCD, read per call:
+// unset = the family's default, 0 = linear everywhere, 1 = placed everywhere, a comma list of family names = those stay
+// linear and the others are placed.
+bool ns_cluster_placed(const char* family);
+
 // ---------------------------------------------------------------- the granule
 // High word: the tag (the step that consumes it, so a buffer is never reset between steps); low word: 32 payload bits -
 // one fp32, or two bf16 that the kernel packs itself.

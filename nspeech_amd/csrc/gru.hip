@@ -61,6 +61,7 @@ struct GruArgs {
   u64* xbuf;                          // [chains][granules per chain]
   int* status;
   int dbg;                            // NS_GRU_DBG (timing experiments only, 0 in production): 1 no prefetch, 2 no result stores
+  int xcd;                            // H = 256: the workgroups of a chain share an XCD (ns_cluster_place; NS_CLUSTER_XCD, family "gru")
   long long* trace;                   // NS_GRU_TRACE=1 (diagnostic instantiation): [wave][8] segment sums of workgroup 0, 10 ns ticks
 };
 
@@ -288,7 +289,9 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
   int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int chain = blockIdx.x / G, g = blockIdx.x % G;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, a.ndir * a.nrg, G, G > 1 && a.xcd != 0);
+  if (!slot.active) return;                           // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, g = slot.member;
   const int d = chain / a.nrg, rg = chain % a.nrg;
   const bool rev = a.reverse[d] != 0;
   const int T_ = a.T;
@@ -424,7 +427,7 @@ __global__ __launch_bounds__(GCfg<H>::FW_WAVES * 64) void gru_fwd_kernel(GruArgs
       GRU_STAMP(5);
     }
 #undef GRU_STAMP
-    if (TRACE && a.trace && blockIdx.x == 0 && lane == 0)
+    if (TRACE && a.trace && (chain | g) == 0 && lane == 0)
       for (int k = 0; k < 8; ++k) a.trace[wave * 8 + k] = tsum[k];
   } else if (wave == C::GW) {
     // ================================================================ prefetcher role: LDS-DMA, two slots ahead
@@ -516,7 +519,9 @@ __global__ __launch_bounds__(GCfg<H>::BW_WAVES * 64) void gru_bwd_kernel(GruArgs
   int* abortf = carve_at<int>(smem, lay.abortf);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int chain = blockIdx.x / G, g = blockIdx.x % G;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, a.ndir * a.nrg, G, G > 1 && a.xcd != 0);
+  if (!slot.active) return;                           // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, g = slot.member;
   const int d = chain / a.nrg, rg = chain % a.nrg;
   const bool rev = a.reverse[d] != 0;
   const int T_ = a.T;
@@ -785,6 +790,7 @@ void fill(GruArgs& a, const ns_gru_seq_params* p0, const ns_gru_seq_params* p1, 
   a.trace = (tr && atoi(tr)) ? carve_at<long long>(work, wl.trace) : nullptr;
   const char* dbg = getenv("NS_GRU_DBG");
   a.dbg = dbg ? atoi(dbg) : 0;
+  a.xcd = (p0->H == 256 && ns_cluster_placed("gru")) ? 1 : 0;      // one workgroup per chain exchanges nothing
 }
 
 }  // namespace
@@ -812,11 +818,11 @@ static void launch_fwd(const GruArgs& a, hipStream_t s) {
   if (a.trace) {       // diagnostic instantiation with in-kernel stamps (never the production path)
     if constexpr (P == 3) {
       (void)hipFuncSetAttribute((const void*)gru_fwd_kernel<H, P, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((gru_fwd_kernel<H, P, T, true>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::FW_WAVES * 64), lds, s, a);
+      hipLaunchKernelGGL((gru_fwd_kernel<H, P, T, true>), dim3((unsigned)ns_cluster_grid(a.ndir * a.nrg, C::G, a.xcd != 0)), dim3(C::FW_WAVES * 64), lds, s, a);
       return;
     }
   }
-  hipLaunchKernelGGL((gru_fwd_kernel<H, P, T>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::FW_WAVES * 64), lds, s, a);
+  hipLaunchKernelGGL((gru_fwd_kernel<H, P, T>), dim3((unsigned)ns_cluster_grid(a.ndir * a.nrg, C::G, a.xcd != 0)), dim3(C::FW_WAVES * 64), lds, s, a);
 }
 template <int H, int P, typename T>
 static void launch_bwd(const GruArgs& a, hipStream_t s) {
@@ -827,7 +833,7 @@ static void launch_bwd(const GruArgs& a, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)gru_bwd_kernel<H, P, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL((gru_bwd_kernel<H, P, T>), dim3((unsigned)(a.ndir * a.nrg * C::G)), dim3(C::BW_WAVES * 64), lds, s, a);
+  hipLaunchKernelGGL((gru_bwd_kernel<H, P, T>), dim3((unsigned)ns_cluster_grid(a.ndir * a.nrg, C::G, a.xcd != 0)), dim3(C::BW_WAVES * 64), lds, s, a);
 }
 
 static int gru_seq_run(const ns_gru_seq_params* p0, const ns_gru_seq_params* p1, void* work, hipStream_t s, int backward) {

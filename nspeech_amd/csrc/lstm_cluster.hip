@@ -49,6 +49,7 @@ struct LstmClusterArgs {
   u64* xbuf;                      // [chains][2][16][granules per row]
   int* status;
   int dbg;                        // NS_CLUSTER_DBG, 0 in production; bit 16: the role-split kernels stamp into `trace`
+  int xcd;                        // the members of a chain share an XCD (ns_cluster_place; NS_CLUSTER_XCD, family "bilstm" / "bilstmf32")
   long long* trace;               // dbg bit 16: [step][8] timestamps of workgroup 0 (100 MHz clock)
 };
 
@@ -65,7 +66,9 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_fwd_kernel(LstmClusterA
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int CS = a.CS, H = a.H;
   const int nrg = (a.N + 15) / 16;
-  const int chain = blockIdx.x / CS, wgc = blockIdx.x % CS;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, 2 * nrg, CS, a.xcd != 0);
+  if (!slot.active) return;                                       // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, wgc = slot.member;
   const int d = chain / nrg, rg = chain % nrg;
   const int n0 = rg * 16;
   const int r16 = lane & 15, g = lane >> 4;
@@ -217,7 +220,9 @@ __global__ __launch_bounds__(CTHREADS) void lstm_cluster_bwd_kernel(LstmClusterA
   bf16_t* dgs = carve_at<bf16_t>(smem, lay.dgs); float* red = carve_at<float>(smem, lay.red);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nrg = (a.N + 15) / 16;
-  const int chain = blockIdx.x / CS, wgc = blockIdx.x % CS;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, 2 * nrg, CS, a.xcd != 0);
+  if (!slot.active) return;                                       // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, wgc = slot.member;
   const int d = chain / nrg, rg = chain % nrg;
   const int n0 = rg * 16;
   const int r16 = lane & 15, g = lane >> 4;
@@ -436,7 +441,9 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nch = (a.N + RPC - 1) / RPC;                        // chains per direction
-  const int chain = blockIdx.x / CS, wgc = blockIdx.x % CS;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, 2 * nch, CS, a.xcd != 0);
+  if (!slot.active) return;                                       // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, wgc = slot.member;
   const int d = chain / nch, rg = chain % nch;                // this workgroup set serves row group rg: batch rows rg * RPC ..
   const int r16 = lane & 15, g = lane >> 4;
   u64* xb0 = a.xbuf + (size_t)(d * nch + rg) * 2 * CS * GPD;             // + parity * CS*GPD + source * GPD
@@ -444,7 +451,7 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
   const int T = a.T;
   if (tid < 3) abortf[tid] = 0;
   // rows >= RPC of the operand images are never read (the narrow forms' B fragments come from rows < RPC only) and stay unwritten
-  if (RPC < 16 && blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
+  if (RPC < 16 && (chain | wgc) == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
 
   if (wave < XW) {
     // ================================================================ compute role.  16 rows: lane (r16, g) owns batch row
@@ -491,7 +498,7 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
       const int t = d ? T - 1 - step : step, buf = step & 1;
       ns_lds_barrier();
       if (abortf[buf]) return;
-      const bool tr = (a.dbg & 16) && blockIdx.x == 0 && tid == 0 && step < 512;
+      const bool tr = (a.dbg & 16) && (chain | wgc) == 0 && tid == 0 && step < 512;
       if (tr) a.trace[step * 8 + 0] = wall_clock64();
       if (step > 0) {
         const bf16_t* hb = hs + (size_t)buf * 16 * H;
@@ -593,7 +600,7 @@ __global__ __launch_bounds__(FW_WAVES * 64) void lstm_cluster2_fwd_kernel(LstmCl
     ns_lds_barrier();
     for (int step = 0; step < T; ++step) {
       const int buf = step & 1;
-      const bool tr = (a.dbg & 16) && blockIdx.x == 0 && lane == 0 && wave == XW && step < 512;
+      const bool tr = (a.dbg & 16) && (chain | wgc) == 0 && lane == 0 && wave == XW && step < 512;
       if (tr) a.trace[step * 8 + 4] = wall_clock64();
       if (step > 0 && CS > 1) {
         const u64* cur = xb0 + (size_t)(step & 1) * CS * GPD;   // published by the peers with tag = step
@@ -754,7 +761,9 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nch = (a.N + RPC - 1) / RPC;                          // chains per direction
-  const int chain = blockIdx.x / CS, wgc = blockIdx.x % CS;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, 2 * nch, CS, a.xcd != 0);
+  if (!slot.active) return;                                       // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, wgc = slot.member;
   const int d = chain / nch, rg = chain % nch;                  // this workgroup set serves row group rg: batch rows rg * RPC ..
   const int r16 = lane & 15, g = lane >> 4;
   u64* xb0 = a.xbuf + (size_t)(d * nch + rg) * 2 * GPC;                    // + parity * GPC
@@ -764,7 +773,7 @@ __global__ __launch_bounds__(X3_WAVES * 64) void lstm_cluster3_fwd_kernel(LstmCl
   if (RPC < 16) {
     // rows >= RPC of the operand images are MFMA padding: zeroed in front of every role's first barrier, never written
     for (int i = tid; i < 2 * 2 * 16 * H / 8; i += X3_WAVES * 64) ((uint4*)hsh)[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
+    if ((chain | wgc) == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
   }
 
   if (wave < X3W) {
@@ -1028,7 +1037,9 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nch = (a.N + RPC - 1) / RPC;                              // chains per direction
-  const int chain = blockIdx.x / CS, wgc = blockIdx.x % CS;
+  const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, 2 * nch, CS, a.xcd != 0);
+  if (!slot.active) return;                                       // padding of a placed grid (exchange.h)
+  const int chain = slot.cluster, wgc = slot.member;
   const int d = chain / nch, rg = chain % nch;                      // this workgroup set serves row group rg: batch rows rg * RPC ..
   const int r16 = lane & 15, g = lane >> 4;
   // exchange: [chain][parity][destination][source][RPC / 2 row pairs][64 units]
@@ -1036,7 +1047,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
   const int u0 = wgc * 64;
   const int T = a.T;
   if (tid == 0) abortf[0] = 0;           // (audit) by wave 0 in front of its first ns_lds_barrier, read behind it
-  if (RPC < 16 && blockIdx.x == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
+  if (RPC < 16 && (chain | wgc) == 0 && tid == 0) a.status[1] = RPC;   // which form ran (tests, A/B tools)
   auto t_of = [&](int step) { return d ? T - 1 - step : step; };
 
   if (wave < XW) {
@@ -1105,7 +1116,7 @@ __global__ __launch_bounds__(BP_WAVES * 64) void lstm_cluster2p_bwd_kernel(LstmC
     do {                                             // see lstm_cluster2_fwd_kernel
       const int t = t_of(T - 1 - bs), buf = bs & 1;
       const int n0 = rg * RPC;
-      const bool tr = (a.dbg & 16) && blockIdx.x == 0 && tid == 0 && bs < 512;
+      const bool tr = (a.dbg & 16) && (chain | wgc) == 0 && tid == 0 && bs < 512;
       if (tr) a.trace[bs * 8 + 0] = wall_clock64();
       // ---- dh of the step after, summed in a fixed order: own block, then the peers' in workgroup order.
       // Granule (source ws, row pair p, unit wu) of this workgroup's block: {tag bs, rows 2p | 2p + 1}.  A lane polls the
@@ -1384,6 +1395,7 @@ static void fill(LstmClusterArgs& a, const ns_lstm_seq_params* p0, const ns_lstm
   a.xbuf = carve_at<u64>(work, wl.xbuf);
   const char* dbg = getenv("NS_CLUSTER_DBG");
   a.dbg = dbg ? atoi(dbg) : 0;
+  a.xcd = ns_cluster_placed("bilstm") ? 1 : 0;
   a.trace = carve_at<long long>(work, wl.trace);
 }
 
@@ -1459,6 +1471,7 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
                  "f32_passes 3 with whT_hi / whT_lo, 16-byte aligned operands");
     LstmClusterArgs a = {};
     fill(a, p0, p1, work);
+    a.xcd = ns_cluster_placed("bilstmf32") ? 1 : 0;      // a family of its own: H / 32 members that all poll the whole chain
     const int RPC = cluster_rows(a.N, a.H / X3_UPW), nch = (a.N + RPC - 1) / RPC;   // chains per direction
     const size_t xbytes = 2 * (size_t)nch * 2 * RPC * (size_t)a.H * sizeof(u64);
     { const int zrc = zero_work(work, xbytes, s); if (zrc) return zrc; }
@@ -1469,7 +1482,7 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
         for (cluster_kernel_t k : widths) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr3 = true;
     }
-    hipLaunchKernelGGL(role_split_form(cluster3_fwd_forms, a.H, RPC), dim3((unsigned)(2 * nch * (a.H / X3_UPW))),
+    hipLaunchKernelGGL(role_split_form(cluster3_fwd_forms, a.H, RPC), dim3((unsigned)ns_cluster_grid(2 * nch, a.H / X3_UPW, a.xcd != 0)),
                        dim3(X3_WAVES * 64), lds3, s, a);
     NS_CHECK_LAUNCH("lstm_cluster3_fwd");
     return NS_OK;
@@ -1483,13 +1496,13 @@ extern "C" int ns_lstm_cluster_fwd(const ns_lstm_seq_params* p0, const ns_lstm_s
   { const int zrc = zero_work(work, xbytes, s); if (zrc) return zrc; }
   if (split) {
     const size_t lds2 = Cluster2FwdLds{a.H, RPC}.bytes;
-    hipLaunchKernelGGL(role_split_form(cluster2_fwd_forms, a.H, RPC), dim3((unsigned)(2 * nch * a.CS)), dim3(FW_WAVES * 64),
+    hipLaunchKernelGGL(role_split_form(cluster2_fwd_forms, a.H, RPC), dim3((unsigned)ns_cluster_grid(2 * nch, a.CS, a.xcd != 0)), dim3(FW_WAVES * 64),
                        lds2, s, a);
     NS_CHECK_LAUNCH("lstm_cluster2_fwd");
     return NS_OK;
   }
   const size_t lds = (size_t)16 * a.H * 2;
-  hipLaunchKernelGGL(lstm_cluster_fwd_kernel, dim3((unsigned)(2 * nch * a.CS)), dim3(CTHREADS), lds, s, a);
+  hipLaunchKernelGGL(lstm_cluster_fwd_kernel, dim3((unsigned)ns_cluster_grid(2 * nch, a.CS, a.xcd != 0)), dim3(CTHREADS), lds, s, a);
   NS_CHECK_LAUNCH("lstm_cluster_fwd");
   return NS_OK;
 }
@@ -1510,7 +1523,7 @@ extern "C" int ns_lstm_cluster_bwd(const ns_lstm_seq_params* p0, const ns_lstm_s
   { const int zrc = zero_work(work, xbytes, s); if (zrc) return zrc; }
   if (psum) {
     const size_t ldsp = Cluster2pBwdLds().bytes;
-    hipLaunchKernelGGL(role_split_form(cluster2p_bwd_forms, a.H, RPC), dim3((unsigned)(2 * nch * a.CS)), dim3(BP_WAVES * 64),
+    hipLaunchKernelGGL(role_split_form(cluster2p_bwd_forms, a.H, RPC), dim3((unsigned)ns_cluster_grid(2 * nch, a.CS, a.xcd != 0)), dim3(BP_WAVES * 64),
                        ldsp, s, a);
     NS_CHECK_LAUNCH("lstm_cluster2p_bwd");
     return NS_OK;
@@ -1521,7 +1534,7 @@ extern "C" int ns_lstm_cluster_bwd(const ns_lstm_seq_params* p0, const ns_lstm_s
     attr = true;
   }
   const size_t lds = ClusterBwdLds{a.H}.bytes;
-  hipLaunchKernelGGL(lstm_cluster_bwd_kernel, dim3((unsigned)(2 * nch * a.CS)), dim3(CTHREADS), lds, s, a);
+  hipLaunchKernelGGL(lstm_cluster_bwd_kernel, dim3((unsigned)ns_cluster_grid(2 * nch, a.CS, a.xcd != 0)), dim3(CTHREADS), lds, s, a);
   NS_CHECK_LAUNCH("lstm_cluster_bwd");
   return NS_OK;
 }
