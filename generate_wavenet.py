@@ -7,12 +7,15 @@ The reference script builds WaveNetModel and needs a wavenet_params.json that th
 for a speaker-conditioned checkpoint of train_wavenet.py --model wavenet, :214-231), restored from
 train_wavenet.py's model.ckpt-<step>.  --fast_generation true (default) at temperature 1.0 = the persistent incremental
 generator on the GPU (one workgroup per waveform; float64 softmax and inverse-CDF draw in the kernel).
+--incremental_temperature true keeps that generator at ANY --temperature - the kernel draws from softmax(logits /
+temperature), scale_prediction below in float64; --temperature 0 is argmax - and then a local condition is accepted at any
+temperature too; it needs --fast_generation true.
 --lc_channels N --local_condition FILE.npy --lc_hold H draw from a locally conditioned checkpoint: the file is float
 [rows, N], row r conditions generated samples r * H .. r * H + H - 1 (a mel spectrogram: H = the hop), the seed in
 front takes row 0; this path is the incremental generator's alone.  Any other
 temperature, or --fast_generation false, takes the full-window path of generate_wavenet.py:104-142: predict_proba over the
 last receptive_field samples, temperature scaling and the draw on the host, including the reference's own consistency
-check at temperature 1.0 (:133-138, scaled == unscaled)."""
+check at temperature 1.0 (:133-138, scaled == unscaled); without --incremental_temperature that routing is unchanged."""
 import argparse
 import os
 import sys
@@ -61,6 +64,10 @@ def scale_prediction(prediction, temperature):
 
 
 def main(args):
+    inc_t = bool(getattr(args, "incremental_temperature", False))
+    if inc_t and not args.fast_generation:
+        raise ValueError("--incremental_temperature true tempers the incremental generator's draws: it needs "
+                         "--fast_generation true (the full-window path scales on the host at any --temperature already)")
     hp = hparams_mod.load("wavenet")
     hp.parse(args.hparams)
     gc = None
@@ -72,9 +79,10 @@ def main(args):
         hp.lc_channels = args.lc_channels
         if not args.local_condition:
             raise ValueError("--lc_channels needs --local_condition FILE.npy")
-        if not (args.fast_generation and args.temperature == 1.0):
+        if not (args.fast_generation and (inc_t or args.temperature == 1.0)):
             raise ValueError("A local condition is drawn from by the incremental generator only: --fast_generation true and "
-                             "--temperature 1.0 (predict_proba takes no local condition).")
+                             "--temperature 1.0, or any --temperature with --incremental_temperature true (predict_proba "
+                             "takes no local condition).")
         lc = np.asarray(np.load(args.local_condition), np.float32)
         if lc.ndim != 2 or lc.shape[1] != args.lc_channels:
             raise ValueError("--local_condition holds %s, expected [rows, %d]" % (lc.shape, args.lc_channels))
@@ -99,8 +107,10 @@ def main(args):
             waveform = [q // 2] * (rf - len(waveform)) + waveform
     else:                                           # silence with a single random sample at the end (:84-86)
         waveform = [q // 2] * (rf - 1) + [int(rng.integers(q))]
-    fast = args.fast_generation and args.temperature == 1.0
+    fast = args.fast_generation and (inc_t or args.temperature == 1.0)
     if fast:
+        if inc_t:
+            cond.update(temperature=args.temperature)
         done = 0
         while done < args.samples:                  # in chunks, so that --save_every can write partial results
             n = min(args.samples - done, args.save_every or args.samples)
@@ -156,6 +166,8 @@ if __name__ == "__main__":
     parser.add_argument("--wav_out_path", type=str, default=None)
     parser.add_argument("--save_every", type=int, default=None)
     parser.add_argument("--fast_generation", type=_str_to_bool, default=True)
+    parser.add_argument("--incremental_temperature", type=_str_to_bool, default=False,
+                        help="keep the incremental generator at any --temperature (0 = argmax); needs --fast_generation true")
     parser.add_argument("--wav_seed", type=str, default=None)
     parser.add_argument("--gc_channels", type=int, default=None)
     parser.add_argument("--gc_cardinality", type=int, default=None)

@@ -974,12 +974,14 @@ int ns_wavenet_softmax(const ns_wavenet_softmax_params* p, ns_stream_t stream);
  * fetched three layers ahead), about 7x faster per sample. */
 typedef struct {
   const void* weights; int w_dtype;
+  float temperature;   /* the draw (version 104), described below; in the 4 bytes that were padding here */
   int64_t off_causal, off_layer0, layer_stride, off_dense_in_layer, off_skip, off_post1, off_post2;
   const int* dilations; int L, R, Dc, S, Q;
   int B, n_seed, total; int64_t queue_rows;
   int* ids; const float* uniform; float* queues; float* probs;
   const void* fgT; const void* deT;
   int engine;   /* with fgT / deT: 0 / 1 = single-wave VALU chain, 2 = MFMA chain + concurrent skip waves (R == Dc == 32) */
+  int argmax;   /* the draw (version 104), described below; in the 4 bytes that were padding here */
   /* The full WaveNetModel's incremental generator (neural_speech/models/wavenet.py:398-437, 487-557), all optional and
    * fp32; with any of them the per-layer kernel runs (fgT / deT = NULL) or, with fgT / deT and engine = 2, the MFMA
    * chain's conditioned instantiation (engines 1 and 3 refuse them):
@@ -1006,6 +1008,20 @@ typedef struct {
    * training's alignment, where the condition of network-input position m joins the pre-activations at m; the clamp
    * lets a seed stand in front of row 0.  Rows up to that of t = total - 1 must exist: NS_ERR_BAD_ARG otherwise. */
   int cond_rows, cond_hold; int64_t cond_t0;
+  /* The draw, on every engine (version 104): the members `temperature` and `argmax` above.
+   * temperature: sample t+1 comes from softmax(logits / temperature) - the
+   * weights are w[j] = exp(((double)lg[j] - (double)m) * inv_t) in float64, m the maximum of the float32 logits, inv_t =
+   * 1.0 / (double)temperature formed once per call on the host, and the inverse CDF is taken at uniform * sum(w) as
+   * before (generate_wavenet.py:124-130 up to float64 rounding).  0 = 1.0: the factor is exactly 1 and the draws are those of a
+   * call without the field.  Negative or non-finite: NS_ERR_BAD_ARG.
+   * argmax != 0: sample t+1 is the lowest j with lg[j] == m; uniform is not read for the pick (it stays a required
+   * pointer) and temperature, once checked, plays no part.
+   * probs receives the distribution the last sample was drawn from: the tempered one with temperature, the
+   * temperature-1 distribution whose maximum was taken with argmax.
+   * The two members stand further up, `temperature` behind w_dtype and `argmax` behind engine, in the two 4-byte gaps
+   * the struct's alignment left: every member of version 103 keeps its offset, cond_t0 stays the last member and the
+   * size stays 248 bytes.  A caller built against 103 passes whatever its padding held there: zero the whole struct
+   * (memset, or a ctypes / calloc'd block) before filling it. */
 } ns_wavenet_generate_params;
 #define NS_WN_HELPERS 4
 size_t ns_wavenet_post_bytes(int B);

@@ -310,6 +310,24 @@ __device__ __forceinline__ void gen_load(GenLayerW<W>& w, const ns_wavenet_gener
   }
 }
 
+// The draw of sample t+1 (all generation kernels): weights ex[j] = exp((lg[j] - m) * inv_t) in float64, m the block
+// maximum of the float32 logits and inv_t = 1 / temperature, formed once by the launcher (1.0 when temperature is unset:
+// the product is exact and the weights are what they were without the factor) - softmax(logits / temperature).
+// gen_walk: the inverse CDF at u = uniform * sum(ex), one thread.  gen_first_max (argmax): the lowest j with lg[j] == m.
+__device__ __forceinline__ int gen_walk(const double* ex, double u, int Q) {
+  double c = 0.0;
+  for (int j = 0; j < Q; ++j) {
+    c += ex[j];
+    if (u < c) return j;
+  }
+  return Q - 1;
+}
+__device__ __forceinline__ int gen_first_max(const float* lg, float m, int Q) {
+  for (int j = 0; j < Q; ++j)
+    if (lg[j] == m) return j;
+  return Q - 1;
+}
+
 struct GenLds {                                   // dynamic LDS of wn_generate_kernel
   int R, Dc, S, Q;
   LdsCarve c = {};
@@ -324,7 +342,7 @@ struct GenLds {                                   // dynamic LDS of wn_generate_
   int bytes = c.off;
 };
 template <typename W>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p) {
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p, double inv_t) {
   extern __shared__ float gsm[];
   const int R = p.R, Dc = p.Dc, S = p.S, Q = p.Q;
   const GenLds lay{R, Dc, S, Q};
@@ -437,19 +455,12 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
     float m = -3.0e38f;
     for (int j = tid; j < Q; j += GEN_THREADS) m = fmaxf(m, lg[j]);
     m = block_max(m, part);
-    for (int j = tid; j < Q; j += GEN_THREADS) ex[j] = exp((double)lg[j] - (double)m);   // float64 softmax as predict_proba
+    for (int j = tid; j < Q; j += GEN_THREADS) ex[j] = exp(((double)lg[j] - (double)m) * inv_t);   // float64 softmax as predict_proba, at 1 / temperature
     __syncthreads();
     if (tid == 0) {
       double se = 0.0;
       for (int j = 0; j < Q; ++j) se += ex[j];
-      const double u = (double)un[t + 1 - p.n_seed] * se;
-      double c = 0.0;
-      int pick = Q - 1;
-      for (int j = 0; j < Q; ++j) {
-        c += ex[j];
-        if (u < c) { pick = j; break; }
-      }
-      ids[t + 1] = pick;
+      ids[t + 1] = p.argmax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
       if (p.probs)                                               // the distribution of the LAST drawn sample
         for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
     }
@@ -543,7 +554,7 @@ struct FastLds {                                  // dynamic LDS of wn_generate_
   int bytes = c.off;
 };
 template <int C>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p) {
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p, double inv_t) {
   extern __shared__ float gsm[];
   const int S = p.S, Q = p.Q, L = p.L;
   const FastLds lay{L, C, S, Q};
@@ -616,19 +627,12 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavene
     float m = -3.0e38f;
     for (int j = tid; j < Q; j += GEN_THREADS) m = fmaxf(m, lg[j]);
     m = block_max(m, red);
-    for (int j = tid; j < Q; j += GEN_THREADS) ex[j] = exp((double)lg[j] - (double)m);
+    for (int j = tid; j < Q; j += GEN_THREADS) ex[j] = exp(((double)lg[j] - (double)m) * inv_t);
     __syncthreads();
     if (tid == 0) {
       double se = 0.0;
       for (int j = 0; j < Q; ++j) se += ex[j];
-      const double u = (double)un[t + 1 - p.n_seed] * se;
-      double c = 0.0;
-      int pick = Q - 1;
-      for (int j = 0; j < Q; ++j) {
-        c += ex[j];
-        if (u < c) { pick = j; break; }
-      }
-      ids[t + 1] = pick;
+      ids[t + 1] = p.argmax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
       if (p.probs)
         for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
     }
@@ -785,7 +789,7 @@ struct ChainLds {                                 // dynamic LDS of wn_generate_
   O bytes = c.off;
 };
 template <bool COND>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p) {
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p, double inv_t) {
   extern __shared__ float gsm[];
   constexpr int C = 32;
   const int S = p.S, Q = p.Q, L = p.L;
@@ -852,10 +856,11 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
           gen_matvec8<8, COND>(wb + p.off_post1, S, S, h0, h1, part, true, tp, p.post1_bias);
           gen_matvec8<8, COND>(wb + p.off_post2, S, Q, h1, lg, part, false, tp, p.post2_bias);
         }
+        const bool amax = p.argmax != 0;
         float m = -3.0e38f;
         for (int j = tid; j < Q; j += GEN_THREADS) m = fmaxf(m, lg[j]);
         m = block_max(m, red);
-        for (int j = tid; j < Q; j += GEN_THREADS) ex[j] = exp((double)lg[j] - (double)m);
+        for (int j = tid; j < Q; j += GEN_THREADS) ex[j] = exp(((double)lg[j] - (double)m) * inv_t);
         __syncthreads();
         if (Q <= GEN_THREADS) {
           // inverse CDF in parallel: inclusive scan of the float64 weights, pick = #{j : cdf[j] <= u} (the first j with
@@ -879,28 +884,22 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
             se += tw;
           }
           const double u = (double)un[t + 1 - p.n_seed] * se;
-          const unsigned long long bal = __ballot(tid < Q && off + sc <= u);
-          if (lane == 0) wcnt[wave] = __popcll(bal);
+          // argmax: the lowest j with lg[j] == m instead - each wave's first hit (Q - 1 without one), the least of them below
+          const unsigned long long bal = amax ? __ballot(tid < Q && lg[tid] == m) : __ballot(tid < Q && off + sc <= u);
+          if (lane == 0) wcnt[wave] = amax ? (bal ? wave * 64 + (int)__ffsll(bal) - 1 : Q - 1) : __popcll(bal);
           if (p.probs && t + 2 == p.total && tid < Q)        // the distribution of the LAST drawn sample
             p.probs[(long)b * Q + tp] = (float)(v / se);
           __syncthreads();
           if (tid == 0) {
-            int cnt = 0;
+            int cnt = 0, first = Q - 1;
     #pragma unroll
-            for (int w = 0; w < GEN_THREADS / 64; ++w) cnt += wcnt[w];
-            ids[t + 1] = min(cnt, Q - 1);
+            for (int w = 0; w < GEN_THREADS / 64; ++w) { cnt += wcnt[w]; first = min(first, wcnt[w]); }
+            ids[t + 1] = amax ? first : min(cnt, Q - 1);
           }
         } else if (tid == 0) {
           double se = 0.0;
           for (int j = 0; j < Q; ++j) se += ex[j];
-          const double u = (double)un[t + 1 - p.n_seed] * se;
-          double c = 0.0;
-          int pick = Q - 1;
-          for (int j = 0; j < Q; ++j) {
-            c += ex[j];
-            if (u < c) { pick = j; break; }
-          }
-          ids[t + 1] = pick;
+          ids[t + 1] = amax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
           if (p.probs)
             for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
         }
@@ -1141,6 +1140,10 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
     NS_CHECK_ARG(last < p->cond_rows, "ns_wavenet_generate: position %lld of the condition needs row %lld, cond has %d rows of %d samples",
                  (long long)((int64_t)p->total - 1 + p->cond_t0), (long long)last, p->cond_rows, p->cond_hold);
   }
+  // temperature 0 = 1.0 (an all-zero field is the call as it was); argmax takes the maximum of the temperature-1 logits
+  NS_CHECK_ARG(std::isfinite(p->temperature) && p->temperature >= 0.f,
+               "ns_wavenet_generate: temperature %g must be finite and not negative (0 = 1.0)", (double)p->temperature);
+  const double inv_t = (p->argmax || p->temperature == 0.f) ? 1.0 : 1.0 / (double)p->temperature;
   if (p->fgT && p->deT) {
     NS_CHECK_ARG(p->w_dtype == NS_BF16 && p->R == p->Dc && (p->R == 32 || p->R == 16) && p->S % 8 == 0 && p->Q % 8 == 0 && p->S / 8 <= GEN_THREADS &&
                      GEN_THREADS % (p->S / 8) == 0 && GEN_THREADS % (p->Q / 8) == 0,
@@ -1172,23 +1175,23 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
       if (full) {                            // + the condition row and the dense biases
         const size_t lds4 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 1}.bytes;
         NS_CHECK_ARG(lds4 <= WN_CHAIN_LDS_MAX, "ns_wavenet_generate: state and condition row do not fit in LDS (ns_wavenet_chain_fits)");
-        hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p);
+        hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p, inv_t);
         NS_CHECK_LAUNCH("wavenet_generate_mfma_cond");
         return NS_OK;
       }
-      hipLaunchKernelGGL(wn_generate_mfma_kernel<false>, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p);
+      hipLaunchKernelGGL(wn_generate_mfma_kernel<false>, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p, inv_t);
       NS_CHECK_LAUNCH("wavenet_generate_mfma");
       return NS_OK;
     }
-    if (p->R == 32) hipLaunchKernelGGL(wn_generate_fast_kernel<32>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p);
-    else hipLaunchKernelGGL(wn_generate_fast_kernel<16>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p);
+    if (p->R == 32) hipLaunchKernelGGL(wn_generate_fast_kernel<32>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t);
+    else hipLaunchKernelGGL(wn_generate_fast_kernel<16>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t);
     NS_CHECK_LAUNCH("wavenet_generate_fast");
     return NS_OK;
   }
   NS_CHECK_ARG(carve_aligned(gl.ex, sizeof(double)),
                "ns_wavenet_generate: the per-layer kernel needs an even Dc (its float64 row follows 3 Dc floats in LDS)");
-  if (p->w_dtype == NS_BF16) hipLaunchKernelGGL(wn_generate_kernel<bf16_t>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p);
-  else hipLaunchKernelGGL(wn_generate_kernel<float>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p);
+  if (p->w_dtype == NS_BF16) hipLaunchKernelGGL(wn_generate_kernel<bf16_t>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t);
+  else hipLaunchKernelGGL(wn_generate_kernel<float>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t);
   NS_CHECK_LAUNCH("wavenet_generate");
   return NS_OK;
 }

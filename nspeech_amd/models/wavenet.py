@@ -660,7 +660,7 @@ class SimpleWaveNet(object):
         return probs
 
     def generate(self, seed_ids, n_samples, uniforms=None, seed=0, exact=None, fast=True, engine=None, global_conditions=None,
-                 local_conditions=None, hold=1, t0=0):
+                 local_conditions=None, hold=1, t0=0, temperature=1.0):
         """Incremental generation (generate_wavenet.py:56-142): seed_ids int [B, n_seed] (or [n_seed]) of mu-law codes,
         n_seed >= receptive field; returns int32 [B, n_seed + n_samples].  uniforms [B, n_samples] in [0,1) drive the
         categorical draws (default: numpy Generator(seed)).  Weights: the fp32 master copy when exact (default in fp32
@@ -672,7 +672,16 @@ class SimpleWaveNet(object):
         (_forward: lc_rows row m joins the pre-activations at network-input position m).  Rows are never repeated past
         the end: too few for n_seed + n_samples positions is a ValueError.
         A model with conditions or biases runs on the MFMA chain (last_engine 2) where the unconditioned one does - bf16
-        weights, R == Dc == 32 - and on the per-layer kernel (last_engine 0) elsewhere; engines 1 and 3 take neither."""
+        weights, R == Dc == 32 - and on the per-layer kernel (last_engine 0) elsewhere; engines 1 and 3 take neither.
+        temperature > 0 (every engine, with and without conditions): the draws come from softmax(logits / temperature),
+        formed in float64 inside the kernel - generate_wavenet.py:124-130's scale_prediction; 1.0 is the plain draw, bit
+        for bit.  temperature == 0: argmax - every sample is the lowest code with the largest float32 logit, and
+        `uniforms` / `seed` have no effect.  Negative or non-finite: ValueError.  last_probs [B * Q] holds the
+        distribution the LAST sample came from: the tempered softmax(logits / temperature) for temperature > 0, the
+        temperature-1 softmax whose maximum was taken for temperature == 0."""
+        temperature = float(temperature)
+        if not math.isfinite(temperature) or temperature < 0:
+            raise ValueError("temperature %r: a finite number > 0 for a tempered draw, 0 for argmax" % (temperature,))
         if self.scalar_input:
             raise NotImplementedError("Incremental generation does not support scalar input yet.")       # wavenet.py:643-645
         if self.lc and local_conditions is None:
@@ -752,7 +761,8 @@ class SimpleWaveNet(object):
             post_x = torch.empty(ops.wavenet_post_floats(B), dtype=torch.float32, device=dev)
             extra = dict(extra, post_x=post_x, helper_stream=self._helper_stream)
         ops.wavenet_generate(W, offs, dil, self.L, self.R, self.Dc, self.S, self.Q, B, n_seed, total, qrows, ids, un, queues,
-                             probs=self.last_probs, fgT=fgT, deT=deT, engine=engine, **extra)
+                             probs=self.last_probs, fgT=fgT, deT=deT, engine=engine, temperature=temperature or 1.0,
+                             argmax=temperature == 0, **extra)
         if engine == 3:             # the call's stream takes the helpers' end in: post_x is free behind it
             torch.cuda.current_stream(dev).wait_stream(self._helper_stream)
             self.last_status = extra["post_x"][:1].view(torch.int32)

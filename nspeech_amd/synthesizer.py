@@ -83,11 +83,12 @@ class Synthesizer(object):
         hparams_mod.set_hparams(mine)
         return self
 
-    def _wavenet_vocode_batch(self, mels, seed=0, global_conditions=None):
+    def _wavenet_vocode_batch(self, mels, seed=0, global_conditions=None, temperature=1.0):
         """mels float [B, T, num_mels] -> float32 [B, T * hop] in [-1, 1], ONE generate call: row r of a mel conditions
         samples r * hop .. r * hop + hop - 1; the seed - receptive-field copies of mu_law_encode(0) - stands at t0 = -rf
         and takes row 0.  Waveform i draws from np.random.default_rng(seed + i).random(T * hop), so B = 1 is the stream
-        generate(seed=seed) draws itself.  No inv_preemphasis: the WaveNet feeder's waveforms are not pre-emphasised."""
+        generate(seed=seed) draws itself.  temperature: generate's - softmax(logits / temperature) draws, 0 = argmax (then
+        the uniforms have no effect).  No inv_preemphasis: the WaveNet feeder's waveforms are not pre-emphasised."""
         from .models.wavenet import mu_law_decode, mu_law_encode
         v, hop = self.vocoder, self._vocoder_hop
         mels = np.asarray(mels, np.float32)
@@ -95,16 +96,18 @@ class Synthesizer(object):
         silence = int(mu_law_encode(np.zeros(1, np.float32), v.Q)[0])
         uniforms = np.stack([np.random.default_rng(seed + i).random(n) for i in range(B)])
         ids = v.generate(np.full((B, v.rf), silence, np.int32), n, uniforms=uniforms, global_conditions=global_conditions,
-                         local_conditions=mels, hold=hop, t0=-v.rf)
+                         local_conditions=mels, hold=hop, t0=-v.rf, temperature=temperature)
         return mu_law_decode(ids[:, v.rf:].cpu().numpy(), v.Q)
 
-    def _wavenet_vocode(self, mel, seed=0, global_conditions=None):
+    def _wavenet_vocode(self, mel, seed=0, global_conditions=None, temperature=1.0):
         """mel float [T, num_mels] -> float32 [T * hop]: _wavenet_vocode_batch of the one mel."""
-        return self._wavenet_vocode_batch(np.asarray(mel, np.float32)[None], seed=seed, global_conditions=global_conditions)[0]
+        return self._wavenet_vocode_batch(np.asarray(mel, np.float32)[None], seed=seed, global_conditions=global_conditions,
+                                          temperature=temperature)[0]
 
-    def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0):
+    def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0, temperature=1.0):
         """vocoder="wavenet" (after load_vocoder): the mel output through the WaveNet; seed: of the draws' random stream
-        (generate(seed=)), unused by Griffin-Lim."""
+        (generate(seed=)); temperature: of the draws (generate(temperature=): below 1 trades hiss for muffling, 0 is the
+        deterministic argmax vocode).  Both unused by Griffin-Lim."""
         if vocoder not in ("griffin_lim", "wavenet"):
             raise ValueError("vocoder %r: 'griffin_lim' or 'wavenet'" % (vocoder,))
         if vocoder == "wavenet" and self.vocoder is None:
@@ -120,7 +123,7 @@ class Synthesizer(object):
             lin = m.linear_outputs[0].float().cpu().numpy()
             m.check_status()    # (as below: invalid outputs are never vocoded)
             gc = np.asarray([speaker_id]) if self.vocoder.gc else None
-            wav = self._wavenet_vocode(mel, seed=seed, global_conditions=gc)
+            wav = self._wavenet_vocode(mel, seed=seed, global_conditions=gc, temperature=temperature)
             return wav[:audio.find_endpoint(wav)], mel, lin
         wav = audio.inv_spectrogram_tensorflow(m.linear_outputs[0].contiguous())
         mel = m.mel_outputs[0].float().cpu().numpy()
@@ -131,7 +134,7 @@ class Synthesizer(object):
         wav = wav[:audio.find_endpoint(wav)]
         return wav, mel, lin
 
-    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0):
+    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0, temperature=1.0):
         """synthesize for a list of texts: [(wav, mel, lin)] in the order of `texts`, every entry with the shapes and
         dtypes synthesize returns.  speaker_ids: one int for all, or one id per text.  More than MAX_BATCH texts run as
         consecutive chunks of at most MAX_BATCH in the given order (never sorted: see below); [] returns [].
@@ -139,8 +142,9 @@ class Synthesizer(object):
           griffin_lim: one griffin_lim_gpu on linear_outputs [N, T, F], one audio.finish_waves (inv_preemphasis and
             find_endpoint of all N on the device), one copy to the host each of the waves, the ends, the mels and the
             linears, check_status() behind them as in synthesize, wav[i] = y[i, :ends[i]];
-          wavenet: one generate for the chunk, text i of the LIST drawing from np.random.default_rng(seed + i); mu-law
-            decoding and find_endpoint per row on the host, no pre-emphasis.
+          wavenet: one generate for the chunk, text i of the LIST drawing from np.random.default_rng(seed + i) at
+            `temperature` (generate(temperature=), 0 = argmax; unused by Griffin-Lim); mu-law decoding and find_endpoint
+            per row on the host, no pre-emphasis.
         Row i is the row of a PADDED batch: the encoder's convolutions read the padding behind a shorter text, as the
         reference's graph would, and other kernels run at N > 2 than at N = 1 (model.last_paths["decode"]).  So entry i
         is close to synthesize(texts[i]), not bit-equal to it - and depends on which texts share its chunk.  The WaveNet
@@ -171,7 +175,8 @@ class Synthesizer(object):
                 mels = m.mel_outputs.float().cpu().numpy()
                 lins = m.linear_outputs.float().cpu().numpy()
                 m.check_status()            # (as in synthesize: invalid outputs are never vocoded)
-                full = self._wavenet_vocode_batch(mels, seed=seed + start, global_conditions=spk if self.vocoder.gc else None)
+                full = self._wavenet_vocode_batch(mels, seed=seed + start, global_conditions=spk if self.vocoder.gc else None,
+                                                  temperature=temperature)
                 wavs = [w[:audio.find_endpoint(w)] for w in full]
             else:
                 y, ends = audio.finish_waves(audio.griffin_lim_gpu(m.linear_outputs))
