@@ -20,7 +20,7 @@ import torch
 from .. import ops
 from .._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SOFTSIGN, ACT_TANH
 from . import params as P_
-from .tacotron2 import Tacotron2, _LazyAudio, _round_up
+from .tacotron2 import Tacotron2, _round_up
 
 
 class Act(object):
@@ -82,6 +82,7 @@ class Tacotron(Tacotron2):
     padl, padr = 8, 8     # bank widths up to 16: 'same' needs 7 left / 8 right; the data gradient the mirror
     use_attn_cluster = os.environ.get("NS_TACO1_ATTN_CLUSTER", "1") != "0"     # persistent attention loop (csrc/attn_gru.hip)
     LAYOUT = staticmethod(P_.taco1_layout)
+    ENC_CBHG, POST_CBHG = "encoder_cbhg", "post_cbhg"     # variable scopes of the two CBHG modules
     KW = 1    # Bahdanau = location-sensitive kernel with a 1-tap zero filter
 
     # num_speakers > 1 (tacotron.py:41-66): a 128-wide projection joins the decoder prenet output as in Tacotron-2
@@ -95,32 +96,27 @@ class Tacotron(Tacotron2):
             ops.cast2d(self.flat_p, 1, self.layout.size, self.layout.size, self.flat_s, self.layout.size, False)
         if not hasattr(self, "tsh"):
             self.tsh = {}
-        hp = self._hparams
+        hp, tr = self._hparams, self._shadowT
         dev, T = self.device, self.T
 
-        def tr(key, name, r0, rows, cols):
-            if key not in self.tsh:
-                self.tsh[key] = torch.zeros(cols * rows, dtype=T, device=dev)
-            ops.cast2d(self.flat_p, rows, cols, cols, self.tsh[key], rows, True, src_off=self._o(name) + r0 * cols)
-
         def gru(key, scope, cin, H):
-            tr(key + "_gT", scope + "/gates/kernel", cin, H, 2 * H)
-            tr(key + "_cT", scope + "/candidate/kernel", cin, H, H)
+            tr(key + "_gT", scope + "/gates/kernel", H, 2 * H, cin)
+            tr(key + "_cT", scope + "/candidate/kernel", H, H, cin)
 
         Dsp = self.Dsp
-        for cb in ("encoder_cbhg", "post_cbhg"):
-            cin = P_.cbhg_highway_widths(hp.speaker_embed_dim if Dsp and cb == "encoder_cbhg" else 0)[-1]
+        for cb in (self.ENC_CBHG, self.POST_CBHG):
+            cin = P_.cbhg_highway_widths(hp.speaker_embed_dim if Dsp and cb == self.ENC_CBHG else 0)[-1]
             for d in ("fw", "bw"):
                 gru("%s_%s" % (cb, d), "%s/bidirectional_rnn/%s/gru_cell" % (cb, d), cin, 128)
         A, D, M, E = hp.attention_dim, hp.decoder_dim, hp.num_mels, 256
         gru("gru_1", "decoder/gru_1", D, D)
         gru("gru_2", "decoder/gru_2", D, D)
         # attention GRU: the whole [x | h] kernels transposed (x = prenet output is not hoistable)
-        tr("att_gT", "decoder/attention_gru/gates/kernel", 0, 128 + Dsp + A, 2 * A)
-        tr("att_cT", "decoder/attention_gru/candidate/kernel", 0, 128 + Dsp + A, A)
-        tr("w1cT", "decoder/decoder_prenet/dense_1/kernel", M, E, 256)
-        tr("w2T", "decoder/decoder_prenet/dense_2/kernel", 0, 256, 128)
-        tr("wqT", "decoder/attention/query_layer/kernel", 0, A, A)
+        tr("att_gT", "decoder/attention_gru/gates/kernel", 128 + Dsp + A, 2 * A)
+        tr("att_cT", "decoder/attention_gru/candidate/kernel", 128 + Dsp + A, A)
+        tr("w1cT", "decoder/decoder_prenet/dense_1/kernel", E, 256, M)
+        tr("w2T", "decoder/decoder_prenet/dense_2/kernel", 256, 128)
+        tr("wqT", "decoder/attention/query_layer/kernel", A, A)
         if "wcl" not in self.tsh:
             self.tsh["wcl"] = torch.zeros(A, dtype=torch.float32, device=dev)      # zero location term
         F = hp.num_freq
@@ -709,13 +705,7 @@ class Tacotron(Tacotron2):
         for i in (1, 2):
             for f, nm in (("wg", "gates/kernel"), ("bg", "gates/bias"), ("wc", "candidate/kernel"), ("bc", "candidate/bias")):
                 setattr(q, "%s_%d" % (f, i), ops.ptr(fp, o("decoder/gru_%d/%s" % (i, nm))))
-        # folded feedback (exact fp32): wpf = W_out[:, last frame] . W_prenet1[frame rows], bpf = b_out[last frame] . same + b1
-        wpf = buf("pd_wpf", D * 256, torch.float32)
-        bpf = buf("pd_bpf", 256, torch.float32)
-        kp, bp = o("decoder/output_projection/kernel"), o("decoder/output_projection/bias")
-        ops.gemm(fp, fp, wpf, D, 256, M, M * r, 256, 256, b_mode=1, a_off=kp + (r - 1) * M, b_off=w1, f32_passes=0)
-        ops.gemm(fp, fp, bpf, 1, 256, M, M * r, 256, 256, b_mode=1, a_off=bp + (r - 1) * M, b_off=w1, bias=fp,
-                 bias_off=b1, f32_passes=0)
+        wpf, bpf = self.folded_feedback(D)
         q.wpf, q.bpf = ops.ptr(wpf), ops.ptr(bpf)
         y2 = buf("pd_y2", N * S1 * D, torch.float32)
         q.y2 = ops.ptr(y2)
@@ -730,7 +720,8 @@ class Tacotron(Tacotron2):
         self._status_words[("decode", "fwd")] = work
         # the output projection over the whole y2 history (tacotron.py:76), off the loop's critical path
         dec = buf("pd_dec", N * S1 * M * r, torch.float32)
-        ops.gemm(y2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=kp, bias=fp, bias_off=bp)
+        ops.gemm(y2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=o("decoder/output_projection/kernel"),
+                 bias=fp, bias_off=o("decoder/output_projection/bias"))
         return dec, al, S1
 
     def forward_infer(self):
@@ -751,37 +742,20 @@ class Tacotron(Tacotron2):
             self._sig = sig
         self._tape = []
         ops.F32_PASSES = self.passes_fwd
-        W, o, tsh, buf = self._W(T_), self._o, self.tsh, self._buf
-        # whole-kernel transposes for the [input | h] steps of the two decoder GRUs
-        for key, scope in (("gru_1", "decoder/gru_1"), ("gru_2", "decoder/gru_2")):
-            for suf, nm, cols in (("_gTf", "/gates/kernel", 2 * D), ("_cTf", "/candidate/kernel", D)):
-                if key + suf not in tsh:
-                    tsh[key + suf] = torch.zeros(cols * 2 * D, dtype=T_, device=self.device)
-                ops.cast2d(self.flat_p, 2 * D, cols, cols, tsh[key + suf], 2 * D, True, src_off=o(scope + nm))
-        for key, nm, rows, cols in (("w1T_full", "decoder/decoder_prenet/dense_1/kernel", M + E, 256),
-                                    ("wprojT", "decoder/attention_projection/kernel", A + E, D),
-                                    ("woutT", "decoder/output_projection/kernel", D, M * r)):
-            if key not in tsh:
-                tsh[key] = torch.zeros(rows * cols, dtype=T_, device=self.device)
-            ops.cast2d(self.flat_p, rows, cols, cols, tsh[key], rows, True, src_off=o(nm))
+        o, tsh, buf = self._o, self.tsh, self._buf
+        # whole-kernel transposes for the [input | h] steps of the two decoder GRUs, the prenet and the projections
+        for key in ("gru_1", "gru_2"):
+            self._shadowT(key + "_gTf", "decoder/%s/gates/kernel" % key, 2 * D, 2 * D)
+            self._shadowT(key + "_cTf", "decoder/%s/candidate/kernel" % key, 2 * D, D)
+        self._shadowT("w1T_full", "decoder/decoder_prenet/dense_1/kernel", M + E, 256)
+        self._shadowT("wprojT", "decoder/attention_projection/kernel", A + E, D)
+        self._shadowT("woutT", "decoder/output_projection/kernel", D, M * r)
+        self.dims = dict(N=N, Ti=Ti, To=To, S=S, Pi=Pi, Po=Po, Fp=Fp)
         lengths = self.input_lengths
-        emb = Act(self, "emb", N, Pi, self.padl, Ti, hp.embedding_dim)
-        ops.embedding_fwd(self.inputs, self.flat_p, emb.buf, N, Ti, Pi, self.padl, hp.embedding_dim, self.vocab,
-                          table_off=o("embedding/embedding"))
-        pn = list(hp.encoder_prenet)
-        x = self._dense("pre1", emb, "prenet/dense_1", pn[0], ACT_RELU)
-        x = self._dense("pre2", x, "prenet/dense_2", pn[1], ACT_RELU)
-        spk = self._speaker_rows(N)
-        enc = self._cbhg("enc", x, lengths, "encoder_cbhg", hp.encoder_cbhg_banks, list(hp.encoder_cbhg_bank_sizes), False,
-                         spk=spk)
+        enc, spk_dec, keys, keys_t = self._encoder(False)
         Dsp = self.Dsp
         XI = 128 + Dsp
-        spk_dec = self._dense("spk_dec", spk, "decoder/dense", Dsp, ACT_SOFTSIGN, mask=False) if Dsp else None
-        keys = buf("keys", N * Pi * A, torch.float32)
-        ops.gemm(enc.buf, W, keys, N * Pi, A, E, E, A, A, b_mode=1, b_off=o("attention_decoder/memory_layer/kernel"))
         Tia = _round_up(Ti, 8)
-        keys_t = buf("keys_t", N * A * Tia, torch.float32)
-        ops.keys_transpose(keys, keys_t, N, Ti, Tia, Pi, self.padl, A)
         # The whole free-running loop as ONE persistent launch per 16 utterances (csrc/attn_gru.hip "free-running
         # synthesis") where the widths and T_in allow, at every batch size; otherwise one decoder step = ~28 dependent
         # launches from here.  last_paths["decode"] says which ran.
@@ -835,19 +809,55 @@ class Tacotron(Tacotron2):
                 ops.gemm(y2, tsh["woutT"], dec, N, M * r, D, D, D, S1 * M * r, c_off=sl * M * r, bias=self.flat_p,
                          bias_off=o("decoder/output_projection/bias"))
                 ops.copy3d(dec, xp, N, 1, M, (S1 * M * r, 0), (S1 * XP, 0), src_off=sl * M * r + (r - 1) * M, dst_off=nx * XP)
-        melp = Act(self, "mel_pad", N, Po, self.padl, To, M)
-        ops.copy3d(dec, melp.buf, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
-        post = self._cbhg("post", melp, None, "post_cbhg", hp.post_cbhg_banks, list(hp.post_cbhg_bank_sizes) + [M], False)
-        lin = buf("lin_out", N * Po * Fp, torch.float32)
-        ops.gemm(post.buf, tsh["wl_pad"], lin, N * Po, Fp, 256, 256, Fp, Fp, b_mode=1, bias=tsh["bl_pad"])
+        self._tail(Act(self, "dec_out", N, S1, 1, S, M * r, buf=dec), al, S1, False)
         self._tape = []
-        self.dims = dict(N=N, Ti=Ti, To=To, S=S, Pi=Pi, Po=Po, Fp=Fp)
-        self.mel_outputs = dec[:N * S1 * M * r].view(N, S1, M * r)[:, 1:S + 1].reshape(N, To, M)
-        self.decoder_outputs = self.mel_outputs
-        self.linear_outputs = lin[:N * Po * Fp].view(N, Po, Fp)[:, self.padl:self.padl + To, :F]
-        self.alignments = al[:N * S1 * Tia].view(N, S1, Tia)[:, 1:S + 1, :Ti].permute(0, 2, 1)
-        self.audio = _LazyAudio(self)           # tacotron.py:107, vocoded when read
         return self
+
+    # ------------------------------------------------------------------ sections shared by training and synthesis
+    def _encoder(self, training):
+        """embedding -> prenet -> CBHG (tacotron.py:38-62), the decoder's speaker projection and the attention memory.
+        Returns (enc, spk_dec, keys, keys_t)."""
+        hp, o = self._hparams, self._o
+        d = self.dims
+        N, Ti, Pi = d["N"], d["Ti"], d["Pi"]
+        A, E = hp.attention_dim, 256
+        emb = Act(self, "emb", N, Pi, self.padl, Ti, hp.embedding_dim)
+        ops.embedding_fwd(self.inputs, self.flat_p, emb.buf, N, Ti, Pi, self.padl, hp.embedding_dim, self.vocab,
+                          table_off=o("embedding/embedding"))
+        if training:
+            self._tape.append(lambda: ops.embedding_bwd(self.inputs, emb.grad, self.flat_g, N, Ti, Pi, self.padl,
+                                                        hp.embedding_dim, self.vocab, dtable_off=o("embedding/embedding")))
+        pn = list(hp.encoder_prenet)
+        x = self._dense("pre1", emb, "prenet/dense_1", pn[0], ACT_RELU)
+        x = self._dense("pre2", x, "prenet/dense_2", pn[1], ACT_RELU)
+        spk = self._speaker_rows(N)
+        enc = self._cbhg("enc", x, self.input_lengths, self.ENC_CBHG, hp.encoder_cbhg_banks,
+                         list(hp.encoder_cbhg_bank_sizes), training, spk=spk)
+        spk_dec = self._dense("spk_dec", spk, "decoder/dense", self.Dsp, ACT_SOFTSIGN, mask=False) if self.Dsp else None
+        keys = self._buf("keys", N * Pi * A, torch.float32)
+        ops.gemm(enc.buf, self._W(self.T), keys, N * Pi, A, E, E, A, A, b_mode=1, b_off=o(self.MEMORY))
+        Tia = _round_up(Ti, 8)
+        keys_t = self._buf("keys_t", N * A * Tia, torch.float32)
+        ops.keys_transpose(keys, keys_t, N, Ti, Tia, Pi, self.padl, A)
+        return enc, spk_dec, keys, keys_t
+
+    def _tail(self, dec, al, S1, training):
+        """post CBHG + linear head (tacotron.py:92-98) and the output views.  dec: the decoder's frames as an Act in the
+        [N, S1, M*r] slot layout.  Returns (melp, post, lin)."""
+        hp, d = self._hparams, self.dims
+        N, To, Po, Fp = d["N"], d["To"], d["Po"], d["Fp"]
+        r, M = hp.outputs_per_step, hp.num_mels
+        melp = Act(self, "mel_pad", N, Po, self.padl, To, M)
+        ops.copy3d(dec.buf, melp.buf, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
+        if training:
+            self._tape.append(lambda: ops.copy3d(melp.grad, dec.grad, N, To, M, (Po * M, M), (S1 * M * r, M),
+                                                 src_off=self.padl * M, dst_off=M * r, accumulate=1))
+        post = self._cbhg("post", melp, None, self.POST_CBHG, hp.post_cbhg_banks, list(hp.post_cbhg_bank_sizes) + [M],
+                          training)
+        lin = self._buf("lin_out", N * Po * Fp, torch.float32)
+        ops.gemm(post.buf, self.tsh["wl_pad"], lin, N * Po, Fp, 256, 256, Fp, Fp, b_mode=1, bias=self.tsh["bl_pad"])
+        self._set_outputs(dec.buf, al, S1, lin)
+        return melp, post, lin
 
     # ------------------------------------------------------------------ forward (training)
     def forward_train(self):
@@ -872,29 +882,11 @@ class Tacotron(Tacotron2):
         o = self._o
         lengths = self.input_lengths
 
-        # ---- encoder: embedding -> prenet -> CBHG (tacotron.py:38-62)
-        emb = Act(self, "emb", N, Pi, self.padl, Ti, hp.embedding_dim)
-        ops.embedding_fwd(self.inputs, self.flat_p, emb.buf, N, Ti, Pi, self.padl, hp.embedding_dim, self.vocab,
-                          table_off=o("embedding/embedding"))
-        self._tape.append(lambda: ops.embedding_bwd(self.inputs, emb.grad, g, N, Ti, Pi, self.padl, hp.embedding_dim,
-                                                    self.vocab, dtable_off=o("embedding/embedding")))
-        pn = list(hp.encoder_prenet)
-        x = self._dense("pre1", emb, "prenet/dense_1", pn[0], ACT_RELU)
-        x = self._dense("pre2", x, "prenet/dense_2", pn[1], ACT_RELU)
-        spk = self._speaker_rows(N)
-        enc = self._cbhg("enc", x, lengths, "encoder_cbhg", hp.encoder_cbhg_banks, list(hp.encoder_cbhg_bank_sizes), True,
-                         spk=spk)
+        # ---- encoder, attention memory
+        enc, self._spk_dec, keys, keys_t = self._encoder(True)
         self._enc = enc
         Dsp = self.Dsp
-        self._spk_dec = self._dense("spk_dec", spk, "decoder/dense", Dsp, ACT_SOFTSIGN, mask=False) if Dsp else None
-
-        # ---- attention memory
-        keys = self._buf("keys", N * Pi * A, torch.float32)
-        om = o("attention_decoder/memory_layer/kernel")
-        ops.gemm(enc.buf, W, keys, N * Pi, A, E, E, A, A, b_mode=1, b_off=om)
         Tia = _round_up(Ti, 8)
-        keys_t = self._buf("keys_t", N * A * Tia, torch.float32)
-        ops.keys_transpose(keys, keys_t, N, Ti, Tia, Pi, self.padl, A)
 
         # ---- attention RNN over all steps (teacher forced): prenet (-> | speaker projection) -> GRU(A) -> Bahdanau
         XI = 128 + Dsp                            # the GRU's input width
@@ -987,7 +979,6 @@ class Tacotron(Tacotron2):
         decA = Act(self, "dec_out", N, S1, 1, S, M * r, dtype=torch.float32)
         op_, ob_ = o("decoder/output_projection/kernel"), o("decoder/output_projection/bias")
         ops.gemm(y2.buf, W, decA.buf, y2.rows, M * r, D, D, M * r, M * r, b_mode=1, b_off=op_, bias=self.flat_p, bias_off=ob_)
-        dec = decA.buf
 
         def out_proj_bwd():
             dd = self._buf("t:ddec", y2.rows * M * r, T_)
@@ -998,22 +989,9 @@ class Tacotron(Tacotron2):
             ops.gemm(dd, W, y2.grad, y2.rows, D, M * r, M * r, M * r, D, a_mode=0, b_mode=0, b_off=op_, accumulate=1)
         self._tape.append(out_proj_bwd)
 
-        # ---- post CBHG + linear head (tacotron.py:92-98)
-        melp = Act(self, "mel_pad", N, Po, self.padl, To, M)
-        ops.copy3d(dec, melp.buf, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
-        self._tape.append(lambda: ops.copy3d(melp.grad, decA.grad, N, To, M, (Po * M, M), (S1 * M * r, M),
-                                             src_off=self.padl * M, dst_off=M * r, accumulate=1))
-        post = self._cbhg("post", melp, None, "post_cbhg", hp.post_cbhg_banks, list(hp.post_cbhg_bank_sizes) + [M], True)
-        lin = self._buf("lin_out", N * Po * Fp, torch.float32)
-        ops.gemm(post.buf, tsh["wl_pad"], lin, N * Po, Fp, 256, 256, Fp, Fp, b_mode=1, bias=tsh["bl_pad"])
-
+        melp, post, lin = self._tail(decA, al, S1, True)
         self._state = dict(keys=keys, keys_t=keys_t, fr=fr, f1=f1, p1=p1, xa=xa, xc=xc, hc=hc, ru=ru, cc=cc, q=q, al=al,
                            al_t=al_t, hcA=hcA, y2=y2, decA=decA, melp=melp, post=post, lin=lin, Tia=Tia)
-        self.mel_outputs = dec[:N * S1 * M * r].view(N, S1, M * r)[:, 1:].reshape(N, To, M)
-        self.decoder_outputs = self.mel_outputs
-        self.linear_outputs = lin[:N * Po * Fp].view(N, Po, Fp)[:, self.padl:self.padl + To, :F]
-        self.alignments = al[:N * S1 * Tia].view(N, S1, Tia)[:, 1:, :Ti].permute(0, 2, 1)
-        self.audio = _LazyAudio(self)           # tacotron.py:107, vocoded when read
         return self
 
     # ------------------------------------------------------------------ loss + backward
@@ -1177,7 +1155,7 @@ class Tacotron(Tacotron2):
         ops.keys_transpose_add(dkeys, dkeys_t, N, Ti, Tia, Pi, self.padl, A)
         dkeys_T = buf("att_dkeys_T", N * Pi * A, T_)
         ops.copy3d(dkeys, dkeys_T, 1, N * Pi, A, (0, A), (0, A))
-        om = o("attention_decoder/memory_layer/kernel")
+        om = o(self.MEMORY)
         ops.gemm(enc.buf, dkeys_T, g, E, A, N * Pi, E, A, A, a_mode=1, b_mode=1, c_off=om, accumulate=2, split_k=sk(N * Pi, E, A))
         ops.gemm(dkeys_T, W, enc.grad, N * Pi, E, A, A, A, E, a_mode=0, b_mode=0, b_off=om, accumulate=1)
         # dvalues[n] += align[n]^T . dctx[n], all utterances in one batched launch

@@ -16,6 +16,7 @@ MI355X-first restructuring of the training step (results identical to the refere
 """
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -53,8 +54,25 @@ class _LazyAudio(object):
         return audio.inv_spectrogram_tensorflow(self._m.linear_outputs.float().contiguous())
 
 
+class ConvStack(namedtuple("ConvStack", "scope tag layers cin channels width act dtype presplit lstm units")):
+    """One conv1d + BatchNorm stack of the graph, stated once for both forward passes and for backward().
+    scope: format of a layer's variable scope; tag: prefix of its buffer names; act: the activation of every layer but
+    the last; dtype: storage; presplit: a layer may hand its output to the next one as a pre-split bf16 pair (postnet
+    only); lstm, units: scope and width of the BiLSTM that reads the stack (None, 0: the postnet has none)."""
+    __slots__ = ()
+
+    def tag_of(self, i):
+        return "%s%d" % (self.tag, i)
+
+    def layer(self, i):
+        """(scope, tag, activation, input channels) of layer i."""
+        return (self.scope % i, "%s%d" % (self.tag, i), self.act if i < self.layers - 1 else ACT_NONE,
+                self.cin if i == 0 else self.channels)
+
+
 class Tacotron2(object):
     padl, padr = PADL, PADR
+    MEMORY = "attention_decoder/memory_layer/kernel"     # keys = values . W_memory, in both Tacotron models
     LAYOUT = staticmethod(P_.taco2_layout)
     _speaker_width = staticmethod(P_.taco2_speaker_width)
 
@@ -323,6 +341,26 @@ class Tacotron2(object):
     def _lin_pad(self, F):
         """Padded column count of the linear head / linear_outputs buffer."""
         return _round_up(F, 128) if (self.Tx == torch.bfloat16 and F >= 512) else _round_up(F, 16)
+
+    def _shadowT(self, key, name, rows, cols, r0=0):
+        """tsh[key] = the k-contiguous copy of rows r0 .. r0 + rows of the [*, cols] kernel `name`, in the storage dtype."""
+        if key not in self.tsh:
+            self.tsh[key] = torch.zeros(cols * rows, dtype=self.T, device=self.device)
+        ops.cast2d(self.flat_p, rows, cols, cols, self.tsh[key], rows, True, src_off=self._o(name) + r0 * cols)
+
+    def folded_feedback(self, D):
+        """The free-running decoders' frame feedback folded into the first prenet layer (exact fp32):
+        wpf = W_proj[:, last frame] . W_prenet1[frame rows], bpf = b_proj[last frame] . same + b1.  Returns (wpf, bpf)."""
+        hp, fp, o = self._hparams, self.flat_p, self._o
+        r, M = hp.outputs_per_step, hp.num_mels
+        wpf = self._buf("fold_wpf", D * 256, torch.float32)
+        bpf = self._buf("fold_bpf", 256, torch.float32)
+        kp, bp = o("decoder/output_projection/kernel"), o("decoder/output_projection/bias")
+        w1 = o("decoder/decoder_prenet/dense_1/kernel")
+        ops.gemm(fp, fp, wpf, D, 256, M, M * r, 256, 256, b_mode=1, a_off=kp + (r - 1) * M, b_off=w1, f32_passes=0)
+        ops.gemm(fp, fp, bpf, 1, 256, M, M * r, 256, 256, b_mode=1, a_off=bp + (r - 1) * M, b_off=w1, bias=fp,
+                 bias_off=o("decoder/decoder_prenet/dense_1/bias"), f32_passes=0)
+        return wpf, bpf
 
     # ------------------------------------------------------------------ buffers
     def _buf(self, name, numel, dtype, zero=True):
@@ -973,6 +1011,170 @@ class Tacotron2(object):
         ops.embedding_bwd(self.speaker_ids, dse, g, N, 1, 1, 0, sd, self.n_speakers,
                           dtable_off=self._o("speaker/speaker_embed"))
 
+    # ------------------------------------------------------------------ graph sections shared by training and synthesis
+    @property
+    def stacks(self):
+        st = self.__dict__.get("_stacks")
+        if st is None:
+            hp = self._hparams
+            st = self._stacks = dict(
+                enc=ConvStack("encoder/conv_%d", "enc", hp.encoder_conv_layers, hp.embedding_dim, hp.encoder_conv_channels,
+                              hp.encoder_conv_width, ACT_RELU, self.T, False, "encoder/encoder_lstm", hp.encoder_lstm_units),
+                post=ConvStack("decoder_postnet/postnet_conv_%d", "post", hp.postnet_conv_layers, hp.num_mels,
+                               hp.postnet_conv_channels, hp.postnet_conv_width, ACT_TANH, self.T, True, None, 0),
+                exp=ConvStack("expand/conv_%d", "exp", hp.expand_conv_layers, hp.num_mels, hp.expand_conv_channels,
+                              hp.expand_conv_width, ACT_RELU, self.Tx, False, "expand/encoder_lstm", hp.expand_lstm_units))
+        return st
+
+    def _stack_fwd(self, st, x, N, T, Pp, training):
+        """The layers of one ConvStack over x.  Returns (output, [input of layer 0, ..., input of the reader])."""
+        ins = [x]
+        for i in range(st.layers):
+            scope, tag, act, cin = st.layer(i)
+            # a layer whose consumer runs on the 256-tile kernel hands its output over as a pre-split bf16 pair
+            nxt = (st.presplit and i + 1 < st.layers
+                   and self._x256_split_ok(st.tag_of(i + 1), N * Pp, st.channels, st.channels, st.width))
+            split_in = isinstance(x, tuple)
+            x = self._conv_fwd(scope, None if split_in else x, cin, st.channels, st.width, act, N, T, Pp, tag,
+                               training=training, D=st.dtype, xsplit=x if split_in else None, emit_split=nxt)
+            ins.append(x)
+        return x, ins
+
+    def _stack_bwd(self, st, ins, dy, spare, N, T, Pp, defer, into=None):
+        """Backward of _stack_fwd, top layer first.  dy: the gradient wrt the stack's output; it and `spare` take the
+        layers' input gradients in turn, and each data-gradient product leaves the BatchNorm-backward sums of the layer
+        below (the producer of dy did that for the top layer).  Layer 0's input gradient is added to `into` where given,
+        else it is in the returned buffer."""
+        cur, nxt = dy, spare
+        for i in range(st.layers - 1, -1, -1):
+            scope, tag, act, cin = st.layer(i)
+            last = i == 0 and into is not None
+            self._conv_bwd(scope, ins[i], cur, cin, st.channels, st.width, act, N, T, Pp, tag, into if last else nxt,
+                           dx_accumulate=last, D=st.dtype, defer=defer, stats_for=st.tag_of(i - 1) if i > 0 else None)
+            cur, nxt = nxt, cur
+        return cur
+
+    def _post_dense(self):
+        return self._o("decoder_postnet/dense/kernel"), self._o("decoder_postnet/dense/bias")
+
+    def encoder(self, training):
+        """embedding -> conv stack -> BiLSTM -> keys = values . W_memory (tacotron2.py:37-60; the values are already zero
+        past each length).  Returns (enc, keys); the training pass keeps the layer inputs for backward()."""
+        hp, st = self._hparams, self.stacks["enc"]
+        N, Ti = self.inputs.shape
+        Pi = self.dims["Pi"]
+        A, E = hp.attention_dim, 2 * st.units
+        x = self._buf("enc_x0", N * Pi * st.cin, self.T)
+        ops.embedding_fwd(self.inputs, self.flat_p, x, N, Ti, Pi, self.padl, st.cin, self.vocab,
+                          table_off=self._o("embedding/embedding"))
+        x, ins = self._stack_fwd(st, x, N, Ti, Pi, training)
+        enc = self._bilstm_fwd(st.lstm, x, st.channels, st.units, N, Ti, Pi, self.input_lengths, "encl", "enc")
+        if training:
+            self._enc_in = ins
+            self._tick("encoder")
+        keys = self._buf("keys", N * Pi * A, torch.float32)
+        ops.gemm(enc, self._W(self.T), keys, N * Pi, A, E, E, A, A, b_mode=1, b_off=self._o(self.MEMORY))
+        return enc, keys
+
+    def attn_block(self, enc, keys, training):
+        """Buffers and arguments (ns_taco2_attn_params, through ops._attn_params) of the attention RNN over all S steps
+        in the [N, S+1, X] slot layout: what the teacher-forced pass and the one-launch synthesis decoder share.  The
+        frames fed back are the targets when training and <GO> = zeros otherwise: then the frame term f1 is the prenet
+        bias in every slot (only slot 1 is read)."""
+        hp = self._hparams
+        T_, buf, o, W, fp = self.T, self._buf, self._o, self._W(self.T), self.flat_p
+        d = self.dims
+        N, Ti, To, S, Pi = d["N"], d["Ti"], d["To"], d["S"], d["Pi"]
+        r, M = hp.outputs_per_step, hp.num_mels
+        E, A = 2 * hp.encoder_lstm_units, hp.attention_dim
+        S1, Dsp = S + 1, self.Dsp
+        XA = 128 + Dsp + A
+        fr = buf("dec_fr", N * S1 * M, T_)
+        if training and S > 1:   # slot s+1 <- mel_targets[:, s*r-1] for s >= 1 ; slot 1 stays <GO> = 0
+            ops.copy3d(self.mel_targets, fr, N, S - 1, M, (To * M, r * M), (S1 * M, M), src_off=(r - 1) * M,
+                       dst_off=2 * M)
+        f1 = buf("dec_f1", N * S1 * 256, torch.float32)
+        w1 = o("decoder/decoder_prenet/dense_1/kernel")
+        ops.gemm(fr, W, f1, N * S1, 256, M, M, 256, 256, b_mode=1, b_off=w1, bias=fp,
+                 bias_off=o("decoder/decoder_prenet/dense_1/bias"))
+        Tia = _round_up(Ti, 8)
+        p1 = buf("dec_p1", N * S1 * 256, T_)
+        xa = buf("dec_xa", N * S1 * XA, T_)
+        if Dsp:     # the per-utterance speaker projection sits between the prenet output and h in every slot
+            ops.copy3d(self._speaker_fwd(N), xa, N, S1, Dsp, (Dsp, 0), (S1 * XA, XA), dst_off=128)
+        hc = buf("dec_hc", N * S1 * (A + E), T_)
+        ca = buf("dec_ca", N * S1 * A, torch.float32)
+        ga = buf("dec_ga", N * S1 * 4 * A, T_)
+        q = buf("dec_q", N * S1 * A, torch.float32)
+        al = buf("dec_al", N * S1 * Tia, torch.float32)
+        # projected memory: values . W1c once per pass, so that inside the loop the context kernel yields the next
+        # step's prenet layer directly and the 512-wide contexts are formed after the loop (DESIGN 2)
+        pv = None
+        if self.use_pv or not training:
+            pv = buf("dec_pv", N * Pi * 256, T_)
+            ops.gemm(enc, W, pv, N * Pi, 256, E, E, 256, 256, b_mode=1, b_off=w1 + M * 256)
+        # the natural-layout weights: the persistent kernels keep them in registers
+        return dict(
+            pv=pv, Dsp=Dsp, dtype=ops.dt(hc), N=N, S=S, Ti=Ti, Pi=Pi, padl_i=self.padl, Tia=Tia, A=A, E=E, D1=256, D2=128,
+            kw=7, lengths=self.input_lengths, keys=keys, values=enc, f1=f1,
+            b2=(fp, o("decoder/decoder_prenet/dense_2/bias")), batt=(fp, o("decoder/attention_lstm/bias")),
+            wcl=self.tsh["wcl"], v=(fp, o("decoder/attention/attention_v")),
+            p1=p1, xa=xa, hc=hc, ca=ca, ga=ga, q=q, align=al,
+            w2=(W, o("decoder/decoder_prenet/dense_2/kernel")), watt=(W, o("decoder/attention_lstm/kernel")),
+            wq=(W, o("decoder/attention/query_layer/kernel")))
+
+    def tail(self, dec, al, S1, training):
+        """Everything behind the decoder (tacotron2.py:89-107): postnet + residual, expand net, linear head and the
+        output views.  dec, al: the frames and alignments in the [N, S1, X] slot layout (step s in slot s+1)."""
+        hp = self._hparams
+        T_, buf, W = self.T, self._buf, self._W(self.T)
+        d = self.dims
+        N, To, Po, Fp = d["N"], d["To"], d["Po"], d["Fp"]
+        r, M = hp.outputs_per_step, hp.num_mels
+        post, exp = self.stacks["post"], self.stacks["exp"]
+        tick = self._tick if training else (lambda label: None)
+        decp = buf("decp", N * Po * M, torch.float32)
+        pin = buf("post_in", N * Po * M, T_)
+        ops.copy3d(dec, decp, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
+        ops.copy3d(dec, pin, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
+        x, pins = self._stack_fwd(post, pin, N, To, Po, training)
+        mel = buf("mel_out", N * Po * M, torch.float32)
+        kd, bd = self._post_dense()
+        Cp = post.channels
+        ops.gemm(x, W, mel, N * Po, M, Cp, Cp, M, M, b_mode=1, b_off=kd, bias=self.flat_p, bias_off=bd,
+                 row_mask=(Po, self.padl, self.padl + To, 0))
+        ops.copy3d(decp, mel, N, Po, M, (Po * M, M), (Po * M, M), accumulate=1)
+        tick("postnet")
+        ein = buf("exp_in", N * Po * M, exp.dtype)
+        ops.copy3d(mel, ein, N, Po, M, (Po * M, M), (Po * M, M))
+        x, eins = self._stack_fwd(exp, ein, N, To, Po, training)
+        if training:
+            self._post_in, self._exp_in = pins, eins
+        tick("expand_conv")
+        Hx = exp.units
+        ex = self._bilstm_fwd(exp.lstm, x, exp.channels, Hx, N, To, Po, None, "expl", "exp", D=exp.dtype)
+        tick("expand_lstm")
+        lin = buf("lin_out", N * Po * Fp, torch.float32)
+        if "wl_padT" in self.tsh:
+            ops.gemm(ex, self.tsh["wl_padT"], lin, N * Po, Fp, 2 * Hx, 2 * Hx, 2 * Hx, Fp, b_mode=0, bias=self.tsh["bl_pad"])
+        else:
+            ops.gemm(ex, self.tsh["wl_pad"], lin, N * Po, Fp, 2 * Hx, 2 * Hx, Fp, Fp, b_mode=1, bias=self.tsh["bl_pad"])
+        tick("linear")
+        return self._set_outputs(dec, al, S1, lin, mel)
+
+    def _set_outputs(self, dec, al, S1, lin, mel=None):
+        """The output attributes as views of the padded buffers.  mel=None (Tacotron-1): mel_outputs are the decoder's."""
+        hp, d, padl = self._hparams, self.dims, self.padl
+        N, Ti, To, S, Po, Fp = d["N"], d["Ti"], d["To"], d["S"], d["Po"], d["Fp"]
+        r, M, F = hp.outputs_per_step, hp.num_mels, hp.num_freq
+        Tia = _round_up(Ti, 8)
+        self.decoder_outputs = dec[:N * S1 * M * r].view(N, S1, M * r)[:, 1:S + 1].reshape(N, To, M)
+        self.mel_outputs = self.decoder_outputs if mel is None else mel[:N * Po * M].view(N, Po, M)[:, padl:padl + To]
+        self.linear_outputs = lin[:N * Po * Fp].view(N, Po, Fp)[:, padl:padl + To, :F]
+        self.alignments = al[:N * S1 * Tia].view(N, S1, Tia)[:, 1:S + 1, :Ti].permute(0, 2, 1)
+        self.audio = _LazyAudio(self)           # vocoded when read
+        return self
+
     # ------------------------------------------------------------------ training forward
     def forward_train(self):
         hp = self._hparams
@@ -996,74 +1198,20 @@ class Tacotron2(object):
         self._tick("start")
         ops.F32_PASSES = self.passes_fwd
         ops.CELL_CLIP = self.cell_clip
-        Tx = self.Tx
 
-        # ---- encoder (tacotron2.py:37-60)
-        emb = hp.embedding_dim
-        x = self._buf("enc_x0", N * Pi * emb, T_)
-        ops.embedding_fwd(self.inputs, self.flat_p, x, N, Ti, Pi, self.padl, emb, self.vocab,
-                          table_off=self._o("embedding/embedding"))
-        cin = emb
-        self._enc_in = [x]
-        for i in range(hp.encoder_conv_layers):
-            act = ACT_RELU if i < hp.encoder_conv_layers - 1 else ACT_NONE
-            x = self._conv_fwd("encoder/conv_%d" % i, x, cin, hp.encoder_conv_channels, hp.encoder_conv_width, act,
-                               N, Ti, Pi, "enc%d" % i)
-            cin = hp.encoder_conv_channels
-            self._enc_in.append(x)
-        enc = self._bilstm_fwd("encoder/encoder_lstm", x, cin, hp.encoder_lstm_units, N, Ti, Pi, self.input_lengths,
-                               "encl", "enc")
-        self._tick("encoder")
-        # keys = values . W_memory (values = encoder outputs, already zero past each length)
-        keys = self._buf("keys", N * Pi * A, torch.float32)
-        ops.gemm(enc, self._W(self.T), keys, N * Pi, A, E, E, A, A, b_mode=1,
-                 b_off=self._o("attention_decoder/memory_layer/kernel"))
+        enc, keys = self.encoder(True)
 
-        # ---- decoder, attention RNN for all steps (tacotron2.py:63-83, teacher forced)
-        fr = self._buf("dec_fr", N * S1 * M, T_)
-        if S > 1:   # slot s+1 <- mel_targets[:, s*r-1] for s >= 1 ; slot 1 stays <GO> = 0
-            ops.copy3d(self.mel_targets, fr, N, S - 1, M, (To * M, r * M), (S1 * M, M), src_off=(r - 1) * M,
-                       dst_off=2 * M)
-        f1 = self._buf("dec_f1", N * S1 * 256, torch.float32)
-        w1 = self._o("decoder/decoder_prenet/dense_1/kernel")
-        ops.gemm(fr, self._W(self.T), f1, N * S1, 256, M, M, 256, 256, b_mode=1, b_off=w1, bias=self.flat_p,
-                 bias_off=self._o("decoder/decoder_prenet/dense_1/bias"))
-        Tia = _round_up(Ti, 8)
-        p1 = self._buf("dec_p1", N * S1 * 256, T_)
-        Dsp = self.Dsp
-        xa = self._buf("dec_xa", N * S1 * (128 + Dsp + A), T_)
-        if Dsp:     # the per-utterance speaker projection sits between the prenet output and h in every slot
-            ops.copy3d(self._speaker_fwd(N), xa, N, S1, Dsp, (Dsp, 0), (S1 * (128 + Dsp + A), 128 + Dsp + A), dst_off=128)
-        hc = self._buf("dec_hc", N * S1 * (A + E), T_)
-        ca = self._buf("dec_ca", N * S1 * A, torch.float32)
-        ga = self._buf("dec_ga", N * S1 * 4 * A, T_)
-        q = self._buf("dec_q", N * S1 * A, torch.float32)
-        al = self._buf("dec_al", N * S1 * Tia, torch.float32)
-        # projected memory: values . W1c once per pass, so that inside the loop the context kernel yields the next
-        # step's prenet layer directly and the 512-wide contexts are formed after the loop
-        pv = None
-        if self.use_pv:
-            pv = self._buf("dec_pv", N * Pi * 256, T_)
-            ops.gemm(enc, self._W(self.T), pv, N * Pi, 256, E, E, 256, 256, b_mode=1, b_off=w1 + M * 256)
-        self._attn_args = dict(
-            pv=pv, Dsp=Dsp,
-            dtype=ops.dt(hc), N=N, S=S, Ti=Ti, Pi=Pi, padl_i=self.padl, Tia=Tia, A=A, E=E, D1=256, D2=128, kw=7,
-            lengths=self.input_lengths, keys=keys, values=enc, f1=f1,
+        # ---- decoder, attention RNN for all steps (tacotron2.py:63-83, teacher forced): the shared block plus what only
+        # the training kernels read (transposed shadows, the per-step path's keys_t / work, the context part W1c)
+        args = self._attn_args = self.attn_block(enc, keys, True)
+        Tia, hc, al = args["Tia"], args["hc"], args["align"]
+        args.update(
             w1cT=self.tsh["w1cT"], w2T=self.tsh["w2T"], wattT=self.tsh["wattT"], wqT=self.tsh["wqT"],
-            b2=(self.flat_p, self._o("decoder/decoder_prenet/dense_2/bias")),
-            batt=(self.flat_p, self._o("decoder/attention_lstm/bias")),
-            wcl=self.tsh["wcl"], v=(self.flat_p, self._o("decoder/attention/attention_v")),
-            p1=p1, xa=xa, hc=hc, ca=ca, ga=ga, q=q, align=al,
             keys_t=self._buf("dec_keys_t", N * A * Tia, torch.float32),
             work=self._buf("attn_work", N * (E + 9 * Tia + 2 * A + A * Tia) + 64, torch.float32),
             wattT_hi=self.tsh.get("wattT_hi"), wattT_lo=self.tsh.get("wattT_lo"),
-            align_t=self._buf("dec_al_t", N * S1 * Tia, T_))
-        # the natural-layout weights: the persistent kernel keeps them in registers (the backward call needs them anyway)
-        w2 = self._o("decoder/decoder_prenet/dense_2/kernel")
-        wa = self._o("decoder/attention_lstm/kernel")
-        wq = self._o("decoder/attention/query_layer/kernel")
-        self._attn_args.update(w1c=(self._W(self.T), w1 + M * 256), w2=(self._W(self.T), w2),
-                               watt=(self._W(self.T), wa), wq=(self._W(self.T), wq))
+            align_t=self._buf("dec_al_t", N * S1 * Tia, T_),
+            w1c=(self._W(self.T), self._o("decoder/decoder_prenet/dense_1/kernel") + M * 256))
         self._attn_cluster_fwd = self.use_attn_cluster and ops.taco2_attn_cluster_supported(**self._attn_args)
         if self._attn_cluster_fwd:
             cw = self._buf("attn_cluster_work", ops.taco2_attn_cluster_work_floats(**self._attn_args), torch.float32)
@@ -1108,62 +1256,7 @@ class Tacotron2(object):
                  bias_off=self._o("decoder/output_projection/bias"))
         self._tick("dec_lstm")
 
-        # ---- postnet + residual (tacotron2.py:89-95)
-        decp = self._buf("decp", N * Po * M, torch.float32)
-        pin = self._buf("post_in", N * Po * M, T_)
-        ops.copy3d(dec, decp, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
-        ops.copy3d(dec, pin, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=self.padl * M)
-        x = pin
-        cin = M
-        self._post_in = [x]
-        Cp = hp.postnet_conv_channels
-        for i in range(hp.postnet_conv_layers):
-            act = ACT_TANH if i < hp.postnet_conv_layers - 1 else ACT_NONE
-            # a layer whose consumer runs on the 256-tile kernel hands its output over as a pre-split bf16 pair
-            nxt = i + 1 < hp.postnet_conv_layers and self._x256_split_ok("post%d" % (i + 1), N * Po, Cp, Cp, hp.postnet_conv_width)
-            split_in = isinstance(x, tuple)
-            x = self._conv_fwd("decoder_postnet/postnet_conv_%d" % i, None if split_in else x, cin, Cp,
-                               hp.postnet_conv_width, act, N, To, Po, "post%d" % i, xsplit=x if split_in else None,
-                               emit_split=nxt)
-            cin = Cp
-            self._post_in.append(x)
-        mel = self._buf("mel_out", N * Po * M, torch.float32)
-        ops.gemm(x, self._W(self.T), mel, N * Po, M, Cp, Cp, M, M, b_mode=1,
-                 b_off=self._o("decoder_postnet/dense/kernel"), bias=self.flat_p,
-                 bias_off=self._o("decoder_postnet/dense/bias"), row_mask=(Po, self.padl, self.padl + To, 0))
-        ops.copy3d(decp, mel, N, Po, M, (Po * M, M), (Po * M, M), accumulate=1)
-        self._tick("postnet")
-
-        # ---- expand net + linear head (tacotron2.py:97-107)
-        ein = self._buf("exp_in", N * Po * M, Tx)
-        ops.copy3d(mel, ein, N, Po, M, (Po * M, M), (Po * M, M))
-        x = ein
-        cin = M
-        self._exp_in = [x]
-        Cx = hp.expand_conv_channels
-        for i in range(hp.expand_conv_layers):
-            act = ACT_RELU if i < hp.expand_conv_layers - 1 else ACT_NONE
-            x = self._conv_fwd("expand/conv_%d" % i, x, cin, Cx, hp.expand_conv_width, act, N, To, Po, "exp%d" % i,
-                               D=Tx)
-            cin = Cx
-            self._exp_in.append(x)
-        self._tick("expand_conv")
-        Hx = hp.expand_lstm_units
-        ex = self._bilstm_fwd("expand/encoder_lstm", x, cin, Hx, N, To, Po, None, "expl", "exp", D=Tx)
-        self._tick("expand_lstm")
-        lin = self._buf("lin_out", N * Po * Fp, torch.float32)
-        if "wl_padT" in self.tsh:
-            ops.gemm(ex, self.tsh["wl_padT"], lin, N * Po, Fp, 2 * Hx, 2 * Hx, 2 * Hx, Fp, b_mode=0, bias=self.tsh["bl_pad"])
-        else:
-            ops.gemm(ex, self.tsh["wl_pad"], lin, N * Po, Fp, 2 * Hx, 2 * Hx, Fp, Fp, b_mode=1, bias=self.tsh["bl_pad"])
-        self._tick("linear")
-
-        self.mel_outputs = mel[:N * Po * M].view(N, Po, M)[:, self.padl:self.padl + To]
-        self.linear_outputs = lin[:N * Po * Fp].view(N, Po, Fp)[:, self.padl:self.padl + To, :F]
-        self.decoder_outputs = dec[:rows * M * r].view(N, S1, M * r)[:, 1:].reshape(N, To, M)
-        self.alignments = al[:N * S1 * Tia].view(N, S1, Tia)[:, 1:, :Ti].permute(0, 2, 1)
-        self.audio = _LazyAudio(self)
-        return self
+        return self.tail(dec, al, S1, True)
 
     # ------------------------------------------------------------------ loss + backward
     def backward(self):
@@ -1196,7 +1289,8 @@ class Tacotron2(object):
         self._tick("loss")
 
         # ---- linear head
-        Hx = hp.expand_lstm_units
+        est, pst, cst = self.stacks["exp"], self.stacks["post"], self.stacks["enc"]
+        Hx = est.units
         ex = B["expl_h"]
         rows_o = N * Po
         dwl = self._buf("d_wl_pad", 2 * Hx * Fp, torch.float32)
@@ -1218,54 +1312,33 @@ class Tacotron2(object):
             self._defer("head", head_wgrad, now=True)
         self._tick("linear_bwd")
         # ---- expand BiLSTM + convs
-        Cx = hp.expand_conv_channels
         dx = self._buf("d_act_a", rows_o * 512, torch.float32)
         dx2 = self._buf("d_act_b", rows_o * 512, torch.float32)
-        self._bilstm_bwd("expand/encoder_lstm", self._exp_in[-1], dex, Cx, Hx, N, To, Po, None, "expl", dx, D=Tx,
-                         defer="head", stats_for="exp%d" % (hp.expand_conv_layers - 1))
+        self._bilstm_bwd(est.lstm, self._exp_in[-1], dex, est.channels, Hx, N, To, Po, None, "expl", dx, D=Tx,
+                         defer="head", stats_for=est.tag_of(est.layers - 1))
         self._tick("expand_lstm_bwd")
-        cur, nxt = dx, dx2
-        for i in range(hp.expand_conv_layers - 1, -1, -1):
-            act = ACT_RELU if i < hp.expand_conv_layers - 1 else ACT_NONE
-            cin = M if i == 0 else Cx
-            if i == 0:   # gradient lands on mel_outputs, on top of the mel-loss gradient
-                self._conv_bwd("expand/conv_0", self._exp_in[0], cur, cin, Cx, hp.expand_conv_width, act, N, To, Po,
-                               "exp0", dmel, dx_accumulate=True, D=Tx, defer="head")
-            else:
-                self._conv_bwd("expand/conv_%d" % i, self._exp_in[i], cur, cin, Cx, hp.expand_conv_width, act, N, To,
-                               Po, "exp%d" % i, nxt, D=Tx, defer="head", stats_for="exp%d" % (i - 1))
-                cur, nxt = nxt, cur
+        # the gradient lands on mel_outputs, on top of the mel-loss gradient
+        self._stack_bwd(est, self._exp_in, dx, dx2, N, To, Po, "head", into=dmel)
         self._tick("expand_conv_bwd")
         # ---- postnet: mel = dec + dense(postnet(dec))
-        Cp = hp.postnet_conv_channels
+        Cp = pst.channels
         dmel_t = self._buf("d_mel_t", rows_o * M, T_)
         ops.copy3d(dmel, dmel_t, 1, rows_o, M, (0, M), (0, M))
-        ko = self._o("decoder_postnet/dense/kernel")
+        ko, bo = self._post_dense()
         post_h = self._post_in[-1]
 
         def postdense_wgrad():      # operands: the postnet's saved output and d_mel_t, a buffer of this call's own
             ops.gemm(post_h, dmel_t, g, Cp, M, rows_o, Cp, M, M, a_mode=1, b_mode=1, c_off=ko, accumulate=2,
                      split_k=self._splitk(rows_o, Cp, M))
-            ops.colsum(dmel_t, M, rows_o, M, g, out_off=self._o("decoder_postnet/dense/bias"))
+            ops.colsum(dmel_t, M, rows_o, M, g, out_off=bo)
         if self._on_main("postdense"):
             postdense_wgrad()
         else:
             self._defer("postnet", postdense_wgrad, eager=True, pure=True)
-        cur, nxt = dx, dx2
-        ops.gemm(dmel_t, self._W(self.T), cur, rows_o, Cp, M, M, M, Cp, a_mode=0, b_mode=0, b_off=ko,
-                 row_mask=(Po, self.padl, self.padl + To, 0), **self._dy_stats_kw("post%d" % (hp.postnet_conv_layers - 1)))
-        for i in range(hp.postnet_conv_layers - 1, -1, -1):
-            act = ACT_TANH if i < hp.postnet_conv_layers - 1 else ACT_NONE
-            cin = M if i == 0 else Cp
-            if i == 0:   # accumulate into dmel: total gradient wrt decoder_outputs
-                self._conv_bwd("decoder_postnet/postnet_conv_0", self._post_in[0], cur, cin, Cp,
-                               hp.postnet_conv_width, act, N, To, Po, "post0", dmel, dx_accumulate=True,
-                               defer="postnet")
-            else:
-                self._conv_bwd("decoder_postnet/postnet_conv_%d" % i, self._post_in[i], cur, cin, Cp,
-                               hp.postnet_conv_width, act, N, To, Po, "post%d" % i, nxt, defer="postnet",
-                               stats_for="post%d" % (i - 1))
-                cur, nxt = nxt, cur
+        ops.gemm(dmel_t, self._W(self.T), dx, rows_o, Cp, M, M, M, Cp, a_mode=0, b_mode=0, b_off=ko,
+                 row_mask=(Po, self.padl, self.padl + To, 0), **self._dy_stats_kw(pst.tag_of(pst.layers - 1)))
+        # accumulates into dmel: the total gradient wrt decoder_outputs
+        self._stack_bwd(pst, self._post_in, dx, dx2, N, To, Po, "postnet", into=dmel)
         self._tick("postnet_bwd")
         # ---- decoder output projection (grad wrt decoder_outputs sits in dmel, padded layout)
         rows = N * S1
@@ -1426,27 +1499,20 @@ class Tacotron2(object):
         enc = B["encl_h"]
         dkeys_t = self._buf("d_keys_t", N * Pi * A, T_)
         ops.copy3d(dkeys, dkeys_t, 1, N * Pi, A, (0, A), (0, A))
-        om = self._o("attention_decoder/memory_layer/kernel")
+        om = self._o(self.MEMORY)
         ops.gemm(enc, dkeys_t, g, E, A, N * Pi, E, A, A, a_mode=1, b_mode=1, c_off=om, accumulate=2,
                  split_k=sk(N * Pi, E, A))
         ops.gemm(dkeys_t, self._W(self.T), dvalues, N * Pi, E, A, A, A, E, a_mode=0, b_mode=0, b_off=om, accumulate=1)
         self._tick("attn_wgrad")
         # ---- encoder; the queued weight gradients run beside it on the second stream
         self._flush_deferred()
-        He = hp.encoder_lstm_units
-        Ce = hp.encoder_conv_channels
+        Ce = cst.channels
         rows_i = N * Pi
         ea = self._buf("d_enc_a", rows_i * max(Ce, hp.embedding_dim), torch.float32)
         eb = self._buf("d_enc_b", rows_i * max(Ce, hp.embedding_dim), torch.float32)
-        self._bilstm_bwd("encoder/encoder_lstm", self._enc_in[-1], dvalues, Ce, He, N, Ti, Pi, self.input_lengths,
-                         "encl", ea, defer="encoder", stats_for="enc%d" % (hp.encoder_conv_layers - 1))
-        cur, nxt = ea, eb
-        for i in range(hp.encoder_conv_layers - 1, -1, -1):
-            act = ACT_RELU if i < hp.encoder_conv_layers - 1 else ACT_NONE
-            cin = hp.embedding_dim if i == 0 else Ce
-            self._conv_bwd("encoder/conv_%d" % i, self._enc_in[i], cur, cin, Ce, hp.encoder_conv_width, act, N, Ti, Pi,
-                           "enc%d" % i, nxt, defer="encoder", stats_for=("enc%d" % (i - 1)) if i > 0 else None)
-            cur, nxt = nxt, cur
+        self._bilstm_bwd(cst.lstm, self._enc_in[-1], dvalues, Ce, cst.units, N, Ti, Pi, self.input_lengths,
+                         "encl", ea, defer="encoder", stats_for=cst.tag_of(cst.layers - 1))
+        cur = self._stack_bwd(cst, self._enc_in, ea, eb, N, Ti, Pi, "encoder")
         ops.embedding_bwd(self.inputs, cur, g, N, Ti, Pi, self.padl, hp.embedding_dim, self.vocab,
                           dtable_off=self._o("embedding/embedding"))
         self._tick("encoder_bwd")

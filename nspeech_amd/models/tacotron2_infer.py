@@ -8,22 +8,15 @@ import torch
 
 from .. import ops
 from .. import _lib as L
-from .._lib import ACT_NONE, ACT_RELU, ACT_TANH
-from .tacotron2 import PADL, PADR, _LazyAudio, _round_up
+from .._lib import ACT_RELU
+from .tacotron2 import PADL, PADR, _round_up
 
 
 def _infer_shadows(m):
     """k-contiguous copies of whole kernels for the fused [input | h] steps."""
-    hp = m._hparams
-    T, dev = m.T, m.device
+    hp, tr = m._hparams, m._shadowT
     M, E, A, D = hp.num_mels, 2 * hp.encoder_lstm_units, hp.attention_dim, hp.decoder_lstm_units
     r = hp.outputs_per_step
-
-    def tr(key, name, rows, cols):
-        if key not in m.tsh:
-            m.tsh[key] = torch.zeros(cols * rows, dtype=T, device=dev)
-        ops.cast2d(m.flat_p, rows, cols, cols, m.tsh[key], rows, True, src_off=m._o(name))
-
     tr("w1T_full", "decoder/decoder_prenet/dense_1/kernel", M + E, 256)
     tr("l1T_full", "decoder/lstm_1/kernel", A + E + D, 4 * D)
     tr("l2T_full", "decoder/lstm_2/kernel", 2 * D, 4 * D)
@@ -51,54 +44,22 @@ def _lstm_step(m, a, a_off, a_sn, K, wT, bias_off, c_prev, c_prev_off, c_sn, h_o
     L.call("ns_lstm_step", p, ops.stream())
 
 
-def _decode_persistent(m, N, Ti, Pi, Tia, S, enc, keys):
+def _decode_persistent(m, args):
     """The whole free-running decoder loop as ONE persistent launch (ns_taco2_decode, csrc/attn_cluster.hip "free-running
-    decode"): attention-RNN clusters + register-resident decoder LSTMs + folded frame feedback.  Returns (dec, al, S1)
-    in the [N, S+1, X] slot layout, or None when the shape is not covered (more than two utterances, other widths)."""
+    decode"): attention-RNN clusters + register-resident decoder LSTMs + folded frame feedback.  args: the model's
+    attn_block().  Returns (dec, al, S1) in the [N, S+1, X] slot layout, or None when the shape is not covered (more than
+    two utterances, other widths)."""
     import ctypes as C
     hp = m._hparams
-    T_ = m.T
-    r, M = hp.outputs_per_step, hp.num_mels
-    E, A, D = 2 * hp.encoder_lstm_units, hp.attention_dim, hp.decoder_lstm_units
-    S1 = S + 1
-    buf, o, W = m._buf, m._o, m._W(T_)
-    Dsp = m.Dsp
-    XA = 128 + Dsp + A
-    # <GO> frame = zeros: the frame term of step 0 is the prenet bias (every slot gets it; only slot 1 is read)
-    fr = buf("dec_fr", N * S1 * M, T_)
-    f1 = buf("dec_f1", N * S1 * 256, torch.float32)
-    w1 = o("decoder/decoder_prenet/dense_1/kernel")
-    ops.gemm(fr, W, f1, N * S1, 256, M, M, 256, 256, b_mode=1, b_off=w1, bias=m.flat_p,
-             bias_off=o("decoder/decoder_prenet/dense_1/bias"))
-    pv = buf("dec_pv", N * Pi * 256, T_)
-    ops.gemm(enc, W, pv, N * Pi, 256, E, E, 256, 256, b_mode=1, b_off=w1 + M * 256)
-    xa = buf("dec_xa", N * S1 * XA, T_)
-    if Dsp:
-        ops.copy3d(m._speaker_fwd(N), xa, N, S1, Dsp, (Dsp, 0), (S1 * XA, XA), dst_off=128)
-    al = buf("dec_al", N * S1 * Tia, torch.float32)
-    args = dict(
-        pv=pv, Dsp=Dsp, dtype=ops.dt(xa), N=N, S=S, Ti=Ti, Pi=Pi, padl_i=PADL, Tia=Tia, A=A, E=E, D1=256, D2=128, kw=7,
-        lengths=m.input_lengths, keys=keys, values=enc, f1=f1,
-        b2=(m.flat_p, o("decoder/decoder_prenet/dense_2/bias")), batt=(m.flat_p, o("decoder/attention_lstm/bias")),
-        wcl=m.tsh["wcl"], v=(m.flat_p, o("decoder/attention/attention_v")),
-        p1=buf("dec_p1", N * S1 * 256, T_), xa=xa, hc=buf("dec_hc", N * S1 * (A + E), T_),
-        ca=buf("dec_ca", N * S1 * A, torch.float32), ga=buf("dec_ga", N * S1 * 4 * A, T_),
-        q=buf("dec_q", N * S1 * A, torch.float32), align=al,
-        w2=(W, o("decoder/decoder_prenet/dense_2/kernel")), watt=(W, o("decoder/attention_lstm/kernel")),
-        wq=(W, o("decoder/attention/query_layer/kernel")))
+    r, M, D = hp.outputs_per_step, hp.num_mels, hp.decoder_lstm_units
+    N, S1 = args["N"], args["S"] + 1
+    buf, o, fp = m._buf, m._o, m.flat_p
     q = L.struct("ns_taco2_decode_params")
     q.att = ops._attn_params(args)
     q.D = D
-    fp = m.flat_p
     q.w_l1, q.b_l1 = ops.ptr(fp, o("decoder/lstm_1/kernel")), ops.ptr(fp, o("decoder/lstm_1/bias"))
     q.w_l2, q.b_l2 = ops.ptr(fp, o("decoder/lstm_2/kernel")), ops.ptr(fp, o("decoder/lstm_2/bias"))
-    # folded feedback (exact fp32): wpf = W_proj[:, last frame] . W_prenet1[frame rows], bpf = b_proj[last frame] . same + b1
-    wpf = buf("dec_wpf", D * 256, torch.float32)
-    bpf = buf("dec_bpf", 256, torch.float32)
-    kp, bp = o("decoder/output_projection/kernel"), o("decoder/output_projection/bias")
-    ops.gemm(fp, fp, wpf, D, 256, M, M * r, 256, 256, b_mode=1, a_off=kp + (r - 1) * M, b_off=w1, f32_passes=0)
-    ops.gemm(fp, fp, bpf, 1, 256, M, M * r, 256, 256, b_mode=1, a_off=bp + (r - 1) * M, b_off=w1, bias=fp,
-             bias_off=o("decoder/decoder_prenet/dense_1/bias"), f32_passes=0)
+    wpf, bpf = m.folded_feedback(D)
     q.wpf, q.bpf = ops.ptr(wpf), ops.ptr(bpf)
     h2 = buf("dec_h2", N * S1 * D, torch.float32)
     q.h2 = ops.ptr(h2)
@@ -112,8 +73,9 @@ def _decode_persistent(m, N, Ti, Pi, Tia, S, enc, keys):
     m._status_words[("decode", "fwd")] = work
     # the output projection over the whole history (tacotron2.py:73), off the loop's critical path
     dec = buf("dec_out", N * S1 * M * r, torch.float32)
-    ops.gemm(h2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=kp, bias=fp, bias_off=bp)
-    return dec, al, S1
+    ops.gemm(h2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=o("decoder/output_projection/kernel"), bias=fp,
+             bias_off=o("decoder/output_projection/bias"))
+    return dec, args["align"], S1
 
 
 def _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t):
@@ -224,15 +186,10 @@ def _decode_rows32(m, N, Ti, Pi, Tia, S, S1, enc, keys_t):
     if Dsp:
         for i in (0, 1):
             ops.rows32_pack_rows(m._speaker_fwd(N), Dsp, N, Dsp, xa[i], XA, 128)
-    # folded feedback (exact fp32): wpf = W_proj[:, last frame] . W1[frame rows], bpf = b_proj[last frame] . same + b1
     w1 = o("decoder/decoder_prenet/dense_1/kernel")
     b1 = o("decoder/decoder_prenet/dense_1/bias")
     kp, bp = o("decoder/output_projection/kernel"), o("decoder/output_projection/bias")
-    wpf = buf("r32_wpf", D * 256, f32)
-    bpf = buf("r32_bpf", 256, f32)
-    ops.gemm(fp, fp, wpf, D, 256, M, M * r, 256, 256, b_mode=1, a_off=kp + (r - 1) * M, b_off=w1, f32_passes=0)
-    ops.gemm(fp, fp, bpf, 1, 256, M, M * r, 256, 256, b_mode=1, a_off=bp + (r - 1) * M, b_off=w1, bias=fp, bias_off=b1,
-             f32_passes=0)
+    wpf, bpf = m.folded_feedback(D)
     pv = buf("r32_pv", N * Pi * 256, f32)
     ops.gemm(enc, fp, pv, N * Pi, 256, E, E, 256, 256, b_mode=1, b_off=w1 + M * 256)
 
@@ -320,15 +277,12 @@ def forward_infer(m):
 
 def _infer_body(m):
     hp = m._hparams
-    T_ = m.T
     N, Ti = m.inputs.shape
-    r, M, F = hp.outputs_per_step, hp.num_mels, hp.num_freq
     S = int(hp.max_iters)
-    To = S * r
-    Fp = m._lin_pad(F)
-    E, A, D = 2 * hp.encoder_lstm_units, hp.attention_dim, hp.decoder_lstm_units
+    To = S * hp.outputs_per_step
     Pi, Po = Ti + PADL + PADR, To + PADL + PADR
     S1 = S + 2
+    m.dims = dict(N=N, Ti=Ti, To=To, S=S, Pi=Pi, Po=Po, Fp=m._lin_pad(hp.num_freq))
     sig = ("infer", N, Ti, S)
     if sig != m._sig:
         m._bufs.clear()
@@ -336,25 +290,11 @@ def _infer_body(m):
     ops.F32_PASSES = m.passes_fwd
     ops.CELL_CLIP = m.cell_clip
     _infer_shadows(m)
-    W = m._W(T_)
-    buf = m._buf
-    o = m._o
 
-    # ---- encoder with moving-average BatchNorm
-    emb = hp.embedding_dim
-    x = buf("enc_x0", N * Pi * emb, T_)
-    ops.embedding_fwd(m.inputs, m.flat_p, x, N, Ti, Pi, PADL, emb, m.vocab, table_off=m._o("embedding/embedding"))
-    cin = emb
-    for i in range(hp.encoder_conv_layers):
-        act = ACT_RELU if i < hp.encoder_conv_layers - 1 else ACT_NONE
-        x = m._conv_fwd("encoder/conv_%d" % i, x, cin, hp.encoder_conv_channels, hp.encoder_conv_width, act, N, Ti, Pi,
-                        "enc%d" % i, training=False)
-        cin = hp.encoder_conv_channels
-    enc = m._bilstm_fwd("encoder/encoder_lstm", x, cin, hp.encoder_lstm_units, N, Ti, Pi, m.input_lengths, "encl", "enc")
-    keys = buf("keys", N * Pi * A, torch.float32)
-    ops.gemm(enc, W, keys, N * Pi, A, E, E, A, A, b_mode=1, b_off=m._o("attention_decoder/memory_layer/kernel"))
-    Tia = _round_up(Ti, 8)
-    keys_t = buf("dec_keys_t", N * A * Tia, torch.float32)
+    # ---- encoder with moving-average BatchNorm; the step launches read the keys transposed
+    enc, keys = m.encoder(False)
+    A, Tia = hp.attention_dim, _round_up(Ti, 8)
+    keys_t = m._buf("dec_keys_t", N * A * Tia, torch.float32)
     L.check(L.lib().ns_taco2_keys_transpose(
         L.C.c_void_p(ops.ptr(keys)), L.C.c_void_p(ops.ptr(keys_t)), N, Ti, Tia, Pi, PADL, A,
         L.C.c_void_p(ops.stream())), "ns_taco2_keys_transpose")
@@ -363,7 +303,7 @@ def _infer_body(m):
     # widths), else a chain of single-step launches
     # (the one-launch decoder has plain cells: with a zoneout rate the step launches apply its expectation)
     one_launch = getattr(m, "use_decode_kernel", True) and m.zoneout_rate <= 0.0
-    done = _decode_persistent(m, N, Ti, Pi, Tia, S, enc, keys) if one_launch else None
+    done = _decode_persistent(m, m.attn_block(enc, keys, False)) if one_launch else None
     if done is not None:
         m.last_paths["decode"] = "persistent"
         dec, al, S1 = done
@@ -374,45 +314,5 @@ def _infer_body(m):
         m.last_paths["decode"] = "step"
         dec, al = _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
 
-    # ---- postnet, residual, expand, linear head (inference BatchNorm)
-    decp = buf("decp", N * Po * M, torch.float32)
-    pin = buf("post_in", N * Po * M, T_)
-    ops.copy3d(dec, decp, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=PADL * M)
-    ops.copy3d(dec, pin, N, To, M, (S1 * M * r, M), (Po * M, M), src_off=M * r, dst_off=PADL * M)
-    x, cin, Cp = pin, M, hp.postnet_conv_channels
-    for i in range(hp.postnet_conv_layers):
-        act = ACT_TANH if i < hp.postnet_conv_layers - 1 else ACT_NONE
-        # as in the training pass: a layer whose consumer runs on the 256-tile kernel hands its output over pre-split
-        nxt = i + 1 < hp.postnet_conv_layers and m._x256_split_ok("post%d" % (i + 1), N * Po, Cp, Cp, hp.postnet_conv_width)
-        split_in = isinstance(x, tuple)
-        x = m._conv_fwd("decoder_postnet/postnet_conv_%d" % i, None if split_in else x, cin, Cp, hp.postnet_conv_width, act,
-                        N, To, Po, "post%d" % i, training=False, xsplit=x if split_in else None, emit_split=nxt)
-        cin = Cp
-    mel = buf("mel_out", N * Po * M, torch.float32)
-    ops.gemm(x, W, mel, N * Po, M, Cp, Cp, M, M, b_mode=1, b_off=o("decoder_postnet/dense/kernel"), bias=m.flat_p,
-             bias_off=o("decoder_postnet/dense/bias"), row_mask=(Po, PADL, PADL + To, 0))
-    ops.copy3d(decp, mel, N, Po, M, (Po * M, M), (Po * M, M), accumulate=1)
-    Tx = m.Tx
-    ein = buf("exp_in", N * Po * M, Tx)
-    ops.copy3d(mel, ein, N, Po, M, (Po * M, M), (Po * M, M))
-    x, cin, Cx = ein, M, hp.expand_conv_channels
-    for i in range(hp.expand_conv_layers):
-        act = ACT_RELU if i < hp.expand_conv_layers - 1 else ACT_NONE
-        x = m._conv_fwd("expand/conv_%d" % i, x, cin, Cx, hp.expand_conv_width, act, N, To, Po, "exp%d" % i,
-                        training=False, D=Tx)
-        cin = Cx
-    Hx = hp.expand_lstm_units
-    ex = m._bilstm_fwd("expand/encoder_lstm", x, cin, Hx, N, To, Po, None, "expl", "exp", D=Tx)
-    lin = buf("lin_out", N * Po * Fp, torch.float32)
-    if "wl_padT" in m.tsh:
-        ops.gemm(ex, m.tsh["wl_padT"], lin, N * Po, Fp, 2 * Hx, 2 * Hx, 2 * Hx, Fp, b_mode=0, bias=m.tsh["bl_pad"])
-    else:
-        ops.gemm(ex, m.tsh["wl_pad"], lin, N * Po, Fp, 2 * Hx, 2 * Hx, Fp, Fp, b_mode=1, bias=m.tsh["bl_pad"])
-
-    m.dims = dict(N=N, Ti=Ti, To=To, S=S, Pi=Pi, Po=Po, Fp=Fp)
-    m.mel_outputs = mel[:N * Po * M].view(N, Po, M)[:, PADL:PADL + To]
-    m.linear_outputs = lin[:N * Po * Fp].view(N, Po, Fp)[:, PADL:PADL + To, :F]
-    m.decoder_outputs = dec[:N * S1 * M * r].view(N, S1, M * r)[:, 1:S + 1].reshape(N, To, M)
-    m.alignments = al[:N * S1 * Tia].view(N, S1, Tia)[:, 1:S + 1, :Ti].permute(0, 2, 1)
-    m.audio = _LazyAudio(m)
-    return m
+    # ---- postnet, residual, expand, linear head (inference BatchNorm), output views
+    return m.tail(dec, al, S1, False)
