@@ -10,6 +10,10 @@ generator on the GPU (one workgroup per waveform; float64 softmax and inverse-CD
 --incremental_temperature true keeps that generator at ANY --temperature - the kernel draws from softmax(logits /
 temperature), scale_prediction below in float64; --temperature 0 is argmax - and then a local condition is accepted at any
 temperature too; it needs --fast_generation true.
+--stop_at_endpoint true (default false: the output is what it was) arms the incremental generator with
+audio.endpoint_rule() - it stops drawing behind the first 0.8 s that stay under -40 dB, where audio.find_endpoint would
+cut the finished waveform - and writes the waveform cut at that end; it needs the incremental generator as well, in one
+call (no --save_every).
 --lc_channels N --local_condition FILE.npy --lc_hold H draw from a locally conditioned checkpoint: the file is float
 [rows, N], row r conditions generated samples r * H .. r * H + H - 1 (a mel spectrogram: H = the hop), the seed in
 front takes row 0; this path is the incremental generator's alone.  Any other
@@ -68,6 +72,13 @@ def main(args):
     if inc_t and not args.fast_generation:
         raise ValueError("--incremental_temperature true tempers the incremental generator's draws: it needs "
                          "--fast_generation true (the full-window path scales on the host at any --temperature already)")
+    stop = bool(getattr(args, "stop_at_endpoint", False))
+    if stop and not (args.fast_generation and (inc_t or args.temperature == 1.0)):
+        raise ValueError("--stop_at_endpoint true is the incremental generator's own stop: it needs --fast_generation true and "
+                         "--temperature 1.0, or any --temperature with --incremental_temperature true")
+    if stop and getattr(args, "save_every", None):
+        raise ValueError("--stop_at_endpoint true draws in one call (the rule counts silence across the whole waveform): "
+                         "no --save_every")
     hp = hparams_mod.load("wavenet")
     hp.parse(args.hparams)
     gc = None
@@ -111,6 +122,8 @@ def main(args):
     if fast:
         if inc_t:
             cond.update(temperature=args.temperature)
+        if stop:
+            cond.update(endpoint=audio.endpoint_rule())
         done = 0
         while done < args.samples:                  # in chunks, so that --save_every can write partial results
             n = min(args.samples - done, args.save_every or args.samples)
@@ -121,6 +134,10 @@ def main(args):
                 r0, r1 = max(0, t0) // H, (done + n - 1) // H
                 cond.update(local_conditions=lc[None, r0:r1 + 1], hold=H, t0=t0 - r0 * H)
             ids = net.generate(np.asarray(waveform[-rf:], np.int32), n, uniforms=rng.random((1, n)), **cond)
+            if stop:                                # (one chunk) the generated samples in front of their end point
+                n_kept = int(net.last_ends[0].item())
+                print("End point at sample {} of {}".format(n_kept, n))
+                ids = ids[:, :rf + n_kept]
             waveform.extend(int(x) for x in ids[0, rf:].cpu().numpy())
             done += n
             print("Sample {:3<d}/{:3<d}".format(done, args.samples), end="\r")
@@ -168,6 +185,8 @@ if __name__ == "__main__":
     parser.add_argument("--fast_generation", type=_str_to_bool, default=True)
     parser.add_argument("--incremental_temperature", type=_str_to_bool, default=False,
                         help="keep the incremental generator at any --temperature (0 = argmax); needs --fast_generation true")
+    parser.add_argument("--stop_at_endpoint", type=_str_to_bool, default=False,
+                        help="stop drawing at the end point audio.find_endpoint would cut at; needs the incremental generator")
     parser.add_argument("--wav_seed", type=str, default=None)
     parser.add_argument("--gc_channels", type=int, default=None)
     parser.add_argument("--gc_cardinality", type=int, default=None)

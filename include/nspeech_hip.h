@@ -1031,6 +1031,31 @@ size_t ns_wavenet_post_bytes(int B);
 int ns_wavenet_chain_fits(int L, int R, int S, int Q, int cond);
 int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t stream);
 
+/* ns_wavenet_generate that stops each waveform at its end point (version 105): utils/audio.py's find_endpoint applied
+ * by the generator to its own output while it draws, so that the samples the caller would cut away are never drawn.
+ * A struct and an entry point of their own: ns_wavenet_generate_params keeps its members and its size.
+ * A drawn sample is silent when its code < below.  mu_law_decode is increasing in the code, so find_endpoint's
+ * "max(wav[x : x + window]) < threshold" is "every code of the window < below" for the one integer below = the number
+ * of codes whose decoded value is < threshold (models/wavenet.py:endpoint_code); 0: nothing is silent, Q: everything.
+ * With n = total - n_seed and j = 0 .. n - 1 the index of a drawn sample (ids[b, n_seed + j]; seed samples take no part):
+ *   end[b] = x + hop for the smallest x in hop, 2 hop, .. with x < n - window whose samples j = x .. x + window - 1 are
+ *            all silent; n when there is none.
+ * That is find_endpoint's loop as it stands: the window at x = 0 is never tested, the bound x < n - window is strict, and
+ * window need not be a multiple of hop.  The caller keeps ids[b, n_seed : n_seed + end[b]].
+ * A waveform whose rule fires stops drawing: its last drawn sample is j = x + window - 1, ids[b, n_seed + x + window ..]
+ * are not written (they stay what the caller put there), and neither is its row of probs.  The draws are causal: what
+ * stands in front of the stop is what ns_wavenet_generate draws there, bit for bit.  The other waveforms of the call go
+ * on, each from its own row of uniform; uniform and the condition rows are still sized for total.
+ * stop == NULL is ns_wavenet_generate(p, stream) exactly (which is this call with NULL).
+ * NS_ERR_BAD_ARG before any launch: end == NULL; below outside 0 .. Q; window < 1, hop < 1 or hop > window; engine 3
+ * (its helper workgroups would wait for a chain workgroup that has left). */
+typedef struct {
+  int below;             /* a drawn sample is silent when its code < below; 0 .. Q */
+  int64_t window, hop;   /* find_endpoint's window_length and hop_length, 1 <= hop <= window */
+  int64_t* end;          /* [B], device */
+} ns_wavenet_stop_params;
+int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, const ns_wavenet_stop_params* stop, ns_stream_t stream);
+
 /* ------------------------------------------------------------------ audio DSP (utils/audio.py)
  * Radix-2 Stockham FFTs of n_fft points run inside LDS, one workgroup per frame; no MFMA,
  * the kernels are bandwidth / latency bound.  window = periodic Hann(win) and

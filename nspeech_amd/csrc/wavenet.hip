@@ -9,6 +9,7 @@
 //   ns_wavenet_softmax    float64 softmax of logit rows (predict_proba)                  (:436-453)
 //   ns_wavenet_softmax_ce mean softmax cross-entropy against integer targets    (:479-502) and d/dlogits
 //   ns_wavenet_generate   incremental sample-by-sample generation (persistent)  (generate_wavenet.py:56-142)
+//   ns_wavenet_generate_until  the same, every waveform stopped at its end point     (utils/audio.py find_endpoint)
 #include "exchange.h"
 #include "carve.h"
 
@@ -328,6 +329,29 @@ __device__ __forceinline__ int gen_first_max(const float* lg, float m, int Q) {
   return Q - 1;
 }
 
+// The end-point rule (ns_wavenet_stop_params; st.end == NULL: not armed, nothing below runs).  Thread 0, where it stores
+// ids[t+1], counts the silent drawn samples (code < below) that end at j = t + 1 - n_seed; the counter lives in LDS - in
+// the MFMA kernel a register that lives through the chain is one too many.  The window that starts at x = j + 1 - window
+// is complete with sample j and fires when run >= window, x is one of hop, 2 hop, .. and x < n - window (strict):
+// audio.find_endpoint's loop, windows completing in the order of x, so the first to fire is the smallest.  `fired` is
+// set in front of the barrier that follows the store and never cleared; every thread reads it behind that barrier and
+// leaves, so the exit is uniform over the workgroup and no wave is left waiting at a later barrier.
+struct GenStop { int run, fired; };
+__device__ __forceinline__ void gen_stop_init(const ns_wavenet_stop_params& st, GenStop* gs, long n, int b) {
+  ns_lds_poke(&gs->run, 0);
+  ns_lds_poke(&gs->fired, 0);
+  if (st.end) st.end[b] = n;                       // until the rule fires: thread 0 writes both, in program order
+}
+__device__ __forceinline__ void gen_stop_step(const ns_wavenet_stop_params& st, GenStop* gs, int id, long j, long n, int b) {
+  const int run = id < st.below ? ns_lds_peek(&gs->run) + 1 : 0;
+  ns_lds_poke(&gs->run, run);
+  const long x = j + 1 - st.window;
+  if (run >= st.window && x >= st.hop && x < n - st.window && x % st.hop == 0) {
+    st.end[b] = x + st.hop;
+    ns_lds_poke(&gs->fired, 1);
+  }
+}
+
 struct GenLds {                                   // dynamic LDS of wn_generate_kernel
   int R, Dc, S, Q;
   LdsCarve c = {};
@@ -342,7 +366,7 @@ struct GenLds {                                   // dynamic LDS of wn_generate_
   int bytes = c.off;
 };
 template <typename W>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p, double inv_t) {
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
   extern __shared__ float gsm[];
   const int R = p.R, Dc = p.Dc, S = p.S, Q = p.Q;
   const GenLds lay{R, Dc, S, Q};
@@ -359,7 +383,9 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
   const int jz = tid % (2 * Dc), kz0 = tid / (2 * Dc), kzs = GEN_THREADS / (2 * Dc);   // fg element q: k = q*kzs + kz0
   const int jd = tid % R, kd0 = tid / R, kds = GEN_THREADS / R;
   __shared__ int dil[128];
+  __shared__ GenStop gs;
   for (int i = tid; i < p.L && i < 128; i += GEN_THREADS) dil[i] = p.dilations[i];
+  if (tid == 0) gen_stop_init(st, &gs, p.total - p.n_seed, b);
   __syncthreads();
   GenLayerW<W> wa, wbuf;
   for (int t = 1; t < p.total; ++t) {
@@ -460,11 +486,14 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
     if (tid == 0) {
       double se = 0.0;
       for (int j = 0; j < Q; ++j) se += ex[j];
-      ids[t + 1] = p.argmax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
-      if (p.probs)                                               // the distribution of the LAST drawn sample
+      const int id = p.argmax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
+      ids[t + 1] = id;
+      if (st.end) gen_stop_step(st, &gs, id, t + 1 - p.n_seed, p.total - p.n_seed, b);
+      if (p.probs && t + 2 == p.total)                           // the distribution of the LAST drawn sample
         for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
     }
     __syncthreads();
+    if (st.end && ns_lds_peek(&gs.fired)) return;                // the rule fired: every thread leaves behind the barrier
   }
 }
 
@@ -554,7 +583,7 @@ struct FastLds {                                  // dynamic LDS of wn_generate_
   int bytes = c.off;
 };
 template <int C>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p, double inv_t) {
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
   extern __shared__ float gsm[];
   const int S = p.S, Q = p.Q, L = p.L;
   const FastLds lay{L, C, S, Q};
@@ -564,6 +593,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavene
   double* ex = carve_at<double>(gsm, lay.ex);
   __shared__ int dil[128];
   __shared__ long qoff[128];
+  __shared__ GenStop gs;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
   const bf16_t* wb = (const bf16_t*)p.weights;
   int* ids = p.ids + (long)b * p.total;
@@ -572,6 +602,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavene
   if (tid == 0) {
     long q = 0;
     for (int i = 0; i < L; ++i) { dil[i] = p.dilations[i]; qoff[i] = q; q += p.dilations[i]; }
+    gen_stop_init(st, &gs, p.total - p.n_seed, b);
   }
   __syncthreads();
   for (int t = 1; t < p.total; ++t) {
@@ -632,11 +663,14 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavene
     if (tid == 0) {
       double se = 0.0;
       for (int j = 0; j < Q; ++j) se += ex[j];
-      ids[t + 1] = p.argmax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
-      if (p.probs)
+      const int id = p.argmax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
+      ids[t + 1] = id;
+      if (st.end) gen_stop_step(st, &gs, id, t + 1 - p.n_seed, p.total - p.n_seed, b);
+      if (p.probs && t + 2 == p.total)
         for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
     }
     __syncthreads();
+    if (st.end && ns_lds_peek(&gs.fired)) return;                // the rule fired: every thread leaves behind the barrier
   }
 }
 
@@ -789,7 +823,7 @@ struct ChainLds {                                 // dynamic LDS of wn_generate_
   O bytes = c.off;
 };
 template <bool COND>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p, double inv_t) {
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
   extern __shared__ float gsm[];
   constexpr int C = 32;
   const int S = p.S, Q = p.Q, L = p.L;
@@ -801,6 +835,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   __shared__ int dil[128];
   __shared__ long qoff[128];
   __shared__ int chain_pos;
+  __shared__ GenStop gs;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
   const bf16_t* wb = (const bf16_t*)p.weights;
   const bf16_t* fgT = (const bf16_t*)p.fgT;
@@ -811,6 +846,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   if (tid == 0) {
     long q = 0;
     for (int i = 0; i < L; ++i) { dil[i] = p.dilations[i]; qoff[i] = q; q += p.dilations[i]; }
+    gen_stop_init(st, &gs, p.total - p.n_seed, b);
   }
   if constexpr (COND) {
     for (int i = tid; i < L * C; i += GEN_THREADS)
@@ -894,17 +930,23 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
             int cnt = 0, first = Q - 1;
     #pragma unroll
             for (int w = 0; w < GEN_THREADS / 64; ++w) { cnt += wcnt[w]; first = min(first, wcnt[w]); }
-            ids[t + 1] = amax ? first : min(cnt, Q - 1);
+            const int id = amax ? first : min(cnt, Q - 1);
+            ids[t + 1] = id;
+            if (st.end) gen_stop_step(st, &gs, id, t + 1 - p.n_seed, p.total - p.n_seed, b);
           }
         } else if (tid == 0) {
           double se = 0.0;
           for (int j = 0; j < Q; ++j) se += ex[j];
-          ids[t + 1] = amax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
-          if (p.probs)
+          const int id = amax ? gen_first_max(lg, m, Q) : gen_walk(ex, (double)un[t + 1 - p.n_seed] * se, Q);
+          ids[t + 1] = id;
+          if (st.end) gen_stop_step(st, &gs, id, t + 1 - p.n_seed, p.total - p.n_seed, b);
+          if (p.probs && t + 2 == p.total)
             for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
         }
         __syncthreads();
-        return true;
+        // the end-point rule fired: thread 0 set gs.fired in front of this barrier, every thread of both sample loops
+        // reads it here and returns - the path of a timed-out hand-over
+        return !(st.end && ns_lds_peek(&gs.fired));
   };
   if (wave == 0) {
     for (int t = 1; t < p.total; ++t) {
@@ -1031,7 +1073,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
 #undef MF_RROW
       __syncthreads();
       if (!emit) continue;
-      if (!gen_post(t)) return;                              // (engine 3: a hand-over timed out)
+      if (!gen_post(t)) return;                              // (the end-point rule fired; engine 3: a hand-over timed out)
     }
   } else {
     // COND: the condition row in ctab is `crow`, and the first position (on the condition's time axis) of the next row
@@ -1110,7 +1152,7 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
       }
       __syncthreads();
       if (!emit) continue;
-      if (!gen_post(t)) return;                              // (engine 3: a hand-over timed out)
+      if (!gen_post(t)) return;                              // (the end-point rule fired; engine 3: a hand-over timed out)
     }
   }
 }
@@ -1120,8 +1162,21 @@ extern "C" int ns_wavenet_chain_fits(int L, int R, int S, int Q, int cond) {
   return L > 0 && R > 0 && S > 0 && Q > 0 && ChainLds<size_t>{(size_t)L, (size_t)R, (size_t)S, (size_t)Q, (size_t)cond}.bytes <= WN_CHAIN_LDS_MAX;
 }
 
-extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t s) {
+extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t s) { return ns_wavenet_generate_until(p, nullptr, s); }
+
+extern "C" int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, const ns_wavenet_stop_params* stop, ns_stream_t s) {
   NS_CHECK_ARG(p && p->weights && p->ids && p->queues && p->uniform && p->dilations, "ns_wavenet_generate: null");
+  ns_wavenet_stop_params st = {};                  // end = NULL: the rule is not armed, the kernels draw all of total - n_seed
+  if (stop) {
+    NS_CHECK_ARG(stop->end, "ns_wavenet_generate_until: stop->end is NULL (one int64 per waveform)");
+    NS_CHECK_ARG(stop->below >= 0 && stop->below <= p->Q, "ns_wavenet_generate_until: below %d outside 0 .. Q = %d", stop->below, p->Q);
+    NS_CHECK_ARG(stop->window >= 1 && stop->hop >= 1 && stop->hop <= stop->window,
+                 "ns_wavenet_generate_until: window %lld and hop %lld must satisfy 1 <= hop <= window", (long long)stop->window,
+                 (long long)stop->hop);
+    NS_CHECK_ARG(p->engine != 3, "ns_wavenet_generate_until: engine 3 takes no stop (its helper workgroups would wait for a chain "
+                                 "workgroup that has left): engine 2");
+    st = *stop;
+  }
   NS_CHECK_ARG(p->B > 0 && p->n_seed >= 2 && p->total > p->n_seed && p->L > 0 && p->L <= 128, "ns_wavenet_generate: bad sizes");
   NS_CHECK_ARG(GEN_THREADS % (2 * p->Dc) == 0 && GEN_THREADS % p->R == 0 && 2 * p->R * 2 * p->Dc <= GEN_FG * GEN_THREADS &&
                    p->Dc * p->R <= GEN_DE * GEN_THREADS && p->Dc <= GEN_SK && p->S <= GEN_THREADS && p->Q <= 1024,
@@ -1175,23 +1230,23 @@ extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_strea
       if (full) {                            // + the condition row and the dense biases
         const size_t lds4 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 1}.bytes;
         NS_CHECK_ARG(lds4 <= WN_CHAIN_LDS_MAX, "ns_wavenet_generate: state and condition row do not fit in LDS (ns_wavenet_chain_fits)");
-        hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p, inv_t);
+        hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p, inv_t, st);
         NS_CHECK_LAUNCH("wavenet_generate_mfma_cond");
         return NS_OK;
       }
-      hipLaunchKernelGGL(wn_generate_mfma_kernel<false>, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p, inv_t);
+      hipLaunchKernelGGL(wn_generate_mfma_kernel<false>, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p, inv_t, st);
       NS_CHECK_LAUNCH("wavenet_generate_mfma");
       return NS_OK;
     }
-    if (p->R == 32) hipLaunchKernelGGL(wn_generate_fast_kernel<32>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t);
-    else hipLaunchKernelGGL(wn_generate_fast_kernel<16>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t);
+    if (p->R == 32) hipLaunchKernelGGL(wn_generate_fast_kernel<32>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t, st);
+    else hipLaunchKernelGGL(wn_generate_fast_kernel<16>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t, st);
     NS_CHECK_LAUNCH("wavenet_generate_fast");
     return NS_OK;
   }
   NS_CHECK_ARG(carve_aligned(gl.ex, sizeof(double)),
                "ns_wavenet_generate: the per-layer kernel needs an even Dc (its float64 row follows 3 Dc floats in LDS)");
-  if (p->w_dtype == NS_BF16) hipLaunchKernelGGL(wn_generate_kernel<bf16_t>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t);
-  else hipLaunchKernelGGL(wn_generate_kernel<float>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t);
+  if (p->w_dtype == NS_BF16) hipLaunchKernelGGL(wn_generate_kernel<bf16_t>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t, st);
+  else hipLaunchKernelGGL(wn_generate_kernel<float>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t, st);
   NS_CHECK_LAUNCH("wavenet_generate");
   return NS_OK;
 }

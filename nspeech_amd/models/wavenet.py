@@ -50,6 +50,18 @@ def mu_law_decode(ids, q):
     return (np.sign(sig) * (1 / mu) * ((1 + mu) ** np.abs(sig) - 1)).astype(np.float32)
 
 
+def endpoint_code(q, threshold):
+    """audio.find_endpoint's threshold on the codes: `below`, the number of codes c with float(mu_law_decode(c, q)) <
+    threshold - the comparison find_endpoint makes on a decoded waveform.  The decode is increasing in the code, so those
+    are the codes 0 .. below - 1 and "max of a window < threshold" is "every code of the window < below"; ValueError if
+    they are not (the decode has changed and the integer rule no longer stands for the float one)."""
+    silent = np.asarray([float(v) < threshold for v in mu_law_decode(np.arange(int(q)), int(q))])
+    below = int(silent.sum())
+    if not silent[:below].all():
+        raise ValueError("the codes below %r are not 0 .. %d: mu_law_decode is not increasing in the code" % (threshold, below - 1))
+    return below
+
+
 class SimpleWaveNet(object):
     """create_model('simple_wavenet', hparams).  dtype: 'fp32' (exact FMA, parity tests) or 'bf16'."""
 
@@ -660,7 +672,7 @@ class SimpleWaveNet(object):
         return probs
 
     def generate(self, seed_ids, n_samples, uniforms=None, seed=0, exact=None, fast=True, engine=None, global_conditions=None,
-                 local_conditions=None, hold=1, t0=0, temperature=1.0):
+                 local_conditions=None, hold=1, t0=0, temperature=1.0, endpoint=None):
         """Incremental generation (generate_wavenet.py:56-142): seed_ids int [B, n_seed] (or [n_seed]) of mu-law codes,
         n_seed >= receptive field; returns int32 [B, n_seed + n_samples].  uniforms [B, n_samples] in [0,1) drive the
         categorical draws (default: numpy Generator(seed)).  Weights: the fp32 master copy when exact (default in fp32
@@ -678,10 +690,24 @@ class SimpleWaveNet(object):
         for bit.  temperature == 0: argmax - every sample is the lowest code with the largest float32 logit, and
         `uniforms` / `seed` have no effect.  Negative or non-finite: ValueError.  last_probs [B * Q] holds the
         distribution the LAST sample came from: the tempered softmax(logits / temperature) for temperature > 0, the
-        temperature-1 softmax whose maximum was taken for temperature == 0."""
+        temperature-1 softmax whose maximum was taken for temperature == 0.
+        endpoint = (window_length, hop_length, threshold) - audio.endpoint_rule()'s three numbers - (every engine but 3,
+        with and without conditions): each waveform stops drawing where audio.find_endpoint would cut its decoded
+        samples - behind the first window, at x = hop_length, 2 hop_length, .. with x < n_samples - window_length, of
+        window_length drawn samples that all decode below threshold; the kernel compares codes with endpoint_code(Q,
+        threshold).  last_ends (int64 [B] on the device) holds find_endpoint(mu_law_decode(ids[b, n_seed:], Q)) of every
+        row, n_samples where the rule did not fire (and in every row when endpoint is None).  The draws are causal, so
+        ids[b, : n_seed + last_ends[b]] is what the call without endpoint returns there, bit for bit; a stopped row
+        was drawn up to the end of the window that fired (last_ends[b] - hop_length + window_length samples), the
+        returned array keeps its shape and holds zeros behind that, and the row's last_probs stay zero.  Automatic
+        engine selection never picks engine 3 with an endpoint (its helper workgroups would wait for a waveform that
+        has left); engine=3 with one is a ValueError."""
         temperature = float(temperature)
         if not math.isfinite(temperature) or temperature < 0:
             raise ValueError("temperature %r: a finite number > 0 for a tempered draw, 0 for argmax" % (temperature,))
+        if endpoint is not None and engine == 3:
+            raise ValueError("engine 3 takes no endpoint (its helper workgroups would wait for a waveform that has stopped): "
+                             "engine 2 runs the same chain without helpers")
         if self.scalar_input:
             raise NotImplementedError("Incremental generation does not support scalar input yet.")       # wavenet.py:643-645
         if self.lc and local_conditions is None:
@@ -737,7 +763,7 @@ class SimpleWaveNet(object):
             # per-layer kernel, as before the chain took them
             if extra and (engine == 1 or not ops.wavenet_chain_fits(self.L, self.R, self.S, self.Q, True)):
                 shadows, engine = False, 0
-            if not extra and engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
+            if endpoint is None and not extra and engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
                     and self._helper(dev) is not None:
                 engine = 3          # + the post-processing products on four helper workgroups per waveform (weights in registers)
         if shadows:
@@ -760,9 +786,14 @@ class SimpleWaveNet(object):
             assert self._helper(dev) is not None, "engine 3 needs a stream that runs beside the current one"
             post_x = torch.empty(ops.wavenet_post_floats(B), dtype=torch.float32, device=dev)
             extra = dict(extra, post_x=post_x, helper_stream=self._helper_stream)
+        self.last_ends = torch.full((B,), total - n_seed, dtype=torch.int64, device=dev)
+        stop = None
+        if endpoint is not None:
+            window_length, hop_length, threshold = endpoint
+            stop = (endpoint_code(self.Q, threshold), int(window_length), int(hop_length), self.last_ends)
         ops.wavenet_generate(W, offs, dil, self.L, self.R, self.Dc, self.S, self.Q, B, n_seed, total, qrows, ids, un, queues,
                              probs=self.last_probs, fgT=fgT, deT=deT, engine=engine, temperature=temperature or 1.0,
-                             argmax=temperature == 0, **extra)
+                             argmax=temperature == 0, stop=stop, **extra)
         if engine == 3:             # the call's stream takes the helpers' end in: post_x is free behind it
             torch.cuda.current_stream(dev).wait_stream(self._helper_stream)
             self.last_status = extra["post_x"][:1].view(torch.int32)

@@ -913,10 +913,13 @@ def wavenet_chain_fits(L_, R, S, Q, cond):
 
 def wavenet_generate(weights, offs, dilations, L_, R, Dc, S, Q, B, n_seed, total, queue_rows, ids, uniform, queues, probs=None,
                      fgT=None, deT=None, engine=0, cond=None, dense_bias=None, skip_bias=None, post1_bias=None, post2_bias=None,
-                     post_x=None, helper_stream=None, cond_rows=0, cond_hold=0, cond_t0=0, temperature=0.0, argmax=False):
+                     post_x=None, helper_stream=None, cond_rows=0, cond_hold=0, cond_t0=0, temperature=0.0, argmax=False,
+                     stop=None):
     """cond_rows > 1: cond is [B, cond_rows, L, 2Dc], one row per cond_hold samples, ids[.., 0] at position cond_t0 of the
     condition's time axis (include/nspeech_hip.h).  temperature: the draws come from softmax(logits / temperature), 0 = 1.0;
-    argmax: the lowest index of the largest logit instead of a draw.  Both are the C fields, checked by the launcher."""
+    argmax: the lowest index of the largest logit instead of a draw.  Both are the C fields, checked by the launcher.
+    stop = (below, window, hop, end): ns_wavenet_generate_until - a waveform stops drawing where find_endpoint's rule
+    (every code of a window < below) first holds, end int64 [B] on the device receives the end points."""
     p = L.struct("ns_wavenet_generate_params")
     _fill(p, cond_rows=cond_rows, cond_hold=cond_hold, cond_t0=cond_t0, temperature=float(temperature), argmax=int(bool(argmax)))
     if post_x is not None:
@@ -928,4 +931,11 @@ def wavenet_generate(weights, offs, dilations, L_, R, Dc, S, Q, B, n_seed, total
           off_post1=offs["post1"], off_post2=offs["post2"], dilations=ptr(dilations), L=L_, R=R, Dc=Dc, S=S, Q=Q, B=B,
           n_seed=n_seed, total=total, queue_rows=queue_rows, ids=ptr(ids), uniform=ptr(uniform), queues=ptr(queues),
           probs=ptr(probs), fgT=ptr(fgT), deT=ptr(deT), engine=engine)
-    L.call("ns_wavenet_generate", p, stream())
+    if stop is None:
+        L.call("ns_wavenet_generate", p, stream())
+        return
+    below, window, hop, end = stop
+    assert end.dtype == torch.int64 and end.is_contiguous() and end.numel() >= B, "stop: end is int64 [B]"
+    st = L.struct("ns_wavenet_stop_params")
+    _fill(st, below=int(below), window=int(window), hop=int(hop), end=ptr(end))
+    L.check(L.lib().ns_wavenet_generate_until(C_.byref(p), C_.byref(st), C_.c_void_p(stream())), "ns_wavenet_generate_until")

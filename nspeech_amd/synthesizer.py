@@ -83,12 +83,16 @@ class Synthesizer(object):
         hparams_mod.set_hparams(mine)
         return self
 
-    def _wavenet_vocode_batch(self, mels, seed=0, global_conditions=None, temperature=1.0):
+    def _wavenet_vocode_batch(self, mels, seed=0, global_conditions=None, temperature=1.0, endpoint=False):
         """mels float [B, T, num_mels] -> float32 [B, T * hop] in [-1, 1], ONE generate call: row r of a mel conditions
         samples r * hop .. r * hop + hop - 1; the seed - receptive-field copies of mu_law_encode(0) - stands at t0 = -rf
         and takes row 0.  Waveform i draws from np.random.default_rng(seed + i).random(T * hop), so B = 1 is the stream
         generate(seed=seed) draws itself.  temperature: generate's - softmax(logits / temperature) draws, 0 = argmax (then
-        the uniforms have no effect).  No inv_preemphasis: the WaveNet feeder's waveforms are not pre-emphasised."""
+        the uniforms have no effect).  No inv_preemphasis: the WaveNet feeder's waveforms are not pre-emphasised.
+        endpoint=True: the generator stops every waveform at its end point (generate(endpoint=audio.endpoint_rule())) and
+        the call returns (waves, ends) - waves a list of B float32 arrays, waves[i] the ends[i] samples in front of
+        waveform i's end point, equal to full[i, :audio.find_endpoint(full[i])] of the call without it; only what was
+        drawn is copied to the host and decoded."""
         from .models.wavenet import mu_law_decode, mu_law_encode
         v, hop = self.vocoder, self._vocoder_hop
         mels = np.asarray(mels, np.float32)
@@ -96,18 +100,24 @@ class Synthesizer(object):
         silence = int(mu_law_encode(np.zeros(1, np.float32), v.Q)[0])
         uniforms = np.stack([np.random.default_rng(seed + i).random(n) for i in range(B)])
         ids = v.generate(np.full((B, v.rf), silence, np.int32), n, uniforms=uniforms, global_conditions=global_conditions,
-                         local_conditions=mels, hold=hop, t0=-v.rf, temperature=temperature)
-        return mu_law_decode(ids[:, v.rf:].cpu().numpy(), v.Q)
+                         local_conditions=mels, hold=hop, t0=-v.rf, temperature=temperature,
+                         endpoint=audio.endpoint_rule() if endpoint else None)
+        if not endpoint:
+            return mu_law_decode(ids[:, v.rf:].cpu().numpy(), v.Q)
+        ends = [int(e) for e in v.last_ends.cpu().numpy()]
+        return [mu_law_decode(ids[i, v.rf:v.rf + ends[i]].cpu().numpy(), v.Q) for i in range(B)], ends
 
     def _wavenet_vocode(self, mel, seed=0, global_conditions=None, temperature=1.0):
         """mel float [T, num_mels] -> float32 [T * hop]: _wavenet_vocode_batch of the one mel."""
         return self._wavenet_vocode_batch(np.asarray(mel, np.float32)[None], seed=seed, global_conditions=global_conditions,
                                           temperature=temperature)[0]
 
-    def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0, temperature=1.0):
+    def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True):
         """vocoder="wavenet" (after load_vocoder): the mel output through the WaveNet; seed: of the draws' random stream
         (generate(seed=)); temperature: of the draws (generate(temperature=): below 1 trades hiss for muffling, 0 is the
-        deterministic argmax vocode).  Both unused by Griffin-Lim."""
+        deterministic argmax vocode); stop_at_endpoint: the generator applies find_endpoint's rule to its own output and
+        stops drawing at the end of the first silent window, instead of drawing all T * hop samples and cutting on the
+        host (False) - the same array, bit for bit.  All three unused by Griffin-Lim."""
         if vocoder not in ("griffin_lim", "wavenet"):
             raise ValueError("vocoder %r: 'griffin_lim' or 'wavenet'" % (vocoder,))
         if vocoder == "wavenet" and self.vocoder is None:
@@ -123,6 +133,10 @@ class Synthesizer(object):
             lin = m.linear_outputs[0].float().cpu().numpy()
             m.check_status()    # (as below: invalid outputs are never vocoded)
             gc = np.asarray([speaker_id]) if self.vocoder.gc else None
+            if stop_at_endpoint:
+                wavs, _ = self._wavenet_vocode_batch(mel[None], seed=seed, global_conditions=gc, temperature=temperature,
+                                                     endpoint=True)
+                return wavs[0], mel, lin
             wav = self._wavenet_vocode(mel, seed=seed, global_conditions=gc, temperature=temperature)
             return wav[:audio.find_endpoint(wav)], mel, lin
         wav = audio.inv_spectrogram_tensorflow(m.linear_outputs[0].contiguous())
@@ -134,7 +148,7 @@ class Synthesizer(object):
         wav = wav[:audio.find_endpoint(wav)]
         return wav, mel, lin
 
-    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0, temperature=1.0):
+    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True):
         """synthesize for a list of texts: [(wav, mel, lin)] in the order of `texts`, every entry with the shapes and
         dtypes synthesize returns.  speaker_ids: one int for all, or one id per text.  More than MAX_BATCH texts run as
         consecutive chunks of at most MAX_BATCH in the given order (never sorted: see below); [] returns [].
@@ -143,8 +157,9 @@ class Synthesizer(object):
             find_endpoint of all N on the device), one copy to the host each of the waves, the ends, the mels and the
             linears, check_status() behind them as in synthesize, wav[i] = y[i, :ends[i]];
           wavenet: one generate for the chunk, text i of the LIST drawing from np.random.default_rng(seed + i) at
-            `temperature` (generate(temperature=), 0 = argmax; unused by Griffin-Lim); mu-law decoding and find_endpoint
-            per row on the host, no pre-emphasis.
+            `temperature` (generate(temperature=), 0 = argmax; unused by Griffin-Lim), every waveform stopped at its
+            end point by the generator itself (stop_at_endpoint, as in synthesize; False: all T * hop samples drawn
+            and find_endpoint per row on the host - the same arrays); mu-law decoding on the host, no pre-emphasis.
         Row i is the row of a PADDED batch: the encoder's convolutions read the padding behind a shorter text, as the
         reference's graph would, and other kernels run at N > 2 than at N = 1 (model.last_paths["decode"]).  So entry i
         is close to synthesize(texts[i]), not bit-equal to it - and depends on which texts share its chunk.  The WaveNet
@@ -176,8 +191,8 @@ class Synthesizer(object):
                 lins = m.linear_outputs.float().cpu().numpy()
                 m.check_status()            # (as in synthesize: invalid outputs are never vocoded)
                 full = self._wavenet_vocode_batch(mels, seed=seed + start, global_conditions=spk if self.vocoder.gc else None,
-                                                  temperature=temperature)
-                wavs = [w[:audio.find_endpoint(w)] for w in full]
+                                                  temperature=temperature, endpoint=bool(stop_at_endpoint))
+                wavs = full[0] if stop_at_endpoint else [w[:audio.find_endpoint(w)] for w in full]
             else:
                 y, ends = audio.finish_waves(audio.griffin_lim_gpu(m.linear_outputs))
                 y, ends = y.cpu().numpy(), ends.cpu().numpy()

@@ -567,11 +567,19 @@ def _griffin_lim(S):
     return griffin_lim_gpu(np.asarray(S, dtype=np.float32).T, raw_magnitude=True).cpu().numpy()
 
 
-def find_endpoint(wav, threshold_db=-40, min_silence_sec=0.8):
+def endpoint_rule(threshold_db=-40, min_silence_sec=0.8):
+    """(window_length, hop_length, threshold) of find_endpoint at the current hparams: the end of a clip is hop_length
+    behind the start x = hop_length, 2 hop_length, .. of the first window of window_length samples that are all below
+    threshold.  find_endpoint, finish_waves and the WaveNet generator's own stop (generate(endpoint=)) take them here."""
     hp = get_hparams()
     window_length = int(hp.sample_rate * min_silence_sec)
     hop_length = int(window_length / 4)
     threshold = np.power(10.0, threshold_db * 0.05)
+    return window_length, hop_length, threshold
+
+
+def find_endpoint(wav, threshold_db=-40, min_silence_sec=0.8):
+    window_length, hop_length, threshold = endpoint_rule(threshold_db, min_silence_sec)
     for x in range(hop_length, len(wav) - window_length, hop_length):
         if np.max(wav[x:x + window_length]) < threshold:
             return x + hop_length
@@ -595,9 +603,8 @@ def finish_waves(wavs, threshold_db=-40, min_silence_sec=0.8):
     assert x.dim() == 2, "finish_waves takes [L] or [N, L]"
     x = x.contiguous()              # x and y share one row stride: L
     N, Lw = x.shape
-    window_length = int(hp.sample_rate * min_silence_sec)
-    hop_length = int(window_length / 4)
-    threshold = float(np.power(10.0, threshold_db * 0.05))
+    window_length, hop_length, threshold = endpoint_rule(threshold_db, min_silence_sec)
+    threshold = float(threshold)
     y = torch.empty((N, Lw), dtype=torch.float32, device=dev)
     ends = torch.zeros(N, dtype=torch.int64, device=dev)
     if N > 0 and Lw > 0:            # (an empty clip has no device address to hand over: its end is 0)
