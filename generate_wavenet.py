@@ -14,6 +14,11 @@ temperature too; it needs --fast_generation true.
 audio.endpoint_rule() - it stops drawing behind the first 0.8 s that stay under -40 dB, where audio.find_endpoint would
 cut the finished waveform - and writes the waveform cut at that end; it needs the incremental generator as well, in one
 call (no --save_every).
+--stream_chunk N (the incremental generator again, not with --save_every) draws the same --samples with the same
+random numbers as the run without it, as ONE generation resumed every N samples (generate_stream: no re-seeding, unlike
+--save_every), and rewrites --wav_out_path after every chunk while the next one is being drawn; the finished file is the
+file of the run without the flag.  With --stop_at_endpoint true the partial files hold what has been drawn and the
+finished one is cut at the end point.
 --lc_channels N --local_condition FILE.npy --lc_hold H draw from a locally conditioned checkpoint: the file is float
 [rows, N], row r conditions generated samples r * H .. r * H + H - 1 (a mel spectrogram: H = the hop), the seed in
 front takes row 0; this path is the incremental generator's alone.  Any other
@@ -79,6 +84,13 @@ def main(args):
     if stop and getattr(args, "save_every", None):
         raise ValueError("--stop_at_endpoint true draws in one call (the rule counts silence across the whole waveform): "
                          "no --save_every")
+    chunk = getattr(args, "stream_chunk", None)
+    if chunk and not (args.fast_generation and (inc_t or args.temperature == 1.0)):
+        raise ValueError("--stream_chunk N hands out the incremental generator's samples while it draws: it needs "
+                         "--fast_generation true and --temperature 1.0, or any --temperature with --incremental_temperature true")
+    if chunk and getattr(args, "save_every", None):
+        raise ValueError("--stream_chunk N and --save_every N are two ways to write partial results (one generator resumed "
+                         "chunk by chunk, or one restarted per chunk): one of them")
     hp = hparams_mod.load("wavenet")
     hp.parse(args.hparams)
     gc = None
@@ -125,6 +137,24 @@ def main(args):
         if stop:
             cond.update(endpoint=audio.endpoint_rule())
         done = 0
+        if chunk:                                   # ONE generator, resumed chunk by chunk: the run without chunking, heard earlier
+            if lc is not None:                      # (as below at done = 0, n = samples: every row is on the device from the start)
+                cond.update(local_conditions=lc[None, :(args.samples - 1) // args.lc_hold + 1], hold=args.lc_hold, t0=-rf)
+            first = len(waveform)
+            stream = net.generate_stream(np.asarray(waveform[-rf:], np.int32), args.samples, chunk,
+                                         uniforms=rng.random((1, args.samples)), **cond)
+            for piece in stream:
+                waveform.extend(int(x) for x in piece[0])
+                done = stream.drawn
+                print("Sample {:3<d}/{:3<d}".format(done, args.samples), end="\r")
+                last = done >= args.samples or (stop and bool(stream.fired[0]))
+                if args.wav_out_path and not last:
+                    write_wav(mu_law_decode(np.asarray(waveform), q), SAMPLE_RATE, args.wav_out_path)
+            if stop:                                # the generated samples in front of their end point
+                n_kept = int(net.last_ends[0].item())
+                print("End point at sample {} of {}".format(n_kept, args.samples))
+                del waveform[first + n_kept:]
+            done = args.samples
         while done < args.samples:                  # in chunks, so that --save_every can write partial results
             n = min(args.samples - done, args.save_every or args.samples)
             if lc is not None:
@@ -187,6 +217,8 @@ if __name__ == "__main__":
                         help="keep the incremental generator at any --temperature (0 = argmax); needs --fast_generation true")
     parser.add_argument("--stop_at_endpoint", type=_str_to_bool, default=False,
                         help="stop drawing at the end point audio.find_endpoint would cut at; needs the incremental generator")
+    parser.add_argument("--stream_chunk", type=int, default=None,
+                        help="write --wav_out_path after every N samples of ONE resumed generation; needs the incremental generator")
     parser.add_argument("--wav_seed", type=str, default=None)
     parser.add_argument("--gc_channels", type=int, default=None)
     parser.add_argument("--gc_cardinality", type=int, default=None)

@@ -1056,6 +1056,42 @@ typedef struct {
 } ns_wavenet_stop_params;
 int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, const ns_wavenet_stop_params* stop, ns_stream_t stream);
 
+/* ns_wavenet_generate_until, one span of its sample loop per call (version 106): the generation is resumable, so a
+ * caller can take the samples of one span from ids while the next span draws (models/wavenet.py generate_stream).
+ * A struct and an entry point of their own: the two structs above keep their members and their sizes, and the two entry
+ * points above are this call with span == NULL.
+ * The generator's loop runs steps t = 1 .. total - 1.  Step t
+ *   reads ids[b, t - 1] and ids[b, t];
+ *   reads and rewrites row t % dilation of every layer's ring in queues;
+ *   takes the condition row of t (max(0, t + cond_t0) / cond_hold);
+ *   draws ids[b, t + 1] from uniform[b, t + 1 - n_seed] when n_seed <= t + 1 < total (the steps in front of that walk the
+ *   seed), and with t + 2 == total writes probs.
+ * Every one of these comes from the absolute t and from the caller's buffers, so a step needs nothing of the launch
+ * that ran the step before it except the end-point rule's pair {run, fired} (run: the silent drawn samples that end at
+ * the last one; fired: the rule has fired and the waveform has stopped), which lived in LDS.  It is carried in
+ * carry[b] = {run, fired}.
+ * This call runs steps t_begin <= t < t_end.  A series of calls over [1, a), [a, b), .., [z, total) on ONE stream, every
+ * call with the same p and stop, nothing else touching ids, queues, uniform, carry, stop->end and probs in between,
+ * leaves exactly what the single call leaves, bit for bit: ids, queues, stop->end, probs, and the unwritten tail of a
+ * stopped waveform.  The boundaries may lie anywhere, inside the seed too, and a span that draws nothing is legal.
+ *   t_begin == 1: the caller has zeroed queues; the call sets carry[b] = {0, 0} and end[b] = total - n_seed as
+ *                 ns_wavenet_generate_until does, then runs.
+ *   t_begin > 1:  nothing is initialised; with a stop, run and fired are read from carry[b], and a waveform whose fired is
+ *                 set returns at once: its ids, queues, end and probs stay as the span that fired left them.
+ *   carry[b] is written back when a waveform leaves the call: at the end of the span and where the rule fires.
+ *   probs is written by the span that holds step total - 2 alone.
+ * span == NULL is ns_wavenet_generate_until(p, stop, stream) exactly, and so is a span of [1, total) (which, with a stop,
+ * also leaves carry).  stop == NULL: carry may be NULL; a carry that is given receives {0, 0}.
+ * NS_ERR_BAD_ARG before any launch, behind every refusal of ns_wavenet_generate_until, which stay as they are:
+ * 1 <= t_begin < t_end <= total violated; stop != NULL with carry == NULL; engine 3 with any span (its helper kernel
+ * lives for one call). */
+typedef struct {
+  int64_t t_begin, t_end;  /* this call runs steps t_begin <= t < t_end; 1 <= t_begin < t_end <= total */
+  int* carry;              /* [B, 2] device ints {run, fired} of the end-point rule */
+} ns_wavenet_span_params;
+int ns_wavenet_generate_span(const ns_wavenet_generate_params* p, const ns_wavenet_stop_params* stop,
+                             const ns_wavenet_span_params* span, ns_stream_t stream);
+
 /* ------------------------------------------------------------------ audio DSP (utils/audio.py)
  * Radix-2 Stockham FFTs of n_fft points run inside LDS, one workgroup per frame; no MFMA,
  * the kernels are bandwidth / latency bound.  window = periodic Hann(win) and

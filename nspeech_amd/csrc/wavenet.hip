@@ -10,6 +10,7 @@
 //   ns_wavenet_softmax_ce mean softmax cross-entropy against integer targets    (:479-502) and d/dlogits
 //   ns_wavenet_generate   incremental sample-by-sample generation (persistent)  (generate_wavenet.py:56-142)
 //   ns_wavenet_generate_until  the same, every waveform stopped at its end point     (utils/audio.py find_endpoint)
+//   ns_wavenet_generate_span   the same, one span of the sample loop per call: resumable, the base of streamed synthesis
 #include "exchange.h"
 #include "carve.h"
 
@@ -336,11 +337,64 @@ __device__ __forceinline__ int gen_first_max(const float* lg, float m, int Q) {
 // audio.find_endpoint's loop, windows completing in the order of x, so the first to fire is the smallest.  `fired` is
 // set in front of the barrier that follows the store and never cleared; every thread reads it behind that barrier and
 // leaves, so the exit is uniform over the workgroup and no wave is left waiting at a later barrier.
-struct GenStop { int run, fired; };
-__device__ __forceinline__ void gen_stop_init(const ns_wavenet_stop_params& st, GenStop* gs, long n, int b) {
-  ns_lds_poke(&gs->run, 0);
-  ns_lds_poke(&gs->fired, 0);
-  if (st.end) st.end[b] = n;                       // until the rule fires: thread 0 writes both, in program order
+//
+// A span (ns_wavenet_span_params, a launch argument beside inv_t and st): the launch runs steps t0 <= t < t1 of the
+// sample loop.  A step is complete at its closing barrier and takes everything else from the absolute t - the ring row
+// t % dilation, the condition row, the uniform - and from global memory (ids, queues), so the pair above is all that a
+// later launch has to be handed: thread 0 stores it to carry[b] at every exit (gen_stop_save: the end of the span and
+// the fired return, where it has itself written the pair or reads it behind the barrier that guards `fired`) and the
+// launch with t0 > 1 takes it from there instead of clearing it; a waveform that had fired runs no step (gen_span_end),
+// uniformly as above.
+// SPAN (a template argument of the three kernel bodies): the plain calls (span == NULL) launch the kernels of SPAN =
+// false, in which the bounds are the constants 1 and total and nothing of the above is compiled - the kernels as they
+// were before spans, names and arguments included: every one of them holds more scalars than it has registers for, and
+// one more bound that lives through the sample loop moved the unconditioned MFMA chain by 0.5 us per drawn sample
+// (profiles/wavenet_stream.txt).
+struct GenStop { int run, fired; int* carry; };   // carry: this waveform's pair in device memory, NULL = not carried
+struct GenSpan { int t0, t1; int* carry; };
+// (the pointer waits in LDS for the exits: as a launch argument that lives through the sample loop it takes two scalar
+// registers the kernels do not have - the single-wave chain at C = 32 went from 12 to 16 bytes of scratch per lane)
+template <bool SPAN>
+__device__ __forceinline__ void gen_stop_init(const ns_wavenet_stop_params& st, const GenSpan& sp, GenStop* gs, long n, int b) {
+  if constexpr (SPAN) {
+    int* carry = sp.carry ? sp.carry + 2 * b : nullptr;
+    const bool resume = sp.t0 > 1 && st.end;
+    ns_lds_poke(&gs->run, resume ? carry[0] : 0);
+    ns_lds_poke(&gs->fired, resume ? carry[1] : 0);
+    ns_lds_poke(&gs->carry, carry);
+    if (st.end && sp.t0 == 1) st.end[b] = n;       // until the rule fires: thread 0 writes both, in program order
+  } else {
+    ns_lds_poke(&gs->run, 0);
+    ns_lds_poke(&gs->fired, 0);
+    if (st.end) st.end[b] = n;                     // until the rule fires: thread 0 writes both, in program order
+  }
+}
+template <bool SPAN>
+__device__ __forceinline__ void gen_stop_save(const GenStop* gs) {
+  if constexpr (SPAN) {
+    int* carry = ns_lds_peek(&gs->carry);
+    if (carry) {
+      carry[0] = ns_lds_peek(&gs->run);
+      carry[1] = ns_lds_peek(&gs->fired);
+    }
+  }
+}
+// behind the opening barrier: where this launch's sample loop ends - t1, or t0 (no step at all: the launch falls through
+// to its exit) for a waveform that fired in an earlier span.  Every thread reads the same word, and the bound is handed
+// back as a scalar: an early return here instead cost the conditioned MFMA kernel a scratch frame.
+__device__ __forceinline__ int gen_span_end(const ns_wavenet_stop_params& st, const GenSpan& sp, const GenStop* gs) {
+  return __builtin_amdgcn_readfirstlane((st.end && ns_lds_peek(&gs->fired)) ? sp.t0 : sp.t1);
+}
+#define GEN_SPAN_BOUNDS()                                                       \
+  const int t_begin = SPAN ? sp.t0 : 1;                                         \
+  int t_end = p.total;                                                          \
+  if constexpr (SPAN) t_end = gen_span_end(st, sp, &gs)
+// behind the barrier that closes a drawn sample: true when the rule has fired (every thread reads the same word)
+template <bool SPAN>
+__device__ __forceinline__ bool gen_stop_left(const ns_wavenet_stop_params& st, const GenStop* gs, int tid) {
+  if (!(st.end && ns_lds_peek(&gs->fired))) return false;
+  if (tid == 0) gen_stop_save<SPAN>(gs);
+  return true;
 }
 __device__ __forceinline__ void gen_stop_step(const ns_wavenet_stop_params& st, GenStop* gs, int id, long j, long n, int b) {
   const int run = id < st.below ? ns_lds_peek(&gs->run) + 1 : 0;
@@ -365,8 +419,9 @@ struct GenLds {                                   // dynamic LDS of wn_generate_
   int ex = c.take<double>(Q);                  // [Q]; 8-byte aligned when Dc is even (the launcher checks)
   int bytes = c.off;
 };
-template <typename W>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
+// (arguments by value: through references the float instantiation spilled two registers to scratch memory)
+template <typename W, bool SPAN>
+__device__ __forceinline__ void wn_generate_body(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st, GenSpan sp) {
   extern __shared__ float gsm[];
   const int R = p.R, Dc = p.Dc, S = p.S, Q = p.Q;
   const GenLds lay{R, Dc, S, Q};
@@ -385,10 +440,11 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
   __shared__ int dil[128];
   __shared__ GenStop gs;
   for (int i = tid; i < p.L && i < 128; i += GEN_THREADS) dil[i] = p.dilations[i];
-  if (tid == 0) gen_stop_init(st, &gs, p.total - p.n_seed, b);
+  if (tid == 0) gen_stop_init<SPAN>(st, sp, &gs, p.total - p.n_seed, b);
   __syncthreads();
+  GEN_SPAN_BOUNDS();
   GenLayerW<W> wa, wbuf;
-  for (int t = 1; t < p.total; ++t) {
+  for (int t = t_begin; t < t_end; ++t) {
     const bool emit = t + 1 >= p.n_seed && t + 1 < p.total;      // sample t+1 must be drawn
     // the condition row of network-input position t (cond_rows > 1: one row per cond_hold samples from cond_t0 on)
     const float* cond = p.cond;
@@ -493,8 +549,19 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_gen
         for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
     }
     __syncthreads();
-    if (st.end && ns_lds_peek(&gs.fired)) return;                // the rule fired: every thread leaves behind the barrier
+    if (st.end && ns_lds_peek(&gs.fired)) break;                 // the rule fired: every thread leaves behind the barrier
   }
+  if (tid == 0) gen_stop_save<SPAN>(&gs);
+}
+
+// the kernel of the plain calls, with its name and its arguments as they were, and the kernel of a span
+template <typename W>
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
+  wn_generate_body<W, false>(p, inv_t, st, GenSpan{});
+}
+template <typename W>
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_span_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st, GenSpan sp) {
+  wn_generate_body<W, true>(p, inv_t, st, sp);
 }
 
 // ---- fast variant (bf16 weights, R == Dc == C): the residual chain of a sample - 50 dependent layers of tiny
@@ -582,8 +649,8 @@ struct FastLds {                                  // dynamic LDS of wn_generate_
   int ex = c.take<double>(Q);                  // [Q]; 8-byte aligned when L * C is even (the launcher checks)
   int bytes = c.off;
 };
-template <int C>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
+template <int C, bool SPAN>
+__device__ __forceinline__ void wn_generate_fast_body(const ns_wavenet_generate_params& p, double inv_t, const ns_wavenet_stop_params& st, const GenSpan& sp) {
   extern __shared__ float gsm[];
   const int S = p.S, Q = p.Q, L = p.L;
   const FastLds lay{L, C, S, Q};
@@ -602,10 +669,11 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavene
   if (tid == 0) {
     long q = 0;
     for (int i = 0; i < L; ++i) { dil[i] = p.dilations[i]; qoff[i] = q; q += p.dilations[i]; }
-    gen_stop_init(st, &gs, p.total - p.n_seed, b);
+    gen_stop_init<SPAN>(st, sp, &gs, p.total - p.n_seed, b);
   }
   __syncthreads();
-  for (int t = 1; t < p.total; ++t) {
+  GEN_SPAN_BOUNDS();
+  for (int t = t_begin; t < t_end; ++t) {
     const bool emit = t + 1 >= p.n_seed && t + 1 < p.total;
     if (wave == 0) {
       float xcur = 0.f;
@@ -670,8 +738,19 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavene
         for (int j = 0; j < Q; ++j) p.probs[(long)b * Q + j] = (float)(ex[j] / se);
     }
     __syncthreads();
-    if (st.end && ns_lds_peek(&gs.fired)) return;                // the rule fired: every thread leaves behind the barrier
+    if (st.end && ns_lds_peek(&gs.fired)) break;                 // the rule fired: every thread leaves behind the barrier
   }
+  if (tid == 0) gen_stop_save<SPAN>(&gs);
+}
+
+// the kernel of the plain calls, with its name and its arguments as they were, and the kernel of a span
+template <int C>
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
+  wn_generate_fast_body<C, false>(p, inv_t, st, GenSpan{});
+}
+template <int C>
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_fast_span_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st, GenSpan sp) {
+  wn_generate_fast_body<C, true>(p, inv_t, st, sp);
 }
 
 // ---- MFMA variant (R == Dc == 32): the residual chain of a sample on the matrix cores of ONE wavefront, the skip
@@ -822,8 +901,8 @@ struct ChainLds {                                 // dynamic LDS of wn_generate_
   O ctab = c.template take<float>(cond ? L * 96 : 0);   // COND: [L][3 * 32]
   O bytes = c.off;
 };
-template <bool COND>
-__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
+template <bool COND, bool SPAN>
+__device__ __forceinline__ void wn_generate_mfma_body(const ns_wavenet_generate_params& p, double inv_t, const ns_wavenet_stop_params& st, const GenSpan& sp) {
   extern __shared__ float gsm[];
   constexpr int C = 32;
   const int S = p.S, Q = p.Q, L = p.L;
@@ -846,13 +925,14 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   if (tid == 0) {
     long q = 0;
     for (int i = 0; i < L; ++i) { dil[i] = p.dilations[i]; qoff[i] = q; q += p.dilations[i]; }
-    gen_stop_init(st, &gs, p.total - p.n_seed, b);
+    gen_stop_init<SPAN>(st, sp, &gs, p.total - p.n_seed, b);
   }
   if constexpr (COND) {
     for (int i = tid; i < L * C; i += GEN_THREADS)
       ctab[(i / C) * 3 * C + 2 * C + i % C] = p.dense_bias ? p.dense_bias[i] : 0.f;
   }
   __syncthreads();
+  GEN_SPAN_BOUNDS();
   const int l15 = lane & 15, kq = lane >> 4;
   const bool afl = l15 == 0;               // lanes that carry row 0 of an A fragment
   // the sample loop is written out once per role: the chain wave and the skip waves then get register allocations of
@@ -946,10 +1026,10 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
         __syncthreads();
         // the end-point rule fired: thread 0 set gs.fired in front of this barrier, every thread of both sample loops
         // reads it here and returns - the path of a timed-out hand-over
-        return !(st.end && ns_lds_peek(&gs.fired));
+        return !gen_stop_left<SPAN>(st, &gs, tid);
   };
   if (wave == 0) {
-    for (int t = 1; t < p.total; ++t) {
+    for (int t = t_begin; t < t_end; ++t) {
       const bool emit = t + 1 >= p.n_seed && t + 1 < p.total;
       if (tid == 0) chain_pos = 0;
       __syncthreads();
@@ -1075,10 +1155,11 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
       if (!emit) continue;
       if (!gen_post(t)) return;                              // (the end-point rule fired; engine 3: a hand-over timed out)
     }
+    if (tid == 0) gen_stop_save<SPAN>(&gs);                 // the end of the span
   } else {
     // COND: the condition row in ctab is `crow`, and the first position (on the condition's time axis) of the next row
     long crow = -1, cnext = 0;
-    for (int t = 1; t < p.total; ++t) {
+    for (int t = t_begin; t < t_end; ++t) {
       const bool emit = t + 1 >= p.n_seed && t + 1 < p.total;
       if constexpr (COND) {
         if (crow < 0 || (long)t + (long)p.cond_t0 >= cnext) {
@@ -1157,14 +1238,50 @@ __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavene
   }
 }
 
+// the kernel of the plain calls, with its name and its arguments as they were, and the kernel of a span
+template <bool COND>
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
+  wn_generate_mfma_body<COND, false>(p, inv_t, st, GenSpan{});
+}
+template <bool COND>
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_span_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st, GenSpan sp) {
+  wn_generate_mfma_body<COND, true>(p, inv_t, st, sp);
+}
+
 constexpr size_t WN_CHAIN_LDS_MAX = 60 * 1024;
 extern "C" int ns_wavenet_chain_fits(int L, int R, int S, int Q, int cond) {
   return L > 0 && R > 0 && S > 0 && Q > 0 && ChainLds<size_t>{(size_t)L, (size_t)R, (size_t)S, (size_t)Q, (size_t)cond}.bytes <= WN_CHAIN_LDS_MAX;
 }
 
-extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t s) { return ns_wavenet_generate_until(p, nullptr, s); }
+extern "C" int ns_wavenet_generate(const ns_wavenet_generate_params* p, ns_stream_t s) { return ns_wavenet_generate_span(p, nullptr, nullptr, s); }
 
 extern "C" int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, const ns_wavenet_stop_params* stop, ns_stream_t s) {
+  return ns_wavenet_generate_span(p, stop, nullptr, s);
+}
+
+// the span kernel with a span, the kernel as it was without
+#define WN_GEN_LAUNCH(lds_, K_, A_)                                                                                              \
+  do {                                                                                                                           \
+    if (span) hipLaunchKernelGGL(K_##_span_kernel<A_>, dim3(p->B), dim3(GEN_THREADS), (lds_), (hipStream_t)s, *p, inv_t, st, sp); \
+    else hipLaunchKernelGGL(K_##_kernel<A_>, dim3(p->B), dim3(GEN_THREADS), (lds_), (hipStream_t)s, *p, inv_t, st);              \
+  } while (0)
+// The span's own refusals stand in front of the first launch of every route, behind all of the plain call's, which keep
+// their order and their wording.
+#define WN_SPAN_CHECK()                                                                                                          \
+  do {                                                                                                                           \
+    if (span) {                                                                                                                  \
+      NS_CHECK_ARG(span->t_begin >= 1 && span->t_begin < span->t_end && span->t_end <= p->total,                                  \
+                   "ns_wavenet_generate_span: steps %lld .. %lld outside 1 <= t_begin < t_end <= total = %d",                      \
+                   (long long)span->t_begin, (long long)span->t_end, p->total);                                                   \
+      NS_CHECK_ARG(!stop || span->carry, "ns_wavenet_generate_span: carry is NULL with a stop (two ints per waveform)");           \
+      NS_CHECK_ARG(p->engine != 3, "ns_wavenet_generate_span: engine 3 takes no span (its helper kernel lives for one call): "    \
+                                   "engine 2");                                                                                   \
+      sp = GenSpan{(int)span->t_begin, (int)span->t_end, span->carry};                                                            \
+    }                                                                                                                            \
+  } while (0)
+
+extern "C" int ns_wavenet_generate_span(const ns_wavenet_generate_params* p, const ns_wavenet_stop_params* stop,
+                                        const ns_wavenet_span_params* span, ns_stream_t s) {
   NS_CHECK_ARG(p && p->weights && p->ids && p->queues && p->uniform && p->dilations, "ns_wavenet_generate: null");
   ns_wavenet_stop_params st = {};                  // end = NULL: the rule is not armed, the kernels draw all of total - n_seed
   if (stop) {
@@ -1199,6 +1316,7 @@ extern "C" int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, co
   NS_CHECK_ARG(std::isfinite(p->temperature) && p->temperature >= 0.f,
                "ns_wavenet_generate: temperature %g must be finite and not negative (0 = 1.0)", (double)p->temperature);
   const double inv_t = (p->argmax || p->temperature == 0.f) ? 1.0 : 1.0 / (double)p->temperature;
+  GenSpan sp = {1, p->total, nullptr};             // span == NULL: every step, nothing carried
   if (p->fgT && p->deT) {
     NS_CHECK_ARG(p->w_dtype == NS_BF16 && p->R == p->Dc && (p->R == 32 || p->R == 16) && p->S % 8 == 0 && p->Q % 8 == 0 && p->S / 8 <= GEN_THREADS &&
                      GEN_THREADS % (p->S / 8) == 0 && GEN_THREADS % (p->Q / 8) == 0,
@@ -1213,6 +1331,7 @@ extern "C" int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, co
         NS_CHECK_ARG(p->post_x && p->helper_stream && p->helper_stream != s && p->S == WN_S && p->Q == WN_Q &&
                          (((uintptr_t)p->post_x) & 15) == 0 && (long)p->B * (1 + NS_WN_HELPERS) <= ns_device_cus(),
                      "ns_wavenet_generate: engine 3 needs post_x, a helper stream of its own, S = 512, Q = 256 and B * 5 workgroups resident");
+        WN_SPAN_CHECK();
         const int zrc = ns_zero_async(p->post_x, (ns_wavenet_post_bytes(p->B) + 15) & ~(size_t)15, (hipStream_t)s);
         if (zrc) return zrc;
         // the helpers start behind the clearing of the exchange region and run beside the chain kernel
@@ -1230,23 +1349,27 @@ extern "C" int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, co
       if (full) {                            // + the condition row and the dense biases
         const size_t lds4 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 1}.bytes;
         NS_CHECK_ARG(lds4 <= WN_CHAIN_LDS_MAX, "ns_wavenet_generate: state and condition row do not fit in LDS (ns_wavenet_chain_fits)");
-        hipLaunchKernelGGL(wn_generate_mfma_kernel<true>, dim3(p->B), dim3(GEN_THREADS), lds4, (hipStream_t)s, *p, inv_t, st);
+        WN_SPAN_CHECK();
+        WN_GEN_LAUNCH(lds4, wn_generate_mfma, true);
         NS_CHECK_LAUNCH("wavenet_generate_mfma_cond");
         return NS_OK;
       }
-      hipLaunchKernelGGL(wn_generate_mfma_kernel<false>, dim3(p->B), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p, inv_t, st);
+      WN_SPAN_CHECK();
+      WN_GEN_LAUNCH(lds3, wn_generate_mfma, false);
       NS_CHECK_LAUNCH("wavenet_generate_mfma");
       return NS_OK;
     }
-    if (p->R == 32) hipLaunchKernelGGL(wn_generate_fast_kernel<32>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t, st);
-    else hipLaunchKernelGGL(wn_generate_fast_kernel<16>, dim3(p->B), dim3(GEN_THREADS), lds2, (hipStream_t)s, *p, inv_t, st);
+    WN_SPAN_CHECK();
+    if (p->R == 32) WN_GEN_LAUNCH(lds2, wn_generate_fast, 32);
+    else WN_GEN_LAUNCH(lds2, wn_generate_fast, 16);
     NS_CHECK_LAUNCH("wavenet_generate_fast");
     return NS_OK;
   }
   NS_CHECK_ARG(carve_aligned(gl.ex, sizeof(double)),
                "ns_wavenet_generate: the per-layer kernel needs an even Dc (its float64 row follows 3 Dc floats in LDS)");
-  if (p->w_dtype == NS_BF16) hipLaunchKernelGGL(wn_generate_kernel<bf16_t>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t, st);
-  else hipLaunchKernelGGL(wn_generate_kernel<float>, dim3(p->B), dim3(GEN_THREADS), lds, (hipStream_t)s, *p, inv_t, st);
+  WN_SPAN_CHECK();
+  if (p->w_dtype == NS_BF16) WN_GEN_LAUNCH(lds, wn_generate, bf16_t);
+  else WN_GEN_LAUNCH(lds, wn_generate, float);
   NS_CHECK_LAUNCH("wavenet_generate");
   return NS_OK;
 }

@@ -62,6 +62,90 @@ def endpoint_code(q, threshold):
     return below
 
 
+def safe_prefix(codes_tail, drawn, below, window, hop):
+    """How many of the `drawn` samples of a waveform that is still being drawn (its end-point rule has not fired) can be
+    handed out without ever passing the cut audio.find_endpoint will make: drawn - min(run, window - hop), run the length
+    of the trailing run of codes < below.  codes_tail: the last drawn codes, at least min(drawn, window - hop) of them.
+    A window that fires later is not complete yet, so its start x >= drawn - window + 1, and its samples in front of
+    `drawn` are silent, so x >= drawn - run; the cut is x + hop, and with no window firing it is the full length."""
+    tail = np.asarray(codes_tail).reshape(-1)[-int(drawn):] if drawn > 0 else np.zeros(0, np.int32)
+    loud = np.nonzero(tail >= below)[0]
+    run = len(tail) - 1 - int(loud[-1]) if len(loud) else len(tail)
+    return int(drawn) - min(run, int(window) - int(hop))
+
+
+class WaveNetStream(object):
+    """The iterator of generate_stream.  It owns, for its lifetime, what the spans share: ids [B, total], queues, the
+    uniforms, the weight shadows, the condition terms (its own copies: another call on the model may reuse the model's
+    buffers), last_probs, last_ends and, with an endpoint, carry int32 [B, 2] = the rule's {run, fired}.
+    Chunk k (drawn samples j0 .. j1 - 1) is the span of steps n_seed + j0 - 1 (1 for the first chunk: it walks the seed) up
+    to n_seed + j1 - 1 (total for the last).  The spans run on the stream that was current at the call; span k + 1 is
+    launched before chunk k is waited for, and chunk k travels to the host on a side stream behind an event recorded
+    after span k (the spans write disjoint parts of ids), so the device never waits for the consumer.  With an endpoint,
+    carry and last_ends as span k left them travel with the chunk (snapshots taken on the spans' stream: the next span
+    rewrites both) and the iteration ends once every waveform has fired.
+    ends / fired: host copies of last_ends and of carry[:, 1] as of the last yielded chunk (None without an endpoint);
+    drawn: the samples yielded so far."""
+
+    def __init__(self, model, g, chunk):
+        m = self.model = model
+        self.args, self.kw = g["args"], dict(g["kw"])
+        for k, v in g["extra"].items():
+            if torch.is_tensor(v):
+                self.kw[k] = v.clone()
+        self.B, self.n_seed, self.total = self.args[8], self.args[9], self.args[10]
+        self.ids, self.uniforms, self.queues = self.args[12], self.args[13], self.args[14]
+        self.last_probs, self.last_ends, self.last_engine = m.last_probs, m.last_ends, g["last_engine"]
+        m.last_engine = self.last_engine
+        dev = self.ids.device
+        n = self.total - self.n_seed
+        self.edges = list(range(0, n, chunk)) + [n]
+        self.main, self.side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        self.carry = self.ends = self.fired = None
+        if self.kw["stop"] is not None:
+            self.carry = torch.zeros(self.B, 2, dtype=torch.int32, device=dev)
+            self._snap = [(torch.empty_like(self.carry), torch.empty_like(self.last_ends)) for _ in range(2)]
+        self.drawn, self._k, self._events = 0, 0, {}
+        self._launch(0)
+
+    def _launch(self, k):
+        j0, j1 = self.edges[k], self.edges[k + 1]
+        t_begin = 1 if k == 0 else self.n_seed + j0 - 1
+        t_end = self.total if k + 2 == len(self.edges) else self.n_seed + j1 - 1
+        with torch.cuda.stream(self.main):
+            ops.wavenet_generate(*self.args, span=(t_begin, t_end, self.carry), **self.kw)
+            if self.carry is not None:
+                self._snap[k % 2][0].copy_(self.carry)
+                self._snap[k % 2][1].copy_(self.last_ends)
+            ev = torch.cuda.Event()
+            ev.record(self.main)
+        self._events[k] = ev
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        k = self._k
+        if k + 1 >= len(self.edges) or (self.fired is not None and self.fired.all()):
+            raise StopIteration
+        if k + 2 < len(self.edges):
+            self._launch(k + 1)
+        j0, j1 = self.edges[k], self.edges[k + 1]
+        self.side.wait_event(self._events.pop(k))
+        with torch.cuda.stream(self.side):
+            out = torch.empty(self.B, j1 - j0, dtype=torch.int32).pin_memory()
+            out.copy_(self.ids[:, self.n_seed + j0:self.n_seed + j1], non_blocking=True)
+            if self.carry is not None:
+                carry, ends = (t.to("cpu", non_blocking=True) for t in self._snap[k % 2])
+            done = torch.cuda.Event()
+            done.record(self.side)
+        done.synchronize()
+        if self.carry is not None:
+            self.fired, self.ends = carry[:, 1].numpy() != 0, ends.numpy().copy()
+        self._k, self.drawn = k + 1, j1
+        return out.numpy()
+
+
 class SimpleWaveNet(object):
     """create_model('simple_wavenet', hparams).  dtype: 'fp32' (exact FMA, parity tests) or 'bf16'."""
 
@@ -702,9 +786,36 @@ class SimpleWaveNet(object):
         returned array keeps its shape and holds zeros behind that, and the row's last_probs stay zero.  Automatic
         engine selection never picks engine 3 with an endpoint (its helper workgroups would wait for a waveform that
         has left); engine=3 with one is a ValueError."""
+        g = self._gen_prepare(seed_ids, n_samples, uniforms, seed, exact, fast, engine, global_conditions, local_conditions, hold,
+                              t0, temperature, endpoint)
+        engine, extra, ids = g["kw"]["engine"], g["extra"], g["args"][12]
+        dev = self.device
+        ops.wavenet_generate(*g["args"], **g["kw"])
+        if engine == 3:             # the call's stream takes the helpers' end in: post_x is free behind it
+            torch.cuda.current_stream(dev).wait_stream(self._helper_stream)
+            self.last_status = extra["post_x"][:1].view(torch.int32)
+            if int(self.last_status.item()) != 0:        # (the caller reads the samples next anyway: one wait here)
+                raise RuntimeError("ns_wavenet_generate: a hand-over between the chain and its helper workgroups timed out "
+                                   "(their workgroups were not resident together?) - the samples are invalid; engine=2 "
+                                   "runs without helpers")
+        self.last_engine = g["last_engine"]
+        a, k = g["args"], g["kw"]
+        self._gen_keep = (k["fgT"], k["deT"], a[13], a[14], a[2], extra)   # keep the operands alive until the stream has used them
+        return ids
+
+    def _gen_prepare(self, seed_ids, n_samples, uniforms, seed, exact, fast, engine, global_conditions, local_conditions, hold,
+                     t0, temperature, endpoint, spans=False):
+        """What a generation forms once, for generate (one call) and generate_stream (a series of spans): the checks, ids
+        with the seed, the uniforms and zeroed queues on the device, the condition terms, the engine and its weight
+        shadows, last_probs and last_ends.  Returns the positional and keyword arguments of ops.wavenet_generate (args,
+        kw), the condition terms (extra) and last_engine.  spans: engine 3 is neither chosen nor taken (its helper kernel
+        lives for one launch)."""
         temperature = float(temperature)
         if not math.isfinite(temperature) or temperature < 0:
             raise ValueError("temperature %r: a finite number > 0 for a tempered draw, 0 for argmax" % (temperature,))
+        if spans and engine == 3:
+            raise ValueError("engine 3 takes no spans (its helper kernel lives for one call): engine 2 runs the same chain "
+                             "without helpers")
         if endpoint is not None and engine == 3:
             raise ValueError("engine 3 takes no endpoint (its helper workgroups would wait for a waveform that has stopped): "
                              "engine 2 runs the same chain without helpers")
@@ -763,7 +874,7 @@ class SimpleWaveNet(object):
             # per-layer kernel, as before the chain took them
             if extra and (engine == 1 or not ops.wavenet_chain_fits(self.L, self.R, self.S, self.Q, True)):
                 shadows, engine = False, 0
-            if endpoint is None and not extra and engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
+            if not spans and endpoint is None and not extra and engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
                     and self._helper(dev) is not None:
                 engine = 3          # + the post-processing products on four helper workgroups per waveform (weights in registers)
         if shadows:
@@ -791,19 +902,29 @@ class SimpleWaveNet(object):
         if endpoint is not None:
             window_length, hop_length, threshold = endpoint
             stop = (endpoint_code(self.Q, threshold), int(window_length), int(hop_length), self.last_ends)
-        ops.wavenet_generate(W, offs, dil, self.L, self.R, self.Dc, self.S, self.Q, B, n_seed, total, qrows, ids, un, queues,
-                             probs=self.last_probs, fgT=fgT, deT=deT, engine=engine, temperature=temperature or 1.0,
-                             argmax=temperature == 0, stop=stop, **extra)
-        if engine == 3:             # the call's stream takes the helpers' end in: post_x is free behind it
-            torch.cuda.current_stream(dev).wait_stream(self._helper_stream)
-            self.last_status = extra["post_x"][:1].view(torch.int32)
-            if int(self.last_status.item()) != 0:        # (the caller reads the samples next anyway: one wait here)
-                raise RuntimeError("ns_wavenet_generate: a hand-over between the chain and its helper workgroups timed out "
-                                   "(their workgroups were not resident together?) - the samples are invalid; engine=2 "
-                                   "runs without helpers")
-        self.last_engine = engine if fgT is not None else 0
-        self._gen_keep = (fgT, deT, un, queues, dil, extra)  # keep the operands alive until the stream has used them
-        return ids
+        args = (W, offs, dil, self.L, self.R, self.Dc, self.S, self.Q, B, n_seed, total, qrows, ids, un, queues)
+        kw = dict(probs=self.last_probs, fgT=fgT, deT=deT, engine=engine, temperature=temperature or 1.0,
+                  argmax=temperature == 0, stop=stop, **extra)
+        return dict(args=args, kw=kw, extra=extra, last_engine=engine if fgT is not None else 0)
+
+    def generate_stream(self, seed_ids, n_samples, chunk, uniforms=None, seed=0, exact=None, fast=True, engine=None,
+                        global_conditions=None, local_conditions=None, hold=1, t0=0, temperature=1.0, endpoint=None):
+        """generate() handed out while it draws: an iterator (WaveNetStream) whose step k yields the int32 host array
+        [B, j1 - j0] of drawn samples j0 = k * chunk .. j1 - 1 (the last chunk may be shorter), every keyword with
+        generate's meaning.  The chunks side by side are generate(...)[:, n_seed:] bit for bit, on the same engine:
+        each chunk is one span of the generator's loop (ns_wavenet_generate_span) over the same ids and queues, no
+        re-seeding in between, and the span behind a chunk is already running when the chunk is copied to the host.
+        Everything generate forms once per call is formed once per stream, before this method returns; all condition
+        rows of the waveform are given up front.  With an endpoint the iteration ends behind the chunk in which the last
+        waveform stopped (the arrays keep generate's zeros behind a row's stop; cut row b at last_ends[b], or hand out
+        safe_prefix of what was drawn so far).  last_engine, last_probs and last_ends are generate's once the
+        iterator is exhausted.  Engine 3 is never chosen and engine=3 is a ValueError (its helper kernel lives for one
+        launch); chunk < 1 is a ValueError."""
+        if int(chunk) < 1:
+            raise ValueError("chunk %r: at least one drawn sample per chunk" % (chunk,))
+        g = self._gen_prepare(seed_ids, n_samples, uniforms, seed, exact, fast, engine, global_conditions, local_conditions, hold,
+                              t0, temperature, endpoint, spans=True)
+        return WaveNetStream(self, g, int(chunk))
 
     def _helper(self, dev):
         """The helper kernel's stream: one that was seen to run BESIDE the current stream (ns_streams_concurrent), or None

@@ -914,12 +914,15 @@ def wavenet_chain_fits(L_, R, S, Q, cond):
 def wavenet_generate(weights, offs, dilations, L_, R, Dc, S, Q, B, n_seed, total, queue_rows, ids, uniform, queues, probs=None,
                      fgT=None, deT=None, engine=0, cond=None, dense_bias=None, skip_bias=None, post1_bias=None, post2_bias=None,
                      post_x=None, helper_stream=None, cond_rows=0, cond_hold=0, cond_t0=0, temperature=0.0, argmax=False,
-                     stop=None):
+                     stop=None, span=None):
     """cond_rows > 1: cond is [B, cond_rows, L, 2Dc], one row per cond_hold samples, ids[.., 0] at position cond_t0 of the
     condition's time axis (include/nspeech_hip.h).  temperature: the draws come from softmax(logits / temperature), 0 = 1.0;
     argmax: the lowest index of the largest logit instead of a draw.  Both are the C fields, checked by the launcher.
     stop = (below, window, hop, end): ns_wavenet_generate_until - a waveform stops drawing where find_endpoint's rule
-    (every code of a window < below) first holds, end int64 [B] on the device receives the end points."""
+    (every code of a window < below) first holds, end int64 [B] on the device receives the end points.
+    span = (t_begin, t_end, carry): ns_wavenet_generate_span - this call runs steps t_begin <= t < t_end of the sample loop;
+    carry int32 [B, 2] on the device holds the rule's {run, fired} between the calls of a series (None without a stop).
+    Every call of a series takes the same other arguments."""
     p = L.struct("ns_wavenet_generate_params")
     _fill(p, cond_rows=cond_rows, cond_hold=cond_hold, cond_t0=cond_t0, temperature=float(temperature), argmax=int(bool(argmax)))
     if post_x is not None:
@@ -931,11 +934,21 @@ def wavenet_generate(weights, offs, dilations, L_, R, Dc, S, Q, B, n_seed, total
           off_post1=offs["post1"], off_post2=offs["post2"], dilations=ptr(dilations), L=L_, R=R, Dc=Dc, S=S, Q=Q, B=B,
           n_seed=n_seed, total=total, queue_rows=queue_rows, ids=ptr(ids), uniform=ptr(uniform), queues=ptr(queues),
           probs=ptr(probs), fgT=ptr(fgT), deT=ptr(deT), engine=engine)
-    if stop is None:
+    if stop is None and span is None:
         L.call("ns_wavenet_generate", p, stream())
         return
-    below, window, hop, end = stop
-    assert end.dtype == torch.int64 and end.is_contiguous() and end.numel() >= B, "stop: end is int64 [B]"
-    st = L.struct("ns_wavenet_stop_params")
-    _fill(st, below=int(below), window=int(window), hop=int(hop), end=ptr(end))
-    L.check(L.lib().ns_wavenet_generate_until(C_.byref(p), C_.byref(st), C_.c_void_p(stream())), "ns_wavenet_generate_until")
+    st = None
+    if stop is not None:
+        below, window, hop, end = stop
+        assert end.dtype == torch.int64 and end.is_contiguous() and end.numel() >= B, "stop: end is int64 [B]"
+        st = L.struct("ns_wavenet_stop_params")
+        _fill(st, below=int(below), window=int(window), hop=int(hop), end=ptr(end))
+    if span is None:
+        L.check(L.lib().ns_wavenet_generate_until(C_.byref(p), C_.byref(st), C_.c_void_p(stream())), "ns_wavenet_generate_until")
+        return
+    t_begin, t_end, carry = span
+    assert carry is None or (carry.dtype == torch.int32 and carry.is_contiguous() and carry.numel() >= 2 * B), "span: carry is int32 [B, 2]"
+    sp = L.struct("ns_wavenet_span_params")
+    _fill(sp, t_begin=int(t_begin), t_end=int(t_end), carry=ptr(carry))
+    L.check(L.lib().ns_wavenet_generate_span(C_.byref(p), C_.byref(st) if st is not None else None, C_.byref(sp),
+                                             C_.c_void_p(stream())), "ns_wavenet_generate_span")

@@ -36,6 +36,46 @@ def batch_chunks(n, size=MAX_BATCH):
     return [(s, min(n, s + size)) for s in range(0, n, size)]
 
 
+class SynthesisStream(object):
+    """What Synthesizer.synthesize_stream returns: .mel [T, num_mels] and .lin [T, num_freq] of the text, and an iteration
+    over float32 pieces of its waveform: mu_law_decode of the vocoder's generate_stream `codes` at B = 1.  rule:
+    generate's endpoint triple - then a piece ends at safe_prefix of the samples drawn so far, the last one at the end
+    point - or None for the uncut waveform."""
+
+    def __init__(self, vocoder, codes, mel, lin, rule):
+        from .models.wavenet import endpoint_code
+        self.vocoder, self.codes, self.mel, self.lin, self.rule = vocoder, codes, mel, lin, rule
+        self.below = endpoint_code(vocoder.Q, rule[2]) if rule is not None else None
+        self._drawn = np.zeros(codes.total - codes.n_seed, np.int32)      # every code drawn so far
+        self._out, self._done = 0, False                                  # samples handed out; the last piece is out
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        from .models.wavenet import mu_law_decode, safe_prefix
+        while not self._done:
+            piece = next(self.codes, None)
+            if self.rule is None:
+                if piece is None:
+                    break
+                return mu_law_decode(piece[0], self.vocoder.Q)
+            drawn = self.codes.drawn
+            if piece is not None:
+                self._drawn[drawn - piece.shape[1]:drawn] = piece[0]
+            if piece is None or self.codes.fired[0]:       # all drawn, or the rule fired in this chunk: up to the end point
+                self._done = True
+                upto = int(self.codes.ends[0])
+            else:
+                window, hop = int(self.rule[0]), int(self.rule[1])
+                upto = safe_prefix(self._drawn[max(0, drawn - (window - hop)):drawn], drawn, self.below, window, hop)
+            if upto > self._out:
+                out = mu_law_decode(self._drawn[self._out:upto], self.vocoder.Q)
+                self._out = upto
+                return out
+        raise StopIteration
+
+
 class Synthesizer(object):
     def __init__(self, hparams, dtype="mixed", device="cuda:0"):
         self.hparams = hparams
@@ -93,19 +133,28 @@ class Synthesizer(object):
         the call returns (waves, ends) - waves a list of B float32 arrays, waves[i] the ends[i] samples in front of
         waveform i's end point, equal to full[i, :audio.find_endpoint(full[i])] of the call without it; only what was
         drawn is copied to the host and decoded."""
-        from .models.wavenet import mu_law_decode, mu_law_encode
+        from .models.wavenet import mu_law_decode
+        v = self.vocoder
+        seed_ids, n, kw = self._wavenet_vocode_args(mels, seed, global_conditions, temperature, endpoint)
+        B = len(seed_ids)
+        ids = v.generate(seed_ids, n, **kw)
+        if not endpoint:
+            return mu_law_decode(ids[:, v.rf:].cpu().numpy(), v.Q)
+        ends = [int(e) for e in v.last_ends.cpu().numpy()]
+        return [mu_law_decode(ids[i, v.rf:v.rf + ends[i]].cpu().numpy(), v.Q) for i in range(B)], ends
+
+    def _wavenet_vocode_args(self, mels, seed, global_conditions, temperature, endpoint):
+        """(seed_ids, n_samples, keywords) of the vocoder's generate / generate_stream for mels float [B, T, num_mels]:
+        _wavenet_vocode_batch's seed silence, uniforms and conditions."""
+        from .models.wavenet import mu_law_encode
         v, hop = self.vocoder, self._vocoder_hop
         mels = np.asarray(mels, np.float32)
         B, n = mels.shape[0], mels.shape[1] * hop
         silence = int(mu_law_encode(np.zeros(1, np.float32), v.Q)[0])
         uniforms = np.stack([np.random.default_rng(seed + i).random(n) for i in range(B)])
-        ids = v.generate(np.full((B, v.rf), silence, np.int32), n, uniforms=uniforms, global_conditions=global_conditions,
-                         local_conditions=mels, hold=hop, t0=-v.rf, temperature=temperature,
-                         endpoint=audio.endpoint_rule() if endpoint else None)
-        if not endpoint:
-            return mu_law_decode(ids[:, v.rf:].cpu().numpy(), v.Q)
-        ends = [int(e) for e in v.last_ends.cpu().numpy()]
-        return [mu_law_decode(ids[i, v.rf:v.rf + ends[i]].cpu().numpy(), v.Q) for i in range(B)], ends
+        return np.full((B, v.rf), silence, np.int32), n, dict(
+            uniforms=uniforms, global_conditions=global_conditions, local_conditions=mels, hold=hop, t0=-v.rf,
+            temperature=temperature, endpoint=audio.endpoint_rule() if endpoint else None)
 
     def _wavenet_vocode(self, mel, seed=0, global_conditions=None, temperature=1.0):
         """mel float [T, num_mels] -> float32 [T * hop]: _wavenet_vocode_batch of the one mel."""
@@ -147,6 +196,33 @@ class Synthesizer(object):
         wav = audio.inv_preemphasis(wav.cpu().numpy())
         wav = wav[:audio.find_endpoint(wav)]
         return wav, mel, lin
+
+    def synthesize_stream(self, text, speaker_id=0, chunk_samples=None, seed=0, temperature=1.0, stop_at_endpoint=True):
+        """synthesize(text, vocoder="wavenet") heard while it is drawn (after load_vocoder; the same refusals).  The
+        Tacotron pass and check_status() run before this returns; the result is an iterable (SynthesisStream) with .mel
+        and .lin set, whose iteration yields float32 pieces of the waveform, one per chunk_samples drawn samples (None:
+        20 hops) - the vocoder's generate_stream, so the generator is never restarted and keeps drawing while a piece
+        is consumed.  seed, temperature: synthesize's.
+        stop_at_endpoint=True: a step hands out only what audio.find_endpoint can no longer cut (safe_prefix of the
+        samples drawn so far - up to window - hop trailing silent samples are held back, and a step with nothing safe
+        yields nothing), the last step hands out the rest up to the end point, and the generator stops drawing there:
+        np.concatenate(list(stream)) is synthesize(text, vocoder="wavenet", same arguments)[0] bit for bit.
+        False: all T * hop samples are yielded as they are drawn, UNCUT - find_endpoint is not applied at all, since
+        what it would cut has been handed out by then."""
+        if self.vocoder is None:
+            raise ValueError("vocoder='wavenet' needs load_vocoder(checkpoint_path, hparams) first")
+        cleaner_names = [x.strip() for x in self.hparams.cleaners.split(",")]
+        seq = text_to_sequence(text, cleaner_names)
+        m = self.model
+        m.initialize(np.asarray([seq], dtype=np.int32), np.asarray([len(seq)], dtype=np.int32),
+                     np.asarray([speaker_id], dtype=np.int32))
+        mel = m.mel_outputs[0].float().cpu().numpy()
+        lin = m.linear_outputs[0].float().cpu().numpy()
+        m.check_status()        # (as in synthesize: invalid outputs are never vocoded)
+        gc = np.asarray([speaker_id]) if self.vocoder.gc else None
+        seed_ids, n, kw = self._wavenet_vocode_args(mel[None], seed, gc, temperature, bool(stop_at_endpoint))
+        chunk = 20 * self._vocoder_hop if chunk_samples is None else int(chunk_samples)
+        return SynthesisStream(self.vocoder, self.vocoder.generate_stream(seed_ids, n, chunk, **kw), mel, lin, kw["endpoint"])
 
     def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True):
         """synthesize for a list of texts: [(wav, mel, lin)] in the order of `texts`, every entry with the shapes and
