@@ -1114,7 +1114,20 @@ int ns_spectrogram(const ns_spectrogram_params* p, ns_stream_t stream);
 
 /* audio.inv_spectrogram_tensorflow (audio.py:51-58,90-123): denormalise -> dB to amplitude ->
  * ^power -> Griffin-Lim with zero initial phase and TF-style (un-centred, un-normalised)
- * STFT / inverse STFT.  spec [N, T, F] normalised, wav [N, (T-1)*hop + win]. */
+ * STFT / inverse STFT.  spec [N, T, F] normalised, wav [N, (T-1)*hop + win].
+ * momentum = a > 0 ("fast Griffin-Lim", Perraudin et al. 2013, in librosa's form; not in the reference): with the
+ *   magnitudes S, b = a / (1 + a) and E_prev = 0 before the first iteration, an iteration is
+ *     E = STFT(y);  A = E - b * E_prev;  E_prev = E;  y = ISTFT(S * A / max(1e-8, |A|)).
+ *   The zero-phase start y0 = ISTFT(S) is unchanged and the first iteration is the plain one (it only stores E), so at
+ *   iters <= 1 the result is that of momentum = 0, bit for bit.  momentum = 0 (a zeroed struct): the reference's
+ *   algorithm, the same launches and the same work area as before the field existed.  NS_ERR_BAD_ARG before any launch
+ *   unless 0 <= momentum < 1 (a NaN is refused).
+ * work, in this order (the caller allocates, contents on entry are never read, nothing is kept between calls):
+ *   the magnitudes [N, T, F] floats, rounded up to an even count; two sets of windowed frames [N, T, win] floats; 256
+ *   spare bytes; with momentum > 0 the history E_prev, fp32, 16 bytes per bin pair (k, n_fft/2 - k), k = 0 .. n_fft/4,
+ *   of every frame, starting at the first 16-byte boundary behind the frames.
+ *   ns_griffin_lim_work_bytes() = 4 * (((N*T*F + 1) & ~1) + 2*N*T*win) + 256
+ *                                 + (momentum > 0 ? 16 * N*T*(n_fft/4 + 1) = 8 * N*T*(n_fft/2 + 2) : 0). */
 typedef struct {
   const float* spec; int N, T;
   int n_fft, hop, win, iters;
@@ -1123,6 +1136,7 @@ typedef struct {
   float* wav;
   float* work;   /* ns_griffin_lim_work_bytes() */
   int raw_magnitude;   /* 1: spec already holds the magnitudes S^power (audio._griffin_lim_tensorflow, audio.py:90-103) */
+  float momentum;      /* 0: off; 0 < momentum < 1: the update above (librosa's default is 0.99) */
 } ns_griffin_lim_params;
 int ns_griffin_lim(const ns_griffin_lim_params* p, ns_stream_t stream);
 size_t ns_griffin_lim_work_bytes(const ns_griffin_lim_params* p);

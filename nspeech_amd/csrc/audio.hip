@@ -154,12 +154,24 @@ extern "C" int ns_spectrogram(const ns_spectrogram_params* p, ns_stream_t s) {
 }
 
 // ------------------------------------------------------------------ Griffin-Lim
+// Momentum ("fast Griffin-Lim", Perraudin et al. 2013, in librosa's form): the phase is taken from A = E - beta E_prev,
+// beta = momentum / (1 + momentum), instead of from E = STFT(y), and E_prev = 0 before the first iteration.  E_prev lives
+// in ONE history buffer that the pair pass updates in place: the thread that normalises the pair (k, M-k) of a frame is
+// the same in every iteration, so it loads its 16 bytes (E_prev[k], E_prev[M-k]), stores (E[k], E[M-k]) in their place
+// and no other thread or kernel reads them (the two kernel forms keep E at different scales there).  MOM is a
+// compile-time variant: 0 = off (the instantiations without momentum are the code they were), GL_MOM_FIRST = the first
+// iteration, which only stores (so nothing ever reads what the caller left in the work area), GL_MOM_NEXT = load,
+// store and subtract.
+typedef float gl_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int GL_MOM_FIRST = 1, GL_MOM_NEXT = 2;
 struct GlArgs {
   ns_griffin_lim_params p;
   float* mag;          // [N,T,F]
   const float* fprev;  // [N,T,win] windowed inverse-FFT frames of the previous iteration
   float* fnext;
   int init;
+  gl_f32x4* hist;      // momentum only: [N,T,n_fft/4+1] the previous iteration's (E[k], E[M-k]), pair k = 0 .. M/2
+  float nbeta;         // -momentum / (1 + momentum)
 };
 
 // overlap-add sum over the (<= win/hop) frames that cover a sample, given the last covering frame f1 and the sample's
@@ -192,6 +204,7 @@ __device__ __forceinline__ float2 gl_unit(float2 e, float m) {      // m * e / m
   const float sc = m / fmaxf(1e-8f, sqrtf(e.x * e.x + e.y * e.y));
   return make_float2(e.x * sc, e.y * sc);
 }
+template <int MOM>
 __global__ __launch_bounds__(FT) void gl_frame_kernel(GlArgs g) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const ns_griffin_lim_params& p = g.p;
@@ -233,9 +246,12 @@ __global__ __launch_bounds__(FT) void gl_frame_kernel(GlArgs g) {
     dst = (Z == bufa) ? bufb : bufa;
   }
   // bins k and M-k together: split -> unit phase x magnitude -> merge, conj(Zt) goes to dst
+  gl_f32x4* hist = MOM ? g.hist + ((long)n * p.T + t) * (M / 2 + 1) : nullptr;
   for (int k = tid; k <= M / 2; k += FT) {
     const int kk = (k == 0) ? 0 : M - k;      // partner bin inside Z (Z[M] = Z[0])
     float2 xa, xb;                            // Xn[k], Xn[M-k]
+    gl_f32x4 h;                               // (E_prev[k], E_prev[M-k]): loaded per pair, in flight across the split
+    if constexpr (MOM == GL_MOM_NEXT) h = hist[k];
     const float2 w = (k == 0) ? make_float2(1.f, 0.f) : tw[k];
     if (g.init) {
       xa = make_float2(mag[k], 0.f);
@@ -245,10 +261,15 @@ __global__ __launch_bounds__(FT) void gl_frame_kernel(GlArgs g) {
       // X[k] = ((A + conj B) - i w (A - conj B)) / 2 ;  X[M-k] = ((B + conj A) + i conj(w) (B - conj A)) / 2
       const float2 s1 = make_float2(A.x + B.x, A.y - B.y), d1 = make_float2(A.x - B.x, A.y + B.y);
       const float2 wd = cmul(w, d1);
-      const float2 ea = make_float2(0.5f * (s1.x + wd.y), 0.5f * (s1.y - wd.x));
+      float2 ea = make_float2(0.5f * (s1.x + wd.y), 0.5f * (s1.y - wd.x));
       const float2 s2 = make_float2(s1.x, -s1.y), d2 = make_float2(-d1.x, d1.y);
       const float2 wc = cmul(make_float2(w.x, -w.y), d2);
-      const float2 eb = make_float2(0.5f * (s2.x - wc.y), 0.5f * (s2.y + wc.x));
+      float2 eb = make_float2(0.5f * (s2.x - wc.y), 0.5f * (s2.y + wc.x));
+      if constexpr (MOM != 0) hist[k] = (gl_f32x4){ea.x, ea.y, eb.x, eb.y};
+      if constexpr (MOM == GL_MOM_NEXT) {     // A = E - beta E_prev
+        ea = make_float2(fmaf(g.nbeta, h.x, ea.x), fmaf(g.nbeta, h.y, ea.y));
+        eb = make_float2(fmaf(g.nbeta, h.z, eb.x), fmaf(g.nbeta, h.w, eb.y));
+      }
       xa = gl_unit(ea, mag[k]);
       xb = gl_unit(eb, mag[M - k]);
     }
@@ -431,8 +452,11 @@ constexpr int GL_NP = 9;                    // pairs (k, M - k) per lane: k = 64
 // The pairs (k, M - k), k = 64 n1 + lane: split -> unit phase x magnitude -> merge, ONCE per pair for both bins; the two
 // results replace Z[k] and Z[M - k] in the wave's natural-order image (no other lane touches those two cells).
 // With t1 = Xn[k] + conj Xn[M-k], c1 = conj(w) (Xn[k] - conj Xn[M-k]):  conj Zt[k] = conj(t1 + i c1), conj Zt[M-k] = t1 - i c1.
-template <bool INIT>
-__device__ __forceinline__ void gl_pairs(v2f* buf, int lane, const float (&mkv)[GL_NP], const float (&mpv)[GL_NP], const v2f (&wv)[GL_NP]) {
+// Momentum: histl = this frame's history + lane, pair k at histl[64 n1]; hv = what the caller loaded from there
+// (GL_MOM_NEXT only); the history holds 2 E, the scale the split leaves, and nb2 = (-beta, -beta).
+template <bool INIT, int MOM>
+__device__ __forceinline__ void gl_pairs(v2f* buf, int lane, const float (&mkv)[GL_NP], const float (&mpv)[GL_NP], const v2f (&wv)[GL_NP],
+                                         gl_f32x4* histl, const gl_f32x4 (&hv)[GL_NP], v2f nb2) {
 #pragma unroll
   for (int n1 = 0; n1 < GL_NP; ++n1) {
     const float mk = mkv[n1], mp = mpv[n1];
@@ -450,8 +474,15 @@ __device__ __forceinline__ void gl_pairs(v2f* buf, int lane, const float (&mkv)[
       //   2 X[k] = s1 - i wd = (s1.x + wd.y, s1.y - wd.x);   2 X[M-k] = (s1.x - wd.y, -s1.y - wd.x)
       const v2f s1 = add_conj(A, B), d1 = sub_conj(A, B);
       const v2f wd = cmulw(d1, w);
-      const v2f ea = add_mi(s1, wd);
-      const v2f eb = add_pi_conj(s1, wd);
+      v2f ea = add_mi(s1, wd);
+      v2f eb = add_pi_conj(s1, wd);
+      if constexpr (MOM != 0) {
+        if (n1 < 8 || lane == 0) histl[64 * n1] = (gl_f32x4){ea.x, ea.y, eb.x, eb.y};
+      }
+      if constexpr (MOM == GL_MOM_NEXT) {                         // A = E - beta E_prev
+        ea = (v2f){hv[n1].x, hv[n1].y} * nb2 + ea;
+        eb = (v2f){hv[n1].z, hv[n1].w} * nb2 + eb;
+      }
       // m e / max(1e-8, |e|) with e = ea / 2
       const v2f na = ea * ea, nb = eb * eb;
       const float sa = mk * __builtin_amdgcn_rsqf(fmaxf(4e-16f, na.x + na.y));
@@ -507,8 +538,12 @@ __device__ __forceinline__ void gl_window_gathered(const gl_u32x2 (&xs)[8][4], c
   }
 }
 
-template <bool INIT>
+// (the nine pairs of history in flight take the variant that loads them from 127 to 187 registers: two workgroups per
+// CU where the LDS admits three.  Held to three waves per SIMD by launch bounds it spills to scratch, so it is not: a
+// launch of 32 clips is bound by its traffic, which the history doubles - profiles/griffin_lim_momentum.txt)
+template <bool INIT, int MOM = 0>
 __global__ __launch_bounds__(GL_WPW * 64) void gl_wave_kernel(GlArgs g) {
+  static_assert(!(INIT && MOM), "the zero-phase pass has no E: momentum starts with the first iteration");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const ns_griffin_lim_params& p = g.p;
   constexpr int M = 1024, N = 2048, F = M + 1;
@@ -536,6 +571,8 @@ __global__ __launch_bounds__(GL_WPW * 64) void gl_wave_kernel(GlArgs g) {
   const float* magk = mag + lane;                              // mag[64 n1 + lane]
   const float* magp = mag + (M - lane);                        // mag[M - k] = magp[-64 n1]
   const v2f* winl = (const v2f*)p.window + lane;               // window[2 (64 n1 + lane)], [.. + 1]
+  gl_f32x4* histl = MOM ? g.hist + ((long)n * p.T + t) * (M / 2 + 1) + lane : nullptr;   // pair k = 64 n1 + lane
+  gl_f32x4 hv[NP];
 #pragma unroll
   for (int n1 = 0; n1 < NP; ++n1) wv[n1] = tw2l[64 * n1];
   if constexpr (!INIT) {
@@ -548,6 +585,14 @@ __global__ __launch_bounds__(GL_WPW * 64) void gl_wave_kernel(GlArgs g) {
     gl_issue_gather<0>(g.fprev + (long)n * p.T * win, p.T, t, p.hop, win, lane, xs);
 #pragma unroll
     for (int n1 = 0; n1 < NP; ++n1) { mkv[n1] = magk[64 * n1]; mpv[n1] = magp[-64 * n1]; }
+    if constexpr (MOM == GL_MOM_NEXT) {
+      // the pairs' history, 16 bytes per lane and 1 KB per instruction, in flight with the loads above
+#pragma unroll
+      for (int n1 = 0; n1 < NP; ++n1) {
+        hv[n1] = (gl_f32x4){0.f, 0.f, 0.f, 0.f};
+        if (n1 < 8 || lane == 0) hv[n1] = histl[64 * n1];
+      }
+    }
     build_table();
     if (traw >= p.T) return;
     gl_window_gathered(xs, winl, win, lane, z);
@@ -572,7 +617,7 @@ __global__ __launch_bounds__(GL_WPW * 64) void gl_wave_kernel(GlArgs g) {
   }
   // ---- the pairs (k, M - k): split -> unit phase x magnitude -> merge; then every lane reads its pass-1 inputs
   //      conj(Zt[64 n1 + lane])
-  gl_pairs<INIT>(buf, lane, mkv, mpv, wv);
+  gl_pairs<INIT, MOM>(buf, lane, mkv, mpv, wv, histl, hv, (v2f){g.nbeta, g.nbeta});
   wave_lds_fence();
 #pragma unroll
   for (int n1 = 0; n1 < 16; ++n1) z[n1] = buf[80 * n1 + lane];
@@ -618,10 +663,15 @@ static bool gl_wave_ok(const ns_griffin_lim_params* p) {
   return p->n_fft == 2048 && (p->hop & 1) == 0 && (p->win & 1) == 0 && p->win <= 4 * p->hop && p->win <= 1024 &&
          (((uintptr_t)p->window) & 7) == 0;
 }
+// the history of the momentum update: 16 bytes (E[k], E[M-k]) per pair k = 0 .. n_fft/4 of every frame
+static size_t gl_hist_bytes(const ns_griffin_lim_params* p) {
+  return p->momentum > 0.f ? sizeof(gl_f32x4) * (size_t)p->N * p->T * (p->n_fft / 4 + 1) : 0;
+}
 extern "C" size_t ns_griffin_lim_work_bytes(const ns_griffin_lim_params* p) {
   if (!p) return 0;
   const size_t F = p->n_fft / 2 + 1;
-  return sizeof(float) * ((((size_t)p->N * p->T * F + 1) & ~(size_t)1) + 2 * (size_t)p->N * p->T * p->win) + 256;
+  return sizeof(float) * ((((size_t)p->N * p->T * F + 1) & ~(size_t)1) + 2 * (size_t)p->N * p->T * p->win) + 256 +
+         gl_hist_bytes(p);
 }
 
 extern "C" int ns_griffin_lim(const ns_griffin_lim_params* p, ns_stream_t s_) {
@@ -630,6 +680,7 @@ extern "C" int ns_griffin_lim(const ns_griffin_lim_params* p, ns_stream_t s_) {
   NS_CHECK_ARG(p->n_fft >= 64 && (p->n_fft & (p->n_fft - 1)) == 0 && p->n_fft <= 4096,
                "ns_griffin_lim: n_fft must be a power of two in [64, 4096]");
   NS_CHECK_ARG(p->win <= p->n_fft && p->hop > 0 && p->hop <= p->win, "ns_griffin_lim: bad window / hop");
+  NS_CHECK_ARG(p->momentum >= 0.f && p->momentum < 1.f, "ns_griffin_lim: momentum must be in [0, 1)");    // (refuses NaN)
   if (p->N <= 0 || p->T <= 0) return NS_OK;
   const size_t F = p->n_fft / 2 + 1;
   GlArgs g;
@@ -637,12 +688,17 @@ extern "C" int ns_griffin_lim(const ns_griffin_lim_params* p, ns_stream_t s_) {
   g.mag = p->work;
   float* fa = p->work + (((size_t)p->N * p->T * F + 1) & ~(size_t)1);     // 8-byte aligned frames (float2 accesses)
   float* fb = fa + (size_t)p->N * p->T * p->win;
+  // the history starts at the first 16-byte boundary behind the frames (inside the 256 spare bytes)
+  const bool mom = p->momentum > 0.f;
+  g.hist = mom ? (gl_f32x4*)(((uintptr_t)(fb + (size_t)p->N * p->T * p->win) + 15) & ~(uintptr_t)15) : nullptr;
+  g.nbeta = -p->momentum / (1.f + p->momentum);
   const size_t lds = sizeof(float2) * (p->n_fft + p->n_fft / 2);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gl_frame_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)gl_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)gl_wave_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void* ks[] = {(const void*)gl_frame_kernel<0>, (const void*)gl_frame_kernel<GL_MOM_FIRST>, (const void*)gl_frame_kernel<GL_MOM_NEXT>,
+                        (const void*)gl_wave_kernel<true>, (const void*)gl_wave_kernel<false>,
+                        (const void*)gl_wave_kernel<false, GL_MOM_FIRST>, (const void*)gl_wave_kernel<false, GL_MOM_NEXT>};
+    for (const void* k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   // n_fft 2048 with even hop / window (the shipped hparams): the wave-per-frame kernel; anything else: one workgroup
@@ -651,17 +707,22 @@ extern "C" int ns_griffin_lim(const ns_griffin_lim_params* p, ns_stream_t s_) {
   const size_t lds_w = sizeof(float2) * (1024 + GL_WPW * GW_PAD);
   dim3 grid(p->T, p->N), grid_w(ceil_div(p->T, GL_WPW), p->N);
   const int Lout = (p->T - 1) * p->hop + p->win;
-  auto launch = [&]() {
+  // v: 0, or which momentum iteration this is (GL_MOM_FIRST stores the history, GL_MOM_NEXT reads it as well)
+  auto launch = [&](int v) {
     if (wavek && g.init) hipLaunchKernelGGL(gl_wave_kernel<true>, grid_w, dim3(GL_WPW * 64), lds_w, s, g);
+    else if (wavek && v == GL_MOM_FIRST) hipLaunchKernelGGL((gl_wave_kernel<false, GL_MOM_FIRST>), grid_w, dim3(GL_WPW * 64), lds_w, s, g);
+    else if (wavek && v == GL_MOM_NEXT) hipLaunchKernelGGL((gl_wave_kernel<false, GL_MOM_NEXT>), grid_w, dim3(GL_WPW * 64), lds_w, s, g);
     else if (wavek) hipLaunchKernelGGL(gl_wave_kernel<false>, grid_w, dim3(GL_WPW * 64), lds_w, s, g);
-    else hipLaunchKernelGGL(gl_frame_kernel, grid, dim3(FT), lds, s, g);
+    else if (v == GL_MOM_FIRST) hipLaunchKernelGGL(gl_frame_kernel<GL_MOM_FIRST>, grid, dim3(FT), lds, s, g);
+    else if (v == GL_MOM_NEXT) hipLaunchKernelGGL(gl_frame_kernel<GL_MOM_NEXT>, grid, dim3(FT), lds, s, g);
+    else hipLaunchKernelGGL(gl_frame_kernel<0>, grid, dim3(FT), lds, s, g);
   };
   g.init = 1; g.fprev = nullptr; g.fnext = fa;
-  launch();
+  launch(0);
   float* cur = fa; float* nxt = fb;
   for (int it = 0; it < p->iters; ++it) {
     g.init = 0; g.fprev = cur; g.fnext = nxt;
-    launch();
+    launch(!mom ? 0 : it == 0 ? GL_MOM_FIRST : GL_MOM_NEXT);
     float* tmp = cur; cur = nxt; nxt = tmp;
   }
   g.fprev = cur;

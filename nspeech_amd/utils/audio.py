@@ -398,9 +398,11 @@ def spectrogram_and_mel_device(y):
     return lin.view(-1, hp.num_freq), mel.view(-1, hp.num_mels)
 
 
-def griffin_lim_gpu(spec, iters=None, raw_magnitude=False):
+def griffin_lim_gpu(spec, iters=None, raw_magnitude=False, momentum=None):
     """spec: torch CUDA tensor or array [T, F] / [N, T, F] (normalised; with raw_magnitude the magnitudes S^power
-    themselves).  Returns a CUDA tensor [L] / [N, L], L = (T-1)*hop + win, before inv_preemphasis (audio.py:51-58)."""
+    themselves).  Returns a CUDA tensor [L] / [N, L], L = (T-1)*hop + win, before inv_preemphasis (audio.py:51-58).
+    iters, momentum: None reads griffin_lim_iters / griffin_lim_momentum of the current hparams.  momentum 0 is the
+    reference's algorithm; 0 < momentum < 1 is the fast Griffin-Lim update (ns_griffin_lim in include/nspeech_hip.h)."""
     hp = get_hparams()
     n_fft, hop, win = _stft_parameters()
     tb = _get_tables()
@@ -421,6 +423,7 @@ def griffin_lim_gpu(spec, iters=None, raw_magnitude=False):
     p.power, p.ref_level_db, p.min_level_db = float(hp.power), float(hp.ref_level_db), float(hp.min_level_db)
     p.window, p.twiddle, p.wav = ops.ptr(tb["window"]), ops.ptr(tb["twiddle"]), ops.ptr(wav)
     p.raw_magnitude = int(bool(raw_magnitude))
+    p.momentum = float(hp.get("griffin_lim_momentum", 0.0) if momentum is None else momentum)
     nbytes = L.lib().ns_griffin_lim_work_bytes
     nbytes.restype = __import__("ctypes").c_size_t
     work = torch.empty((nbytes(__import__("ctypes").byref(p)) + 3) // 4, dtype=torch.float32, device=dev)
