@@ -664,12 +664,16 @@ int ns_gru_pointwise(const ns_gru_pointwise_params* p, ns_stream_t stream);
  * A chain = (direction, 16 batch rows).  H = 128: one workgroup per chain, nothing leaves the CU - the recurrent
  * matrices (128 x 384) live in registers as MFMA fragments (hi and lo planes for three passes), the state in LDS.
  * H = 256: a chain is a cluster of 4 workgroups with 64 units each that exchange r * h and h through `work` as
- * {step tag, fp32} granules (two hops per step).  dtype NS_BF16: single-pass bf16 products; NS_F32: f32_passes 1
- * (operands rounded to bf16 when loaded) or 3 (split-bf16, ~fp32).  Rows with t >= lengths[n] output zeros and carry
- * the state unchanged; h_init (optional) is the initial state (modules.py:165-181).
+ * {step tag, bf16 hi | lo} granules (two hops per step).  dtype NS_BF16: single-pass bf16 products; NS_F32: f32_passes 1
+ * (operands rounded to bf16 when loaded) or 3 (split-bf16, ~fp32).  Rows with t >= lengths[n] (a length may be 0) output
+ * h = 0 exactly and carry the state unchanged: the reverse direction meets the initial state at t = lengths[n] - 1, a
+ * length of 0 gives a row of zeros; h_init (optional) is the initial state (modules.py:165-181).
  * Forward writes the history h (dtype), ru = [r | u] and c (fp32) and rh = r * h_prev (dtype) for the backward pass and
- * the hoisted weight gradients.  Backward reads them plus dh (gradient wrt the outputs) and writes the gate gradients
- * dzg = [dzr | dzu], dzc (dtype) and, optionally, the gradient wrt the initial state.
+ * the hoisted weight gradients.  Backward reads them plus dh (gradient wrt the outputs, ignored where t >= lengths[n])
+ * and writes the gate gradients dzg = [dzr | dzu], dzc (dtype) - exactly 0 where t >= lengths[n], the gradient being
+ * carried unchanged through such steps: the hoisted weight-gradient products run over every row - and, optionally, the
+ * gradient wrt the initial state.  ru, c and rh of steps with t >= lengths[n] hold finite values that mean nothing.
+ * Only the rows n < N and the steps' rows are written (ru and c: whole 16-row groups); no input is changed.
  * fw / bw: one or two directions with equal N, T, H, P, dtype (bw may be NULL).  work: ns_gru_seq_work_bytes();
  * work[0] (int) is a status word, non-zero after the call completes = an exchange timed out, outputs invalid. */
 typedef struct {

@@ -711,11 +711,12 @@ def taco1_attn_cluster(direction, work, **kw):
 
 
 def gru_seq_params(like, N, T, H, P, padl, reverse, lengths, xg, xc, wgT, wcT, wg, ld_wg, wc, ld_wc, h, ld_h, ru, c, rh,
-                   h_init=None, ld_hi=0, dh=None, ld_dh=0, dzg=None, dzc=None, dh_init=None, ld_dhi=0):
-    """One direction of ns_gru_seq_*; pointer arguments are tensors, (tensor, element offset) pairs or None."""
+                   h_init=None, ld_hi=0, dh=None, ld_dh=0, dzg=None, dzc=None, dh_init=None, ld_dhi=0, ld_xg=0, ld_xc=0):
+    """One direction of ns_gru_seq_*; pointer arguments are tensors, (tensor, element offset) pairs or None.  ld_xg / ld_xc
+    default to dense rows (2H / H)."""
     p = L.struct("ns_gru_seq_params")
     _fill(p, dtype=dt(like), N=N, T=T, H=H, P=P, padl=padl, reverse=int(bool(reverse)), f32_passes=F32_PASSES or 0,
-          lengths=ptr(lengths), xg=_pp(xg), ld_xg=2 * H, xc=_pp(xc), ld_xc=H, wgT=_pp(wgT), wcT=_pp(wcT), wg=_pp(wg),
+          lengths=ptr(lengths), xg=_pp(xg), ld_xg=ld_xg or 2 * H, xc=_pp(xc), ld_xc=ld_xc or H, wgT=_pp(wgT), wcT=_pp(wcT), wg=_pp(wg),
           ld_wg=ld_wg, wc=_pp(wc), ld_wc=ld_wc, h=_pp(h), ld_h=ld_h, ru=_pp(ru), c=_pp(c), rh=_pp(rh), h_init=_pp(h_init),
           ld_hi=ld_hi, dh=_pp(dh), ld_dh=ld_dh, dzg=_pp(dzg), dzc=_pp(dzc), dh_init=_pp(dh_init), ld_dhi=ld_dhi)
     return p
