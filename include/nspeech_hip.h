@@ -326,6 +326,31 @@ typedef struct {
 } ns_l1_loss_params;
 int ns_l1_loss(const ns_l1_loss_params* p, ns_stream_t stream);
 
+/* Guided attention loss (Tachibana et al. 2017) and the alignment scores of a batch, with the loss' gradient with
+ * respect to the alignments in the same pass.  Not in the reference: hparam guided_attention_weight, 0 = off.
+ * align fp32 [N, S+1, Tia], step s in slot s+1 (the layout every attention kernel writes).  For row n, with
+ * T_n = in_lengths[n] and S_n = out_steps[n] (NULL: S), each clamped into [1, Tia] / [1, S]:
+ *   W_n[s,t]  = 1 - exp(-(t/T_n - s/S_n)^2 / (2 sigma^2))                    0 <= s < S_n, 0 <= t < T_n
+ *   row_out[2n]   = G_n = 1/(S_n T_n) sum_{s,t} align[n,s+1,t] W_n[s,t]      guided loss of the row, in [0, 1)
+ *   row_out[2n+1] = F_n = 1/S_n sum_s max_{t<T_n} align[n,s+1,t]             focus: 1 = one-hot alignments
+ *   acc[0] = 1/N sum_n G_n, acc[1] = 1/N sum_n F_n                           (nullable; written, not accumulated)
+ *   da0[n,s+1,t] += grad_scale W_n[s,t] / (N S_n T_n)                        (nullable; the valid region only)
+ * Slot 0, the steps s >= S_n and the columns t >= T_n of da0 keep their bits.  Every sum has a fixed order (one
+ * workgroup per row, its lanes and waves in a fixed tree; the batch means add the rows in index order): two calls on the
+ * same inputs give the same bits, and there is no float atomic. */
+typedef struct {
+  int N, S, Tia;
+  const int* in_lengths;
+  const int* out_steps;
+  float sigma;
+  const float* align;
+  float* da0;
+  float grad_scale;
+  float* row_out;
+  float* acc;
+} ns_guided_attention_params;
+int ns_guided_attention(const ns_guided_attention_params* p, ns_stream_t stream);
+
 /* ------------------------------------------------------------------ optimizer
  * tf.clip_by_global_norm + tf.train.AdamOptimizer (tacotron2.py:150-161).
  * ns_sumsq: out[0] += sum g^2.   ns_adam: scale = clip / max(sqrt(gnorm_sq[0]), clip);

@@ -13,7 +13,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-unused
 # every multiply and add rounds on its own (a v_fma_f64 there changes the last bit of some samples)
 extra_flags() {
   case "$1" in
-    audio.hip|attn_cluster.hip|attn_gru.hip) echo "-fno-slp-vectorize" ;;
+    audio.hip|attn_cluster.hip|attn_gru.hip|guided_attn.hip) echo "-fno-slp-vectorize" ;;
     frontend.hip) echo "-fno-slp-vectorize -ffp-contract=off" ;;
     *) echo "" ;;
   esac

@@ -83,12 +83,16 @@ def _pinned_zeros(shape):
     return torch.zeros(shape, dtype=torch.float32, pin_memory=True).numpy()
 
 
-def prepare_batch(batch, outputs_per_step, rng, longest=0, alloc=None):
+def prepare_batch(batch, outputs_per_step, rng, longest=0, alloc=None, target_lengths=None):
     """datafeeder.py:189-220.  batch: list of (ids, speaker_id, mel [T,M], linear [T,F]).
     `longest`: data-parallel runs pass the longest target of the GLOBAL batch (all ranks), so that every rank pads to
-    the same T_out and the mean of the ranks' unmasked mean losses is the global mean."""
+    the same T_out and the mean of the ranks' unmasked mean losses is the global mean.
+    `target_lengths`: a list that receives the frame count of every row, in the order of the returned arrays (the
+    reference never masks the padding, so its batch carries none; the guided attention loss needs them)."""
     batch = list(batch)
     rng.shuffle(batch)
+    if target_lengths is not None:
+        target_lengths.extend(int(e[3].shape[0]) for e in batch)
     Ti = max(len(e[0]) for e in batch)
     To = _round_up(max(max(e[3].shape[0] for e in batch), longest) + 1, outputs_per_step)
     N = len(batch)
@@ -109,14 +113,16 @@ def prepare_batch(batch, outputs_per_step, rng, longest=0, alloc=None):
     return inputs, lengths, speakers, mel, lin
 
 
-def prepare_batch_device(batch, outputs_per_step, rng, longest, device, stream):
+def prepare_batch_device(batch, outputs_per_step, rng, longest, device, stream, target_lengths=None):
     """prepare_batch for examples whose features are CUDA tensors (the HBM-resident cache): the padded target arrays are
     assembled ON the device - a zero fill and one device-to-device copy per utterance, issued on the feeder's own
     stream - so a training batch never crosses PCIe.  Returns the batch with device targets and the event that marks
-    them complete."""
+    them complete.  `target_lengths`: as in prepare_batch."""
     import torch
     batch = list(batch)
     rng.shuffle(batch)
+    if target_lengths is not None:
+        target_lengths.extend(int(e[3].shape[0]) for e in batch)
     Ti = max(len(e[0]) for e in batch)
     To = _round_up(max(max(int(e[3].shape[0]) for e in batch), longest) + 1, outputs_per_step)
     N = len(batch)
@@ -139,7 +145,8 @@ def prepare_batch_device(batch, outputs_per_step, rng, longest, device, stream):
 
 class DataFeeder(object):
     """next_batch() -> (inputs [N,T_in] int32, input_lengths [N], mel [N,T_out,M], linear [N,T_out,F]);
-    `speaker_ids` of the last batch are kept in .speaker_ids (single-speaker corpora: zeros)."""
+    `speaker_ids` of the last batch are kept in .speaker_ids (single-speaker corpora: zeros), the frame count of every
+    row before padding in .target_lengths (int32 [N], in the batch's row order)."""
 
     def __init__(self, hparams, ljspeech=None, seed=0, rank=0, world=1, cmudict=None, prefetch=True, features=None,
                  loader=None, vctk=None, librispeech=None, device=None, pinned=False, device_cache=False, trim=True):
@@ -187,6 +194,7 @@ class DataFeeder(object):
         self._loader = loader or audio.load_wav
         self._trim = trim         # False: the corpus is already trimmed (the reference always trims, process.py:27)
         self.speaker_ids = None
+        self.target_lengths = None
         self._queue = queue.Queue(maxsize=8) if prefetch else None
         self._stop = False
         self._thread = None
@@ -240,10 +248,15 @@ class DataFeeder(object):
         return self._stream
 
     def _prepare(self, batch, r, longest=0):
+        """(the prepared batch, its rows' frame counts): the pair travels through the queue together."""
+        frames = []
         if self._device_cache:
             import torch
-            return prepare_batch_device(batch, r, self._rng, longest, torch.device("cuda", self.device), self._feeder_stream())
-        return prepare_batch(batch, r, self._rng, longest, alloc=self._alloc)
+            b = prepare_batch_device(batch, r, self._rng, longest, torch.device("cuda", self.device), self._feeder_stream(),
+                                     target_lengths=frames)
+        else:
+            b = prepare_batch(batch, r, self._rng, longest, alloc=self._alloc, target_lengths=frames)
+        return b, np.asarray(frames, np.int32)
 
     def _next_group(self):
         n, r = self.hp.batch_size, self.hp.outputs_per_step
@@ -327,6 +340,7 @@ class DataFeeder(object):
             if not self._pending:
                 self._pending = self._next_group()
             b = self._pending.pop(0)
+        b, frames = b
         if len(b) == 6:           # assembled on the device: the caller's stream waits for the feeder's copies
             import torch
             inputs, lengths, speakers, mel, lin, ev = b
@@ -337,6 +351,7 @@ class DataFeeder(object):
         else:
             inputs, lengths, speakers, mel, lin = b
         self.speaker_ids = speakers
+        self.target_lengths = frames
         return inputs, lengths, mel, lin
 
 
@@ -346,7 +361,7 @@ class DeviceStager(object):
     arrays directly) and uploaded with asynchronous copies on a COPY stream of its own; next_batch() makes the compute
     stream wait for that copy's event and returns device tensors for the two big arrays (mel + linear targets, 136 MB
     per step at the LJSpeech batch shape - 2.2 ms of PCIe time that would otherwise sit in front of every step) and the
-    small ones (ids, lengths, speakers) as they came.  The reference's counterpart is the FIFOQueue + feed_dict of
+    small ones (ids, lengths, speakers, frame counts) as they came.  The reference's counterpart is the FIFOQueue + feed_dict of
     datafeeder.py:72-88, which TensorFlow drains into device memory on its own threads."""
 
     def __init__(self, feeder, device):
@@ -356,16 +371,17 @@ class DeviceStager(object):
         from .. import ops
         self.copy_stream = ops.concurrent_stream(self.device)      # one that really runs beside the compute stream
         self.speaker_ids = None
+        self.target_lengths = None
         self._next = None
 
     def _stage(self):
         torch = self.torch
         inputs, lengths, mel, lin = self.feeder.next_batch()
-        speakers = self.feeder.speaker_ids
+        side = (self.feeder.speaker_ids, getattr(self.feeder, "target_lengths", None))     # what travels beside the batch
         if torch.is_tensor(mel):        # HBM-resident feature cache: the batch was assembled on the device
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
-            return inputs, lengths, speakers, mel, lin, ev, None
+            return inputs, lengths, side, mel, lin, ev, None
         pm, pl = torch.from_numpy(mel), torch.from_numpy(lin)
         if not pm.is_pinned():          # a feeder built without pinned=True: one staging copy here, in the caller's thread
             pm, pl = pm.pin_memory(), pl.pin_memory()
@@ -374,17 +390,18 @@ class DeviceStager(object):
             dl = pl.to(self.device, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
-        return inputs, lengths, speakers, dm, dl, ev, (pm, pl)
+        return inputs, lengths, side, dm, dl, ev, (pm, pl)
 
     def next_batch(self):
-        """(inputs, lengths, mel [device], linear [device]); .speaker_ids as DataFeeder.  Stages the batch after it."""
+        """(inputs, lengths, mel [device], linear [device]); .speaker_ids and .target_lengths as DataFeeder.  Stages the
+        batch after it."""
         torch = self.torch
         cur = self._next or self._stage()
-        inputs, lengths, speakers, dm, dl, ev, _pinned = cur
+        inputs, lengths, side, dm, dl, ev, _pinned = cur
         main = torch.cuda.current_stream(self.device)
         main.wait_event(ev)
         dm.record_stream(main)          # allocated on the copy stream, consumed on the compute stream
         dl.record_stream(main)
-        self.speaker_ids = speakers
+        self.speaker_ids, self.target_lengths = side
         self._next = self._stage()
         return inputs, lengths, dm, dl

@@ -640,9 +640,11 @@ class Tacotron(Tacotron2):
                                                     dtable_off=self._o("speaker/speaker_embed")))
         return e
 
-    def initialize(self, text_inputs, input_lengths, speaker_ids=None, mel_targets=None, linear_targets=None):
+    def initialize(self, text_inputs, input_lengths, speaker_ids=None, mel_targets=None, linear_targets=None,
+                   target_lengths=None):
         if linear_targets is not None:
-            return Tacotron2.initialize(self, text_inputs, input_lengths, speaker_ids, mel_targets, linear_targets)
+            return Tacotron2.initialize(self, text_inputs, input_lengths, speaker_ids, mel_targets, linear_targets,
+                                        target_lengths)
         self._set_inputs(text_inputs, input_lengths, speaker_ids)
         self.is_training = False
         self.mel_targets = self.linear_targets = None
@@ -995,9 +997,17 @@ class Tacotron(Tacotron2):
         return self
 
     # ------------------------------------------------------------------ loss + backward
+    def _guided_path(self):
+        """Only the persistent attention backward takes da0; which path a batch takes is known once its forward pass ran."""
+        known = getattr(self, "_state", None) is not None
+        return (not known or self._attn_args is not None,
+                "the launch-per-step attention path of Tacotron-1 (taken by every width but the shipped one, and by "
+                "shapes the persistent kernel refuses) has no da0 term to carry the loss' gradient")
+
     def backward(self):
         hp = self._hparams
         T_ = self.T
+        self._check_guided(*self._guided_path())
         ops.DETERMINISTIC_SPLITK = self.deterministic
         d, st = self.dims, self._state
         N, Ti, To, S, Pi, Po, Fp = d["N"], d["Ti"], d["To"], d["S"], d["Pi"], d["Po"], d["Fp"]
@@ -1083,6 +1093,8 @@ class Tacotron(Tacotron2):
                 ops.copy3d(dhc, src, 1, rows, E, (0, HC), (0, E), src_off=A)
             ops.gemm(src, enc.buf, da0, S1, Ti, E, lda, E, Tia, b_mode=0, a_off=a0, b_off=self.padl * E, batch=N,
                      batch_strides=(S1 * lda, Pi * E, S1 * Tia))
+            if self.guided_weight > 0.0:        # + weight * d(L_att)/d(align), a constant; L_att and the focus into scal[4:6]
+                self._guided_attention(da0, self.scal, 4)
             args = dict(self._attn_args)
             args.update(dhc=dhc, da0=da0, df1=df1, dp2=dp2, dzg=dzg, dzc=dzc, dq=dq, de=de)
             cw = buf("attn_cluster_work_b", ops.taco1_attn_cluster_work_floats(**args), torch.float32)

@@ -104,7 +104,8 @@ class Tacotron2(object):
         need_shadow = torch.bfloat16 in (self.T, self.Tx)
         self.flat_s = torch.zeros(n, dtype=torch.bfloat16, device=dev) if need_shadow else self.flat_p
         self.flat_stats = torch.zeros(self.stat_layout.size, dtype=torch.float32, device=dev)
-        self.scal = torch.zeros(16, dtype=torch.float32, device=dev)  # [0:2] mel, [2:4] lin loss, [8] gnorm^2
+        # [0:2] mel, [2:4] lin loss, [4] guided attention loss, [5] attention focus, [8] gnorm^2, [9] step skipped
+        self.scal = torch.zeros(16, dtype=torch.float32, device=dev)
         self.global_step = 0
         self.world_size = world_size
         self.gradient_clip = 1.0
@@ -134,6 +135,15 @@ class Tacotron2(object):
         self.cell_clip = float(getattr(hparams, "lstm_cell_clip", 0.0) or 0.0)
         if self.cell_clip > 0.0 and self.zoneout_rate > 0.0:
             raise ValueError("lstm_cell_clip together with zoneout_rate is not supported (the zoneout backward pass recomputes the unclipped cell state)")
+        # Guided attention loss (hparams guided_attention_weight / guided_attention_sigma; not in the reference, so the
+        # shipped weight is 0 and the step is the reference's, launch for launch).  Its gradient wrt the alignments does not
+        # depend on them: ns_guided_attention adds it to da0, the term of d(align) that backward() forms in front of the
+        # attention recurrence, and leaves L_att and the focus score in scal[4:6].
+        self.guided_weight = float(getattr(hparams, "guided_attention_weight", 0.0) or 0.0)
+        self.guided_sigma = float(getattr(hparams, "guided_attention_sigma", 0.4))
+        if self.guided_weight < 0.0 or not self.guided_sigma > 0.0:
+            raise ValueError("guided_attention_weight must be >= 0 and guided_attention_sigma > 0 (got %g, %g)"
+                             % (self.guided_weight, self.guided_sigma))
         self.zoneout_base_seed = (int(seed) * 2654435761 + 97) & 0xFFFFFFFF
         self._status_words = {}
         self._bwd_sums = {}       # conv tag -> (sum dy, sum dy*xhat) left by the product that formed that layer's dy
@@ -150,6 +160,9 @@ class Tacotron2(object):
         self.inputs = self.input_lengths = self.mel_targets = self.linear_targets = None
         self.mel_outputs = self.linear_outputs = self.alignments = self.audio = None
         self.loss = self.mel_loss = self.linear_loss = self.learning_rate = None
+        self.attention_loss = self.attention_focus = None    # L_att and the focus score of the last step (or summary)
+        self.target_lengths = None      # frames per utterance before padding (None: every row spans all S steps)
+        self._out_steps = None
         self.gradients = self.flat_g
         self.optimize = None
         self.stats = None
@@ -540,9 +553,46 @@ class Tacotron2(object):
                 raise ValueError("speaker_ids must hold one id in [0, %d) per utterance" % self.n_speakers)
             self.speaker_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
 
-    def initialize(self, text_inputs, input_lengths, speaker_ids=None, mel_targets=None, linear_targets=None):
+    def _set_target_lengths(self, target_lengths):
+        """Frames per utterance before padding (the feeder's .target_lengths), kept on the host: the guided attention loss
+        turns them into decoder steps when it runs.  None: every row spans all S steps (synthetic batches)."""
+        self._out_steps = None
+        if target_lengths is not None:
+            tl = target_lengths.cpu().numpy() if torch.is_tensor(target_lengths) else np.asarray(target_lengths)
+            target_lengths = tl.reshape(-1).astype(np.int64)
+            if target_lengths.shape[0] != self.inputs.shape[0]:
+                raise ValueError("target_lengths must hold one frame count per utterance")
+        self.target_lengths = target_lengths
+
+    def _guided_steps(self):
+        """S_n = min(S, max(1, ceil(target_lengths[n] / outputs_per_step))) as a device int32 [N], or None (S_n = S)."""
+        if self.target_lengths is None:
+            return None
+        if self._out_steps is None:
+            r = self._hparams.outputs_per_step
+            steps = np.clip(-(-self.target_lengths // r), 1, self.dims["S"]).astype(np.int32)
+            self._out_steps = torch.from_numpy(steps).to(self.device)
+        return self._out_steps
+
+    def _guided_attention(self, da0, acc, acc_off=0):
+        """One ns_guided_attention launch on the forward pass' alignments: L_att and the focus score into acc[acc_off:
+        acc_off + 2]; with da0, guided_attention_weight times the loss' gradient is added to it."""
+        d = self.dims
+        N = d["N"]
+        ops.guided_attention(N, d["S"], _round_up(d["Ti"], 8), self.input_lengths, self._guided_steps(), self.guided_sigma,
+                             self._bufs["dec_al"], da0, self.guided_weight, self._buf("ga_rows", 2 * N, torch.float32),
+                             acc, acc_off)
+
+    def _check_guided(self, has_da0, why):
+        """A positive guided_attention_weight needs a backward path of the attention recurrence that takes da0."""
+        if self.guided_weight > 0.0 and not has_da0:
+            raise ValueError("guided_attention_weight = %g: %s" % (self.guided_weight, why))
+
+    def initialize(self, text_inputs, input_lengths, speaker_ids=None, mel_targets=None, linear_targets=None,
+                   target_lengths=None):
         """tacotron2.py:15-128.  Training mode iff linear_targets is given.  Tensors may be numpy
-        arrays or torch tensors; they are moved to the GPU once and the forward pass runs."""
+        arrays or torch tensors; they are moved to the GPU once and the forward pass runs.
+        target_lengths (not in the reference): frames per utterance before padding, for the guided attention loss."""
         dev = self.device
         self._set_inputs(text_inputs, input_lengths, speaker_ids)
         self.is_training = linear_targets is not None
@@ -550,6 +600,7 @@ class Tacotron2(object):
         if self.is_training:
             self.mel_targets = torch.as_tensor(mel_targets).to(dev, torch.float32).contiguous()
             self.linear_targets = torch.as_tensor(linear_targets).to(dev, torch.float32).contiguous()
+            self._set_target_lengths(target_lengths)
             self.forward_train()
         else:
             self.mel_targets = self.linear_targets = None
@@ -559,7 +610,13 @@ class Tacotron2(object):
 
     def add_loss(self):
         """tacotron2.py:130-139: the loss is evaluated together with its gradient in step()."""
+        self._check_guided(*self._guided_path())
         return self
+
+    def _guided_path(self):
+        """(does the attention backward of this model take da0?, the reason if not) - as far as it is known now."""
+        return (bool(self.use_pv), "the attention backward pass without projected memory (use_pv = False) has no da0 term "
+                                   "to carry the loss' gradient")
 
     def learning_rate_at(self, step):
         hp = self._hparams
@@ -604,9 +661,16 @@ class Tacotron2(object):
             vals[name] = dict(min=mn, max=mx, mean=mean, std=math.sqrt(max(sq / n - mean * mean, 0.0)))
         g = gout[:8 * nvar].cpu().numpy().reshape(2 * nvar, 4)[0::2]
         norms = np.sqrt(np.maximum(g[:, 1], 0.0)) / self.world_size
+        # the alignment scores (not in the reference, whose alignment feedback is a plot): the step's own where it trains on
+        # them; at weight 0 one launch without a gradient on the forward pass' alignments, only here
+        att, focus = self.attention_loss, self.attention_focus
+        if att is None:
+            acc = self._buf("ga_acc", 8, torch.float32)
+            self._guided_attention(None, acc)
+            att, focus = (float(x) for x in acc[:2].cpu().numpy())
         out = dict(loss=self.loss, loss_mel=self.mel_loss, loss_linear=self.linear_loss, learning_rate=self.learning_rate,
                    max_gradient_norm=float(norms.max()), gradient_norm={k: float(v) for (k, _), v in zip(ent, norms)},
-                   histograms=vals)
+                   histograms=vals, loss_attention=att, attention_focus=focus)
         return out
 
     # ------------------------------------------------------------------ layer helpers
@@ -1268,6 +1332,7 @@ class Tacotron2(object):
         E, A, D = 2 * hp.encoder_lstm_units, hp.attention_dim, hp.decoder_lstm_units
         S1 = S + 1
         g = self.flat_g
+        self._check_guided(*self._guided_path())
         ops.DETERMINISTIC_SPLITK = self.deterministic
         ops.zero_many((g, self.scal))
         self._deferred = []
@@ -1442,6 +1507,8 @@ class Tacotron2(object):
                 ops.copy3d(dhc, src, 1, rows, E, (0, A + E), (0, E), src_off=A)
             ops.gemm(src, enc, da0, S1, Ti, E, lda, E, Tia, b_mode=0, a_off=a0, b_off=self.padl * E, batch=N,
                      batch_strides=(S1 * lda, Pi * E, S1 * Tia))
+            if self.guided_weight > 0.0:        # + weight * d(L_att)/d(align), a constant; L_att and the focus into scal[4:6]
+                self._guided_attention(da0, self.scal, 4)
             args["da0"] = da0
         args.update(w1c=(self._W(self.T), w1 + M * 256), w2=(self._W(self.T), w2), watt=(self._W(self.T), wa),
                     wq=(self._W(self.T), wq), dhc=dhc, df1=df1, dp2=dp2, dga=dga, dq=dq, dkeys=dkeys, dvalues=dvalues,
@@ -1578,6 +1645,11 @@ class Tacotron2(object):
         self.mel_loss = float(s[0]) / (N * To * hp.num_mels)
         self.linear_loss = 0.5 * float(s[2]) / (N * To * hp.num_freq) + 0.5 * float(s[3]) / (N * To * self._n_prio)
         self.loss = self.mel_loss + self.linear_loss
+        if self.guided_weight > 0.0:
+            self.attention_loss, self.attention_focus = float(s[4]), float(s[5])
+            self.loss += self.guided_weight * self.attention_loss
+        else:
+            self.attention_loss = self.attention_focus = None      # not computed by the step: summary() does on demand
         self.grad_norm = math.sqrt(max(float(s[8]), 0.0)) / self.world_size
         return self.loss
 
@@ -1596,11 +1668,13 @@ class Tacotron2(object):
         ev.record(torch.cuda.current_stream(self.device))
         d = self.dims
         return dict(host=host, event=ev, N=d["N"], To=d["To"], n_prio=self._n_prio, step=self.global_step,
-                    lr=self.learning_rate)
+                    lr=self.learning_rate, guided_weight=self.guided_weight)
 
     def losses_finish(self, handle):
         """Wait for a losses_async() read-back and turn it into (loss, mel_loss, linear_loss).  A skipped optimiser step
-        (a persistent recurrence timed out: ns_adam_params.status) raises here, as read_losses() does."""
+        (a persistent recurrence timed out: ns_adam_params.status) raises here, as read_losses() does.  With a guided
+        attention weight the loss includes the weighted term, and handle["attention_loss"] / handle["attention_focus"]
+        hold that step's two scores (None otherwise)."""
         hp = self._hparams
         handle["event"].synchronize()
         s = handle["host"].numpy()
@@ -1609,14 +1683,21 @@ class Tacotron2(object):
         N, To = handle["N"], handle["To"]
         mel_loss = float(s[0]) / (N * To * hp.num_mels)
         lin_loss = 0.5 * float(s[2]) / (N * To * hp.num_freq) + 0.5 * float(s[3]) / (N * To * handle["n_prio"])
-        return mel_loss + lin_loss, mel_loss, lin_loss
+        loss = mel_loss + lin_loss
+        handle["attention_loss"] = handle["attention_focus"] = None
+        if handle["guided_weight"] > 0.0:
+            handle["attention_loss"], handle["attention_focus"] = float(s[4]), float(s[5])
+            loss += handle["guided_weight"] * handle["attention_loss"]
+        return loss, mel_loss, lin_loss
 
     def step(self, inputs=None, input_lengths=None, mel_targets=None, linear_targets=None, grad_hook=None,
-             read_loss=True, speaker_ids=None):
+             read_loss=True, speaker_ids=None, target_lengths=None):
         """One training step = the reference's sess.run([global_step, loss, optimize]) (train.py:80).
-        read_loss: True = wait and return the loss; "async" = return a losses_async() handle; False = nothing."""
+        read_loss: True = wait and return the loss; "async" = return a losses_async() handle; False = nothing.
+        target_lengths: frames per utterance before padding (the feeder's .target_lengths) for the guided attention
+        loss; None = every row spans all decoder steps."""
         if inputs is not None:
-            self.initialize(inputs, input_lengths, speaker_ids, mel_targets, linear_targets)
+            self.initialize(inputs, input_lengths, speaker_ids, mel_targets, linear_targets, target_lengths)
         else:
             self.forward_train()
         self.backward()

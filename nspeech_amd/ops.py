@@ -370,6 +370,16 @@ def l1_loss(pred, ldp, target, dpred, ldd, N, T, P, padl, F, n_prio, w_all, w_pr
     L.call("ns_l1_loss", p, stream())
 
 
+def guided_attention(N, S, Tia, in_lengths, out_steps, sigma, align, da0, grad_scale, row_out, acc=None, acc_off=0):
+    """Guided attention loss and focus of align fp32 [N, S+1, Tia] (ns_guided_attention): row_out[2n] = G_n,
+    row_out[2n+1] = F_n, acc[acc_off], acc[acc_off + 1] = their batch means; with da0 the loss' gradient times grad_scale
+    is added to it.  in_lengths / out_steps: device int32 [N] (out_steps None: S for every row)."""
+    p = L.struct("ns_guided_attention_params")
+    _fill(p, N=N, S=S, Tia=Tia, in_lengths=ptr(in_lengths), out_steps=ptr(out_steps), sigma=sigma, align=ptr(align),
+          da0=ptr(da0), grad_scale=grad_scale, row_out=ptr(row_out), acc=ptr(acc, acc_off))
+    L.call("ns_guided_attention", p, stream())
+
+
 def sumsq(x, n, out, out_off=0, work=None):
     p = L.struct("ns_sumsq_params")
     _fill(p, x=ptr(x), n=n, out=ptr(out, out_off), work=ptr(work))

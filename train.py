@@ -80,7 +80,7 @@ def train_step(model, batches, world=1):
     the next batch (targets already on their way to the GPU, see DeviceStager), run the step, read the loss back.
     Returns the loss (the mean over the ranks when data-parallel, so that every rank takes the same abort decision)."""
     inputs, lengths, mel, lin = batches.next_batch()
-    loss = model.step(inputs, lengths, mel, lin, speaker_ids=batches.speaker_ids)
+    loss = model.step(inputs, lengths, mel, lin, speaker_ids=batches.speaker_ids, target_lengths=batches.target_lengths)
     if world > 1:
         t = torch.tensor([loss], device="cuda")
         torch.distributed.all_reduce(t)
@@ -110,7 +110,8 @@ class LossPipeline(object):
     def step(self):
         """Issue one step; returns (step, loss, learning rate) of the step BEFORE it, or None on the first call."""
         inputs, lengths, mel, lin = self.batches.next_batch()
-        handle = self.model.step(inputs, lengths, mel, lin, speaker_ids=self.batches.speaker_ids, read_loss="async")
+        handle = self.model.step(inputs, lengths, mel, lin, speaker_ids=self.batches.speaker_ids, read_loss="async",
+                                 target_lengths=self.batches.target_lengths)
         done = self._finish(self.pending) if self.pending is not None else None
         self.pending = handle
         return done
@@ -124,7 +125,8 @@ class LossPipeline(object):
 def write_summary(path, step, stats):
     """One JSON object per summary step in LOGDIR/events.jsonl: what the reference hands tf.summary.FileWriter
     (train.py:63,91-93; tacotron2.py:163-188) as scalars - loss, loss_mel, loss_linear, learning_rate,
-    max_gradient_norm - plus the per-variable gradient norms and min / max / mean / std of the four value histograms."""
+    max_gradient_norm - plus the per-variable gradient norms and min / max / mean / std of the four value histograms, and
+    the two alignment scores loss_attention / attention_focus (hparam guided_attention_weight; computed at weight 0 too)."""
     import json
     with open(path, "a") as f:
         f.write(json.dumps(dict(step=int(step), wall_time=time.time(), **stats)) + "\n")
