@@ -1026,10 +1026,14 @@ typedef struct {
    * 512 skip sums, helper h forms hidden units 128 h .. 128 h + 127 (its columns of post1) and their share of all 256
    * logits (its rows of post2), the chain workgroup adds the four partial vectors in a fixed order - two hand-offs of
    * self-flagging {tag, value} granules through post_x instead of two matrix-vector products from L2.
-   * post_x: ns_wavenet_post_bytes(B) of device memory, zeroed by the call; helper_stream: a stream that runs BESIDE the
-   * call's own (ns_streams_concurrent) - the helper kernel is launched on it first; post_x[0] (int) is a status word
-   * (non-zero after the call = a wait timed out, the samples are invalid).  S = 512, Q = 256, B * (1 + 4) <= the CUs. */
-  void* post_x; void* helper_stream;   /* helper_stream: an ns_stream_t */
+   * post_x: ns_wavenet_post_bytes(B) of device memory, zeroed by the call on its own stream.  Chain and helpers are the
+   * workgroups of ONE launch on that stream (version 107): a grid of B * (1 + NS_WN_HELPERS), roles dealt by block index,
+   * five workgroups per waveform that spin on each other's granules - so S = 512, Q = 256 and B * (1 + 4) <= the CUs
+   * (every workgroup resident) is the whole precondition, NS_ERR_BAD_ARG otherwise.  Every wait is bounded; post_x[0]
+   * (int) is a status word (non-zero after the call = a wait timed out, the samples are invalid).
+   * helper_stream: ignored from version 107 on, any value is accepted (up to 106 the helpers were a kernel of their own
+   * on this stream); the member keeps its place, so no offset moves. */
+  void* post_x; void* helper_stream;
   /* A condition that changes along the waveform (a local condition, which the reference's generator never built:
    * wavenet.py:487).  cond_rows 0 or 1: cond is [B, L, 2Dc] as above.  cond_rows > 1: cond is [B, cond_rows, L, 2Dc],
    * one row per cond_hold (>= 1) samples; cond_t0 is the position of ids[.., 0] on the condition's time axis (may be
@@ -1112,8 +1116,8 @@ int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, const ns_wave
  * span == NULL is ns_wavenet_generate_until(p, stop, stream) exactly, and so is a span of [1, total) (which, with a stop,
  * also leaves carry).  stop == NULL: carry may be NULL; a carry that is given receives {0, 0}.
  * NS_ERR_BAD_ARG before any launch, behind every refusal of ns_wavenet_generate_until, which stay as they are:
- * 1 <= t_begin < t_end <= total violated; stop != NULL with carry == NULL; engine 3 with any span (its helper kernel
- * lives for one call). */
+ * 1 <= t_begin < t_end <= total violated; stop != NULL with carry == NULL; engine 3 with any span (its helper
+ * workgroups live for one call). */
 typedef struct {
   int64_t t_begin, t_end;  /* this call runs steps t_begin <= t < t_end; 1 <= t_begin < t_end <= total */
   int* carry;              /* [B, 2] device ints {run, fired} of the end-point rule */

@@ -796,15 +796,15 @@ __device__ __forceinline__ bool wn_get(const u64* p, unsigned tag, float& v, int
   return true;
 }
 
-// helper h of waveform b = block b * NS_WN_HELPERS + h.  512 threads.  post1: thread (n = tid % 128, kq = tid / 128) keeps
-// W1[128 kq .. +128][128 h + n] (64 registers of bf16 pairs); post2: thread (q = tid % 256, kh = tid / 256) keeps
-// W2[128 h + 64 kh .. +64][q] (32 registers).
-__global__ __launch_bounds__(512) void wn_post_helper_kernel(ns_wavenet_generate_params p) {
+// the helper role of wn_generate_mfma_helped_kernel: helper h of waveform b.  512 threads.  post1: thread (n = tid % 128,
+// kq = tid / 128) keeps W1[128 kq .. +128][128 h + n] (64 registers of bf16 pairs); post2: thread (q = tid % 256,
+// kh = tid / 256) keeps W2[128 h + 64 kh .. +64][q] (32 registers).
+__device__ __forceinline__ void wn_post_helper(const ns_wavenet_generate_params& p, int b, int h) {
   __shared__ float hv[WN_S];
   __shared__ float h1v[128];
   __shared__ float part[512];
   __shared__ int abortf;
-  const int tid = threadIdx.x, b = blockIdx.x / NS_WN_HELPERS, h = blockIdx.x % NS_WN_HELPERS;
+  const int tid = threadIdx.x;
   int* status = (int*)p.post_x;
   u64* x = (u64*)((char*)p.post_x + 256) + (size_t)b * WN_XW;
   u64 *xh0 = x, *xlg = x + WN_S + h * WN_Q;
@@ -814,15 +814,19 @@ __global__ __launch_bounds__(512) void wn_post_helper_kernel(ns_wavenet_generate
   {
     const bf16_t* W1 = wb + p.off_post1 + 128 * h + n1;          // [k][n], row stride S
     const bf16_t* W2 = wb + p.off_post2 + q2;                    // [k][q], row stride Q
+    // (16 loads at a time: beside the chain role the scheduler otherwise forms all 192 addresses ahead of the loads and
+    // spills 30 registers; once per call, in front of the seed walk)
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
       const int k = 128 * kq + 2 * i;
       w1[i] = (unsigned)*(const unsigned short*)(W1 + (long)k * WN_S) | ((unsigned)*(const unsigned short*)(W1 + (long)(k + 1) * WN_S) << 16);
+      if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
       const int k = 128 * h + 64 * kh + 2 * i;
       w2[i] = (unsigned)*(const unsigned short*)(W2 + (long)k * WN_Q) | ((unsigned)*(const unsigned short*)(W2 + (long)(k + 1) * WN_Q) << 16);
+      if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
     }
   }
   if (tid == 0) abortf = 0;
@@ -902,7 +906,8 @@ struct ChainLds {                                 // dynamic LDS of wn_generate_
   O bytes = c.off;
 };
 template <bool COND, bool SPAN>
-__device__ __forceinline__ void wn_generate_mfma_body(const ns_wavenet_generate_params& p, double inv_t, const ns_wavenet_stop_params& st, const GenSpan& sp) {
+__device__ __forceinline__ void wn_generate_mfma_body(const ns_wavenet_generate_params& p, double inv_t, const ns_wavenet_stop_params& st, const GenSpan& sp,
+                                                      const int b) {
   extern __shared__ float gsm[];
   constexpr int C = 32;
   const int S = p.S, Q = p.Q, L = p.L;
@@ -915,7 +920,7 @@ __device__ __forceinline__ void wn_generate_mfma_body(const ns_wavenet_generate_
   __shared__ long qoff[128];
   __shared__ int chain_pos;
   __shared__ GenStop gs;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bf16_t* wb = (const bf16_t*)p.weights;
   const bf16_t* fgT = (const bf16_t*)p.fgT;
   const bf16_t* deT = (const bf16_t*)p.deT;
@@ -1241,11 +1246,21 @@ __device__ __forceinline__ void wn_generate_mfma_body(const ns_wavenet_generate_
 // the kernel of the plain calls, with its name and its arguments as they were, and the kernel of a span
 template <bool COND>
 __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st) {
-  wn_generate_mfma_body<COND, false>(p, inv_t, st, GenSpan{});
+  wn_generate_mfma_body<COND, false>(p, inv_t, st, GenSpan{}, blockIdx.x);
 }
 template <bool COND>
 __global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_span_kernel(ns_wavenet_generate_params p, double inv_t, ns_wavenet_stop_params st, GenSpan sp) {
-  wn_generate_mfma_body<COND, true>(p, inv_t, st, sp);
+  wn_generate_mfma_body<COND, true>(p, inv_t, st, sp, blockIdx.x);
+}
+// engine 3: the chain and its helpers in ONE grid of B * (1 + NS_WN_HELPERS) workgroups, roles dealt by blockIdx as in
+// every other persistent kernel here - workgroup 5 b is waveform b's chain, 5 b + 1 + h its helper h.  The two roles
+// spin on each other's granules, so the hand-overs meet only if every workgroup of the grid is resident at once: the
+// launcher's B * (1 + NS_WN_HELPERS) <= CUs is the whole precondition (one grid, dispatched in index order, a workgroup
+// per CU), and a hand-over that does not meet it ends in the bounded waits and the status word, not in a hang.
+__global__ __launch_bounds__(GEN_THREADS) void wn_generate_mfma_helped_kernel(ns_wavenet_generate_params p, double inv_t) {
+  const int b = blockIdx.x / (1 + NS_WN_HELPERS), role = blockIdx.x % (1 + NS_WN_HELPERS);
+  if (role) wn_post_helper(p, b, role - 1);
+  else wn_generate_mfma_body<false, false>(p, inv_t, ns_wavenet_stop_params{}, GenSpan{}, b);   // (engine 3 takes no stop)
 }
 
 constexpr size_t WN_CHAIN_LDS_MAX = 60 * 1024;
@@ -1274,7 +1289,7 @@ extern "C" int ns_wavenet_generate_until(const ns_wavenet_generate_params* p, co
                    "ns_wavenet_generate_span: steps %lld .. %lld outside 1 <= t_begin < t_end <= total = %d",                      \
                    (long long)span->t_begin, (long long)span->t_end, p->total);                                                   \
       NS_CHECK_ARG(!stop || span->carry, "ns_wavenet_generate_span: carry is NULL with a stop (two ints per waveform)");           \
-      NS_CHECK_ARG(p->engine != 3, "ns_wavenet_generate_span: engine 3 takes no span (its helper kernel lives for one call): "    \
+      NS_CHECK_ARG(p->engine != 3, "ns_wavenet_generate_span: engine 3 takes no span (its helper workgroups live for one call): " \
                                    "engine 2");                                                                                   \
       sp = GenSpan{(int)span->t_begin, (int)span->t_end, span->carry};                                                            \
     }                                                                                                                            \
@@ -1327,25 +1342,18 @@ extern "C" int ns_wavenet_generate_span(const ns_wavenet_generate_params* p, con
     NS_CHECK_ARG(p->engine == 3 || !p->post_x, "ns_wavenet_generate: post_x belongs to engine 3");
     if (p->engine == 2 || p->engine == 3) {
       NS_CHECK_ARG(p->R == 32 && p->S / 8 <= 64 && p->S * 7 <= GEN_THREADS * 8, "ns_wavenet_generate: the MFMA chain needs R == Dc == 32, S <= 512");
+      const size_t lds3 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 0}.bytes;
       if (p->engine == 3) {
-        NS_CHECK_ARG(p->post_x && p->helper_stream && p->helper_stream != s && p->S == WN_S && p->Q == WN_Q &&
-                         (((uintptr_t)p->post_x) & 15) == 0 && (long)p->B * (1 + NS_WN_HELPERS) <= ns_device_cus(),
-                     "ns_wavenet_generate: engine 3 needs post_x, a helper stream of its own, S = 512, Q = 256 and B * 5 workgroups resident");
+        NS_CHECK_ARG(p->post_x && p->S == WN_S && p->Q == WN_Q && (((uintptr_t)p->post_x) & 15) == 0 &&
+                         (long)p->B * (1 + NS_WN_HELPERS) <= ns_device_cus(),
+                     "ns_wavenet_generate: engine 3 needs post_x, S = 512, Q = 256 and B * 5 workgroups resident");
         WN_SPAN_CHECK();
         const int zrc = ns_zero_async(p->post_x, (ns_wavenet_post_bytes(p->B) + 15) & ~(size_t)15, (hipStream_t)s);
         if (zrc) return zrc;
-        // the helpers start behind the clearing of the exchange region and run beside the chain kernel
-        hipEvent_t ev;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, (hipStream_t)s) != hipSuccess ||
-            hipStreamWaitEvent((hipStream_t)p->helper_stream, ev, 0) != hipSuccess) {
-          ns_set_error("ns_wavenet_generate: could not order the helper stream behind the call's");
-          return NS_ERR_LAUNCH;
-        }
-        (void)hipEventDestroy(ev);
-        hipLaunchKernelGGL(wn_post_helper_kernel, dim3(p->B * NS_WN_HELPERS), dim3(512), 0, (hipStream_t)p->helper_stream, *p);
-        NS_CHECK_LAUNCH("wavenet_post_helper");
+        hipLaunchKernelGGL(wn_generate_mfma_helped_kernel, dim3(p->B * (1 + NS_WN_HELPERS)), dim3(GEN_THREADS), lds3, (hipStream_t)s, *p, inv_t);
+        NS_CHECK_LAUNCH("wavenet_generate_mfma_helped");
+        return NS_OK;
       }
-      const size_t lds3 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 0}.bytes;
       if (full) {                            // + the condition row and the dense biases
         const size_t lds4 = (size_t)ChainLds<>{p->L, p->R, p->S, p->Q, 1}.bytes;
         NS_CHECK_ARG(lds4 <= WN_CHAIN_LDS_MAX, "ns_wavenet_generate: state and condition row do not fit in LDS (ns_wavenet_chain_fits)");

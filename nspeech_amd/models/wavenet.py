@@ -789,10 +789,8 @@ class SimpleWaveNet(object):
         g = self._gen_prepare(seed_ids, n_samples, uniforms, seed, exact, fast, engine, global_conditions, local_conditions, hold,
                               t0, temperature, endpoint)
         engine, extra, ids = g["kw"]["engine"], g["extra"], g["args"][12]
-        dev = self.device
         ops.wavenet_generate(*g["args"], **g["kw"])
-        if engine == 3:             # the call's stream takes the helpers' end in: post_x is free behind it
-            torch.cuda.current_stream(dev).wait_stream(self._helper_stream)
+        if engine == 3:
             self.last_status = extra["post_x"][:1].view(torch.int32)
             if int(self.last_status.item()) != 0:        # (the caller reads the samples next anyway: one wait here)
                 raise RuntimeError("ns_wavenet_generate: a hand-over between the chain and its helper workgroups timed out "
@@ -808,13 +806,13 @@ class SimpleWaveNet(object):
         """What a generation forms once, for generate (one call) and generate_stream (a series of spans): the checks, ids
         with the seed, the uniforms and zeroed queues on the device, the condition terms, the engine and its weight
         shadows, last_probs and last_ends.  Returns the positional and keyword arguments of ops.wavenet_generate (args,
-        kw), the condition terms (extra) and last_engine.  spans: engine 3 is neither chosen nor taken (its helper kernel
-        lives for one launch)."""
+        kw), the condition terms (extra) and last_engine.  spans: engine 3 is neither chosen nor taken (its helper
+        workgroups live for one launch)."""
         temperature = float(temperature)
         if not math.isfinite(temperature) or temperature < 0:
             raise ValueError("temperature %r: a finite number > 0 for a tempered draw, 0 for argmax" % (temperature,))
         if spans and engine == 3:
-            raise ValueError("engine 3 takes no spans (its helper kernel lives for one call): engine 2 runs the same chain "
+            raise ValueError("engine 3 takes no spans (its helper workgroups live for one call): engine 2 runs the same chain "
                              "without helpers")
         if endpoint is not None and engine == 3:
             raise ValueError("engine 3 takes no endpoint (its helper workgroups would wait for a waveform that has stopped): "
@@ -874,8 +872,8 @@ class SimpleWaveNet(object):
             # per-layer kernel, as before the chain took them
             if extra and (engine == 1 or not ops.wavenet_chain_fits(self.L, self.R, self.S, self.Q, True)):
                 shadows, engine = False, 0
-            if not spans and endpoint is None and not extra and engine == 2 and self.S == 512 and self.Q == 256 and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count \
-                    and self._helper(dev) is not None:
+            if not spans and endpoint is None and not extra and engine == 2 and self.S == 512 and self.Q == 256 \
+                    and B * 5 <= torch.cuda.get_device_properties(dev).multi_processor_count:
                 engine = 3          # + the post-processing products on four helper workgroups per waveform (weights in registers)
         if shadows:
             # column-major bf16 shadows of the layer kernels for the single-wave chain (a lane loads its whole column)
@@ -894,9 +892,7 @@ class SimpleWaveNet(object):
             fgT = torch.cat([fgT[:, :, :32][:, :, perm], fgT[:, :, 32:][:, :, perm]], dim=2).contiguous()
             deT = deT[:, :, perm].contiguous()
         if engine == 3:
-            assert self._helper(dev) is not None, "engine 3 needs a stream that runs beside the current one"
-            post_x = torch.empty(ops.wavenet_post_floats(B), dtype=torch.float32, device=dev)
-            extra = dict(extra, post_x=post_x, helper_stream=self._helper_stream)
+            extra = dict(extra, post_x=torch.empty(ops.wavenet_post_floats(B), dtype=torch.float32, device=dev))
         self.last_ends = torch.full((B,), total - n_seed, dtype=torch.int64, device=dev)
         stop = None
         if endpoint is not None:
@@ -918,21 +914,13 @@ class SimpleWaveNet(object):
         rows of the waveform are given up front.  With an endpoint the iteration ends behind the chunk in which the last
         waveform stopped (the arrays keep generate's zeros behind a row's stop; cut row b at last_ends[b], or hand out
         safe_prefix of what was drawn so far).  last_engine, last_probs and last_ends are generate's once the
-        iterator is exhausted.  Engine 3 is never chosen and engine=3 is a ValueError (its helper kernel lives for one
-        launch); chunk < 1 is a ValueError."""
+        iterator is exhausted.  Engine 3 is never chosen and engine=3 is a ValueError (its helper workgroups live for
+        one launch); chunk < 1 is a ValueError."""
         if int(chunk) < 1:
             raise ValueError("chunk %r: at least one drawn sample per chunk" % (chunk,))
         g = self._gen_prepare(seed_ids, n_samples, uniforms, seed, exact, fast, engine, global_conditions, local_conditions, hold,
                               t0, temperature, endpoint, spans=True)
         return WaveNetStream(self, g, int(chunk))
-
-    def _helper(self, dev):
-        """The helper kernel's stream: one that was seen to run BESIDE the current stream (ns_streams_concurrent), or None
-        (then the helpers would start only after the chain kernel: engine 2 it is)."""
-        if getattr(self, "_helper_stream", None) is None:
-            s = ops.concurrent_stream(dev)
-            self._helper_stream = s if ops.streams_concurrent(torch.cuda.current_stream(dev), s) else False
-        return self._helper_stream or None
 
     def _generator_terms(self, B, W, global_conditions, local_conditions=None):
         """What the full model's incremental generator adds per layer (wavenet.py:398-437), formed once per call:

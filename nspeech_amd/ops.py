@@ -924,7 +924,7 @@ def wavenet_chain_fits(L_, R, S, Q, cond):
 
 def wavenet_generate(weights, offs, dilations, L_, R, Dc, S, Q, B, n_seed, total, queue_rows, ids, uniform, queues, probs=None,
                      fgT=None, deT=None, engine=0, cond=None, dense_bias=None, skip_bias=None, post1_bias=None, post2_bias=None,
-                     post_x=None, helper_stream=None, cond_rows=0, cond_hold=0, cond_t0=0, temperature=0.0, argmax=False,
+                     post_x=None, cond_rows=0, cond_hold=0, cond_t0=0, temperature=0.0, argmax=False,
                      stop=None, span=None):
     """cond_rows > 1: cond is [B, cond_rows, L, 2Dc], one row per cond_hold samples, ids[.., 0] at position cond_t0 of the
     condition's time axis (include/nspeech_hip.h).  temperature: the draws come from softmax(logits / temperature), 0 = 1.0;
@@ -936,9 +936,7 @@ def wavenet_generate(weights, offs, dilations, L_, R, Dc, S, Q, B, n_seed, total
     Every call of a series takes the same other arguments."""
     p = L.struct("ns_wavenet_generate_params")
     _fill(p, cond_rows=cond_rows, cond_hold=cond_hold, cond_t0=cond_t0, temperature=float(temperature), argmax=int(bool(argmax)))
-    if post_x is not None:
-        p.post_x, p.helper_stream = ptr(post_x), helper_stream.cuda_stream
-    _fill(p, cond=ptr(cond), dense_bias=ptr(dense_bias), skip_bias=ptr(skip_bias), post1_bias=ptr(post1_bias),
+    _fill(p, post_x=ptr(post_x), cond=ptr(cond), dense_bias=ptr(dense_bias), skip_bias=ptr(skip_bias), post1_bias=ptr(post1_bias),
           post2_bias=ptr(post2_bias))
     _fill(p, weights=ptr(weights), w_dtype=dt(weights), off_causal=offs["causal"], off_layer0=offs["layer0"],
           layer_stride=offs["layer_stride"], off_dense_in_layer=offs["dense_in_layer"], off_skip=offs["skip"],

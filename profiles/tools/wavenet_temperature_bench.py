@@ -2,8 +2,7 @@
 wavenet.yaml widths (50 layers, R = Dc = 32, S = 512, Q = 256), 2000 drawn samples behind a receptive-field seed, bf16
 weights, batch 1 and 32, on
 
-  engine 3              simple_wavenet, MFMA chain + helper workgroups (engine 2 is reported in its place, and said so,
-                        where no stream runs beside the current one)
+  engine 3              simple_wavenet, MFMA chain + helper workgroups
   engine 2              simple_wavenet, MFMA chain
   engine 2 conditioned  use_biases + lc_channels=80 at hold=250: one mel row per hop of audio.yaml
 
@@ -50,10 +49,10 @@ def resources(csrc):
     print("  %-34s %6s %6s %14s %12s" % ("kernel", "VGPRs", "SGPRs", "scratch B/lane", "VGPR spills"))
     for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
         name = b.split()[0]
-        m = re.match(r"_Z\d+(wn_generate\w*kernel)I(\w+?)E+v", name)
+        m = re.match(r"_Z\d+(wn_generate\w*kernel)(?:I(\w+?)E+v|\d)", name)       # a template's instantiation, or a plain kernel
         if not m:
             continue
-        arg = {"Lb1": "<true>", "Lb0": "<false>", "Li32": "<32>", "Li16": "<16>", "DF16b": "<bf16>", "f": "<float>"}.get(m.group(2), m.group(2))
+        arg = {"Lb1": "<true>", "Lb0": "<false>", "Li32": "<32>", "Li16": "<16>", "DF16b": "<bf16>", "f": "<float>", None: ""}.get(m.group(2), m.group(2))
 
         def num(key):
             return int(re.search(re.escape(key) + r": (\d+)", b).group(1))
@@ -106,14 +105,11 @@ def main():
     local.load_numpy_params(p)
     rf, hold = simple.rf, 250
     rng = np.random.default_rng(0)
-    helper = simple._helper(torch.device("cuda:0")) is not None
-    if not helper:
-        print("no stream runs beside the current one here: the rows named engine 3 ran on engine 2")
     rows = []
     for B in (1, 32):
         seed = rng.integers(0, 256, size=(B, rf)).astype(np.int32)
         mel = rng.standard_normal((B, (n - 1) // hold + 1, 80)).astype(np.float32)
-        rows += [("engine 3, batch %d" % B, simple, seed, {}, 3 if helper else 2),
+        rows += [("engine 3, batch %d" % B, simple, seed, {}, 3),
                  ("engine 2, batch %d" % B, simple, seed, dict(engine=2), 2),
                  ("engine 2 conditioned, batch %d" % B, local, seed, dict(local_conditions=mel, hold=hold, t0=-rf), 2)]
     modes = [m for m in MODES if parent is not None or not m[1]]

@@ -58,6 +58,21 @@ def test_the_valu_chain_still_takes_no_condition():
     assert rc == ERR_ARG and "conditions / biases" in msg
 
 
+def test_engine_3_no_longer_consults_helper_stream():
+    # the helpers are workgroups of the chain's own launch: helper_stream keeps its place in the struct and is ignored.
+    # NULL, and the call's own stream, once failed engine 3's precondition; now such a block passes it and a span is
+    # refused with the span's message, which stands behind that precondition
+    lib = _lib.lib()
+    sp = _lib.struct("ns_wavenet_span_params")
+    sp.t_begin, sp.t_end, sp.carry = 5, 9, 0x1000
+    call_stream = 0x3000                     # never followed: the refusal stands in front of the first enqueue
+    for hs in (0, call_stream):
+        p = _params(fgT=0x1000, deT=0x1000, engine=3, S=512, Q=256, post_x=0x1000, helper_stream=hs)
+        rc = lib.ns_wavenet_generate_span(ctypes.byref(p), None, ctypes.byref(sp), ctypes.c_void_p(call_stream))
+        msg = lib.ns_last_error().decode()
+        assert rc == ERR_ARG and msg.startswith("ns_wavenet_generate_span: engine 3 takes no span"), msg
+
+
 def test_the_per_layer_kernel_refuses_an_odd_dc():
     # Dc = 1 passes every divisibility check (512 % (2 Dc) == 0), but the kernel's float64 row follows 3 Dc floats in LDS:
     # an odd Dc leaves it 4 bytes off an 8-byte boundary

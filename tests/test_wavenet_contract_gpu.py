@@ -49,8 +49,11 @@ Worst error / bound on the MI355X (every test prints its own, `pytest -s`):
   generator, bf16 rule      max / mean against mfma;  max / mean against pure
     engine 2                0.16 / 0.31;  0.25 / 0.51        conditioned 0.15 / 0.18;  0.25 / 0.50
     engine 2, 66 layers     0.03 / 0.17;  0.27 / 0.55        with biases (S 512, Q 256) 0.42 / 0.16;  0.25 / 0.52
-    engine 3                0.32 / 0.82;  0.30 / 0.55        66 layers 0.48 / 0.80;  0.29 / 0.53
-  every id of every run equals the reference's (34 cases x 2 seed lengths x 3 waveforms x 24 draws; engine 3 ran)
+    engine 3                0.32 / 0.82;  0.30 / 0.55        66 layers 0.55 / 0.80;  0.29 / 0.53
+                            (chain and helpers in one grid; the two-kernel form before it: the same figures, and the
+                            same bits in ids and last_probs on every engine-3 case)
+  every id of every run equals the reference's (34 cases x 2 seed lengths x 3 waveforms x 24 draws; engine 3 runs on
+  every runtime configuration)
   bf16 training pass        max / mean against train_bf16;  against pure at most 0.27 / 0.50 throughout
     simple_wavenet          logits, loss < 0.01;  gradients at most 0.02 / 0.06 (filter)
     wavenet, biases + lc    logits 0.12 / 0.02   loss 0.11   gradients at most 0.25 / 0.08 (postprocess2_bias / gate)
@@ -241,8 +244,6 @@ def _model(c, dev):
 def test_generator_draws_the_reference_run(dev, c):
     preset, rule, gkw, engine = FORMS[c.form]
     m = _model(c, dev)
-    if c.form == "engine3" and m._helper(dev) is None:
-        pytest.skip("no stream runs beside the current one on this runtime configuration: engine 2 is what generate() takes")
     for extra in SEED_EXTRA:
         d = gen_data(c, extra)
         ref = references(c, extra)
@@ -277,6 +278,53 @@ def test_generator_draws_the_reference_run(dev, c):
         assert np.array_equal(again, got) and torch.equal(m.last_probs.view(c.B, c.Q).cpu(), lps[-1])
         if engine == 3:
             assert int(m.last_status.item()) == 0
+
+
+@pytest.mark.parametrize("c", [c for c in GEN_CASES if c.form == "engine3"], ids=gen_id)
+def test_engine_3_under_any_current_stream(dev, c):
+    """Chain and helpers are one grid on the call's stream, so engine 3 is chosen and meets its hand-overs under whatever
+    stream is current: the default one, then two fresh ones, on ONE model with the same seeds and uniforms.  Every run
+    reports engine 3 and status 0, draws the reference's ids, and ids and last_probs are bit-identical across the three
+    (the arithmetic does not depend on the stream)."""
+    m = _model(c, dev)
+    for extra in SEED_EXTRA:
+        d, ref = gen_data(c, extra), references(c, extra)
+        m.load_numpy_params(d["params"])
+        runs = []
+        for s in (None, torch.cuda.Stream(dev), torch.cuda.Stream(dev)):
+            if s is not None:
+                s.wait_stream(torch.cuda.current_stream(dev))     # the parameters were loaded on the default stream
+            with torch.cuda.stream(s):
+                ids = m.generate(d["seeds"].copy(), N_DRAW, uniforms=ref["un"].copy())
+                assert m.last_engine == 3 and int(m.last_status.item()) == 0, (s, m.last_engine)
+                runs.append((ids.cpu(), m.last_probs.cpu()))
+            torch.cuda.synchronize(dev)
+        assert np.array_equal(runs[0][0].numpy(), ref["ids"])
+        for ids, probs in runs[1:]:
+            assert torch.equal(ids, runs[0][0]) and torch.equal(probs, runs[0][1])
+
+
+def test_engine_3_at_the_residency_bound(dev):
+    """The largest batch engine 3 accepts, B = CUs // 5: a grid of 5 B workgroups, the CU count or up to four short of it,
+    every one resident.  generate() takes engine 3 by itself, the status stays 0 and 6 draws coincide with engine 2's in
+    the share of rows test_wavenet_helper_engine_equals_the_chain_engine demands (0.6: a draw on a CDF edge may fall the
+    other way, the histories part there); one waveform more runs on engine 2 by itself."""
+    c = Gen("engine3", 32, 512, 256, 2, 4)
+    d = gen_data(c, 5)
+    m = _model(c, dev)
+    m.load_numpy_params(d["params"])
+    B = torch.cuda.get_device_properties(dev).multi_processor_count // 5
+    rng = np.random.RandomState(9)
+    seeds = rng.randint(0, c.Q, size=(B + 1, d["n_seed"])).astype(np.int32)
+    un = np.random.default_rng(3).random((B + 1, 6))
+    a = m.generate(seeds[:B], 6, uniforms=un[:B]).cpu().numpy()
+    assert m.last_engine == 3 and int(m.last_status.item()) == 0, m.last_engine
+    b = m.generate(seeds[:B], 6, uniforms=un[:B], engine=2).cpu().numpy()
+    assert m.last_engine == 2
+    agree = (a == b).all(axis=1)
+    assert agree.mean() >= 0.6, agree
+    m.generate(seeds, 6, uniforms=un)
+    assert m.last_engine == 2, m.last_engine
 
 
 # ------------------------------------------------------------------------------------------------------------ bf16 training

@@ -69,7 +69,7 @@ def test_a_bad_stop_is_refused(over, word):
 
 def test_engine_3_takes_no_stop():
     # everything engine 3 asks for is there (as far as a host check can tell): the stop alone is refused, in front of the
-    # clearing of post_x and the helper launch
+    # clearing of post_x and the launch
     rc, msg = _refused(_params(fgT=0x1000, deT=0x1000, engine=3, S=512, Q=256, post_x=0x1000, helper_stream=0x2000), _stop())
     assert rc == ERR_ARG and msg.startswith("ns_wavenet_generate_until:") and "engine 3" in msg, msg
 

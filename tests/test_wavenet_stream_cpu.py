@@ -91,7 +91,7 @@ def test_a_stop_needs_a_carry(route):
 
 def test_engine_3_takes_no_span():
     # everything engine 3 asks for is there (as far as a host check can tell): the span alone is refused, in front of the
-    # clearing of post_x and the helper launch - even the span of the whole loop
+    # clearing of post_x and the launch - even the span of the whole loop
     for sp in (_span(1, 20), _span(5, 9), _span(1, 20, carry=None)):
         rc, msg = _refused(_params(fgT=0x1000, deT=0x1000, engine=3, S=512, Q=256, post_x=0x1000, helper_stream=0x2000), None, sp)
         assert rc == ERR_ARG and msg.startswith("ns_wavenet_generate_span:") and "engine 3" in msg, msg
