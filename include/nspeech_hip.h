@@ -360,16 +360,21 @@ int ns_guided_attention(const ns_guided_attention_params* p, ns_stream_t stream)
  * data-parallel rank; without it the block sums meet in one float atomic (order varies from run to run). */
 typedef struct { const float* x; int64_t n; float* out; float* work; } ns_sumsq_params;
 int ns_sumsq(const ns_sumsq_params* p, ns_stream_t stream);
+/* How many status words one ns_adam call looks at (12 up to version 107).  Every launch clears its own work area, so
+ * each consulted launch of a step has a word of its own: a Tacotron-1 step registers 22 (two BiGRU groups and the
+ * attention RNN, forward and backward, and the two decoder GRUs' 2 x 4 time windows of each pass). */
+#define NS_ADAM_STATUS_MAX 32
 typedef struct {
   float* p; const float* g; float* m; float* v; int64_t n;
   const float* gnorm_sq; float clip; float grad_scale;
   float lr_t, beta1, beta2, eps;
   void* shadow_bf16;
-  /* status words of the step's persistent recurrences (ns_lstm_wide_* / ns_lstm_cluster_* / ns_taco2_attn_cluster_*:
-   * the first int of their work buffers; unused entries NULL).  If any is non-zero - an exchange timed out, that pass's
-   * outputs and therefore this gradient are invalid - NOTHING is updated and *skipped (nullable) is set to 1, on the
-   * device, without a host round trip in front of the optimiser. */
-  const int* status[12];
+  /* status words of the step's persistent recurrences (ns_lstm_wide_* / ns_lstm_cluster_* / ns_gru_seq_* /
+   * ns_taco2_attn_cluster_* / ns_taco1_attn_cluster_*: the first int of their work buffers; unused entries NULL).  If
+   * any is non-zero - an exchange timed out, that pass's outputs and therefore this gradient are invalid - NOTHING is
+   * updated and *skipped (nullable) is set to 1, on the device, without a host round trip in front of the optimiser.
+   * The guard holds only for a word that no later launch of the step clears: one work area per consulted launch. */
+  const int* status[NS_ADAM_STATUS_MAX];
   float* skipped;
 } ns_adam_params;
 int ns_adam(const ns_adam_params* p, ns_stream_t stream);

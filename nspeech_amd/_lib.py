@@ -31,10 +31,11 @@ _CTYPES = {
 
 
 def _parse_header():
-    """Return ({struct name: ctypes.Structure subclass}, [exported function names])."""
+    """Return ({struct name: ctypes.Structure subclass}, [exported function names], {#define name: int})."""
     src = open(HEADER_PATH).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     src = re.sub(r"//[^\n]*", "", src)
+    consts = {k: int(v) for k, v in re.findall(r"^#define\s+(NS_\w+)\s+(\d+)\s*$", src, flags=re.M)}
     structs = {}
     for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
         fields = []
@@ -48,7 +49,7 @@ def _parse_header():
                 nm = nm.strip()
                 is_ptr = bool(star) or nm.startswith("*")
                 nm = nm.lstrip("* ")
-                arr = re.match(r"(\w+)\[(\d+)\]$", nm)
+                arr = re.match(r"(\w+)\[(\w+)\]$", nm)
                 if is_ptr:
                     ct = C.c_void_p
                 elif base in structs:           # a parameter block embedded in another one
@@ -57,15 +58,16 @@ def _parse_header():
                     ct = _CTYPES[base]
                 if arr:
                     nm = arr.group(1)
-                    ct = ct * int(arr.group(2))
+                    ct = ct * (consts.get(arr.group(2)) or int(arr.group(2)))      # a #define'd count or a literal
                 fields.append((nm, ct))
         structs[name] = type(name, (C.Structure,), {"_fields_": fields})
     funcs = re.findall(r"\b(ns_\w+)\s*\(", src)
     funcs = sorted(set(f for f in funcs if not f.endswith("_params")))
-    return structs, funcs
+    return structs, funcs, consts
 
 
-STRUCTS, FUNCS = _parse_header()
+STRUCTS, FUNCS, CONSTS = _parse_header()
+NS_ADAM_STATUS_MAX = CONSTS["NS_ADAM_STATUS_MAX"]
 
 
 def struct(name):

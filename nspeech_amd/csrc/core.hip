@@ -71,7 +71,7 @@ extern "C" int ns_cluster_probe(int clusters, int members, int placed, int* xcc,
   return NS_OK;
 }
 
-extern "C" int ns_version(void) { return 107; }
+extern "C" int ns_version(void) { return 108; }
 extern "C" const char* ns_device_arch(void) { return "gfx950"; }
 extern "C" const char* ns_last_error(void) { return g_err; }
 

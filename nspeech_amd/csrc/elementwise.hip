@@ -876,7 +876,7 @@ __global__ void adam_kernel(ns_adam_params p) {
   // reads the same words, which no kernel of this step writes any more)
   bool bad = false;
 #pragma unroll
-  for (int i = 0; i < 12; ++i)
+  for (int i = 0; i < NS_ADAM_STATUS_MAX; ++i)
     if (p.status[i] && __hip_atomic_load(p.status[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) bad = true;
   if (bad) {
     if (blockIdx.x == 0 && threadIdx.x == 0 && p.skipped) *p.skipped = 1.f;

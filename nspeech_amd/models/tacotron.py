@@ -266,6 +266,41 @@ class Tacotron(Tacotron2):
         """One GRU direction over the whole sequence (see _gru_group)."""
         self._gru_group(tag, [dict(tag=tag, scope=scope, key=key, reverse=reverse, col=col)], x, H, lengths, out, h0)
 
+    def _gru_dir(self, dd, x, out, H):
+        """Completes the record of one GRU direction - dd: tag, scope, key (of its transposed shadows), reverse, col -
+        over the input x with its h history in out.buf columns [col, col + H): parameter offsets and buffers."""
+        tag, scope, rows, f32 = dd["tag"], dd["scope"], x.rows, torch.float32
+        dd.update(x=x, out=out, H=H)
+        dd["og"], dd["oc"] = self._o(scope + "/gates/kernel"), self._o(scope + "/candidate/kernel")
+        dd["bg"], dd["bc"] = self._o(scope + "/gates/bias"), self._o(scope + "/candidate/bias")
+        dd["xg"] = self._buf("gru:%s_xg" % tag, rows * 2 * H, f32)
+        dd["xc"] = self._buf("gru:%s_xc" % tag, rows * H, f32)
+        # saved gates: [rows, 2H] / [rows, H] for the step launches; the persistent kernels keep them in an order of their
+        # own over whole 16-row groups (ns_gru_seq_params.ru) - the buffers serve either
+        srows = max(rows, (x.N + 15) // 16 * 16 * x.T)
+        dd["ru"] = self._buf("gru:%s_ru" % tag, srows * 2 * H, f32)
+        dd["cc"] = self._buf("gru:%s_c" % tag, srows * H, f32)
+        dd["rh"] = self._buf("gru:%s_rh" % tag, rows * H, self.T)
+        dd["gT"], dd["cT"] = self.tsh[dd["key"] + "_gT"], self.tsh[dd["key"] + "_cT"]
+        return dd
+
+    def _gru_params(self, dd, win, lengths, h_init, bwd=False, dh_init=None):
+        """The ns_gru_seq parameter block of the steps win = [t0, t1) of one direction, h_init the state in front of
+        them (None: zeros).  bwd: with the gradient arrays; dh_init receives the gradient wrt h_init.  A window is the same
+        arrays with the first row moved to t0: every [N*P, .] array is addressed as row n * P + padl + t, and the saved
+        gates of step t0 start N16 * t0 rows into theirs."""
+        x, out, H, (t0, t1) = dd["x"], dd["out"], dd["H"], win
+        W, cin, N16 = self._W(self.T), x.C, (x.N + 15) // 16 * 16
+        kw = {}
+        if bwd:
+            kw = dict(dh=(out.grad, dd["col"]), ld_dh=out.C, dzg=dd["dzg"], dzc=dd["dzc"])
+            if dh_init is not None:
+                kw.update(dh_init=dh_init, ld_dhi=H)
+        return ops.gru_seq_params(out.buf, x.N, t1 - t0, H, x.P, x.padl + t0, dd["reverse"], lengths, dd["xg"], dd["xc"],
+                                  dd["gT"], dd["cT"], (W, dd["og"] + cin * 2 * H), 2 * H, (W, dd["oc"] + cin * H), H,
+                                  (out.buf, dd["col"]), out.C, (dd["ru"], N16 * t0 * 2 * H), (dd["cc"], N16 * t0 * H),
+                                  dd["rh"], h_init=h_init, ld_hi=H, **kw)
+
     def _gru_group(self, label, dirs, x, H, lengths, out, h0=None):
         """One or two GRU directions (a BiGRU's fw / bw cells, modules.py:172-181) over the same input x, outputs in
         out.buf columns [col, col + H) of each direction.  The input halves of both gate products are hoisted GEMMs; the
@@ -288,49 +323,26 @@ class Tacotron(Tacotron2):
             ops.copy3d(h0.buf, h0f, 1, N, H, (0, H), (0, H))
         lens = self._host_lengths if lengths is not None else [T] * N
         for dd in dirs:
-            tag, scope = dd["tag"], dd["scope"]
-            dd["og"], dd["oc"] = self._o(scope + "/gates/kernel"), self._o(scope + "/candidate/kernel")
-            dd["bg"], dd["bc"] = self._o(scope + "/gates/bias"), self._o(scope + "/candidate/bias")
-            dd["xg"] = self._buf("gru:%s_xg" % tag, rows * 2 * H, torch.float32)
-            dd["xc"] = self._buf("gru:%s_xc" % tag, rows * H, torch.float32)
+            self._gru_dir(dd, x, out, H)
             ops.gemm(x.buf, W, dd["xg"], rows, 2 * H, cin, cin, 2 * H, 2 * H, b_mode=1, b_off=dd["og"], bias=self.flat_p,
                      bias_off=dd["bg"])
             ops.gemm(x.buf, W, dd["xc"], rows, H, cin, cin, H, H, b_mode=1, b_off=dd["oc"], bias=self.flat_p, bias_off=dd["bc"])
-            # saved gates: [rows, 2H] / [rows, H] for the step launches; the persistent kernels keep them in an order of their
-            # own over whole 16-row groups (ns_gru_seq_params.ru) - the buffers serve either
-            srows = max(rows, (N + 15) // 16 * 16 * T)
-            dd["ru"] = self._buf("gru:%s_ru" % tag, srows * 2 * H, torch.float32)
-            dd["cc"] = self._buf("gru:%s_c" % tag, srows * H, torch.float32)
-            dd["rh"] = self._buf("gru:%s_rh" % tag, rows * H, self.T)
-            dd["gT"], dd["cT"] = self.tsh[dd["key"] + "_gT"], self.tsh[dd["key"] + "_cT"]
             dd["first"] = [int(lens[n]) - 1 if dd["reverse"] else 0 for n in range(N)]
 
-        def params(dd, bwd):
-            kw = {}
-            if bwd:
-                kw = dict(dh=(out.grad, dd["col"]), ld_dh=ldh, dzg=dd["dzg"], dzc=dd["dzc"])
-                if h0 is not None:
-                    kw.update(dh_init=dd["dh0"], ld_dhi=H)
-            # every [N*P, .] array is addressed as row n * P + padl + t: the arrays start at row 0
-            return ops.gru_seq_params(hb, N, T, H, P, padl, dd["reverse"], lengths, dd["xg"], dd["xc"], dd["gT"], dd["cT"],
-                                      (W, dd["og"] + cin * 2 * H), 2 * H, (W, dd["oc"] + cin * H), H, (hb, dd["col"]), ldh,
-                                      dd["ru"], dd["cc"], dd["rh"], h_init=h0f, ld_hi=H, **kw)
-
-        def persistent(bwd):
+        def persistent(direction):
+            """The whole sequence as one launch - the window (0, T) from the initial state h0 - where the kernels take it."""
             if not self.use_gru_seq or len(dirs) > 2:
-                return None
-            pp = [params(dd, bwd) for dd in dirs]
-            p1 = pp[1] if len(pp) > 1 else None
-            return (pp[0], p1) if ops.gru_seq_supported(pp[0], p1, backward=bwd) else None
+                return False
+            bwd = direction == "bwd"
+            pp = [self._gru_params(dd, (0, T), lengths, h0f, bwd, dd.get("dh0")) for dd in dirs] + [None]
+            if not ops.gru_seq_supported(pp[0], pp[1], backward=bwd):
+                return False
+            self._persistent(label, direction, ops.gru_seq_work_floats(pp[0]),
+                             lambda w: ops.gru_seq(direction, pp[0], pp[1], w), "seq")
+            return True
 
-        pp = persistent(False)
-        if pp is not None:
-            work = self._buf("gru:%s_work" % label, ops.gru_seq_work_floats(pp[0]), torch.float32)
-            ops.gru_seq("fwd", pp[0], pp[1], work)
-            self._status_words[(label, "fwd")] = work
-            self.last_paths["%s:fwd" % label] = "seq"
-        else:
-            self.last_paths["%s:fwd" % label] = "step"
+        if not persistent("fwd"):
+            self._per_step(label, "fwd")
             for dd in dirs:
                 self._gru_steps_fwd(dd, N, P, padl, T, H, ldh, lengths, hb, h0, h0f)
 
@@ -343,16 +355,10 @@ class Tacotron(Tacotron2):
                 ops.zero(dd["dzc"])
                 if h0 is not None:
                     dd["dh0"] = self._buf("gru:%s_dh0" % dd["tag"], N * H, torch.float32)
-            pb = persistent(True)
-            if pb is not None:
-                work = self._buf("gru:%s_work" % label, ops.gru_seq_work_floats(pb[0]), torch.float32)
-                ops.gru_seq("bwd", pb[0], pb[1], work)
-                self._status_words[(label, "bwd")] = work
-                self.last_paths["%s:bwd" % label] = "seq"
-            else:
+            if not persistent("bwd"):
                 if self.last_paths.get("%s:fwd" % label) == "seq":
                     raise RuntimeError("GRU %s: the persistent forward kernel's saved gates are private to ns_gru_seq_bwd" % label)
-                self.last_paths["%s:bwd" % label] = "step"
+                self._per_step(label, "bwd")
                 for dd in dirs:
                     self._gru_steps_bwd(dd, N, P, padl, T, H, ldh, lengths, hb, out.grad, cin, h0f)
             for dd in reversed(dirs):
@@ -382,44 +388,17 @@ class Tacotron(Tacotron2):
         nch = self.GRU_PIPE_CHUNKS
         edges = [T * c // nch for c in range(nch + 1)]
         wins = [(edges[c], edges[c + 1]) for c in range(nch)]
-        N16 = (N + 15) // 16 * 16
         h1 = self._new("dec_h1", x1, H); y1 = self._new("dec_y1", x1, H)
         h2 = self._new("dec_h2", x1, H); y2 = self._new("dec_y2", x1, H)
         gr = []
         for k, (tag, xin) in enumerate((("gru_1", x1), ("gru_2", y1))):
-            scope = "decoder/" + tag
-            dd = dict(tag=tag, key=tag, reverse=False, col=0, x=xin, out=(h1, h2)[k])
-            dd["og"], dd["oc"] = self._o(scope + "/gates/kernel"), self._o(scope + "/candidate/kernel")
-            dd["bg"], dd["bc"] = self._o(scope + "/gates/bias"), self._o(scope + "/candidate/bias")
-            dd["xg"] = self._buf("gru:%s_xg" % tag, rows * 2 * H, f32)
-            dd["xc"] = self._buf("gru:%s_xc" % tag, rows * H, f32)
-            dd["ru"] = self._buf("gru:%s_ru" % tag, max(rows, N16 * T) * 2 * H, f32)
-            dd["cc"] = self._buf("gru:%s_c" % tag, max(rows, N16 * T) * H, f32)
-            dd["rh"] = self._buf("gru:%s_rh" % tag, rows * H, T_)
-            dd["gT"], dd["cT"] = self.tsh[tag + "_gT"], self.tsh[tag + "_cT"]
+            dd = self._gru_dir(dict(tag=tag, scope="decoder/" + tag, key=tag, reverse=False, col=0), xin, (h1, h2)[k], H)
             dd["hi"] = [None] + [self._buf("gru:%s_hi%d" % (tag, c), N * H, f32) for c in range(1, nch)]
-            dd["work"] = self._buf("gru:%s_work" % tag, 1, f32)
-            gr.append(dd)
-
-        def params(dd, c, bwd):
-            t0, t1 = wins[c]
-            hb = dd["out"].buf
-            kw = {}
-            if bwd:
-                kw = dict(dh=(dd["out"].grad, 0), ld_dh=H, dzg=dd["dzg"], dzc=dd["dzc"])
-                if c > 0:
-                    kw.update(dh_init=dd["dhi"], ld_dhi=H)
-            # a window = the same arrays with the first row moved to t0: every [N*P, .] array is addressed as row n * P + padl + t
-            return ops.gru_seq_params(hb, N, t1 - t0, H, P, padl + t0, False, None, dd["xg"], dd["xc"], dd["gT"], dd["cT"],
-                                      (W, dd["og"] + D * 2 * H), 2 * H, (W, dd["oc"] + D * H), H, (hb, 0), H,
-                                      (dd["ru"], N16 * t0 * 2 * H), (dd["cc"], N16 * t0 * H), dd["rh"],
-                                      h_init=dd["hi"][c], ld_hi=H, **kw)
-
-        for dd in gr:
-            p0 = params(dd, 1, False)
+            p0 = self._gru_params(dd, wins[1], None, dd["hi"][1])
             if not ops.gru_seq_supported(p0, None, backward=False):
                 return None
-            dd["work"] = self._buf("gru:%s_work" % dd["tag"], ops.gru_seq_work_floats(p0), f32)
+            dd["floats"] = ops.gru_seq_work_floats(p0)
+            gr.append(dd)
         g1, g2 = gr
         ops.zero_many((h1.buf, h2.buf, y1.buf))       # (y1's pad rows: the windows below write the steps' rows only)
         ops.gemm(x1.buf, W, g1["xg"], rows, 2 * H, D, D, 2 * H, 2 * H, b_mode=1, b_off=g1["og"], bias=self.flat_p, bias_off=g1["bg"])
@@ -441,11 +420,13 @@ class Tacotron(Tacotron2):
             dst.wait_event(ev)
 
         def window(dd, c, direction):
-            t0, _ = wins[c]
-            if direction == "fwd" and c > 0:        # the state in front of the window is its initial state
+            t0, bwd = wins[c][0], direction == "bwd"
+            if not bwd and c > 0:                   # the state in front of the window is its initial state
                 ops.copy3d(dd["out"].buf, dd["hi"][c], N, 1, H, (P * H, 0), (H, 0), src_off=(padl + t0 - 1) * H)
-            ops.gru_seq(direction, params(dd, c, direction == "bwd"), None, dd["work"])
-            if direction == "bwd" and c > 0:        # ... and its gradient belongs to the row in front of the window
+            p = self._gru_params(dd, wins[c], None, dd["hi"][c], bwd, dd["dhi"] if bwd and c > 0 else None)
+            # (slot: a work area per window - each launch clears its own, and every window's status word is read after the step)
+            self._persistent(dd["tag"], direction, dd["floats"], lambda w: ops.gru_seq(direction, p, None, w), "seq", slot=c)
+            if bwd and c > 0:                       # ... and its gradient belongs to the row in front of the window
                 ops.copy3d(dd["dhi"], dd["out"].grad, N, 1, H, (H, 0), (P * H, 0), dst_off=(padl + t0 - 1) * H, accumulate=1)
 
         def rows_of(c, C):                  # (I, J, strides, offset) of a window's rows in a [N*P, C] array
@@ -469,9 +450,6 @@ class Tacotron(Tacotron2):
         hand_over(sb, main)
         ops.copy3d(y1.buf, y2.buf, 1, rows, H, (0, H), (0, H))
         ops.copy3d(h2.buf, y2.buf, 1, rows, H, (0, H), (0, H), accumulate=1)
-        for dd in gr:
-            self._status_words[(dd["tag"], "fwd")] = dd["work"]
-            self.last_paths["%s:fwd" % dd["tag"]] = "seq"
         self.last_paths["gru_pair"] = "pipelined x%d" % nch
 
         def bwd():
@@ -505,8 +483,6 @@ class Tacotron(Tacotron2):
             hand_over(sb, main)
             ops.copy3d(y1.grad, x1.grad, 1, rows, H, (0, H), (0, H), accumulate=1)
             for dd in (g2, g1):
-                self._status_words[(dd["tag"], "bwd")] = dd["work"]
-                self.last_paths["%s:bwd" % dd["tag"]] = "seq"
                 self._gru_hoisted_bwd(dd, dd["x"], H, dd["out"].buf, H, None, input_grads=dd is g1)
         self._tape.append(bwd)
         return y2
@@ -716,10 +692,8 @@ class Tacotron(Tacotron2):
             return None
         fn = lib.ns_taco1_decode_work_bytes
         fn.restype = C.c_size_t
-        # a work buffer of its own: a status word shared with another persistent kernel could be cleared under a raised one
-        work = buf("t1_decode_work", (int(fn(C.byref(q))) + 3) // 4, torch.float32)
-        L.check(lib.ns_taco1_decode(C.byref(q), C.c_void_p(ops.ptr(work)), C.c_void_p(ops.stream())), "ns_taco1_decode")
-        self._status_words[("decode", "fwd")] = work
+        self._persistent("decode", None, (int(fn(C.byref(q))) + 3) // 4, lambda work: L.check(
+            lib.ns_taco1_decode(C.byref(q), C.c_void_p(ops.ptr(work)), C.c_void_p(ops.stream())), "ns_taco1_decode"), "persistent")
         # the output projection over the whole y2 history (tacotron.py:76), off the loop's critical path
         dec = buf("pd_dec", N * S1 * M * r, torch.float32)
         ops.gemm(y2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=o("decoder/output_projection/kernel"),
@@ -765,10 +739,9 @@ class Tacotron(Tacotron2):
         if getattr(self, "use_decode_kernel", True):
             done = self._decode_persistent(N, Ti, Pi, Tia, S, enc, keys, spk_dec)
         if done is not None:
-            self.last_paths["decode"] = "persistent"
             dec, al, S1 = done
         else:
-            self.last_paths["decode"] = "step"
+            self._per_step("decode", None)
             XP, XA, HC, X1 = M + E, XI + A, A + E, 2 * D
             xp = buf("i_xp", N * S1 * XP, T_); p1 = buf("i_p1", N * 256, T_)
             xa = buf("i_xa", N * S1 * XA, T_); xc = buf("i_xc", N * max(XA, X1), T_)
@@ -935,15 +908,13 @@ class Tacotron(Tacotron2):
             if Dsp:      # the candidate kernel's operand rows [p2 | speaker projection | r * h]: the kernel fills the outer parts
                 ops.copy3d(self._spk_dec.buf, xc, N, S1, Dsp, (Dsp, 0), (S1 * XA, XA), dst_off=128)
             ops.gemm(enc.buf, W, pvb, N * Pi, 256, E, E, 256, 256, b_mode=1, b_off=w1 + M * 256)
-            cw = self._buf("attn_cluster_work", ops.taco1_attn_cluster_work_floats(**self._attn_args), torch.float32)
-            ops.taco1_attn_cluster("fwd", cw, **self._attn_args)
-            self._status_words[("attn", "fwd")] = cw
+            self._persistent("attn", "fwd", ops.taco1_attn_cluster_work_floats(**self._attn_args),
+                             lambda w: ops.taco1_attn_cluster("fwd", w, **self._attn_args), "cluster")
             # contexts of all steps: hc[n, :, A:] = align[n] . values[n] (slot 0: a zero alignment row)
             ops.gemm(al_t, enc.buf, hc, S1, E, Ti, Tia, E, HC, b_mode=1, b_off=self.padl * E, c_off=A, batch=N,
                      batch_strides=(S1 * Tia, Pi * E, S1 * HC))
-            self.last_paths["attn:fwd"] = "cluster"
         else:
-            self.last_paths["attn:fwd"] = "step"
+            self._per_step("attn", "fwd")
             for s in range(S):
                 sl, pv = s + 1, s
                 ops.gemm(hc, tsh["w1cT"], p1, N, 256, E, S1 * HC, E, S1 * 256, a_off=pv * HC + A, c_off=sl * 256, act=ACT_RELU,
@@ -1097,9 +1068,8 @@ class Tacotron(Tacotron2):
                 self._guided_attention(da0, self.scal, 4)
             args = dict(self._attn_args)
             args.update(dhc=dhc, da0=da0, df1=df1, dp2=dp2, dzg=dzg, dzc=dzc, dq=dq, de=de)
-            cw = buf("attn_cluster_work_b", ops.taco1_attn_cluster_work_floats(**args), torch.float32)
-            ops.taco1_attn_cluster("bwd", cw, **args)
-            self._status_words[("attn", "bwd")] = cw
+            self._persistent("attn", "bwd", ops.taco1_attn_cluster_work_floats(**args),
+                             lambda w: ops.taco1_attn_cluster("bwd", w, **args), "cluster")
             dctx32 = buf("att_dctx32", rows * E, torch.float32)
             ops.copy3d(dhc, dctx32, 1, rows, E, (0, HC), (0, E), src_off=A)
             ops.gemm(df1, W, dctx32, rows, E, 256, 256, 256, E, a_mode=0, b_mode=0, a_off=256, b_off=w1 + M * 256, accumulate=1)
@@ -1107,9 +1077,8 @@ class Tacotron(Tacotron2):
                 dctx_t = dctx32
             else:
                 ops.copy3d(dctx32, dctx_t, 1, rows, E, (0, E), (0, E))
-            self.last_paths["attn:bwd"] = "cluster"
         else:
-            self.last_paths["attn:bwd"] = "step"
+            self._per_step("attn", "bwd")
             for s in range(S - 1, -1, -1):
                 sl, pv = s + 1, s
                 last = s == S - 1

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._lib import ACT_NONE, ACT_RELU, ACT_SOFTSIGN, ACT_TANH
+from .._lib import ACT_NONE, ACT_RELU, ACT_SOFTSIGN, ACT_TANH, NS_ADAM_STATUS_MAX
 from ..utils.text.symbols import symbols
 from . import params as P_
 
@@ -924,13 +924,10 @@ class Tacotron2(object):
         Returns True where the wide kernel ran (only it writes the h planes of h_bf16 / h_lo_bf16)."""
         p = ops.lstm_seq_params(*a, **kw)
         if self.use_wide and ops.lstm_wide_supported(p, direction == "bwd"):
-            w = self._buf("lstm_wide_work_%s_%s" % (tag, direction), ops.lstm_wide_work_floats(p), torch.float32)
-            ops.lstm_wide(direction, p, w)
-            self._status_words[(tag, direction)] = w
-            self.last_paths["%s:%s" % (tag, direction)] = "wide"
+            self._persistent(tag, direction, ops.lstm_wide_work_floats(p), lambda w: ops.lstm_wide(direction, p, w), "wide")
             return True
         ops.lstm_seq_call(direction, p)
-        self.last_paths["%s:%s" % (tag, direction)] = "step"
+        self._per_step(tag, direction)
         return False
 
     def _h_planes(self, name, rows, D):
@@ -951,14 +948,34 @@ class Tacotron2(object):
         # kernel saves the gates as bf16
         ok = pair[0].dtype == NS_BF16 or getattr(self, "_bilstm_f32c", {}).get(tag, False)
         if self.use_cluster and ok and ops.lstm_cluster_supported(pair[0], pair[1], direction == "bwd"):
-            work = self._buf("lstm_cluster_work_%s_%s" % (tag, direction), ops.lstm_cluster_work_floats(pair[0]),
-                             torch.float32)
-            ops.lstm_cluster(direction, pair[0], pair[1], work)
-            self._status_words[(tag, direction)] = work
-            self.last_paths["%s:%s" % (tag, direction)] = "cluster"
+            self._persistent(tag, direction, ops.lstm_cluster_work_floats(pair[0]),
+                             lambda w: ops.lstm_cluster(direction, pair[0], pair[1], w), "cluster")
         else:
             ops.lstm_seq2(direction, pair[0], pair[1])
-            self.last_paths["%s:%s" % (tag, direction)] = "step"
+            self._per_step(tag, direction)
+
+    # One work area per consulted launch, registered in one place (DESIGN "LDS and work-area layouts").  Every launcher
+    # clears its work area, status word included, so a word that check_status() and ns_adam are to see must belong to
+    # an area that no later launch of the step is handed: the area's name IS the key the word is registered under.
+    def _persistent(self, tag, direction, floats, launch, path, slot=None):
+        """One persistent launch: launch(work) on a work area of `floats` floats that only the launch (tag, direction[,
+        slot]) ever gets, whose first int - the status word - check_status() and apply_gradients() then read.  slot: the
+        window of a recurrence that is cut in time; direction None: a launch that has no backward twin ("decode")."""
+        base = (tag,) if direction is None else (tag, direction)
+        key = base if slot is None else base + (slot,)
+        self._per_step(tag, direction, path, keep=len(key))
+        work = self._buf("work:" + ":".join(str(k) for k in key), floats, torch.float32)
+        launch(work)
+        self._status_words[key] = work
+        return work
+
+    def _per_step(self, tag, direction, path="step", keep=0):
+        """The launch-per-step counterpart: records the path and drops the status words an earlier shape left under this
+        name (keep: the key length of the persistent form that is about to register)."""
+        base = (tag,) if direction is None else (tag, direction)
+        for k in [k for k in self._status_words if k[:len(base)] == base and len(k) != keep]:
+            del self._status_words[k]
+        self.last_paths[":".join(base)] = path
 
     def check_status(self):
         """Raise if a persistent kernel reported an exchange timeout (host sync)."""
@@ -1278,12 +1295,11 @@ class Tacotron2(object):
             w1c=(self._W(self.T), self._o("decoder/decoder_prenet/dense_1/kernel") + M * 256))
         self._attn_cluster_fwd = self.use_attn_cluster and ops.taco2_attn_cluster_supported(**self._attn_args)
         if self._attn_cluster_fwd:
-            cw = self._buf("attn_cluster_work", ops.taco2_attn_cluster_work_floats(**self._attn_args), torch.float32)
-            ops.taco2_attn_cluster("fwd", cw, **self._attn_args)
-            self._status_words[("attn", "fwd")] = cw
+            self._persistent("attn", "fwd", ops.taco2_attn_cluster_work_floats(**args),
+                             lambda w: ops.taco2_attn_cluster("fwd", w, **args), "cluster")
         else:
-            ops.taco2_attn("fwd", **self._attn_args)
-        self.last_paths["attn:fwd"] = "cluster" if self._attn_cluster_fwd else "step"
+            ops.taco2_attn("fwd", **args)
+            self._per_step("attn", "fwd")
         self._tick("attn_rnn")
 
         # ---- decoder LSTMs with hoisted inputs, then the projection (tacotron2.py:67-73)
@@ -1527,12 +1543,11 @@ class Tacotron2(object):
         # that MI355X misreads beside MFMA waves of another kernel (profiles/r04_determinism.txt item 4); the form is gone
         # from every kernel (tests/test_isa_guard_cpu.py) and so is the wait.
         if self._attn_cluster_fwd:
-            cw = self._buf("attn_cluster_work_b", ops.taco2_attn_cluster_work_floats(**args), torch.float32)
-            ops.taco2_attn_cluster("bwd", cw, **args)
-            self._status_words[("attn", "bwd")] = cw
+            self._persistent("attn", "bwd", ops.taco2_attn_cluster_work_floats(**args),
+                             lambda w: ops.taco2_attn_cluster("bwd", w, **args), "cluster")
         else:
             ops.taco2_attn("bwd", **args)
-        self.last_paths["attn:bwd"] = "cluster" if self._attn_cluster_fwd else "step"
+            self._per_step("attn", "bwd")
         self._tick("attn_rnn_bwd")
         # hoisted weight gradients of the attention RNN
         p1, xa, fr = B["dec_p1"], B["dec_xa"], B["dec_fr"]
@@ -1613,8 +1628,9 @@ class Tacotron2(object):
         # a persistent recurrence that timed out leaves an invalid gradient: the kernel then updates nothing and raises
         # scal[9]; read_losses() reports it.  No host round trip in front of the optimiser.
         status = list(self._status_words.values())
-        if len(status) > 12:
-            raise RuntimeError("more persistent recurrences (%d) than ns_adam_params.status holds (12)" % len(status))
+        if len(status) > NS_ADAM_STATUS_MAX:
+            raise RuntimeError("more persistent recurrences (%d) than ns_adam_params.status holds (%d)"
+                               % (len(status), NS_ADAM_STATUS_MAX))
         if self.reducer is not None and getattr(self.reducer, "active", False) and status:
             # data parallel: the skip must be COLLECTIVE - a rank whose recurrence timed out has already put
             # its invalid gradient into the sum, so every rank has to drop the update, not just that one.  The largest

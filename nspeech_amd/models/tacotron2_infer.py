@@ -68,9 +68,8 @@ def _decode_persistent(m, args):
         return None
     fn = lib.ns_taco2_decode_work_bytes
     fn.restype = C.c_size_t
-    work = buf("decode_work", (int(fn(C.byref(q))) + 3) // 4, torch.float32)
-    L.check(lib.ns_taco2_decode(C.byref(q), C.c_void_p(ops.ptr(work)), C.c_void_p(ops.stream())), "ns_taco2_decode")
-    m._status_words[("decode", "fwd")] = work
+    m._persistent("decode", None, (int(fn(C.byref(q))) + 3) // 4, lambda work: L.check(
+        lib.ns_taco2_decode(C.byref(q), C.c_void_p(ops.ptr(work)), C.c_void_p(ops.stream())), "ns_taco2_decode"), "persistent")
     # the output projection over the whole history (tacotron2.py:73), off the loop's critical path
     dec = buf("dec_out", N * S1 * M * r, torch.float32)
     ops.gemm(h2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=o("decoder/output_projection/kernel"), bias=fp,
@@ -305,13 +304,12 @@ def _infer_body(m):
     one_launch = getattr(m, "use_decode_kernel", True) and m.zoneout_rate <= 0.0
     done = _decode_persistent(m, m.attn_block(enc, keys, False)) if one_launch else None
     if done is not None:
-        m.last_paths["decode"] = "persistent"
         dec, al, S1 = done
     elif _rows32_ok(m, N):
-        m.last_paths["decode"] = "rows32"
+        m._per_step("decode", None, "rows32")
         dec, al = _decode_rows32(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
     else:
-        m.last_paths["decode"] = "step"
+        m._per_step("decode", None)
         dec, al = _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
 
     # ---- postnet, residual, expand, linear head (inference BatchNorm), output views

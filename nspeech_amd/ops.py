@@ -399,7 +399,7 @@ def adam(pw, g, m, v, n, gnorm_sq, clip, grad_scale, lr_t, beta1, beta2, eps, sh
     p = L.struct("ns_adam_params")
     _fill(p, p=ptr(pw), g=ptr(g), m=ptr(m), v=ptr(v), n=n, gnorm_sq=ptr(gnorm_sq), clip=clip,
           grad_scale=grad_scale, lr_t=lr_t, beta1=beta1, beta2=beta2, eps=eps, shadow_bf16=ptr(shadow), skipped=ptr(skipped))
-    assert len(status) <= 12
+    assert len(status) <= L.NS_ADAM_STATUS_MAX
     for i, w in enumerate(status):
         p.status[i] = ptr(w)
     L.call("ns_adam", p, stream())

@@ -40,8 +40,8 @@ def main():
         m.backward()
     torch.cuda.synchronize()
     m.check_status()
-    report("forward", m._bufs["attn_cluster_work"], FWD, 200)
-    report("backward", m._bufs["attn_cluster_work_b"], BWD, 200)
+    report("forward", m._status_words[("attn", "fwd")], FWD, 200)
+    report("backward", m._status_words[("attn", "bwd")], BWD, 200)
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@ for _ in range(2):
     m.initialize(inputs, lengths, None, mel, lin)
     m.backward()
 torch.cuda.synchronize()
-w = m._bufs["lstm_cluster_work_%s_bwd" % os.environ.get("NS_TRACE_TAG", "expl")]
+w = m._status_words[(os.environ.get("NS_TRACE_TAG", "expl"), "bwd")]
 N, H = 32, (hp.expand_lstm_units if os.environ.get("NS_TRACE_TAG", "expl") == "expl" else hp.encoder_lstm_units)
 chains = 2 * ((N + 15) // 16 + 1)
 off = 256 + 4096 + chains * 2 * 16 * (4 * H // 2) * 8

@@ -24,7 +24,7 @@ def main():
     for _ in range(2):
         m.initialize(inputs, lengths, None, mel, lin)
     torch.cuda.synchronize()
-    w = m._bufs["lstm_cluster_work_expl_fwd"]
+    w = m._status_words[("expl", "fwd")]
     N, H = 32, hp.expand_lstm_units
     chains = 2 * ((N + 15) // 16 + 1)
     off = 256 + 4096 + chains * 2 * 16 * (4 * H // 2) * 8

@@ -113,8 +113,8 @@ def model_pass(kind):
                 for k, v in sums.items():           # (a key that occurs several times per pass: the sum per pass)
                     table.setdefault(k, {}).setdefault(name, []).append(sum(v) / 3)
                 if kind == "taco2" and os.environ.get("NS_ATTN_TRACE"):
-                    fs, fw = attn_stamps(m._bufs["attn_cluster_work"], 200, (3, 8))
-                    bs, bw = attn_stamps(m._bufs["attn_cluster_work_b"], 200, (4, 7))
+                    fs, fw = attn_stamps(m._status_words[("attn", "fwd")], 200, (3, 8))
+                    bs, bw = attn_stamps(m._status_words[("attn", "bwd")], 200, (4, 7))
                     print("round %d %-6s attention stamps, us per step: forward %.3f (X2 wait %.3f, X3 wait %.3f) | backward %.3f "
                           "(E2 wait %.3f, E3 wait %.3f)" % (rnd, name, fs, fw[0], fw[1], bs, bw[0], bw[1]), flush=True)
     finally:

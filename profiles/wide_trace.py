@@ -55,9 +55,9 @@ def main():
         m.backward()
     torch.cuda.synchronize()
     m.check_status()
-    for k in sorted(m._bufs):
-        if k.startswith("lstm_wide_work_"):
-            (report_ps if k.endswith("_bwd") else report)(k[len("lstm_wide_work_"):], m._bufs[k], 200)
+    for key in sorted(m._status_words):
+        if m.last_paths.get(":".join(key)) == "wide":
+            (report_ps if key[1] == "bwd" else report)("_".join(key), m._status_words[key], 200)
 
 
 if __name__ == "__main__":

@@ -1120,6 +1120,8 @@ def adam_cases():
     one("second-trip", 4096 * 256 + 3, norm=37.7, grad_scale=0.5, status_n=12, seed=83)
     for slot in (0, 5, 11):
         one("n257-raised-%d" % slot, 257, norm=37.7, status_n=12, raised=slot, seed=84)
+    for slot in (12, 31):          # the first slot past the twelve of version 107 and the last of NS_ADAM_STATUS_MAX = 32
+        one("n257-raised-%d" % slot, 257, norm=37.7, status_n=32, raised=slot, seed=84)
     return out
 
 
