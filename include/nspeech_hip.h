@@ -754,6 +754,22 @@ typedef struct {
 } ns_highway_params;
 int ns_highway(const ns_highway_params* p, ns_stream_t stream);
 
+/* ------------------------------------------------------------------ dropout on rows
+ * y[n, t, u] = x[n, t, u] * keep(seed, t0 + t, n0 + n, u) * scale  for n < N, t < T, u < U, element (n, t, u) at
+ * n * sn + t * st + u of x and of y ((dtype), element strides; y may be x).  keep = 0 iff
+ * ns_zone_keep(seed, t0 + t, n0 + n, u, thr) (csrc/common.h), else 1: the masks of the persistent attention kernels
+ * (ns_taco2_attn_params.drop_*), for the forms that build the prenet out of single launches.  Forward and backward are
+ * this same operation (on the activations and on their gradients).  Elements outside the U columns are not touched. */
+typedef struct {
+  int dtype;
+  int N, T, U;
+  int64_t sn, st;
+  const void* x; void* y;
+  uint32_t thr, seed; float scale;
+  int t0, n0;
+} ns_dropout_rows_params;
+int ns_dropout_rows(const ns_dropout_rows_params* p, ns_stream_t stream);
+
 /* ------------------------------------------------------------------ Tacotron-2 attention RNN
  * The part of the decoder loop that is recurrent through the attention state
  * (tacotron2.py:63-83 with AttentionWrapper(PrenetWrapper(LSTMBlockCell(256)),
@@ -812,6 +828,15 @@ typedef struct {
    * see ns_attention_post_bwd_params.part); NULL = float atomics */
   float* post_part;
   float cell_clip;                 /* the attention LSTM's (and, in ns_taco2_decode, the decoder LSTMs') cell_clip, as in ns_lstm_seq_params */
+  /* Prenet dropout (modules.py:21-27 with training=True; inverted dropout).  drop_thr != 0:
+   *   p1 = relu(..) * keep1 * drop_scale,  p2 = relu(..) * keep2 * drop_scale,  drop_scale = 1 / (1 - rate),
+   * where unit u of batch row n at decoder step s (0-based; its values live in slot s+1) is DROPPED (keep = 0) iff
+   * ns_zone_keep(drop_seed1 | drop_seed2, s, n, u, drop_thr) is true (csrc/common.h; the generator of
+   * ns_lstm_seq_params' zoneout masks, one stream per layer).  The histories p1 / xa[:, :, :D2] hold the dropped, scaled
+   * values, so the backward pass finds the mask in their sign and only multiplies dp2 / df1 by drop_scale.
+   * drop_thr = 0 (a zero-initialised block): off, whatever the other three fields hold.  Training only: the decode
+   * entries refuse a block with drop_thr != 0. */
+  uint32_t drop_thr, drop_seed1, drop_seed2; float drop_scale;
 } ns_taco2_attn_params;
 int ns_taco2_attn_fwd(const ns_taco2_attn_params* p, ns_stream_t stream);
 int ns_taco2_attn_bwd(const ns_taco2_attn_params* p, ns_stream_t stream);
@@ -870,6 +895,10 @@ typedef struct {
    * rows are D2+Dsp+A wide with the per-utterance projection written into columns D2..D2+Dsp of every xa slot by the caller,
    * wg / wc hold all D2+Dsp+A rows, and the caller forms the projection's gradient from dzg / dzc after the backward call. */
   int Dsp;
+  /* Prenet dropout on p1 / p2, exactly as in ns_taco2_attn_params (same generator, index convention and backward rule);
+   * drop_thr = 0: off.  ns_taco1_decode refuses a block with drop_thr != 0.  These entries issue one launch for all N rows
+   * (N * 8 <= the device's CUs), so n is the row of the batch as it stands. */
+  uint32_t drop_thr, drop_seed1, drop_seed2; float drop_scale;
 } ns_taco1_attn_params;
 int ns_taco1_attn_cluster_supported(const ns_taco1_attn_params* p);
 size_t ns_taco1_attn_cluster_work_bytes(const ns_taco1_attn_params* p);

@@ -719,6 +719,16 @@ static int check_attn(const ns_taco2_attn_params* p, const char* who) {
   return NS_OK;
 }
 
+// Prenet dropout of the step-launch forms (ns_taco2_attn_params.drop_*): the rows [nb, nb + nn) of one slot, in place,
+// from the masks the persistent kernels draw (ns_dropout_rows).  layer 1: U = D1 columns of p1 / df1, 2: D2 of xa / dp2.
+static int attn_drop_rows(const ns_taco2_attn_params& p, int layer, void* rows, long sn, int U, int st, int nb, int nn, hipStream_t s) {
+  if (!p.drop_thr) return NS_OK;
+  ns_dropout_rows_params d = {};
+  d.dtype = p.dtype; d.N = nn; d.T = 1; d.U = U; d.sn = sn; d.st = 0; d.x = rows; d.y = rows;
+  d.thr = p.drop_thr; d.seed = layer == 1 ? p.drop_seed1 : p.drop_seed2; d.scale = p.drop_scale; d.t0 = st; d.n0 = nb;
+  return ns_dropout_rows(&d, s);
+}
+
 // projected-memory form, step 0: p1[slot 1] = relu(f1[slot 1]) (the context before the first step is zero)
 template <typename T>
 __global__ void attn_p1_init_kernel(const float* f1, T* p1, int N, long S1, int D1) {
@@ -772,9 +782,14 @@ static int attn_fwd_t(const ns_taco2_attn_params& p, hipStream_t s) {
                         S1 * D1, dt, nullptr, NS_ACT_RELU, p.f1 + (nb * S1 + slot) * D1, S1 * D1, nullptr, 0, s);
         if (rc) return rc;
       }
+      // (either form has written this step's p1 by now: the dropout of layer 1 goes over the stored row)
+      rc = attn_drop_rows(p, 1, p1 + (nb * S1 + slot) * D1, S1 * D1, (int)D1, st, nb, nn, s);
+      if (rc) return rc;
       // p2 = relu(p1 . W2 + b2) -> xa[:, 0:D2]
       rc = gemm_small(dt, nn, D2, D1, p1 + (nb * S1 + slot) * D1, S1 * D1, p.w2T, D1, xa + (nb * S1 + slot) * XA,
                       S1 * XA, dt, p.b2, NS_ACT_RELU, nullptr, 0, nullptr, 0, s);
+      if (rc) return rc;
+      rc = attn_drop_rows(p, 2, xa + (nb * S1 + slot) * XA, S1 * XA, (int)D2, st, nb, nn, s);
       if (rc) return rc;
     }
     // attention LSTM on [p2 | h_prev]
@@ -1017,10 +1032,14 @@ static int attn_bwd_t(const ns_taco2_attn_params& p, hipStream_t s) {
       rc = gemm_small(dt, nn, (int)D2, (int)(4 * A), dga, S1 * 4 * A, p.watt, 4 * A, (T*)p.dp2 + (nb * S1 + slot) * D2,
                       S1 * D2, dt, nullptr, NS_ACT_NONE, nullptr, 0, xa + (nb * S1 + slot) * XA, S1 * XA, s);
       if (rc) return rc;
+      rc = attn_drop_rows(p, 2, (T*)p.dp2 + (nb * S1 + slot) * D2, S1 * D2, (int)D2, st, nb, nn, s);
+      if (rc) return rc;
       // dp1pre = (dp2pre . W2^T) * (p1 > 0)
       rc = gemm_small(dt, nn, (int)D1, (int)D2, (T*)p.dp2 + (nb * S1 + slot) * D2, S1 * D2, p.w2, D2,
                       (T*)p.df1 + (nb * S1 + slot) * D1, S1 * D1, dt, nullptr, NS_ACT_NONE, nullptr, 0,
                       p1 + (nb * S1 + slot) * D1, S1 * D1, s);
+      if (rc) return rc;
+      rc = attn_drop_rows(p, 1, (T*)p.df1 + (nb * S1 + slot) * D1, S1 * D1, (int)D1, st, nb, nn, s);
       if (rc) return rc;
       // dctx_carry = dp1pre . W1c^T   (projected-memory form: folded into the next da kernel and the hoisted product)
       if (st > 0 && !pvm) {

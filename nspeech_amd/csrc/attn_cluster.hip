@@ -66,6 +66,7 @@ struct ACArgs {
   // free-running decode (taco2_decode_kernel): the next step's frame term f1 arrives as granules from the decoder-LSTM
   // workgroups ([N][D1], tag = consuming step + 1) and the alignment goes out to them ([N][Tia], tag = step + 1)
   u64* f1x; u64* alx;
+  int n0;                    // the launch's first utterance as a row of the call's batch: the dropout masks count batch rows
 };
 constexpr size_t TRACE_BYTES = 256 * 16 * sizeof(long long);
 // (grid index 0 is cluster 0, member 0 under either placement, and the first attention workgroup of the decode kernel)
@@ -98,7 +99,11 @@ struct FwdLds {                            // dynamic LDS of attn_fwd_body<*, C,
   int cst_s = c.take<float>((KWMAX + 1) * (C::A + KPAD));     // [KWMAX + 1][A + KPAD]  folded location filter, attention_v
   int bytes = c.off;
 };
-template <typename T, typename C, bool INFER>
+// DROP = prenet dropout (ns_taco2_attn_params.drop_thr != 0): an instantiation of its own, so that the kernel that runs with
+// the option off is, instruction for instruction, the one without the option (a run-time branch on drop_thr in the one
+// kernel cost 0.4 us per step with the option OFF: the compiler scheduled the step differently around it -
+// profiles/prenet_dropout.txt, section 2).  The masks are wave-uniform in nothing but their seeds: every lane hashes its own unit.
+template <typename T, typename C, bool INFER, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const int bid) {
   constexpr int A = C::A, D1 = C::D1, D2 = C::D2, UPW = C::UPW, GC = C::GC, K = C::K;
   constexpr int GG = C::GG, GK = C::GK, P2G = C::P2G, P2K = C::P2K, QG = C::QG, QK = C::QK, CXG = C::CXG;
@@ -185,10 +190,14 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
     for (int i = tid; i < TSMAX * D1; i += CT) pv_s[i] = (i / D1) < tn ? ldf(pvn + i) : 0.f;
     for (int i = tid; i < 256 + 2 * APAD; i += CT) al[i] = 0.f;
     for (int i = tid; i < K; i += CT) xs[i] = 0.f;
-    if (tid < D1) p1s[tid] = fmaxf(p.f1[((long)n * S1 + 1) * D1 + tid], 0.f);     // context before the first step is 0
+    if (tid < D1) {                                                                // context before the first step is 0
+      float v = fmaxf(p.f1[((long)n * S1 + 1) * D1 + tid], 0.f);
+      if constexpr (DROP) v = ns_prenet_drop(v, p.drop_seed1, 0, a.n0 + n, tid, p.drop_thr, p.drop_scale);
+      p1s[tid] = v;
+      // slot 1 of p1 (history): the share of this workgroup
+      if (tid / (D1 / CG) == g) stf((T*)p.p1 + ((long)n * S1 + 1) * D1 + tid, v);
+    }
   }
-  // slot 1 of p1 (history): the share of this workgroup
-  if (tid < D1 && tid / (D1 / CG) == g) stf((T*)p.p1 + ((long)n * S1 + 1) * D1 + tid, fmaxf(p.f1[((long)n * S1 + 1) * D1 + tid], 0.f));
   __syncthreads();
 
   for (int st = 0; st < p.S; ++st) {
@@ -214,6 +223,7 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
 #pragma unroll
       for (int q = 0; q < P2G; ++q) s += red[q * D2 + tid];
       s = fmaxf(s, 0.f);
+      if constexpr (DROP) s = ns_prenet_drop(s, p.drop_seed2, st, a.n0 + n, tid, p.drop_thr, p.drop_scale);
       xs[tid] = s;
       if (tid / (D2 / CG) == g) stf((T*)p.xa + ((long)n * S1 + slot) * XA + tid, s);
     }
@@ -414,7 +424,8 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < CG; ++q) s = fmaf(scl[q], gath[q * X3N + tid], s);
-      const float v = fmaxf(fmaf(s, inv, f1n), 0.f);
+      float v = fmaxf(fmaf(s, inv, f1n), 0.f);
+      if constexpr (DROP) if (st + 1 < p.S) v = ns_prenet_drop(v, p.drop_seed1, st + 1, a.n0 + n, tid, p.drop_thr, p.drop_scale);
       p1s[tid] = v;
       if (st + 1 < p.S && tid / (D1 / CG) == g) stf((T*)p.p1 + ((long)n * S1 + slot + 1) * D1 + tid, v);
     }
@@ -423,12 +434,12 @@ __device__ __forceinline__ void attn_fwd_body(const ACArgs& a, float* sm, const 
   }
 }
 
-template <typename T, typename C>
+template <typename T, typename C, bool DROP>
 __global__ __launch_bounds__(CT) void attn_cluster_fwd_kernel(ACArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm_attn_fwd[];
   const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, a.p.N, CG, a.xcd != 0);
   if (!slot.active) return;                                 // padding of a placed grid (exchange.h)
-  attn_fwd_body<T, C, false>(a, sm_attn_fwd, slot.cluster * CG + slot.member);
+  attn_fwd_body<T, C, false, DROP>(a, sm_attn_fwd, slot.cluster * CG + slot.member);
 }
 
 // ===================================================================================== backward
@@ -499,7 +510,7 @@ struct BwdLds {                            // dynamic LDS of attn_cluster_bwd_ke
   int gts1 = c.take<float>(C::GC);
   int bytes = c.off;
 };
-template <typename T, typename C>
+template <typename T, typename C, bool DROP>          // DROP: as attn_fwd_body
 __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
   constexpr int A = C::A, D1 = C::D1, D2 = C::D2, UPW = C::UPW, GC = C::GC, K = C::K;
   constexpr int NQ = C::NQ, CPQ = C::CPQ, PPT = C::PPT, W2H = C::W2H, W2K = C::W2K, CCN = C::CCN, E3N = C::E3N, UL = C::UL;
@@ -578,6 +589,8 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
     if (tid < 48) sc[tid] = 0.f;
   }
   float dcc = 0.f;                         // cell-state gradient carried to the step before (owner lanes)
+  // prenet dropout: d (relu(z) keep scale) / dz, the keep part read from the history (a dropped unit's saved output is 0)
+  auto dsc = [&](float s) { if constexpr (DROP) return s * p.drop_scale; else return s; };
   // history of a step, one value per thread and role (read straight from the forward pass' buffers)
   float h_q = 0.f, h_p1 = 0.f, h_p2 = 0.f, h_alp = 0.f, h_a = 0.f, h_da0 = 0.f, h_gt = 0.f;
   float h_dhc = 0.f, h_c = 0.f, h_cp = 0.f;
@@ -849,7 +862,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < CG; ++q) s += gath[q * E3N + tid];
-      s = p2m[tid] > 0.f ? s : 0.f;
+      s = p2m[tid] > 0.f ? dsc(s) : 0.f;
       dp2s[tid] = s;
       if (tid / (D2 / CG) == g) stf((T*)p.dp2 + rowS * D2 + tid, s);
     } else if (tid < D2 + UPW) {
@@ -880,7 +893,7 @@ __global__ __launch_bounds__(CT) void attn_cluster_bwd_kernel(ACArgs a) {
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < W2H; ++q) s += red[q * D1 + tid];
-      s = p1m[tid] > 0.f ? s : 0.f;
+      s = p1m[tid] > 0.f ? dsc(s) : 0.f;
       dvec[tid] = s;
       if (tid / (D1 / CG) == g) stf((T*)p.df1 + rowS * D1 + tid, s);
     }
@@ -1204,9 +1217,9 @@ extern "C" size_t ns_taco2_attn_cluster_work_bytes(const ns_taco2_attn_params* p
   return AbiWork{(size_t)p->N}.bytes;
 }
 
-template <typename T, typename C>
+template <typename T, typename C, bool DROP>
 static int launch_fwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) {
-  ACArgs a;
+  ACArgs a = {};
   a.p = *p;
   const FwdWork<C> wl{(size_t)p->N};
   a.status = carve_at<int>(work, wl.status);
@@ -1219,7 +1232,7 @@ static int launch_fwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
   constexpr size_t lds = FwdLds<C>().bytes;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_cluster_fwd_kernel<T, C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)attn_cluster_fwd_kernel<T, C, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   // chunks of at most 32 utterances: one workgroup per CU, every cluster of a launch resident at once
@@ -1244,7 +1257,8 @@ static int launch_fwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
     b.p.align_t = p->align_t ? (char*)p->align_t + (long)n0 * S1 * p->Tia * esz : nullptr;
     b.x2 = a.x2 + (size_t)n0 * CG * C::X2N;
     b.x3 = a.x3 + (size_t)n0 * CG * C::X3N;
-    hipLaunchKernelGGL((attn_cluster_fwd_kernel<T, C>), dim3(ns_cluster_grid(nn, CG, b.xcd != 0)), dim3(CT), lds, s, b);
+    b.n0 = n0;
+    hipLaunchKernelGGL((attn_cluster_fwd_kernel<T, C, DROP>), dim3(ns_cluster_grid(nn, CG, b.xcd != 0)), dim3(CT), lds, s, b);
   }
   NS_CHECK_LAUNCH("attn_cluster_fwd");
   // the transposed keys the per-step forward leaves behind for either backward path (hoisted sums over the steps)
@@ -1266,17 +1280,17 @@ extern "C" int ns_taco2_attn_cluster_fwd(const ns_taco2_attn_params* p, void* wo
   NS_CHECK_ARG(p->keys && p->f1 && p->w2 && p->watt && p->wq && p->b2 && p->batt && p->wcl && p->v && p->p1 && p->xa &&
                    p->hc && p->ca && p->ga && p->q && p->align && p->align_t && p->values, "ns_taco2_attn_cluster_fwd: null pointer");
   if (p->dtype == NS_BF16) {
-    if (p->A == 256) return launch_fwd<bf16_t, Cfg<256, 256, 128>>(p, work, s);
-    return launch_fwd<bf16_t, Cfg<64, 256, 128>>(p, work, s);
+    if (p->A == 256) return p->drop_thr ? launch_fwd<bf16_t, Cfg<256, 256, 128>, true>(p, work, s) : launch_fwd<bf16_t, Cfg<256, 256, 128>, false>(p, work, s);
+    return p->drop_thr ? launch_fwd<bf16_t, Cfg<64, 256, 128>, true>(p, work, s) : launch_fwd<bf16_t, Cfg<64, 256, 128>, false>(p, work, s);
   }
-  if (p->A == 256) return launch_fwd<float, Cfg<256, 256, 128>>(p, work, s);
-  return launch_fwd<float, Cfg<64, 256, 128>>(p, work, s);
+  if (p->A == 256) return p->drop_thr ? launch_fwd<float, Cfg<256, 256, 128>, true>(p, work, s) : launch_fwd<float, Cfg<256, 256, 128>, false>(p, work, s);
+  return p->drop_thr ? launch_fwd<float, Cfg<64, 256, 128>, true>(p, work, s) : launch_fwd<float, Cfg<64, 256, 128>, false>(p, work, s);
 }
 
 
-template <typename T, typename C>
+template <typename T, typename C, bool DROP>
 static int launch_bwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) {
-  ACArgs a;
+  ACArgs a = {};
   a.p = *p;
   const BwdWork<C> wl{(size_t)p->N};
   a.status = carve_at<int>(work, wl.status);
@@ -1289,7 +1303,7 @@ static int launch_bwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
   constexpr size_t lds = BwdLds<C>().bytes;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_cluster_bwd_kernel<T, C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)attn_cluster_bwd_kernel<T, C, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   const long S1 = p->S + 1, esz = sizeof(T);
@@ -1316,7 +1330,7 @@ static int launch_bwd(const ns_taco2_attn_params* p, void* work, hipStream_t s) 
     b.x2 = a.x2 + (size_t)n0 * CG * C::A;
     b.x3 = a.x3 + (size_t)n0 * CG * C::E3N;
     b.x1 = a.x1 + (size_t)n0 * CG;
-    hipLaunchKernelGGL((attn_cluster_bwd_kernel<T, C>), dim3(ns_cluster_grid(b.p.N, CG, b.xcd != 0)), dim3(CT), lds, s, b);
+    hipLaunchKernelGGL((attn_cluster_bwd_kernel<T, C, DROP>), dim3(ns_cluster_grid(b.p.N, CG, b.xcd != 0)), dim3(CT), lds, s, b);
   }
   NS_CHECK_LAUNCH("attn_cluster_bwd");
   return ns_attn_bwd_post<T>(*p, s);       // keys_t: written by either forward
@@ -1331,11 +1345,11 @@ extern "C" int ns_taco2_attn_cluster_bwd(const ns_taco2_attn_params* p, void* wo
                    p->dv && p->dwcl && p->work && p->align_t && p->de && p->dctx_t && p->keys_t && p->da0,
                "ns_taco2_attn_cluster_bwd: null pointer");
   if (p->dtype == NS_BF16) {
-    if (p->A == 256) return launch_bwd<bf16_t, BCfg<256, 256, 128>>(p, work, s);
-    return launch_bwd<bf16_t, BCfg<64, 256, 128>>(p, work, s);
+    if (p->A == 256) return p->drop_thr ? launch_bwd<bf16_t, BCfg<256, 256, 128>, true>(p, work, s) : launch_bwd<bf16_t, BCfg<256, 256, 128>, false>(p, work, s);
+    return p->drop_thr ? launch_bwd<bf16_t, BCfg<64, 256, 128>, true>(p, work, s) : launch_bwd<bf16_t, BCfg<64, 256, 128>, false>(p, work, s);
   }
-  if (p->A == 256) return launch_bwd<float, BCfg<256, 256, 128>>(p, work, s);
-  return launch_bwd<float, BCfg<64, 256, 128>>(p, work, s);
+  if (p->A == 256) return p->drop_thr ? launch_bwd<float, BCfg<256, 256, 128>, true>(p, work, s) : launch_bwd<float, BCfg<256, 256, 128>, false>(p, work, s);
+  return p->drop_thr ? launch_bwd<float, BCfg<64, 256, 128>, true>(p, work, s) : launch_bwd<float, BCfg<64, 256, 128>, false>(p, work, s);
 }
 
 // ------------------------------------------------------------------ free-running decode, C ABI
@@ -1361,7 +1375,7 @@ extern "C" size_t ns_taco2_decode_work_bytes(const ns_taco2_decode_params* q) {
 template <typename T, typename C, int E, int D>
 static int launch_decode(const ns_taco2_decode_params* q, void* work, hipStream_t s) {
   const ns_taco2_attn_params* p = &q->att;
-  DecArgs d;
+  DecArgs d = {};
   d.att.p = *p;
   const DecWork<C, D> wl{(size_t)p->N};
   d.att.status = carve_at<int>(work, wl.att.status);
@@ -1407,6 +1421,7 @@ extern "C" int ns_taco2_decode(const ns_taco2_decode_params* q, void* work, ns_s
   NS_CHECK_ARG(decode_shape_ok(q), "ns_taco2_decode: unsupported shape (needs the attention-cluster shapes, N <= 2, and "
                "(A, E, D) = (256, 512, 1024) or (64, 64, 64))");
   const ns_taco2_attn_params* p = &q->att;
+  NS_CHECK_ARG(p->drop_thr == 0, "ns_taco2_decode: prenet dropout (att.drop_thr != 0) is a training option");
   NS_CHECK_ARG(p->keys && p->f1 && p->w2 && p->watt && p->wq && p->b2 && p->batt && p->wcl && p->v && p->p1 && p->xa &&
                    p->hc && p->ca && p->ga && p->q && p->align && p->values && q->w_l1 && q->b_l1 && q->w_l2 && q->b_l2 &&
                    q->wpf && q->bpf && q->h2, "ns_taco2_decode: null pointer");

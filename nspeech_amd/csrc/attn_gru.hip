@@ -69,6 +69,8 @@ struct TArgs {
   // ([N][nwd][D1] granules, plus bpf), the alignment goes out as [N][Tia] granules
   u64* f1x; u64* alx; const float* bpf; int nwd;
 };
+// Prenet dropout (ns_taco1_attn_params.drop_*, ns_prenet_drop): taco1_run issues ONE launch for the whole batch (it needs
+// N * 8 <= CUs and never groups the utterances), so the cluster index n of the kernels below IS the row of the batch.
 
 // The partial sums of one frame-term column from the nw decoder workgroups (stride D1), polled by its owner thread and
 // added in a fixed order.  Returns false on time-out / raised status.
@@ -103,7 +105,8 @@ struct FwdLds {                            // dynamic LDS of attn_fwd_body (the 
   int wq_s = c.take<float>(UPW * A);       // [UPW][A]  W_query rows of the own units
   int bytes = c.off;
 };
-template <typename T, bool INFER>
+// DROP = prenet dropout (drop_thr != 0), an instantiation of its own: see attn_cluster.hip, attn_fwd_body
+template <typename T, bool INFER, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const int bid) {
   const ns_taco1_attn_params& p = a.p;
   constexpr FwdLds lay;
@@ -185,9 +188,13 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
     for (int i = tid; i < TSMAX * D1; i += CT) pv_s[i] = (i / D1) < tn ? ldf(pvn + i) : 0.f;
     for (int i = tid; i < K; i += CT) xs[i] = 0.f;
     if (tid < UPW) hloc[tid] = 0.f;
-    if (tid < D1) p1s[tid] = fmaxf(p.f1[((long)n * S1 + 1) * D1 + tid], 0.f);     // the context before the first step is 0
+    if (tid < D1) {                                                                // the context before the first step is 0
+      float v = fmaxf(p.f1[((long)n * S1 + 1) * D1 + tid], 0.f);
+      if constexpr (DROP) v = ns_prenet_drop(v, p.drop_seed1, 0, n, tid, p.drop_thr, p.drop_scale);
+      p1s[tid] = v;
+      if (tid / (D1 / CG) == g) stf((T*)p.p1 + ((long)n * S1 + 1) * D1 + tid, v);
+    }
   }
-  if (tid < D1 && tid / (D1 / CG) == g) stf((T*)p.p1 + ((long)n * S1 + 1) * D1 + tid, fmaxf(p.f1[((long)n * S1 + 1) * D1 + tid], 0.f));
   __syncthreads();
 
   for (int st = 0; st < p.S; ++st) {
@@ -208,6 +215,7 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
 #pragma unroll
       for (int q = 0; q < P2G; ++q) s += red[q * D2 + tid];
       s = fmaxf(s, 0.f);
+      if constexpr (DROP) s = ns_prenet_drop(s, p.drop_seed2, st, n, tid, p.drop_thr, p.drop_scale);
       xs[tid] = s;
       if (tid / (D2 / CG) == g) {
         stf((T*)p.xa + rowS * XA + tid, s);
@@ -372,7 +380,8 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < CG; ++q) s = fmaf(scl[q], gath[q * X3N + tid], s);
-      const float v = fmaxf(fmaf(s, inv, f1n), 0.f);
+      float v = fmaxf(fmaf(s, inv, f1n), 0.f);
+      if constexpr (DROP) if (st + 1 < p.S) v = ns_prenet_drop(v, p.drop_seed1, st + 1, n, tid, p.drop_thr, p.drop_scale);
       p1s[tid] = v;
       if (st + 1 < p.S && tid / (D1 / CG) == g) stf((T*)p.p1 + (rowS + 1) * D1 + tid, v);
     }
@@ -381,12 +390,12 @@ __device__ __forceinline__ void attn_fwd_body(const TArgs& a, float* sm, const i
   }
 }
 
-template <typename T>
+template <typename T, bool DROP>
 __global__ __launch_bounds__(CT) void taco1_attn_fwd_kernel(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const ns_cluster_slot slot = ns_cluster_place(blockIdx.x, a.p.N, CG, a.xcd != 0);
   if (!slot.active) return;                                 // padding of a placed grid (exchange.h)
-  attn_fwd_body<T, false>(a, sm, slot.cluster * CG + slot.member);
+  attn_fwd_body<T, false, DROP>(a, sm, slot.cluster * CG + slot.member);
 }
 
 // ===================================================================================== backward
@@ -424,7 +433,7 @@ struct BwdLds {                            // dynamic LDS of taco1_attn_bwd_kern
   int him = c.take<float>(2 * HIMG);       // [2][HIMG]: qs | p1m | p2m | acur | da0s | rus | cs | hps | dhcs
   int bytes = c.off;
 };
-template <typename T>
+template <typename T, bool DROP>
 __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const ns_taco1_attn_params& p = a.p;
@@ -449,6 +458,8 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
   const int L = min(p.lengths ? p.lengths[n] : p.Ti, p.Ti);
   const int ts = max(1, (L + CG - 1) / CG);
   const int t0 = g * ts, tn = max(0, min(L, t0 + ts) - t0);
+  // prenet dropout: d (relu(z) keep scale) / dz, the keep part read from the history (a dropped unit's saved output is 0)
+  auto dsc = [&](float s) { if constexpr (DROP) return s * p.drop_scale; else return s; };
   u64* e1 = a.x1 + (size_t)n * CG;
   u64* e2 = a.x2 + (size_t)n * CG * A;
   u64* e3a = a.x3 + (size_t)n * CG * K;
@@ -707,7 +718,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
       float s = dp2s[tid];
 #pragma unroll
       for (int q = 0; q < CG; ++q) s += gath[q * K + tid];
-      s = p2m[tid] > 0.f ? s : 0.f;
+      s = p2m[tid] > 0.f ? dsc(s) : 0.f;
       dp2s[tid] = s;
       if (tid / (D2 / CG) == g) stf((T*)p.dp2 + rowS * D2 + tid, s);
     } else if (tid < D2 + UPW) {
@@ -723,7 +734,7 @@ __global__ __launch_bounds__(CT) void taco1_attn_bwd_kernel(TArgs a) {
     ns_lds_barrier();
     if (tid < D1) {
       float s = red[tid] + red[D1 + tid];
-      s = p1m[tid] > 0.f ? s : 0.f;
+      s = p1m[tid] > 0.f ? dsc(s) : 0.f;
       dvec[tid] = s;
       if (tid / (D1 / CG) == g) stf((T*)p.df1 + rowS * D1 + tid, s);
     }
@@ -1101,20 +1112,31 @@ static int taco1_run(const ns_taco1_attn_params* p, void* work, hipStream_t s, i
   { const int zrc = ns_zero_async(work, (used + 15) & ~(size_t)15, s); if (zrc) return zrc; }
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)taco1_attn_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)taco1_attn_fwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)taco1_attn_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)taco1_attn_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const void* k : {(const void*)taco1_attn_fwd_kernel<float, false>, (const void*)taco1_attn_fwd_kernel<bf16_t, false>,
+                          (const void*)taco1_attn_bwd_kernel<float, false>, (const void*)taco1_attn_bwd_kernel<bf16_t, false>,
+                          (const void*)taco1_attn_fwd_kernel<float, true>, (const void*)taco1_attn_fwd_kernel<bf16_t, true>,
+                          (const void*)taco1_attn_bwd_kernel<float, true>, (const void*)taco1_attn_bwd_kernel<bf16_t, true>})
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   a.xcd = ns_cluster_placed("taco1attn") ? 1 : 0;
   const dim3 grid((unsigned)ns_cluster_grid(p->N, CG, a.xcd != 0)), block(CT);
   if (!backward) {
-    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_fwd_kernel<bf16_t>, grid, block, FwdLds().bytes, s, a);
-    else hipLaunchKernelGGL(taco1_attn_fwd_kernel<float>, grid, block, FwdLds().bytes, s, a);
+    if (p->dtype == NS_BF16) {
+      if (p->drop_thr) hipLaunchKernelGGL((taco1_attn_fwd_kernel<bf16_t, true>), grid, block, FwdLds().bytes, s, a);
+      else hipLaunchKernelGGL((taco1_attn_fwd_kernel<bf16_t, false>), grid, block, FwdLds().bytes, s, a);
+    } else {
+      if (p->drop_thr) hipLaunchKernelGGL((taco1_attn_fwd_kernel<float, true>), grid, block, FwdLds().bytes, s, a);
+      else hipLaunchKernelGGL((taco1_attn_fwd_kernel<float, false>), grid, block, FwdLds().bytes, s, a);
+    }
   } else {
-    if (p->dtype == NS_BF16) hipLaunchKernelGGL(taco1_attn_bwd_kernel<bf16_t>, grid, block, BwdLds().bytes, s, a);
-    else hipLaunchKernelGGL(taco1_attn_bwd_kernel<float>, grid, block, BwdLds().bytes, s, a);
+    if (p->dtype == NS_BF16) {
+      if (p->drop_thr) hipLaunchKernelGGL((taco1_attn_bwd_kernel<bf16_t, true>), grid, block, BwdLds().bytes, s, a);
+      else hipLaunchKernelGGL((taco1_attn_bwd_kernel<bf16_t, false>), grid, block, BwdLds().bytes, s, a);
+    } else {
+      if (p->drop_thr) hipLaunchKernelGGL((taco1_attn_bwd_kernel<float, true>), grid, block, BwdLds().bytes, s, a);
+      else hipLaunchKernelGGL((taco1_attn_bwd_kernel<float, false>), grid, block, BwdLds().bytes, s, a);
+    }
   }
   NS_CHECK_LAUNCH(name);
   return NS_OK;
@@ -1162,6 +1184,7 @@ extern "C" int ns_taco1_decode(const ns_taco1_decode_params* q, void* work, ns_s
   NS_CHECK_ARG(ns_taco1_decode_supported(q), "ns_taco1_decode: unsupported shape (needs A = D1 = D = 256, D2 = 128, "
                "T_in <= 256, N >= 1, 32 workgroups resident per two rows of a launch: ns_taco1_decode_max_rows) or a null operand");
   const ns_taco1_attn_params* p = &q->att;
+  NS_CHECK_ARG(p->drop_thr == 0, "ns_taco1_decode: prenet dropout (att.drop_thr != 0) is a training option");
   DArgs d = {};
   d.att.p = *p;
   const DecWork wl{(size_t)p->N};

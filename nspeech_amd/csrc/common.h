@@ -114,6 +114,11 @@ __host__ __device__ __forceinline__ bool ns_zone_keep(uint32_t seed, uint32_t t,
   x = ns_fmix32(x ^ (u * 0x846CA68Bu));
   return (x >> 8) < thr;
 }
+// Prenet dropout (ns_taco2_attn_params.drop_*): the same generator, true = the unit is DROPPED.  relu(z) of unit u of batch
+// row n at decoder step t -> 0 if dropped, else scaled.
+__host__ __device__ __forceinline__ float ns_prenet_drop(float v, uint32_t seed, int t, int n, int u, uint32_t thr, float scale) {
+  return ns_zone_keep(seed, (uint32_t)t, (uint32_t)n, (uint32_t)u, thr) ? 0.f : v * scale;
+}
 
 // tf.contrib.rnn.LSTMBlockCell's cell_clip (lstm_ops: cs = clip(ci .* i + cs_prev .* f, -cell_clip, cell_clip) when the
 // attribute is > 0; its gradient kernel applies no mask for clipped values, so the backward kernels stay as they are and

@@ -1197,3 +1197,62 @@ extern "C" int ns_act_bwd(const ns_act_bwd_params* p, ns_stream_t s) {
   NS_CHECK_LAUNCH("act_bwd");
   return NS_OK;
 }
+
+// ------------------------------------------------------------------ dropout on rows (prenet dropout of the step-launch forms)
+// Four columns per thread: one 16-byte (fp32) / 8-byte (bf16) access where the width, both strides and both bases allow,
+// else the same four columns one by one (a ragged U, odd strides).  The mask is a pure function of (seed, t, n, u):
+// ns_zone_keep, the generator of the persistent attention kernels.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void dropout_rows_kernel(ns_dropout_rows_params p) {
+  const int U4 = (p.U + 3) / 4;
+  const long total = (long)p.N * p.T * U4;
+  const T* x = (const T*)p.x;
+  T* y = (T*)p.y;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int u0 = (int)(idx % U4) * 4;
+    const long nt = idx / U4;
+    const int t = (int)(nt % p.T), n = (int)(nt / p.T);
+    const long o = (long)n * p.sn + (long)t * p.st + u0;
+    const uint32_t tt = (uint32_t)(p.t0 + t), nn = (uint32_t)(p.n0 + n);
+    if constexpr (VEC) {
+      float v[4];
+      if constexpr (sizeof(T) == 4) {
+        const float4 q = *(const float4*)(x + o);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+      } else {
+        const uint2 q = *(const uint2*)(x + o);
+        v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xFFFF0000u);
+        v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xFFFF0000u);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = ns_prenet_drop(v[j], p.seed, (int)tt, (int)nn, u0 + j, p.thr, p.scale);
+      if constexpr (sizeof(T) == 4) {
+        *(float4*)(y + o) = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        alignas(8) T r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = (T)v[j];
+        *(uint2*)(y + o) = *(const uint2*)r;
+      }
+    } else {
+      for (int j = 0; j < 4 && u0 + j < p.U; ++j)
+        stf(y + o + j, ns_prenet_drop(ldf(x + o + j), p.seed, (int)tt, (int)nn, u0 + j, p.thr, p.scale));
+    }
+  }
+}
+extern "C" int ns_dropout_rows(const ns_dropout_rows_params* p, ns_stream_t s) {
+  NS_CHECK_ARG(p && p->x && p->y, "ns_dropout_rows: null");
+  NS_CHECK_ARG(p->dtype == NS_F32 || p->dtype == NS_BF16, "ns_dropout_rows: dtype");
+  NS_CHECK_ARG(p->N >= 0 && p->T >= 0 && p->U >= 0 && p->t0 >= 0 && p->n0 >= 0, "ns_dropout_rows: negative extent or index base");
+  const long total = (long)p->N * p->T * ((p->U + 3) / 4);
+  if (total <= 0) return NS_OK;
+  const size_t esz = p->dtype == NS_BF16 ? 2 : 4;
+  const bool vec = p->U % 4 == 0 && p->sn % 4 == 0 && p->st % 4 == 0 && (uintptr_t)p->x % (4 * esz) == 0 && (uintptr_t)p->y % (4 * esz) == 0;
+  const int grid = (int)min((long)4096, (total + 255) / 256);
+#define NS_DROP_ROWS(T_, V_) hipLaunchKernelGGL((dropout_rows_kernel<T_, V_>), dim3(grid), dim3(256), 0, (hipStream_t)s, *p)
+  if (p->dtype == NS_BF16) { if (vec) NS_DROP_ROWS(bf16_t, true); else NS_DROP_ROWS(bf16_t, false); }
+  else { if (vec) NS_DROP_ROWS(float, true); else NS_DROP_ROWS(float, false); }
+#undef NS_DROP_ROWS
+  NS_CHECK_LAUNCH("dropout_rows");
+  return NS_OK;
+}

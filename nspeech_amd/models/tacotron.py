@@ -803,8 +803,10 @@ class Tacotron(Tacotron2):
             self._tape.append(lambda: ops.embedding_bwd(self.inputs, emb.grad, self.flat_g, N, Ti, Pi, self.padl,
                                                         hp.embedding_dim, self.vocab, dtable_off=o("embedding/embedding")))
         pn = list(hp.encoder_prenet)
-        x = self._dense("pre1", emb, "prenet/dense_1", pn[0], ACT_RELU)
-        x = self._dense("pre2", x, "prenet/dense_2", pn[1], ACT_RELU)
+        # prenet dropout (hparam prenet_dropout, training only): one mask stream per layer, t = the text position
+        drop = self.prenet_dropout_args("encoder") if training else None
+        x = self._prenet_drop(self._dense("pre1", emb, "prenet/dense_1", pn[0], ACT_RELU), drop, 1)
+        x = self._prenet_drop(self._dense("pre2", x, "prenet/dense_2", pn[1], ACT_RELU), drop, 2)
         spk = self._speaker_rows(N)
         enc = self._cbhg("enc", x, self.input_lengths, self.ENC_CBHG, hp.encoder_cbhg_banks,
                          list(hp.encoder_cbhg_bank_sizes), training, spk=spk)
@@ -815,6 +817,19 @@ class Tacotron(Tacotron2):
         keys_t = self._buf("keys_t", N * A * Tia, torch.float32)
         ops.keys_transpose(keys, keys_t, N, Ti, Tia, Pi, self.padl, A)
         return enc, spk_dec, keys, keys_t
+
+    def _prenet_drop(self, y, drop, layer):
+        """Inverted dropout on the text rows of a prenet layer's output, in place; the tape entry (it runs ahead of the
+        layer's own, which reads the ReLU branch from the dropped output) puts the same mask and scale on the gradient."""
+        if drop is None:
+            return y
+        thr, scale, seed = drop[0], drop[1], drop[1 + layer]
+
+        def run(buf):
+            ops.dropout_rows(buf, y.N, y.T, y.C, y.P * y.C, y.C, thr, seed, scale, x_off=y.padl * y.C)
+        run(y.buf)
+        self._tape.append(lambda: run(y.grad))
+        return y
 
     def _tail(self, dec, al, S1, training):
         """post CBHG + linear head (tacotron.py:92-98) and the output views.  dec: the decoder's frames as an Act in the
@@ -902,6 +917,7 @@ class Tacotron(Tacotron2):
                         wq=(W, o("decoder/attention/query_layer/kernel")), b2=(self.flat_p, b2), bg=(self.flat_p, abg),
                         bc=(self.flat_p, abc), v=(self.flat_p, ov), p1=p1, xa=xa, xc=xc, hc=hc, ru=ru, cc=cc, q=q, align=al,
                         align_t=al_t, Dsp=Dsp)
+            args.update(self._dropout_block())
             if ops.taco1_attn_cluster_supported(**args):
                 self._attn_args = args
         if self._attn_args is not None:
@@ -915,12 +931,17 @@ class Tacotron(Tacotron2):
                      batch_strides=(S1 * Tia, Pi * E, S1 * HC))
         else:
             self._per_step("attn", "fwd")
+            drop = self.prenet_dropout_args()      # the masks of the persistent kernel, one launch per row set
             for s in range(S):
                 sl, pv = s + 1, s
                 ops.gemm(hc, tsh["w1cT"], p1, N, 256, E, S1 * HC, E, S1 * 256, a_off=pv * HC + A, c_off=sl * 256, act=ACT_RELU,
                          addend=f1, addend_off=sl * 256, ld_add=S1 * 256)
+                if drop:
+                    ops.dropout_rows(p1, N, 1, 256, S1 * 256, 0, drop[0], drop[2], drop[1], t0=s, x_off=sl * 256)
                 ops.gemm(p1, tsh["w2T"], xa, N, 128, 256, S1 * 256, 256, S1 * XA, a_off=sl * 256, c_off=sl * XA,
                          bias=self.flat_p, bias_off=b2, act=ACT_RELU)
+                if drop:
+                    ops.dropout_rows(xa, N, 1, 128, S1 * XA, 0, drop[0], drop[3], drop[1], t0=s, x_off=sl * XA)
                 ops.copy3d(xa, xc, N, 1, XI, (S1 * XA, 0), (S1 * XA, 0), src_off=sl * XA, dst_off=sl * XA)
                 ops.gemm(xa, tsh["att_gT"], ru, N, 2 * A, XA, S1 * XA, XA, S1 * 2 * A, a_off=sl * XA, c_off=sl * 2 * A,
                          bias=self.flat_p, bias_off=abg, act=ACT_SIGMOID)
@@ -1103,8 +1124,14 @@ class Tacotron(Tacotron2):
                 ops.gemm(dzc, W, tmp128, N, 128, A, S1 * A, A, 128, a_off=sl * A, b_off=ac_, accumulate=1,
                          gate=xa, gate_off=sl * XA, ld_gate=S1 * XA)
                 ops.copy3d(tmp128, dp2, N, 1, 128, (128, 0), (S1 * 128, 0), dst_off=sl * 128)
+                drop = self.prenet_dropout_args()       # the forward pass' seeds (global_step moves in apply_gradients); the
+                                                        # gates above read the dropped p2 / p1: the calls add the scale
+                if drop:
+                    ops.dropout_rows(dp2, N, 1, 128, S1 * 128, 0, drop[0], drop[3], drop[1], t0=s, x_off=sl * 128)
                 ops.gemm(dp2, W, df1, N, 256, 128, S1 * 128, 128, S1 * 256, a_off=sl * 128, b_off=w2, c_off=sl * 256,
                          gate=p1, gate_off=sl * 256, ld_gate=S1 * 256)
+                if drop:
+                    ops.dropout_rows(df1, N, 1, 256, S1 * 256, 0, drop[0], drop[2], drop[1], t0=s, x_off=sl * 256)
                 if s > 0:
                     ops.gemm(df1, W, dctx_carry, N, E, 256, S1 * 256, 256, E, a_off=sl * 256, b_off=w1 + M * 256)
         if Dsp:

@@ -145,6 +145,14 @@ class Tacotron2(object):
             raise ValueError("guided_attention_weight must be >= 0 and guided_attention_sigma > 0 (got %g, %g)"
                              % (self.guided_weight, self.guided_sigma))
         self.zoneout_base_seed = (int(seed) * 2654435761 + 97) & 0xFFFFFFFF
+        # Prenet dropout (hparams prenet_dropout / drop_rate).  The reference's tf.layers.dropout call never gets
+        # training=True (modules.py:21-27), so it is the identity and the shipped switch is false: nothing below changes a
+        # bit of that path.  true: inverted dropout behind both prenet ReLUs in training, masks from the zoneout generator
+        # on streams of their own (prenet_dropout_args); synthesis is the expectation = the identity.
+        self.prenet_dropout = bool(getattr(hparams, "prenet_dropout", False))
+        self.drop_rate = float(getattr(hparams, "drop_rate", 0.0) or 0.0)
+        if self.prenet_dropout and not 0.0 <= self.drop_rate < 1.0:
+            raise ValueError("prenet_dropout needs drop_rate in [0, 1) (got %g)" % self.drop_rate)
         self._status_words = {}
         self._bwd_sums = {}       # conv tag -> (sum dy, sum dy*xhat) left by the product that formed that layer's dy
         # which kernel family ran each recurrence of the last pass: {"attn:fwd": "cluster" | "step",
@@ -913,11 +921,35 @@ class Tacotron2(object):
         if self.zoneout_rate <= 0.0:
             return None
         thr = ops.zoneout_threshold(self.zoneout_rate)
+        base = self._mask_base_seed()
+        return (thr, thr, ops.zoneout_seed(base, self.global_step, 2 * layer),
+                ops.zoneout_seed(base, self.global_step, 2 * layer + 1))
+
+    def _mask_base_seed(self):
+        """The base seed of every counter-based mask stream (zoneout, prenet dropout) with the data-parallel rank folded in."""
         base = self.zoneout_base_seed
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             base ^= (torch.distributed.get_rank() * 0x9E3779B9) & 0xFFFFFFFF      # every rank its own masks
-        return (thr, thr, ops.zoneout_seed(base, self.global_step, 2 * layer),
-                ops.zoneout_seed(base, self.global_step, 2 * layer + 1))
+        return base
+
+    def prenet_dropout_args(self, prenet="decoder"):
+        """(thr, scale, seed_layer1, seed_layer2) of the prenet's dropout for the CURRENT global step, or None when the
+        option is off or the rate is 0 (the kernels then get no dropout block at all).  prenet: "decoder", or "encoder"
+        (Tacotron-1's second prenet, streams of its own).  The backward pass of a step asks again and gets the same seeds."""
+        if not self.prenet_dropout:
+            return None
+        thr = ops.zoneout_threshold(self.drop_rate)
+        if thr == 0:
+            return None
+        base = self._mask_base_seed()
+        return (thr, 1.0 / (1.0 - self.drop_rate),
+                ops.zoneout_seed(base, self.global_step, ops.DROPOUT_STREAMS[prenet + "1"]),
+                ops.zoneout_seed(base, self.global_step, ops.DROPOUT_STREAMS[prenet + "2"]))
+
+    def _dropout_block(self):
+        """prenet_dropout_args() as the drop_* fields of an attention parameter block ({} when off)."""
+        d = self.prenet_dropout_args()
+        return {} if d is None else dict(drop_thr=d[0], drop_scale=d[1], drop_seed1=d[2], drop_seed2=d[3])
 
     def _run_lstm(self, direction, tag, *a, **kw):
         """One decoder LSTM over all steps: the persistent wide-cell kernel when it applies, else one launch per step.
@@ -1293,6 +1325,7 @@ class Tacotron2(object):
             wattT_hi=self.tsh.get("wattT_hi"), wattT_lo=self.tsh.get("wattT_lo"),
             align_t=self._buf("dec_al_t", N * S1 * Tia, T_),
             w1c=(self._W(self.T), self._o("decoder/decoder_prenet/dense_1/kernel") + M * 256))
+        args.update(self._dropout_block())      # training only: attn_block's own arguments (synthesis) never carry it
         self._attn_cluster_fwd = self.use_attn_cluster and ops.taco2_attn_cluster_supported(**self._attn_args)
         if self._attn_cluster_fwd:
             self._persistent("attn", "fwd", ops.taco2_attn_cluster_work_floats(**args),

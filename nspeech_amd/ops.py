@@ -566,6 +566,21 @@ def zoneout_seed(base, step, stream_id):
     return _fmix32(_fmix32((base & 0xFFFFFFFF) ^ ((step * 0x9E3779B9) & 0xFFFFFFFF)) ^ ((stream_id * 0x7FEB352D) & 0xFFFFFFFF))
 
 
+# mask streams of zoneout_seed(): 2..5 are the decoder LSTMs' zoneout (2 * layer, 2 * layer + 1); prenet dropout takes
+# 8, 9 (decoder prenet layers 1, 2) and 10, 11 (Tacotron-1's encoder prenet layers 1, 2)
+DROPOUT_STREAMS = {"decoder1": 8, "decoder2": 9, "encoder1": 10, "encoder2": 11}
+
+
+def dropout_rows(x, N, T, U, sn, st, thr, seed, scale, t0=0, n0=0, x_off=0, y=None, y_off=0):
+    """y[n, t, u] = x[n, t, u] * keep(seed, t0 + t, n0 + n, u) * scale over (dtype) rows at element strides sn / st
+    (ns_dropout_rows; y defaults to x: in place).  keep = 0 where the generator of the zoneout masks says so at threshold
+    thr = zoneout_threshold(rate).  The same call serves activations and their gradients."""
+    p = L.struct("ns_dropout_rows_params")
+    _fill(p, dtype=dt(x), N=N, T=T, U=U, sn=sn, st=st, x=ptr(x, x_off), y=ptr(x if y is None else y, x_off if y is None else y_off),
+          thr=int(thr), seed=int(seed), scale=float(scale), t0=t0, n0=n0)
+    L.call("ns_dropout_rows", p, stream())
+
+
 def lstm_seq(direction, dtype_t, *a, **kw):
     """direction: 'fwd' or 'bwd' (through-time gradient)."""
     p = lstm_seq_params(*a, **kw)
