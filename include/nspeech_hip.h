@@ -1160,13 +1160,27 @@ int ns_wavenet_generate_span(const ns_wavenet_generate_params* p, const ns_waven
                              const ns_wavenet_span_params* span, ns_stream_t stream);
 
 /* ------------------------------------------------------------------ audio DSP (utils/audio.py)
- * Radix-2 Stockham FFTs of n_fft points run inside LDS, one workgroup per frame; no MFMA,
- * the kernels are bandwidth / latency bound.  window = periodic Hann(win) and
- * twiddle[m] = (cos, -sin)(2*pi*m/n_fft), m < n_fft/2, are supplied by the caller (immutable). */
+ * Stockham FFTs inside LDS or registers; no MFMA, the kernels are bandwidth / latency bound.  ns_spectrogram, ns_stft_tf
+ * and ns_istft run a radix-2 transform of n_fft points, one 256-thread workgroup per frame.  ns_griffin_lim runs real
+ * transforms as complex ones of n_fft/2 points in one of two forms (below): radix-4 in LDS, one workgroup per frame, or
+ * in the registers of one wavefront per frame.  window = periodic Hann(win) [win floats] and
+ * twiddle[m] = (cos, -sin)(2*pi*m/n_fft), m < n_fft/2 [n_fft floats], are supplied by the caller (immutable, 4-byte
+ * aligned; an 8-byte aligned window is one condition of the wave form).
+ * Accepted by ns_spectrogram, ns_stft_tf, ns_istft and ns_griffin_lim: n_fft a power of two in [64, 4096] and
+ * win <= n_fft; ns_istft and ns_griffin_lim also ask 0 < hop <= win, ns_stft_tf 0 < hop.  Anything else, or a null
+ * pointer that is not marked optional, is NS_ERR_BAD_ARG before any launch; T <= 0 (ns_griffin_lim: or N <= 0;
+ * ns_stft_tf: T == 0, it refuses T < 0) is a success without a launch.  No entry writes outside the extents given for its outputs and work areas, and none writes
+ * its inputs.  Results are held to a float64 statement of this section (tests/audio_ref.py) within bounds derived from
+ * the float32 formats (tests/test_audio_contract_gpu.py), not to the bit. */
 
 /* audio.spectrogram + audio.melspectrogram in ONE pass over the waveform (audio.py:39-42,61-64
  * with librosa.stft(center=True, reflect) framing, _amp_to_db, _normalize; preemphasis fused).
- * lin_out [T, n_fft/2+1], mel_out [T, n_mels], both normalised, T = 1 + L/hop. */
+ * lin_out [T, n_fft/2+1], mel_out [T, n_mels], both normalised, T = 1 + L/hop.  lin_out, mel_out and stft_out are each
+ * optional (null: not computed, not written; mel_out needs mel_basis [n_mels, n_fft/2+1], any n_mels >= 1).
+ * NS_ERR_BAD_ARG unless L > n_fft/2 (one reflection at either end then reaches every sample a frame needs).  The window
+ * sits at (n_fft - win) / 2, rounded down, in the frame.  preemph != 0: sample i > 0 is wav[i] - preemph * wav[i-1] and
+ * sample 0 is wav[0], taken BEFORE the reflection (a reflected index reads its own left neighbour); preemph == 0: none.
+ * min_level_db of either sign. */
 typedef struct {
   const float* wav; int L;
   float preemph;
@@ -1194,7 +1208,15 @@ int ns_spectrogram(const ns_spectrogram_params* p, ns_stream_t stream);
  *   spare bytes; with momentum > 0 the history E_prev, fp32, 16 bytes per bin pair (k, n_fft/2 - k), k = 0 .. n_fft/4,
  *   of every frame, starting at the first 16-byte boundary behind the frames.
  *   ns_griffin_lim_work_bytes() = 4 * (((N*T*F + 1) & ~1) + 2*N*T*win) + 256
- *                                 + (momentum > 0 ? 16 * N*T*(n_fft/4 + 1) = 8 * N*T*(n_fft/2 + 2) : 0). */
+ *                                 + (momentum > 0 ? 16 * N*T*(n_fft/4 + 1) = 8 * N*T*(n_fft/2 + 2) : 0).
+ *   Nothing behind these bytes is written, and nothing outside wav [N, (T-1)*hop + win].
+ * Two kernel forms.  The wave form (one wavefront per frame, four frames per workgroup) is taken when ALL of these hold:
+ *   n_fft == 2048, hop and win even, win <= 4 * hop (at most four frames cover a sample), win <= 1024, and both
+ *   `window` and `work` 8-byte aligned.  Every other accepted call takes the generic form (one workgroup per frame, any
+ *   number of covering frames, odd hop / win).  The forms sum in different orders and the wave form uses the hardware
+ *   reciprocal square root in the phase step: their results agree within the bounds of the tests, not to the bit.
+ *   A call repeats itself bit for bit, and a clip's row does not depend on the other clips of the call.
+ * raw_magnitude == 0: the magnitudes are formed with the hardware exp2 / log2 (__powf), not with powf. */
 typedef struct {
   const float* spec; int N, T;
   int n_fft, hop, win, iters;
@@ -1216,7 +1238,11 @@ size_t ns_griffin_lim_work_bytes(const ns_griffin_lim_params* p);
  *                window-sum normalisation; wav [(T-1) hop + win].
  *   center == 1: librosa 0.6.0 istft(hop, win): the window centred in the n_fft frame, overlap-add, divided by the
  *                summed squared window where that exceeds FLT_MIN, n_fft/2 trimmed at both ends; wav [(T-1) hop].
- *   work: T * win floats. */
+ *                Where the sum is FLT_MIN or less - 0 < hop == win puts the zero of the Hann window there - the
+ *                overlap-added value is stored as it is, never a quotient.  T == 1: no output sample, work is written.
+ *   The imaginary parts of the DC and the Nyquist bin are ignored, as irfft ignores them.
+ *   work: T * win floats (the windowed frames; contents on entry are never read).
+ * ns_stft_tf: NS_ERR_BAD_ARG unless (T-1) * hop + win <= L; samples behind the last frame are not read. */
 typedef struct {
   const float* wav; int L;
   int n_fft, hop, win, T;
@@ -1234,12 +1260,16 @@ int ns_istft(const ns_istft_params* p, ns_stream_t stream);
 
 /* Element-wise conversions of audio.py:150-171 on device arrays: mode 0 _amp_to_db 20 log10(max(1e-5, x)); 1 _db_to_amp
  * 10^(x / 20); 2 _normalize clip((x - min_level_db) / -min_level_db, 0, 1); 3 _denormalize clip(x, 0, 1) * -min_level_db
- * + min_level_db. */
+ * + min_level_db.  Any other mode: NS_ERR_BAD_ARG.  n <= 0 succeeds without a launch; any n (a grid-stride loop above
+ * 4096 * 256 elements); min_level_db of either sign; y [n]. */
 typedef struct { const float* x; float* y; int64_t n; int mode; float min_level_db; } ns_audio_pointwise_params;
 int ns_audio_pointwise(const ns_audio_pointwise_params* p, ns_stream_t stream);
 
 /* audio.preemphasis (inverse=0: y[n] = x[n] - c x[n-1]) and audio.inv_preemphasis
- * (inverse=1: y[n] = x[n] + c y[n-1]), scipy.signal.lfilter with zero initial state. */
+ * (inverse=1: y[n] = x[n] + c y[n-1]), scipy.signal.lfilter with zero initial state.  Any coef, 0 and negative ones
+ * included; any n (n <= 0 succeeds without a launch); y [n].  inverse=1 runs in one workgroup over tiles of 2048 samples
+ * (blocks of 8 combined by a scan: float32 in that association, not sample after sample) and may run in place, y == x;
+ * inverse=0 may not. */
 typedef struct { const float* x; float* y; int64_t n; float coef; int inverse; } ns_preemphasis_params;
 int ns_preemphasis(const ns_preemphasis_params* p, ns_stream_t stream);
 
