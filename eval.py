@@ -2,7 +2,8 @@
 """Synthesis from a checkpoint, the reference's eval.py surface (eval.py:23-27,62-76): flags --checkpoint --model
 --hparams --gpu --speaker; one `eval-<step>-<i>.wav` per test sentence next to the checkpoint.  The checkpoint may be
 this build's `model.ckpt-<step>` file or a TensorFlow checkpoint prefix (nspeech_amd/utils/tf_bundle.py).
---batch-size B > 1 writes the same files from Synthesizer.synthesize_batch on B sentences at a time."""
+--batch-size B > 1 writes the same files from Synthesizer.synthesize_batch on B sentences at a time.
+--hparams stop_token=true[,stop_threshold=0.4] (a checkpoint trained with the switch): every sentence ends at its stop step."""
 import argparse
 import os
 import re

@@ -351,6 +351,50 @@ typedef struct {
 } ns_guided_attention_params;
 int ns_guided_attention(const ns_guided_attention_params* p, ns_stream_t stream);
 
+/* Tacotron-2 stop token (Shen et al. 2018): the projection of the decoder LSTM output to one logit per step, and in the
+ * same pass either the training term with its gradient or the step at which each utterance stops.  Not in the
+ * reference: hparam stop_token, false = off.
+ * h fp32 or bf16 (h_dtype), element (n, s, d) at h[n*h_sn + s*h_ss + d] with s = 0 the FIRST decoder step (the caller
+ * points h at slot 1 of a slot layout); w fp32 [D], b fp32 [1]; 64 <= D <= 2048, D % 64 == 0.
+ *   z[n,s] = sum_d h[n,s,d] w[d] + b          logits[n*S + s] = z[n,s]   (nullable)
+ * Training form (any of out_steps, dh, acc non-NULL).  S_n = out_steps[n] clamped into [1, S] (NULL: S);
+ * y[n,s] = 1 if s >= S_n - 1 else 0: the step that emits the last real frame and every padded step behind it are
+ * positive, and every step counts in the mean.  sp(x) = max(x, 0) + log1p(exp(-|x|)):
+ *   l[n,s]  = pos_weight y sp(-z) + (1 - y) sp(z)                       pos_weight > 0
+ *   acc[0]  = L_stop = 1/(N S) sum_{n,s} l[n,s]                         (written, not accumulated; nullable)
+ *   acc[1]  = 1/N sum_n |S^_n(threshold 0.5) - S_n|                     (S^_n as below with threshold_logit = 0)
+ *   dz[n,s] = grad_scale/(N S) ((1 - y) sigma(z) - pos_weight y (1 - sigma(z)))         grad_scale >= 0
+ *   dh[n*dh_sn + s*dh_ss + d] += dz[n,s] w[d]      dw[d] += sum_{n,s} dz[n,s] h[n,s,d]      db[0] += sum_{n,s} dz[n,s]
+ * dh, dw, db are fp32 and NULL together.  A row whose dz is exactly zero (grad_scale = 0) is not touched at all.
+ * Everything of dh outside the N*S rows of D elements keeps its bits.
+ * Synthesis form: stop_steps[n] = S^_n = 1 + min{ s : z[n,s] > threshold_logit }, or S when no step qualifies
+ * (nullable; a logit equal to the threshold does not count); the caller forms threshold_logit = log(t / (1 - t)).
+ * work: ns_stop_token_work_floats(N, S, D) floats, no need to clear.  Every sum has a fixed order (a lane's D/64
+ * products, the wave tree, a wave's rows in index order, a workgroup's waves in index order, the workgroups' partials
+ * in index order); the grid depends on (N, S, D) only: two calls on the same inputs give the same bits, on any device,
+ * and there is no float atomic.  The caller owns all memory. */
+typedef struct {
+  int N, S, D;
+  const void* h;
+  int h_dtype;
+  int64_t h_sn, h_ss;
+  const float* w;
+  const float* b;
+  float* logits;
+  const int* out_steps;
+  float pos_weight, grad_scale;
+  float* dh;
+  int64_t dh_sn, dh_ss;
+  float* dw;
+  float* db;
+  float* acc;
+  float threshold_logit;
+  int* stop_steps;
+  float* work;
+} ns_stop_token_params;
+int ns_stop_token(const ns_stop_token_params* p, ns_stream_t stream);
+size_t ns_stop_token_work_floats(int N, int S, int D);
+
 /* ------------------------------------------------------------------ optimizer
  * tf.clip_by_global_norm + tf.train.AdamOptimizer (tacotron2.py:150-161).
  * ns_sumsq: out[0] += sum g^2.   ns_adam: scale = clip / max(sqrt(gnorm_sq[0]), clip);

@@ -6,14 +6,14 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-unused-value"
-# per-file flags.  audio.hip, attn_cluster.hip, attn_gru.hip: no SLP vectorisation - the packed-fp32 instructions it forms out of scalar
+# per-file flags.  audio.hip, attn_cluster.hip, attn_gru.hip, guided_attn.hip, stop_token.hip: no SLP vectorisation - the packed-fp32 instructions it forms out of scalar
 # code pick their operand selects freely, including the src1 high-half select that MI355X misreads beside the MFMA waves of
 # another kernel (profiles/tools/pk_opsel_probe.hip; tests/test_isa_guard_cpu.py keeps every kernel of the library free of
 # that form).  frontend.hip: no contraction either - ns_resample's contract is bit equality with a float64 sum whose
 # every multiply and add rounds on its own (a v_fma_f64 there changes the last bit of some samples)
 extra_flags() {
   case "$1" in
-    audio.hip|attn_cluster.hip|attn_gru.hip|guided_attn.hip) echo "-fno-slp-vectorize" ;;
+    audio.hip|attn_cluster.hip|attn_gru.hip|guided_attn.hip|stop_token.hip) echo "-fno-slp-vectorize" ;;
     frontend.hip) echo "-fno-slp-vectorize -ffp-contract=off" ;;
     *) echo "" ;;
   esac

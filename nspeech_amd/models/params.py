@@ -83,8 +83,12 @@ def taco2_speaker_width(hp):
     return 128 if int(getattr(hp, "num_speakers", 1) or 1) > 1 else 0
 
 
-def taco2_layout(hp, vocab_size):
-    """Variables of tacotron2.py:33-107 (names relative to 'model/inference/')."""
+def taco2_layout(hp, vocab_size, stop_token=None):
+    """Variables of tacotron2.py:33-107 (names relative to 'model/inference/').
+    stop_token (None: hp.stop_token; not in the reference): the stop projection's two variables directly behind the
+    output projection's, inside the decoder group of parallel.bucket_ranges."""
+    if stop_token is None:
+        stop_token = bool(getattr(hp, "stop_token", False))
     tr, st = Layout(), Layout()
     M = hp.num_mels
     emb = hp.embedding_dim
@@ -120,6 +124,9 @@ def taco2_layout(hp, vocab_size):
     _lstm(tr, "decoder/lstm_2", D, D)
     tr.add("decoder/output_projection/kernel", (D, M * hp.outputs_per_step))
     tr.add("decoder/output_projection/bias", (M * hp.outputs_per_step,))
+    if stop_token:
+        tr.add("decoder/stop_projection/kernel", (D, 1))
+        tr.add("decoder/stop_projection/bias", (1,))
     cin = M
     for i in range(hp.postnet_conv_layers):
         _conv_bn(tr, st, "decoder_postnet/postnet_conv_%d" % i, hp.postnet_conv_width, cin,
@@ -217,6 +224,9 @@ def init_values(trainable, stats, seed=0):
     for name, (_, shape) in trainable.entries.items():
         if name == "embedding/embedding":
             p[name] = truncated_normal(rng, shape, 0.01)
+        elif name == "decoder/stop_projection/kernel":
+            # a stream of its own: every other variable of a stop_token model starts where it starts without the switch
+            p[name] = glorot_uniform(np.random.RandomState((seed * 1000003 + 7919) % (2 ** 31)), shape)
         elif name.endswith("/gates/bias"):          # GRUCell: gate bias starts at 1.0
             p[name] = np.ones(shape, np.float32)
         elif name.endswith("/highway/T/bias"):      # modules.py:189-190

@@ -46,6 +46,7 @@ class Act(object):
 
 
 class Tacotron(Tacotron2):
+    HAS_STOP_TOKEN = False    # stop_token = true raises: Tacotron-2 only
     # data parallel: one whole-buffer all-reduce once backward() has been enqueued (parallel.whole_buffer_range)
     _BUCKET_AFTER = {"backward": "all"}
 

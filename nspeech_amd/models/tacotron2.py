@@ -75,6 +75,7 @@ class Tacotron2(object):
     MEMORY = "attention_decoder/memory_layer/kernel"     # keys = values . W_memory, in both Tacotron models
     LAYOUT = staticmethod(P_.taco2_layout)
     _speaker_width = staticmethod(P_.taco2_speaker_width)
+    HAS_STOP_TOKEN = True     # Tacotron-1 has none (its oracle does not expose the decoder state to check one against)
 
     def __init__(self, hparams, device="cuda:0", dtype="bf16", seed=0, world_size=1):
         self._hparams = hparams
@@ -92,6 +93,23 @@ class Tacotron2(object):
         self.passes_fwd = {"bf16": 0, "fp32": 0, "bf16x3": 3, "mixed": 3}[dtype]
         self.passes_bwd = {"bf16": 0, "fp32": 0, "bf16x3": 3, "mixed": 1}[dtype]
         self.vocab = len(symbols)
+        # Stop token (hparams stop_token, stop_token_weight, stop_token_pos_weight, stop_threshold; the Tacotron-2
+        # paper's, not in the reference, so the shipped switch is false and then no variable, no launch and no bit
+        # differs).  true: two variables behind the output projection's, one ns_stop_token launch in backward() that adds
+        # the term's gradient to d_h2 and leaves L_stop and the stop-step error in scal[6:8], and one in the synthesis
+        # graph that leaves stop_logits / stop_steps.
+        self.stop_token = bool(getattr(hparams, "stop_token", False))
+        self.stop_weight = float(getattr(hparams, "stop_token_weight", 1.0))
+        self.stop_pos_weight = float(getattr(hparams, "stop_token_pos_weight", 1.0))
+        self.stop_threshold = float(getattr(hparams, "stop_threshold", 0.5))
+        if not (self.stop_weight >= 0.0 and self.stop_pos_weight > 0.0 and 0.0 < self.stop_threshold < 1.0):
+            raise ValueError("stop_token_weight must be >= 0, stop_token_pos_weight > 0 and 0 < stop_threshold < 1 "
+                             "(got %g, %g, %g)" % (self.stop_weight, self.stop_pos_weight, self.stop_threshold))
+        if self.stop_token and not self.HAS_STOP_TOKEN:
+            raise ValueError("stop_token = true: only the Tacotron-2 model (--model taco2) has a stop token")
+        if self.stop_token and hparams.decoder_lstm_units % 64:
+            raise ValueError("stop_token = true needs decoder_lstm_units to be a multiple of 64 (got %d)"
+                             % hparams.decoder_lstm_units)
         self.layout, self.stat_layout = self.LAYOUT(hparams, self.vocab)
         self.n_speakers = int(getattr(hparams, "num_speakers", 1) or 1)
         self.Dsp = self._speaker_width(hparams)      # 0: single speaker, no speaker variables at all
@@ -104,7 +122,8 @@ class Tacotron2(object):
         need_shadow = torch.bfloat16 in (self.T, self.Tx)
         self.flat_s = torch.zeros(n, dtype=torch.bfloat16, device=dev) if need_shadow else self.flat_p
         self.flat_stats = torch.zeros(self.stat_layout.size, dtype=torch.float32, device=dev)
-        # [0:2] mel, [2:4] lin loss, [4] guided attention loss, [5] attention focus, [8] gnorm^2, [9] step skipped
+        # [0:2] mel, [2:4] lin loss, [4] guided attention loss, [5] attention focus, [6] stop-token loss, [7] stop-step
+        # error, [8] gnorm^2, [9] step skipped
         self.scal = torch.zeros(16, dtype=torch.float32, device=dev)
         self.global_step = 0
         self.world_size = world_size
@@ -169,6 +188,8 @@ class Tacotron2(object):
         self.mel_outputs = self.linear_outputs = self.alignments = self.audio = None
         self.loss = self.mel_loss = self.linear_loss = self.learning_rate = None
         self.attention_loss = self.attention_focus = None    # L_att and the focus score of the last step (or summary)
+        self.stop_loss = self.stop_step_error = None         # L_stop and mean |S^_n - S_n| of the last step (stop_token)
+        self.stop_logits = self.stop_steps = self.decoder_h2 = None      # synthesis (stop_token): see output_lengths()
         self.target_lengths = None      # frames per utterance before padding (None: every row spans all S steps)
         self._out_steps = None
         self.gradients = self.flat_g
@@ -225,13 +246,43 @@ class Tacotron2(object):
         d["global_step"] = torch.tensor(self.global_step)
         return d
 
+    STOP_VARS = ("decoder/stop_projection/kernel", "decoder/stop_projection/bias")
+
     def load_state_dict(self, d):
-        pv = {k: d["model/inference/" + k].numpy() for k in self.layout.entries}
-        sv = {k: d["model/inference/" + k].numpy() for k in self.stat_layout.entries}
+        """A checkpoint written without the stop variables loads into a model that has them (they keep their initial
+        values, their Adam moments are zero), one written with them into a model without (they are ignored); either way
+        the flat Adam moments are re-mapped variable by variable through the other layout, and one line says so."""
+        pre = "model/inference/"
+        ck_stop = pre + self.STOP_VARS[0] in d
+        mine = self.STOP_VARS[0] in self.layout.entries
+        pv = {k: d[pre + k].numpy() for k in self.layout.entries if k not in self.STOP_VARS or ck_stop}
+        if mine and not ck_stop:
+            cur = self.numpy_params()
+            pv.update({k: cur[k] for k in self.STOP_VARS})
+        sv = {k: d[pre + k].numpy() for k in self.stat_layout.entries}
         self.load_numpy(pv, sv)
         if "optimizer/adam_m" in d:
-            self.flat_m.copy_(d["optimizer/adam_m"])
-            self.flat_v.copy_(d["optimizer/adam_v"])
+            m, v = d["optimizer/adam_m"], d["optimizer/adam_v"]
+            if mine != ck_stop:
+                if not self.HAS_STOP_TOKEN:
+                    raise ValueError("the checkpoint holds stop-token variables, which this model cannot have")
+                other, _ = self.LAYOUT(self._hparams, self.vocab, stop_token=ck_stop)
+                hm, hv = np.zeros(self.layout.size, np.float32), np.zeros(self.layout.size, np.float32)
+                sm, sv_ = m.numpy(), v.numpy()
+                for name, (off, shape) in self.layout.entries.items():
+                    if name in other.entries:
+                        n, o = int(np.prod(shape)), other.off(name)
+                        hm[off:off + n] = sm[o:o + n]
+                        hv[off:off + n] = sv_[o:o + n]
+                m, v = torch.from_numpy(hm), torch.from_numpy(hv)
+            self.flat_m.copy_(m)
+            self.flat_v.copy_(v)
+        if mine and not ck_stop:
+            print("load_state_dict: the checkpoint has no stop-token variables: decoder/stop_projection/* keep their "
+                  "initial values, their Adam moments start at zero; every other variable and moment loaded by name")
+        elif ck_stop and not mine:
+            print("load_state_dict: the checkpoint's stop-token variables decoder/stop_projection/* are ignored "
+                  "(stop_token = false); every other variable and moment loaded by name")
         self.global_step = int(d.get("global_step", 0))
 
     def _o(self, name):
@@ -591,6 +642,27 @@ class Tacotron2(object):
                              self._bufs["dec_al"], da0, self.guided_weight, self._buf("ga_rows", 2 * N, torch.float32),
                              acc, acc_off)
 
+    def _stop_token_train(self, h2, dh2):
+        """The stop token's term on the forward pass' h2 history ([N, S+1, D], step s in slot s + 1; fp32 or bf16): one
+        ns_stop_token launch adds stop_token_weight * d(L_stop)/d(h2) to dh2 (same layout, fp32), the variables'
+        gradients to flat_g, and writes L_stop and the stop-step error into scal[6:8]."""
+        d = self.dims
+        N, S, D = d["N"], d["S"], self._hparams.decoder_lstm_units
+        ko, bo = self._o(self.STOP_VARS[0]), self._o(self.STOP_VARS[1])
+        work = self._buf("stop_work", ops.stop_token_work_floats(N, S, D), torch.float32)
+        self.stop_h_dtype = h2.dtype
+        ops.stop_token(N, S, D, h2, (S + 1) * D, D, (self.flat_p, ko), (self.flat_p, bo), work, h_off=D,
+                       out_steps=self._guided_steps(), pos_weight=self.stop_pos_weight, grad_scale=self.stop_weight,
+                       dh=dh2, dh_off=D, dh_sn=(S + 1) * D, dh_ss=D, dw=(self.flat_g, ko), db=(self.flat_g, bo),
+                       acc=self.scal, acc_off=6)
+
+    def output_lengths(self):
+        """Synthesis with stop_token: frames per utterance up to and including its stop step, stop_steps *
+        outputs_per_step, as a NumPy int64 [N] (one host read)."""
+        if self.stop_steps is None:
+            raise ValueError("output_lengths() needs stop_token = true and a synthesis pass")
+        return self.stop_steps.cpu().numpy().astype(np.int64) * int(self._hparams.outputs_per_step)
+
     def _check_guided(self, has_da0, why):
         """A positive guided_attention_weight needs a backward path of the attention recurrence that takes da0."""
         if self.guided_weight > 0.0 and not has_da0:
@@ -679,6 +751,9 @@ class Tacotron2(object):
         out = dict(loss=self.loss, loss_mel=self.mel_loss, loss_linear=self.linear_loss, learning_rate=self.learning_rate,
                    max_gradient_norm=float(norms.max()), gradient_norm={k: float(v) for (k, _), v in zip(ent, norms)},
                    histograms=vals, loss_attention=att, attention_focus=focus)
+        if self.stop_token:         # the last backward pass' own, whether or not its losses were read back since
+            ls, se = (float(x) for x in self.scal[6:8].cpu().numpy())
+            out.update(loss_stop=ls, stop_step_error=se)
         return out
 
     # ------------------------------------------------------------------ layer helpers
@@ -1467,6 +1542,18 @@ class Tacotron2(object):
         self._defer("decoder", proj_wgrad, pure=True)
         dh2 = self._buf("d_h2", rows * D, torch.float32)
         ops.gemm(ddec, self._W(self.T), dh2, rows, D, M * r, M * r, M * r, D, a_mode=0, b_mode=0, b_off=kp)
+        if self.stop_token:         # + stop_token_weight * d(L_stop)/d(h2); its dw / db; L_stop, the step error -> scal[6:8]
+            h_stop = h2
+            if self._bf16_w(T_) is not None:
+                # `mixed`: the backward products read bf16 copies of the forward activations, and so does the term - the
+                # copy of h2 that LSTM 2's weight gradients take.  The wide forward kernel has written it already; where
+                # it has not, it is cast here instead of in front of those products (half the bytes of the fp32 history)
+                h_stop = self._buf("dec_h2_16", rows * D, torch.bfloat16)
+                done1, done2 = getattr(self, "_h16_written", (False, False))
+                if not done2:
+                    ops.cast2d(h2, rows, D, D, h_stop, D, False)
+                    self._h16_written = (done1, True)
+            self._stop_token_train(h_stop, dh2)
         # ---- LSTM2, LSTM1 through time
         work = self._buf("lstm_work_d", 2 * N * D + 64, torch.float32)
         k1, k2 = self._o("decoder/lstm_1/kernel"), self._o("decoder/lstm_2/kernel")
@@ -1699,6 +1786,10 @@ class Tacotron2(object):
             self.loss += self.guided_weight * self.attention_loss
         else:
             self.attention_loss = self.attention_focus = None      # not computed by the step: summary() does on demand
+        self.stop_loss = self.stop_step_error = None
+        if self.stop_token:
+            self.stop_loss, self.stop_step_error = float(s[6]), float(s[7])
+            self.loss += self.stop_weight * self.stop_loss
         self.grad_norm = math.sqrt(max(float(s[8]), 0.0)) / self.world_size
         return self.loss
 
@@ -1717,7 +1808,8 @@ class Tacotron2(object):
         ev.record(torch.cuda.current_stream(self.device))
         d = self.dims
         return dict(host=host, event=ev, N=d["N"], To=d["To"], n_prio=self._n_prio, step=self.global_step,
-                    lr=self.learning_rate, guided_weight=self.guided_weight)
+                    lr=self.learning_rate, guided_weight=self.guided_weight,
+                    stop_weight=self.stop_weight if self.stop_token else None)
 
     def losses_finish(self, handle):
         """Wait for a losses_async() read-back and turn it into (loss, mel_loss, linear_loss).  A skipped optimiser step
@@ -1737,6 +1829,10 @@ class Tacotron2(object):
         if handle["guided_weight"] > 0.0:
             handle["attention_loss"], handle["attention_focus"] = float(s[4]), float(s[5])
             loss += handle["guided_weight"] * handle["attention_loss"]
+        handle["stop_loss"] = handle["stop_step_error"] = None
+        if handle["stop_weight"] is not None:       # stop_token: the weighted term is in the loss, the two scalars here
+            handle["stop_loss"], handle["stop_step_error"] = float(s[6]), float(s[7])
+            loss += handle["stop_weight"] * handle["stop_loss"]
         return loss, mel_loss, lin_loss
 
     def step(self, inputs=None, input_lengths=None, mel_targets=None, linear_targets=None, grad_hook=None,

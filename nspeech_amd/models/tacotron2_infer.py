@@ -1,6 +1,7 @@
 """Free-running Tacotron-2 synthesis (tacotron2.py:15-128 with linear_targets=None):
 TacoTestHelper feeds the last predicted frame back (helpers.py:32-38) and the loop always runs
-max_iters steps (its stop test `all(outputs == 0.0)` never fires).  BatchNorm uses the
+max_iters steps (its stop test `all(outputs == 0.0)` never fires; with hparam stop_token the pass also leaves
+the step at which each utterance stops, _stop_token_infer, and the callers cut there).  BatchNorm uses the
 moving statistics.  Nothing can be hoisted out of the time loop here, so each step is a chain of
 single-step kernels from libnspeech_hip.so: skinny GEMMs, fused LSTM steps on [input | h_prev]
 rows, and the attention energy / context kernels."""
@@ -47,8 +48,8 @@ def _lstm_step(m, a, a_off, a_sn, K, wT, bias_off, c_prev, c_prev_off, c_sn, h_o
 def _decode_persistent(m, args):
     """The whole free-running decoder loop as ONE persistent launch (ns_taco2_decode, csrc/attn_cluster.hip "free-running
     decode"): attention-RNN clusters + register-resident decoder LSTMs + folded frame feedback.  args: the model's
-    attn_block().  Returns (dec, al, S1) in the [N, S+1, X] slot layout, or None when the shape is not covered (more than
-    two utterances, other widths)."""
+    attn_block().  Returns (dec, al, S1, h2) in the [N, S+1, X] slot layout, or None when the shape is not covered (more
+    than two utterances, other widths)."""
     import ctypes as C
     hp = m._hparams
     r, M, D = hp.outputs_per_step, hp.num_mels, hp.decoder_lstm_units
@@ -74,11 +75,12 @@ def _decode_persistent(m, args):
     dec = buf("dec_out", N * S1 * M * r, torch.float32)
     ops.gemm(h2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=o("decoder/output_projection/kernel"), bias=fp,
              bias_off=o("decoder/output_projection/bias"))
-    return dec, args["align"], S1
+    return dec, args["align"], S1, h2
 
 
 def _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t):
-    """One decoder step = 9 dependent launches; step s lives in slot s+1 of every [N, S+2, X] buffer (slot 0 = zeros)."""
+    """One decoder step = 9 dependent launches; step s lives in slot s+1 of every [N, S+2, X] buffer (slot 0 = zeros).
+    Returns (dec, al, h2)."""
     hp = m._hparams
     T_ = m.T
     r, M = hp.outputs_per_step, hp.num_mels
@@ -139,7 +141,25 @@ def _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t):
         # feed the last of the r frames back
         ops.copy3d(dec, xp, N, 1, M, (S1 * M * r, 0), (S1 * XP, 0), src_off=sl * M * r + (r - 1) * M, dst_off=nx * XP)
 
-    return dec, al
+    return dec, al, h2
+
+
+def _stop_token_infer(m, h2, S1):
+    """hparam stop_token: one ns_stop_token launch on the h2 history of whichever decode path ran ([N, S1, D], step s in
+    slot s + 1; fp32, or bf16 on the launch-per-step path of the bf16 mode) - fixed shapes, no host read, so it sits
+    inside the captured graph.  Leaves m.stop_logits [N, S], m.stop_steps int32 [N] (the first step whose stop
+    probability exceeds stop_threshold, counted from 1; S where none does) and m.decoder_h2 [N, S, D], the history used."""
+    hp = m._hparams
+    N, S, D = m.dims["N"], m.dims["S"], hp.decoder_lstm_units
+    logits = m._buf("stop_logits", N * S, torch.float32)
+    steps = m._buf("stop_steps", N, torch.int32)
+    work = m._buf("stop_work", ops.stop_token_work_floats(N, S, D), torch.float32)
+    ops.stop_token(N, S, D, h2, S1 * D, D, (m.flat_p, m._o(m.STOP_VARS[0])), (m.flat_p, m._o(m.STOP_VARS[1])), work,
+                   h_off=D, logits=logits, threshold=m.stop_threshold, stop_steps=steps)
+    m.stop_logits = logits[:N * S].view(N, S)
+    m.stop_steps = steps[:N]
+    m.decoder_h2 = h2[:N * S1 * D].view(N, S1, D)[:, 1:S + 1]
+
 
 def _rows32_ok(m, N):
     """The packed step products (ns_rows32) cover fp32 decoder activations on the matrix core (`mixed`, `bf16x3`)."""
@@ -231,7 +251,7 @@ def _decode_rows32(m, N, Ti, Pi, Tia, S, S1, enc, keys_t):
                    hp_sn=S1 * D, f32_passes=ps, a_rows=(x2[c], X2, 0), rows_out=(x2[n], X2, D))
     # the output projection over the whole history, off the loop's critical path
     ops.gemm(h2, fp, dec, N * S1, M * r, D, D, M * r, M * r, b_mode=1, b_off=kp, bias=fp, bias_off=bp)
-    return dec, al
+    return dec, al, h2
 
 
 def forward_infer(m):
@@ -304,13 +324,15 @@ def _infer_body(m):
     one_launch = getattr(m, "use_decode_kernel", True) and m.zoneout_rate <= 0.0
     done = _decode_persistent(m, m.attn_block(enc, keys, False)) if one_launch else None
     if done is not None:
-        dec, al, S1 = done
+        dec, al, S1, h2 = done
     elif _rows32_ok(m, N):
         m._per_step("decode", None, "rows32")
-        dec, al = _decode_rows32(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
+        dec, al, h2 = _decode_rows32(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
     else:
         m._per_step("decode", None)
-        dec, al = _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
+        dec, al, h2 = _decode_steps(m, N, Ti, Pi, Tia, S, S1, enc, keys_t)
+    if m.stop_token:
+        _stop_token_infer(m, h2, S1)
 
     # ---- postnet, residual, expand, linear head (inference BatchNorm), output views
     return m.tail(dec, al, S1, False)

@@ -380,6 +380,37 @@ def guided_attention(N, S, Tia, in_lengths, out_steps, sigma, align, da0, grad_s
     L.call("ns_guided_attention", p, stream())
 
 
+def stop_token_work_floats(N, S, D):
+    fn = L.lib().ns_stop_token_work_floats
+    fn.restype = C.c_size_t
+    return int(fn(int(N), int(S), int(D)))
+
+
+def stop_token(N, S, D, h, h_sn, h_ss, w, b, work, h_off=0, logits=None, out_steps=None, pos_weight=1.0, grad_scale=0.0,
+               dh=None, dh_off=0, dh_sn=0, dh_ss=0, dw=None, db=None, acc=None, acc_off=0, threshold=None,
+               stop_steps=None):
+    """The stop token's logits z[n, s] = h[n, s, :] . w + b of h (fp32 or bf16; element (n, s, d) at h_off + n * h_sn +
+    s * h_ss + d) and, in the same launch (ns_stop_token): logits fp32 [N, S]; training form (out_steps / dh / acc):
+    acc[acc_off] = L_stop, acc[acc_off + 1] = the mean stop-step error at threshold 0.5, and grad_scale times the
+    term's gradient added to dh (at dh_off, strides dh_sn / dh_ss), dw, db; synthesis form: stop_steps int32 [N] = the
+    first step whose probability exceeds `threshold` (0 < threshold < 1), counted from 1, or S.  w, b, dw, db:
+    (tensor, offset) pairs or tensors; out_steps device int32 [N] or None (S for every row); work: at least
+    stop_token_work_floats(N, S, D) fp32."""
+    import math
+
+    def pair(x):
+        return x if isinstance(x, tuple) else (x, 0)
+    p = L.struct("ns_stop_token_params")
+    _fill(p, N=N, S=S, D=D, h=ptr(h, h_off), h_dtype=dt(h), h_sn=h_sn, h_ss=h_ss, w=ptr(*pair(w)), b=ptr(*pair(b)),
+          logits=ptr(logits), out_steps=ptr(out_steps), pos_weight=pos_weight, grad_scale=grad_scale,
+          dh=ptr(dh, dh_off), dh_sn=dh_sn, dh_ss=dh_ss, dw=ptr(*pair(dw)), db=ptr(*pair(db)), acc=ptr(acc, acc_off),
+          stop_steps=ptr(stop_steps), work=ptr(work))
+    if threshold is not None:
+        p.threshold_logit = math.log(float(threshold) / (1.0 - float(threshold)))
+    assert work.dtype == torch.float32 and work.numel() >= stop_token_work_floats(N, S, D)
+    L.call("ns_stop_token", p, stream())
+
+
 def sumsq(x, n, out, out_off=0, work=None):
     p = L.struct("ns_sumsq_params")
     _fill(p, x=ptr(x), n=n, out=ptr(out, out_off), work=ptr(work))

@@ -8,7 +8,11 @@ WaveNet trained on mel local conditions (train_wavenet.py --hparams lc_channels=
 samples, a seed of receptive-field silence in front of row 0, T * hop samples drawn by the incremental generator.
 
 synthesize_batch(texts, speaker_ids) is the same for many texts: one model pass per 32 of them, one Griffin-Lim call
-(or one WaveNet generate) per pass and one audio.finish_waves for the inv_preemphasis / find_endpoint tail."""
+(or one WaveNet generate) per pass and one audio.finish_waves for the inv_preemphasis / find_endpoint tail.
+
+With hparam stop_token (Tacotron-2) the model also says at which decoder step each utterance stops
+(model.output_lengths()); synthesize / synthesize_stream / synthesize_batch then cut mel and lin there and hand the
+vocoder the cut arrays (use_stop_token=True, the default; False or a model without a stop token: the path as it was)."""
 import numpy as np
 import torch
 
@@ -161,8 +165,20 @@ class Synthesizer(object):
         return self._wavenet_vocode_batch(np.asarray(mel, np.float32)[None], seed=seed, global_conditions=global_conditions,
                                           temperature=temperature)[0]
 
-    def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True):
-        """vocoder="wavenet" (after load_vocoder): the mel output through the WaveNet; seed: of the draws' random stream
+    def _stop_frames(self, use_stop_token):
+        """Frames per row up to and including its stop step (model.output_lengths(), one host read), or None: the model
+        has no stop token, or the caller does not want it used - then nothing is cut."""
+        m = self.model
+        if not (use_stop_token and getattr(m, "stop_token", False)):
+            return None
+        return m.output_lengths()
+
+    def synthesize(self, text, speaker_id=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True,
+                   use_stop_token=True):
+        """use_stop_token (models with hparam stop_token only): mel and lin are cut to model.output_lengths()[0] frames
+        and the vocoder receives the cut arrays; inv_preemphasis and find_endpoint still run behind it and can only cut
+        further.  False, or a model without a stop token: all max_iters * outputs_per_step frames, as ever.
+        vocoder="wavenet" (after load_vocoder): the mel output through the WaveNet; seed: of the draws' random stream
         (generate(seed=)); temperature: of the draws (generate(temperature=): below 1 trades hiss for muffling, 0 is the
         deterministic argmax vocode); stop_at_endpoint: the generator applies find_endpoint's rule to its own output and
         stops drawing at the end of the first silent window, instead of drawing all T * hop samples and cutting on the
@@ -177,9 +193,11 @@ class Synthesizer(object):
         lengths = np.asarray([len(seq)], dtype=np.int32)
         m = self.model
         m.initialize(inputs, lengths, np.asarray([speaker_id], dtype=np.int32))
+        frames = self._stop_frames(use_stop_token)
+        keep = slice(None) if frames is None else slice(0, int(frames[0]))
         if vocoder == "wavenet":
-            mel = m.mel_outputs[0].float().cpu().numpy()
-            lin = m.linear_outputs[0].float().cpu().numpy()
+            mel = m.mel_outputs[0].float().cpu().numpy()[keep]
+            lin = m.linear_outputs[0].float().cpu().numpy()[keep]
             m.check_status()    # (as below: invalid outputs are never vocoded)
             gc = np.asarray([speaker_id]) if self.vocoder.gc else None
             if stop_at_endpoint:
@@ -188,17 +206,19 @@ class Synthesizer(object):
                 return wavs[0], mel, lin
             wav = self._wavenet_vocode(mel, seed=seed, global_conditions=gc, temperature=temperature)
             return wav[:audio.find_endpoint(wav)], mel, lin
-        wav = audio.inv_spectrogram_tensorflow(m.linear_outputs[0].contiguous())
-        mel = m.mel_outputs[0].float().cpu().numpy()
-        lin = m.linear_outputs[0].float().cpu().numpy()
+        wav = audio.inv_spectrogram_tensorflow(m.linear_outputs[0][keep].contiguous())
+        mel = m.mel_outputs[0].float().cpu().numpy()[keep]
+        lin = m.linear_outputs[0].float().cpu().numpy()[keep]
         m.check_status()        # after the host copies (stream synchronised): a persistent BiLSTM kernel that gave up
                                 # on an exchange leaves invalid outputs behind - never vocode those silently
         wav = audio.inv_preemphasis(wav.cpu().numpy())
         wav = wav[:audio.find_endpoint(wav)]
         return wav, mel, lin
 
-    def synthesize_stream(self, text, speaker_id=0, chunk_samples=None, seed=0, temperature=1.0, stop_at_endpoint=True):
-        """synthesize(text, vocoder="wavenet") heard while it is drawn (after load_vocoder; the same refusals).  The
+    def synthesize_stream(self, text, speaker_id=0, chunk_samples=None, seed=0, temperature=1.0, stop_at_endpoint=True,
+                          use_stop_token=True):
+        """synthesize(text, vocoder="wavenet") heard while it is drawn (after load_vocoder; the same refusals;
+        use_stop_token: synthesize's - the vocoder draws only the frames up to the stop step).  The
         Tacotron pass and check_status() run before this returns; the result is an iterable (SynthesisStream) with .mel
         and .lin set, whose iteration yields float32 pieces of the waveform, one per chunk_samples drawn samples (None:
         20 hops) - the vocoder's generate_stream, so the generator is never restarted and keeps drawing while a piece
@@ -216,15 +236,18 @@ class Synthesizer(object):
         m = self.model
         m.initialize(np.asarray([seq], dtype=np.int32), np.asarray([len(seq)], dtype=np.int32),
                      np.asarray([speaker_id], dtype=np.int32))
-        mel = m.mel_outputs[0].float().cpu().numpy()
-        lin = m.linear_outputs[0].float().cpu().numpy()
+        frames = self._stop_frames(use_stop_token)
+        keep = slice(None) if frames is None else slice(0, int(frames[0]))
+        mel = m.mel_outputs[0].float().cpu().numpy()[keep]
+        lin = m.linear_outputs[0].float().cpu().numpy()[keep]
         m.check_status()        # (as in synthesize: invalid outputs are never vocoded)
         gc = np.asarray([speaker_id]) if self.vocoder.gc else None
         seed_ids, n, kw = self._wavenet_vocode_args(mel[None], seed, gc, temperature, bool(stop_at_endpoint))
         chunk = 20 * self._vocoder_hop if chunk_samples is None else int(chunk_samples)
         return SynthesisStream(self.vocoder, self.vocoder.generate_stream(seed_ids, n, chunk, **kw), mel, lin, kw["endpoint"])
 
-    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True):
+    def synthesize_batch(self, texts, speaker_ids=0, vocoder="griffin_lim", seed=0, temperature=1.0, stop_at_endpoint=True,
+                         use_stop_token=True):
         """synthesize for a list of texts: [(wav, mel, lin)] in the order of `texts`, every entry with the shapes and
         dtypes synthesize returns.  speaker_ids: one int for all, or one id per text.  More than MAX_BATCH texts run as
         consecutive chunks of at most MAX_BATCH in the given order (never sorted: see below); [] returns [].
@@ -240,7 +263,13 @@ class Synthesizer(object):
         reference's graph would, and other kernels run at N > 2 than at N = 1 (model.last_paths["decode"]).  So entry i
         is close to synthesize(texts[i]), not bit-equal to it - and depends on which texts share its chunk.  The WaveNet
         rows of different batch sizes are not promised bit-equal either: the condition products are dispatched by
-        shape."""
+        shape.
+        use_stop_token (models with hparam stop_token only; False: the path above, bit for bit): still one model pass per
+        chunk; entry i's mel / lin are cut to its own length model.output_lengths()[i]; the vocoder runs once on the
+        chunk cut to its longest row, and wave i is cut to min(ends[i], the vocoder's length for row i's frame count):
+        audio.griffin_lim_length(frames) for Griffin-Lim, frames * hop for the WaveNet.  The WaveNet's generate offers
+        nothing for rows of unequal length (its local conditions are one [B, T, C] array), so it draws every row to the
+        longest row's length - or to its end point - and the cut happens here."""
         if vocoder not in ("griffin_lim", "wavenet"):
             raise ValueError("vocoder %r: 'griffin_lim' or 'wavenet'" % (vocoder,))
         texts = list(texts)
@@ -262,19 +291,27 @@ class Synthesizer(object):
             inputs, lengths = pad_text_batch(seqs[start:stop])
             spk = speakers[start:stop]
             m.initialize(inputs, lengths, spk)
+            frames = self._stop_frames(use_stop_token)
+            keep = slice(None) if frames is None else slice(0, int(frames.max()))
             if vocoder == "wavenet":
-                mels = m.mel_outputs.float().cpu().numpy()
-                lins = m.linear_outputs.float().cpu().numpy()
+                mels = m.mel_outputs.float().cpu().numpy()[:, keep]
+                lins = m.linear_outputs.float().cpu().numpy()[:, keep]
                 m.check_status()            # (as in synthesize: invalid outputs are never vocoded)
                 full = self._wavenet_vocode_batch(mels, seed=seed + start, global_conditions=spk if self.vocoder.gc else None,
                                                   temperature=temperature, endpoint=bool(stop_at_endpoint))
                 wavs = full[0] if stop_at_endpoint else [w[:audio.find_endpoint(w)] for w in full]
+                limit = None if frames is None else frames * self._vocoder_hop
             else:
-                y, ends = audio.finish_waves(audio.griffin_lim_gpu(m.linear_outputs))
+                y, ends = audio.finish_waves(audio.griffin_lim_gpu(m.linear_outputs[:, keep]))
                 y, ends = y.cpu().numpy(), ends.cpu().numpy()
-                mels = m.mel_outputs.float().cpu().numpy()
-                lins = m.linear_outputs.float().cpu().numpy()
+                mels = m.mel_outputs.float().cpu().numpy()[:, keep]
+                lins = m.linear_outputs.float().cpu().numpy()[:, keep]
                 m.check_status()            # after the host copies, before anything is handed out
                 wavs = [y[i, :int(ends[i])] for i in range(stop - start)]
-            out.extend((wavs[i], mels[i], lins[i]) for i in range(stop - start))
+                limit = None if frames is None else [audio.griffin_lim_length(int(f)) for f in frames]
+            if frames is None:
+                out.extend((wavs[i], mels[i], lins[i]) for i in range(stop - start))
+            else:
+                out.extend((wavs[i][:int(limit[i])], mels[i, :int(frames[i])], lins[i, :int(frames[i])])
+                           for i in range(stop - start))
         return out

@@ -398,6 +398,12 @@ def spectrogram_and_mel_device(y):
     return lin.view(-1, hp.num_freq), mel.view(-1, hp.num_mels)
 
 
+def griffin_lim_length(frames):
+    """Samples griffin_lim_gpu returns for a spectrogram of `frames` frames: (frames - 1) * hop + win."""
+    _, hop, win = _stft_parameters()
+    return (int(frames) - 1) * hop + win
+
+
 def griffin_lim_gpu(spec, iters=None, raw_magnitude=False, momentum=None):
     """spec: torch CUDA tensor or array [T, F] / [N, T, F] (normalised; with raw_magnitude the magnitudes S^power
     themselves).  Returns a CUDA tensor [L] / [N, L], L = (T-1)*hop + win, before inv_preemphasis (audio.py:51-58).

@@ -126,7 +126,8 @@ def write_summary(path, step, stats):
     """One JSON object per summary step in LOGDIR/events.jsonl: what the reference hands tf.summary.FileWriter
     (train.py:63,91-93; tacotron2.py:163-188) as scalars - loss, loss_mel, loss_linear, learning_rate,
     max_gradient_norm - plus the per-variable gradient norms and min / max / mean / std of the four value histograms, and
-    the two alignment scores loss_attention / attention_focus (hparam guided_attention_weight; computed at weight 0 too)."""
+    the two alignment scores loss_attention / attention_focus (hparam guided_attention_weight; computed at weight 0 too);
+    with hparam stop_token also loss_stop and stop_step_error, the stop token's loss and its mean stop-step error."""
     import json
     with open(path, "a") as f:
         f.write(json.dumps(dict(step=int(step), wall_time=time.time(), **stats)) + "\n")
