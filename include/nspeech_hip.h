@@ -663,7 +663,7 @@ typedef struct {
   void* ctx_rows; int ctx_rows_K, ctx_rows_col;
 } ns_attention_step_params;
 int ns_attention_step(const ns_attention_step_params* p, ns_stream_t stream);
-/* keys_t[n,u,t] = keys[n, padl+t, u] */
+/* keys_t[n,u,t] = keys[n, padl+t, u] for t < Ti; the columns [Ti, Tia) of keys_t are written as 0 */
 int ns_taco2_keys_transpose(const float* keys, float* keys_t, int N, int Ti, int Tia, int Pi, int padl, int A,
                             ns_stream_t stream);
 
@@ -698,7 +698,7 @@ typedef struct {
   float* part;
 } ns_attention_post_bwd_params;
 int ns_attention_post_bwd(const ns_attention_post_bwd_params* p, ns_stream_t stream);
-/* keys[n, padl+t, u] += keys_t[n,u,t] */
+/* keys[n, padl+t, u] += keys_t[n,u,t] for t < Ti (the columns [Ti, Tia) of keys_t are not read, no other row of keys is touched) */
 int ns_taco2_keys_transpose_add(float* keys, const float* keys_t, int N, int Ti, int Tia, int Pi, int padl, int A,
                                 ns_stream_t stream);
 

@@ -7,8 +7,8 @@ tests/test_attn_ref_cpu.py), through nspeech_amd.ops:
   cluster2  ns_taco2_attn_cluster_fwd / _bwd (csrc/attn_cluster.hip), A = 64 and A = 256, fp32 and bf16 storage
   cluster1  ns_taco1_attn_cluster_fwd / _bwd (csrc/attn_gru.hip), A = 256, fp32 and bf16 storage
   one       ns_attention_step with and without pv / E2 / pv_out, with ctx_out2, fp32 and bf16 values, and
-            ns_attention_step_bwd with has_carry 0 and 1.  ctx_rows is left out: it needs ns_rows32's packed rows, whose
-            layout tests/test_rows32_gpu.py owns.
+            ns_attention_step_bwd with has_carry 0 and 1.  ctx_rows is held by tests/test_decode_contract_gpu.py, beside
+            ns_rows32's packed rows whose layout tests/decode_ref.py states.
 Errors are measured against the references only, never against another kernel; every valid element of every output
 buffer is compared.
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from decode_ref import unpack_rows as _unpack_rows
 from nspeech_amd import ops
 from nspeech_amd._lib import ACT_NONE, ACT_RELU
 
@@ -13,15 +14,6 @@ pytestmark = pytest.mark.gpu
 
 def _rand(rng, *shape):
     return torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).cuda()
-
-
-def _unpack_rows(rows, K, N):
-    """Host-side reading of packed rows: [row tile][chunk][lane = g * 16 + r16][plane][8 bf16] -> hi + lo as float64 [N, K]."""
-    nkc = (K + 31) // 32
-    raw = rows.view(torch.bfloat16).float().cpu().numpy().astype(np.float64).reshape(2, nkc, 4, 16, 2, 8)
-    val = raw[:, :, :, :, 0, :] + raw[:, :, :, :, 1, :]            # [tile, kc, g, r16, j]
-    full = val.transpose(0, 3, 1, 2, 4).reshape(32, nkc * 32)      # [tile * 16 + r16, kc * 32 + g * 8 + j]
-    return full[:N, :K]
 
 
 @pytest.mark.parametrize("N,K,C", [(32, 1024, 256), (5, 256, 128), (17, 392, 72), (1, 2048, 16)])
