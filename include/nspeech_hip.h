@@ -233,7 +233,14 @@ int ns_bn_fwd(const ns_bn_fwd_params* p, ns_stream_t stream);
  * dgamma/dbeta/dbias += .  work = fp32[200*C] scratch (per-row-block partial sums, added up in a fixed order: every
  * output is bitwise repeatable; no need to clear it).
  * sum_dy / sum_dyxh (both or neither, fp32[C]): the column sums of dy and dy*xhat over the unmasked rows, as left by
- * the product that formed dy (ns_gemm_params.stat_z); without them a reduction pass over dy and z computes them. */
+ * the product that formed dy (ns_gemm_params.stat_z); without them a reduction pass over dy and z computes them.
+ * Given sums are used as they stand by the vector form (C % 4 == 0, ld_dy % 4 == 0, 16-byte aligned operands: dgamma /
+ * dbeta receive exactly one fp32 add of them) and recomputed from dy and z by the scalar form.
+ * `count` is used as given: it is not re-derived from the row mask.  The sums and dpre do not depend on the contents of
+ * masked rows of dy and z (they are not read); masked rows of dpre are written +0.
+ * dpre_dtype: 0, or NS_BF16 with dtype NS_F32; every other combination is NS_ERR_BAD_ARG.
+ * NULL dgamma / dbeta / dbias: that gradient is skipped.
+ * Tested element by element against a float64 contract by tests/test_pointwise_contract_gpu.py. */
 typedef struct {
   const float* dy; const void* z; void* dpre; int dtype;
   int rows, C;

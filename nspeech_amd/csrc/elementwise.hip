@@ -260,7 +260,8 @@ __global__ void bn_bwd_reduce_kernel(ns_bn_bwd_params p) {
   }
 }
 
-// pass 2: dz = gamma*istd*(dy - s1/M - xhat*s2/M); dpre = dz*act'(z); dbias += colsum(dpre)
+// pass 2: dz = gamma*istd*(dy - s1/M - xhat*s2/M); dpre = dz*act'(z); the block's column sums of dpre (the bias gradient)
+// are parked in work[(2*BN_MAX_BLOCKS + b)*C + c], behind the partials of pass 1, and added up in block order by pass 3
 template <typename T>
 __global__ void bn_bwd_apply_kernel(ns_bn_bwd_params p) {
   const T* z = (const T*)p.z;
@@ -301,12 +302,20 @@ __global__ void bn_bwd_apply_kernel(ns_bn_bwd_params p) {
         sb += (float)(T)d;
       }
     }
-    if (p.dbias) atomicAdd(p.dbias + c, sb);
+    if (p.dbias) p.work[(long)(2 * BN_MAX_BLOCKS + blockIdx.x) * p.C + c] = sb;
     if (blockIdx.x == 0) {
       if (p.dgamma) p.dgamma[c] += t2;
       if (p.dbeta) p.dbeta[c] += t1;
     }
   }
+}
+// pass 3: dbias += the row blocks' partial sums in block order (no float atomic: the result does not depend on timing)
+__global__ void bn_bwd_bias_kernel(ns_bn_bwd_params p, int nb) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= p.C) return;
+  float t = 0.f;
+  for (int b = 0; b < nb; ++b) t += p.work[(long)(2 * BN_MAX_BLOCKS + b) * p.C + c];
+  p.dbias[c] += t;
 }
 // Vector forms of the two passes for C % 4 == 0.  A block owns rows/32 rows x 64 channels and reduces through LDS; its
 // sums go to its own slot of `work` (no float atomics: they are slow when contended - MI355X_MICROARCH.md, Global
@@ -519,6 +528,8 @@ extern "C" int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t s_) {
   NS_CHECK_ARG(p && p->dy && p->z && p->dpre && p->mean && p->istd && p->gamma && p->work, "ns_bn_bwd: null");
   NS_CHECK_ARG(!p->sum_dy == !p->sum_dyxh, "ns_bn_bwd: sum_dy and sum_dyxh come together");
   NS_CHECK_ARG(p->ld_dy == 0 || p->ld_dy >= p->C, "ns_bn_bwd: ld_dy < C");
+  NS_CHECK_ARG(p->dpre_dtype == 0 || (p->dpre_dtype == NS_BF16 && p->dtype == NS_F32),
+               "ns_bn_bwd: dpre_dtype %d with dtype %d (0, or NS_BF16 with dtype NS_F32)", p->dpre_dtype, p->dtype);
   NS_CHECK_ARG(!p->no_finalize || (p->sum_dy && bn_bwd_vector_form(p)),
                "ns_bn_bwd: no_finalize needs sum_dy / sum_dyxh, C %% 4 == 0 and 16-byte aligned operands");
   if (bn_bwd_vector_form(p)) {
@@ -555,6 +566,8 @@ extern "C" int ns_bn_bwd(const ns_bn_bwd_params* p, ns_stream_t s_) {
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, *p);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, s, *p);
   }
+  // work: [0, 2*grid*C) the sums' partials | [64C, 64C + grid*C) the bias-gradient partials
+  if (p->dbias) hipLaunchKernelGGL(bn_bwd_bias_kernel, dim3(ceil_div(p->C, 256)), dim3(256), 0, s, *p, grid);
   NS_CHECK_LAUNCH("bn_bwd");
   return NS_OK;
 }

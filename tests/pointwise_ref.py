@@ -21,7 +21,12 @@ expected as they were, so comparing every element is also the margin check.  Thr
             only removes roundings.  The GPU test's bound is 2 x err (the second-order terms); float32 emulations of a
             correct kernel stay within 1 x err (worst ratios, measured by the CPU module over its association orders
             with and without FMA):
-              bn_fwd 0.920  adam 0.998  highway 0.997  act_bwd 0.853  gru_pointwise 0.995  random sums 0.014
+              bn_fwd 0.920  bn_bwd 0.915  adam 0.998  highway 0.997  act_bwd 0.853  gru_pointwise 0.995  random sums 0.014
+            BatchNorm backward (ns_bn_bwd / ns_bn_bwd_finalize): dpre carries the bound of its whole expression, the
+            error of the two column sums included where the call forms them (Exact, an arithmetic that asserts that no
+            operation rounds, replaces RunErr in its exact-by-construction cases); dgamma / dbeta are ONE fp32 add of
+            given sums - exact - or bounded sums; dbias is held to the column sums of the dpre that the same call stored
+            (check()), and bit for bit in the exact cases.
   A value stored as bf16 follows the "bf16 store" rule of tests/test_wavenet_contract_gpu.py (restated in accepts()).
 
 `mut` arguments select the WRONG kernels that the CPU module shows the comparison to reject; None is the contract.
@@ -121,12 +126,42 @@ class RunErr(object):
     def dot2(self, a, b, c, d):
         return self.add(self.mul(a, b), self.mul(c, d))
 
+    def colsum(self, a, n):
+        """Sum over axis 0 of n terms (the others are +0) in an unknown order: the terms' own errors and the module's
+        charge (n - 1) 2^-24 sum |x_i|."""
+        return (a[0].sum(0), a[1].sum(0) + max(n - 1, 0) * U * np.abs(a[0]).sum(0))
+
     def value(self, a):
         return a[0]
 
     def out(self, a, shape=None):
         v, e = np.broadcast_arrays(a[0], a[1])
         return v.astype(np.float64), e.astype(np.float64)
+
+
+def quantum(x):
+    """The largest power of two that divides every element of x (float64 values that are exact binary fractions)."""
+    x = np.abs(np.asarray(x, np.float64).reshape(-1))
+    x = x[x != 0]
+    q = 1.0
+    while x.size and (np.floor(x / q) != x / q).any():
+        q /= 2
+        assert q > 2.0 ** -60
+    return q
+
+
+class Exact(RunErr):
+    """Exact by construction, asserted and not assumed: every operation's result must be an fp32 number as it stands
+    (so no operation rounds, fused or not), every sum must meet assert_exact_sum on its terms' own quantum."""
+
+    def _r(self, v, e):
+        v = np.asarray(v, np.float64)
+        assert (v.astype(np.float32).astype(np.float64) == v).all(), "an intermediate is not an fp32 number"
+        return (v, np.zeros_like(v))
+
+    def colsum(self, a, n):
+        assert_exact_sum(np.abs(a[0]).sum(0), quantum(a[0]))
+        return self._r(a[0].sum(0), 0)
 
 
 class F32(object):
@@ -197,6 +232,20 @@ class F32(object):
         if not self.fma:
             return self.add(self.mul(a, b), self.mul(c, d))
         return self._fma(a, b, self.mul(c, d)) if self.order % 2 == 0 else self._fma(c, d, self.mul(a, b))
+
+    def colsum(self, a, n):
+        """float32 sums over axis 0 in four orders: forward, backward, NumPy's pairwise, 64 interleaved lanes."""
+        a = np.asarray(a, np.float32)
+        seq = lambda v: np.cumsum(v, 0, dtype=np.float32)[-1]
+        k = self.order % 4
+        if k == 0:
+            return seq(a)
+        if k == 1:
+            return seq(a[::-1])
+        if k == 2:
+            return np.add.reduce(a, 0, dtype=np.float32)
+        pad = np.concatenate([a, np.zeros((-len(a) % 64,) + a.shape[1:], np.float32)]).reshape((-1, 64) + a.shape[1:])
+        return seq(seq(pad))
 
     def value(self, a):
         return np.asarray(a, np.float64)
@@ -457,6 +506,140 @@ def expect_bn_fwd(c):
     out = {o: (v, e if e is not None else np.zeros_like(v)) for o, (v, e) in res.items() if o not in ("y_hi", "y_lo")}
     out["y_value"] = (yv, ye)              # the pre-split pair is held to it (pair_accepts) or to the kernel's own y
     return out
+
+
+# BatchNorm backward.  Host restatement of ns_bn_bwd's choice of kernels (bn_bwd_vector_form, bn_bwd_row_blocks and the
+# scalar form's grid in csrc/elementwise.hip): "vector" = bn_bwd_apply4_kernel + bn_bwd_finalize_kernel on the given sums,
+# "fallback" = the same behind bn_bwd_reduce4_kernel + ns_stats_finalize, "scalar" = bn_bwd_reduce_kernel +
+# bn_bwd_apply_kernel (+ the ordered bias pass), which recomputes given sums.  p["off"][buffer] is the element offset of
+# the operand in its buffer; every buffer itself is 16-byte aligned.
+BN_BWD_BUFFERS = ("dy", "z", "dpre", "mean", "istd", "gamma", "work", "sum_dy", "sum_dyxh")
+
+
+def bn_bwd_form(c, byte_offset=None):
+    """byte_offset(buffer) -> the operand's address modulo 16; None: from p["off"] and the element sizes."""
+    p, b = c["p"], c["bufs"]
+    size = lambda k: 2 if b[k][1] == "bf16" else 4
+    at = byte_offset or (lambda k: p["off"][k] * size(k) % 16)
+    al = lambda k, n: at(k) % n == 0
+    ok = p["C"] % 4 == 0 and p["ld_dy"] % 4 == 0 and al("dy", 16) and al("z", 4 * size("z")) and al("dpre", 4 * size("dpre"))
+    ok = ok and all(al(k, 16) for k in ("mean", "istd", "gamma", "work"))
+    if p["sums"]:
+        ok = ok and al("sum_dy", 16) and al("sum_dyxh", 16)
+    return ("vector" if p["sums"] else "fallback") if ok else "scalar"
+
+
+def bn_bwd_row_blocks(c):
+    """(row blocks, rows per block) of the case's form."""
+    rows = c["p"]["rows"]
+    nb = max(1, min(32, -(-rows // 64))) if bn_bwd_form(c) == "scalar" else max(1, min(64, -(-rows // 128)))
+    return nb, -(-rows // nb)
+
+
+def compute_bn_bwd(c, A, mut=None):
+    """include/nspeech_hip.h, ns_bn_bwd: modules.py:194-198 (y = BN(act(pre))) differentiated.  With V the rows that pass
+    the (period, lo, hi) test and xhat = (z - mean) * istd:
+        s1 = sum_V dy, s2 = sum_V dy * xhat (or the given sums as they stand - the vector form), 1 / count formed once and
+        multiplied with (two roundings), dz = gamma * istd * (dy - s1 / count - xhat * s2 / count), dpre = dz * act'(z) in
+        V and +0 elsewhere; act' through z as in compute_act_bwd.  Masked rows of dy and z are not looked at.
+    -> dict(dpre [rows, C], s1, s2 [C]: A values; given: the sums were taken as handed in)."""
+    p, b = c["p"], c["bufs"]
+    rows, C, act, off = p["rows"], p["C"], p["act"], p["off"]
+    vec = lambda name: A.lift(b[name][0][off[name]:off[name] + C])
+    ld = C if mut == "ld_ignored" else (p["ld_dy"] or C)
+    valid = row_valid(rows, p["row_mask"])[:, None]
+    look = np.ones_like(valid) if mut in ("sums_unmasked", "dpre_mask_ignored") else valid
+    dy = A.lift(np.where(look, b["dy"][0][off["dy"] + np.arange(rows)[:, None] * ld + np.arange(C)[None, :]], np.float32(0)))
+    z = A.lift(np.where(look, b["z"][0][off["z"]:off["z"] + rows * C].reshape(rows, C), np.float32(0)))
+    mean, istd, gamma = vec("mean"), vec("istd"), vec("gamma")
+    one, zero = A.lift(np.float32(1)), A.lift(np.zeros((rows, C), np.float32))
+    centred = A.sub(z, mean)
+    xhat = A.mul(centred, istd)
+    given = bool(p["sums"]) and bn_bwd_form(c) == "vector" and mut != "recompute_sums"
+    if given:
+        s1, s2 = vec("sum_dy"), vec("sum_dyxh")
+    else:
+        summed = np.ones_like(valid) if mut == "sums_unmasked" else valid
+        if mut == "drop_last_block":
+            nb, rpb = bn_bwd_row_blocks(c)
+            summed = summed & (np.arange(rows) < (nb - 1) * rpb)[:, None]
+        n = int(summed.sum())
+        s1 = A.colsum(A.where(summed, dy, zero), n)
+        s2 = A.colsum(A.where(summed, A.mul(dy, centred if mut == "s2_no_istd" else xhat), zero), n)
+    inv = A.div(one, A.lift(np.float32(rows if mut == "count_rows" else p["count"])))
+    inner = A.muladd([A.neg(xhat), A.mul(s2, inv)], A.sub(dy, A.mul(s1, inv)))
+    d = A.prod([gamma, inner] if mut == "no_istd_scale" else [gamma, istd, inner])
+    zv = A.value(z)
+    if act == ACT_RELU:
+        d = A.where((zv >= 0) if mut == "relu_at_zero" else (zv > 0), d, zero)
+    elif act == ACT_TANH:
+        d = A.mul(d, A.sub(one, z) if mut == "tanh_linear" else A.muladd([A.neg(z), z], one))
+    elif act == ACT_SIGMOID:
+        d = A.prod([d, z, A.add(one, z) if mut == "sigmoid_plus" else A.sub(one, z)])
+    elif act == ACT_SOFTSIGN:
+        f = A.sub(one, A.abs(z))
+        d = A.mul(d, f) if mut == "softsign_unsquared" else A.prod([d, f, f])
+    return dict(dpre=d if mut == "dpre_mask_ignored" else A.where(valid, d, zero), s1=s1, s2=s2, given=given)
+
+
+def _bn_bwd_slots(c):
+    p = c["p"]
+    return {k: slice(p["off"][k], p["off"][k] + p["C"]) for k in ("dgamma", "dbeta", "dbias") if k in c["bufs"]}
+
+
+def emulate_bn_bwd(c, A, mut=None):
+    """What a float32 kernel that evaluates the contract with arithmetic A leaves in every output buffer."""
+    p, b = c["p"], c["bufs"]
+    rows, C, off = p["rows"], p["C"], p["off"]
+    with np.errstate(all="ignore"):
+        r = compute_bn_bwd(c, A, mut)
+        got = {o: b[o][0].copy() for o in c["outs"]}
+        d32 = np.broadcast_to(A.out(r["dpre"]), (rows, C)).astype(np.float32)
+        stored = store(d32, b["dpre"][1])
+        got["dpre"][off["dpre"]:off["dpre"] + rows * C] = stored.reshape(-1)
+        s1, s2 = np.asarray(A.out(r["s1"]), np.float32), np.asarray(A.out(r["s2"]), np.float32)
+        if mut == "swapped":
+            s1, s2 = s2, s1
+        sb = F32(getattr(A, "order", 0)).colsum(d32 if mut == "dbias_unrounded" else stored, rows)
+        for k, sl in _bn_bwd_slots(c).items():
+            old = np.float32(0) if mut == "overwrite" else b[k][0][sl]
+            got[k][sl] = old + dict(dgamma=s2, dbeta=s1, dbias=sb)[k]              # one fp32 add
+    return got
+
+
+def expect_bn_bwd(c):
+    """dpre: bounded (exact in the exact cases).  dgamma / dbeta: exactly one fp32 add of the given sums (vector form), else
+    bounded.  dbias: in the exact cases the exact sum of the stored dpre; otherwise check() holds it to the kernel's own
+    stored dpre (the header's "summed on the rounded values") and expect() has no entry for it.  work: see check()."""
+    p, b = c["p"], c["bufs"]
+    rows, C, off = p["rows"], p["C"], p["off"]
+    A = Exact() if c["exact"] else RunErr()
+    r = compute_bn_bwd(c, A)
+    res = {"work": (b["work"][0].astype(np.float64), None)}
+    v, e = A.out(r["dpre"])
+    val, err = b["dpre"][0].astype(np.float64), np.zeros(b["dpre"][0].shape)
+    sl = slice(off["dpre"], off["dpre"] + rows * C)
+    val[sl], err[sl] = np.broadcast_to(v, (rows, C)).reshape(-1), np.broadcast_to(e, (rows, C)).reshape(-1)
+    res["dpre"] = (val, None if c["exact"] else err)
+    stored = store(val[sl].astype(np.float32), b["dpre"][1]).astype(np.float64).reshape(rows, C)
+    for k, sl in _bn_bwd_slots(c).items():
+        val, err = b[k][0].astype(np.float64), np.zeros(b[k][0].shape)
+        if k == "dbias":
+            if not c["exact"]:
+                continue
+            assert_exact_sum(np.abs(stored).sum(0) + np.abs(val[sl]), quantum(np.concatenate([stored.reshape(-1), val[sl]])))
+            val[sl] += stored.sum(0)
+            res[k] = (val, None)
+            continue
+        s = r["s2"] if k == "dgamma" else r["s1"]
+        if r["given"]:
+            val[sl] += s[0]                       # two fp32 numbers: their float64 sum is exact, float32() of it the one add
+            res[k] = (val, None)
+        else:
+            v, e = A.out(A.add(A.lift(val[sl]), s))
+            val[sl], err[sl] = v, e
+            res[k] = (val, None if c["exact"] else err)
+    return res
 
 
 def expect_colsum(c, mut=None):
@@ -783,7 +966,8 @@ def expect_zero(c):
 EXPECT = dict(copy3d=expect_copy3d, embedding_fwd=expect_embedding_fwd, embedding_bwd=expect_embedding_bwd,
               bn_fwd=expect_bn_fwd, colsum=expect_colsum, l1_loss=expect_l1_loss, sumsq=expect_sumsq,
               segment_stats=expect_segment_stats, adam=expect_adam, cast2d=expect_cast2d, split_hi_lo=expect_split,
-              gru_pointwise=expect_gru_pointwise, highway=expect_highway, act_bwd=expect_act_bwd, zero=expect_zero)
+              gru_pointwise=expect_gru_pointwise, highway=expect_highway, act_bwd=expect_act_bwd, zero=expect_zero,
+              bn_bwd=expect_bn_bwd)
 
 
 def expect(c):
@@ -1258,6 +1442,150 @@ def act_bwd_cases():
     return out
 
 
+def _bn_bwd_case(name, rows, C, act, dt="f32", ddt=None, mask=None, sums=None, ld=0, col0=0, shift=None, null=(),
+                 no_finalize=False, exact=False, count=None, wrong_sums=False, seed=140):
+    """The name's prefix says which kernels the case must reach (asserted against bn_bwd_form).  shift: the one operand
+    that starts one element off alignment.  Masked rows of dy and z hold 1e30, the columns of a wide dy outside the block
+    NaN, `work` is 200 * C NaNs between sentinels (the guard tail behind it must survive), the gradients are prefilled."""
+    form, ddt = name.split("-")[0], ddt or dt
+    sums = (form == "vector") if sums is None else sums
+    rng = np.random.RandomState(seed)
+    valid = row_valid(rows, mask)
+    nv = int(valid.sum())
+    if exact:
+        assert count or (nv & (nv - 1)) == 0, "the mask makes the count a power of two"
+        half = lambda *shape: (rng.randint(-2, 3, shape) * 0.5).astype(np.float32)
+        z, dy, mean = half(rows, C), half(rows, C), half(C)
+        istd = (2.0 ** rng.randint(-1, 2, C)).astype(np.float32)
+        gamma = (2.0 ** rng.randint(-1, 2, C) * (2 * rng.randint(0, 2, C) - 1)).astype(np.float32)
+        grad = lambda: unit_values(C, rng.randint(1 << 20))
+    else:
+        x = rng.randn(rows, C)
+        z = {ACT_RELU: np.maximum(x, 0), ACT_TANH: np.tanh(x), ACT_SIGMOID: 1 / (1 + np.exp(-x)),
+             ACT_SOFTSIGN: x / (1 + np.abs(x))}.get(act, x).astype(np.float32)
+        tiny = np.float32(2.0 ** -126)                  # the smallest positive normal of fp32 and of bf16 alike
+        special = {ACT_RELU: [0, tiny, 0, tiny], ACT_TANH: [1, -1, 0], ACT_SIGMOID: [0, 1, 1], ACT_SOFTSIGN: [1, -1]}.get(act, [])
+        vr = np.flatnonzero(valid)
+        for i, v in enumerate(special):
+            z[vr[i % len(vr)], (3 * i + 1) % C] = v
+        z = rne_bf16(z) if dt == "bf16" else z
+        dy = rng.randn(rows, C).astype(np.float32)
+        mean = (z[valid].mean(0) + 0.1 * rng.randn(C)).astype(np.float32)
+        istd, gamma = (0.5 + rng.rand(C)).astype(np.float32), (1 + 0.3 * rng.randn(C)).astype(np.float32)
+        grad = lambda: rng.randn(C).astype(np.float32)
+    xhat = (z.astype(np.float64) - mean) * istd
+    s1, s2 = (dy * valid[:, None]).sum(0, dtype=np.float64), (dy * xhat * valid[:, None]).sum(0)
+    if wrong_sums:
+        s1, s2 = rng.randn(C), rng.randn(C)
+    z[~valid] = rne_bf16(np.float32(1e30))
+    dy[~valid] = 1e30
+    if ld:
+        wide = np.full((rows, ld), np.nan, np.float32)
+        wide[:, col0:col0 + C] = dy
+        dy = wide
+    off, bufs = {}, {}
+
+    def put(k, x, d="f32"):
+        sh = 1 if shift == k else 0
+        bufs[k] = (framed(np.concatenate([np.full(sh, SENT, np.float32), np.asarray(x, np.float32).reshape(-1)])), d)
+        off[k] = MARGIN + sh + (col0 if k == "dy" else 0)
+    put("dy", dy), put("z", z, dt), put("dpre", np.full(rows * C, SENT), ddt)
+    put("mean", mean), put("istd", istd), put("gamma", gamma), put("work", np.full(200 * C, np.nan))
+    if sums:
+        put("sum_dy", s1), put("sum_dyxh", s2)
+    for k in ("dgamma", "dbeta", "dbias"):
+        if k not in null:
+            put(k, grad())
+    c = case("bn_bwd", name, dict(rows=rows, C=C, count=float(count or max(1, nv)), act=act, row_mask=mask, dtype=dt, ld_dy=ld,
+                                  sums=bool(sums), no_finalize=no_finalize, off=off), bufs,
+             ["dpre", "work"] + [k for k in ("dgamma", "dbeta", "dbias") if k in bufs], exact)
+    assert bn_bwd_form(c) == form, (name, bn_bwd_form(c))
+    return c
+
+
+def bn_bwd_cases():
+    """Chosen from ns_bn_bwd's conditions.  Scalar form: min(32, ceil(rows / 64)) row blocks of ceil(rows / blocks) rows -
+    65: 33 + 32; 2049: 32 blocks of 65, the last of 34 - and a channel loop of 256 threads (C = 258: a second trip of two).
+    Vector forms: min(64, ceil(rows / 128)) row blocks x ceil(C / 64) column blocks of 16 quads x 16 row lanes, 64 rows per
+    trip - 128: one block; 129: two of 65 and 64, so one lane takes a second trip; 300: three; 8193: 64 of 129 (the finaliser's
+    eight lanes add eight blocks each; ns_stats_finalize's 32 lanes two slots each); C = 4 one quad, 68 a second column block
+    with one quad and a ragged 32-column finaliser block, 132 a third.  Masks: (10, 2, 9) and (7, 3, 7) do not divide the
+    rows, (10, 0, 7) lo = 0, (7, 3, 7) hi = period, (700, 0, 500) and (3000, 0, 2600) leave whole row blocks invalid."""
+    N, R, T, S, Q = ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_SOFTSIGN
+    one = _bn_bwd_case
+    out = [one("scalar-C6-rows70-tanh-mask", 70, 6, T, mask=(10, 2, 9)),
+           one("scalar-C258-rows3-sigmoid", 3, 258, S, seed=141),
+           one("scalar-C8-ld10-none", 5, 8, N, ld=10, seed=142),
+           one("scalar-C6-ld9-col2-tanh-mask", 70, 6, T, ld=9, col0=2, mask=(7, 3, 7), seed=143),
+           one("scalar-C6-rows1-softsign", 1, 6, Q, seed=144),
+           one("scalar-C6-rows65-relu", 65, 6, R, seed=145),
+           one("scalar-C6-rows2049-none-mask", 2049, 6, N, mask=(700, 0, 500), seed=146),
+           one("scalar-C6-rows70-sums-given-tanh-mask", 70, 6, T, mask=(10, 0, 7), sums=True, seed=147),
+           one("scalar-C6-rows130-bf16-relu-mask", 130, 6, R, dt="bf16", mask=(10, 2, 9), seed=148),
+           one("scalar-C6-rows130-bf16dpre-sigmoid", 130, 6, S, ddt="bf16", seed=149),
+           one("scalar-exact-C6-rows160-relu", 160, 6, R, mask=(10, 2, 6), exact=True, seed=150),
+           one("scalar-exact-C6-rows160-count128-none", 160, 6, N, mask=(50, 0, 49), count=128, exact=True, seed=151)]
+    for i, k in enumerate(("z", "dy", "dpre", "mean", "istd", "gamma", "work")):
+        out.append(one("scalar-C8-shifted-%s" % k, 67, 8, (T, R, S, Q, N)[i % 5], shift=k, mask=(10, 2, 9), seed=152 + i))
+    out.append(one("scalar-C8-shifted-sum_dy", 67, 8, T, shift="sum_dy", sums=True, seed=159))
+    for k in ("dgamma", "dbeta", "dbias"):
+        out.append(one("scalar-C6-rows70-no-%s" % k, 70, 6, T, mask=(10, 2, 9), null=(k,), seed=160))
+    for form in ("vector", "fallback"):
+        sd = 170 if form == "vector" else 200
+        out += [one(form + "-C4-rows1-none", 1, 4, N, seed=sd),
+                one(form + "-C68-rows128-tanh-mask", 128, 68, T, mask=(10, 0, 7), seed=sd + 1),
+                one(form + "-C132-rows129-sigmoid-mask", 129, 132, S, mask=(7, 3, 7), seed=sd + 2),
+                one(form + "-C8-rows8193-relu-mask", 8193, 8, R, mask=(3000, 0, 2600), seed=sd + 3),
+                one(form + "-C68-rows300-bf16-softsign-mask", 300, 68, Q, dt="bf16", mask=(10, 2, 9), seed=sd + 4),
+                one(form + "-C68-rows300-bf16dpre-relu-ld80-col8", 300, 68, R, ddt="bf16", ld=80, col0=8, seed=sd + 5),
+                one(form + "-exact-C68-rows160-relu", 160, 68, R, mask=(10, 2, 6), exact=True, seed=sd + 6),
+                one(form + "-exact-C68-rows160-count128-none", 160, 68, N, mask=(50, 0, 49), count=128, exact=True, seed=sd + 7),
+                one(form + "-exact-C8-rows160-bf16dpre-none", 160, 8, N, ddt="bf16", mask=(10, 2, 6), exact=True, seed=sd + 8)]
+        for k in ("dgamma", "dbeta", "dbias"):
+            out.append(one(form + "-C8-rows70-no-%s" % k, 70, 8, T, mask=(10, 2, 9), null=(k,), seed=sd + 9))
+    out += [one("vector-C68-rows300-split-tanh-mask", 300, 68, T, mask=(10, 2, 9), no_finalize=True, seed=190),
+            one("vector-C8-rows8193-split-bf16dpre-none", 8193, 8, N, ddt="bf16", no_finalize=True, seed=191),
+            one("vector-C4-rows1-split-relu", 1, 4, R, no_finalize=True, seed=192),
+            one("vector-C68-rows300-sums-not-the-column-sums", 300, 68, T, mask=(10, 2, 9), wrong_sums=True, seed=193)]
+    return out
+
+
+def _bn_bwd_resum(c):
+    """The given sums of a probe: the column sums of its own dy."""
+    if not c["p"]["sums"]:
+        return c
+    p, b, off = c["p"], c["bufs"], c["p"]["off"]
+    rows, C = p["rows"], p["C"]
+    get = lambda k, n: b[k][0][off[k]:off[k] + n].astype(np.float64)
+    valid = row_valid(rows, p["row_mask"])[:, None]
+    dy = np.where(valid, get("dy", rows * C).reshape(rows, C), 0)
+    xhat = np.where(valid, (get("z", rows * C).reshape(rows, C) - get("mean", C)) * get("istd", C), 0)
+    for k, s in (("sum_dy", dy.sum(0)), ("sum_dyxh", (dy * xhat).sum(0))):
+        x = b[k][0].copy()
+        x[off[k]:off[k] + C] = s
+        b[k] = (x, "f32")
+    return c
+
+
+def bn_bwd_probes():
+    """dy = 0 but a single 1, on the count-128 exact cases (160 rows, rows 49, 99, 149 masked).  Scalar: 3 row blocks of 54,
+    54 and 52 rows.  Vector forms: 2 row blocks of 80 rows - lane l of 16 takes rows l, l + 16, l + 32, l + 48 (the four
+    unrolled slots) and l + 64 (a second trip) of its block - and columns 0 - 63 | 64 - 67.  A row counted twice or dropped
+    makes s1 differ from 1 and shows in every dpre of the column; a masked row's 1 changes nothing."""
+    out = []
+    base = {c["name"]: c for c in bn_bwd_cases()}
+    vec = [("block0-first", 0, 0), ("slot1", 16, 1), ("slot2", 32, 2), ("slot3", 48, 3), ("quad-first", 48, 4), ("lane15", 15, 7),
+           ("lane15-slot3", 63, 8), ("second-trip", 64, 12), ("block0-last", 79, 63), ("block1-first", 80, 64),
+           ("last-valid", 159, 67), ("masked", 99, 5), ("colblock-last", 100, 63), ("colblock-first", 100, 64)]
+    for form in ("fallback", "vector"):
+        at = [(k, MARGIN + r * 68 + ch) for k, r, ch in (vec if form == "fallback" else vec[::3] + vec[-3:-2])]
+        out += probes(base[form + "-exact-C68-rows160-count128-none"], "dy", at)
+    sc = [("block0-first", 0, 0), ("block0-last", 53, 5), ("block1-first", 54, 0), ("block1-last", 107, 2), ("block2-first", 108, 1),
+          ("last-valid", 159, 5), ("masked", 99, 3)]
+    out += probes(base["scalar-exact-C6-rows160-count128-none"], "dy", [(k, MARGIN + r * 6 + ch) for k, r, ch in sc])
+    return [_bn_bwd_resum(c) for c in out]
+
+
 ZERO_BYTES = (16, 48, 4096 + 16, (1 << 20) + 16)
 
 
@@ -1308,6 +1636,21 @@ def check(c, got, factor=2.0):
                 v = pair_accepts(hi, lo, exp["y_value"][0].reshape(-1), exp["y_value"][1].reshape(-1), factor)
             m = Verdict(_margins(got["y_hi"], n).ok and _margins(got["y_lo"], n).ok, 0.0, "a margin was written")
             res["y_hi"] = v if not v.ok or m.ok else m
+        elif c["op"] == "bn_bwd" and o == "work":      # 200 * C floats that the call may use as it likes; nothing beyond them
+            at, n = c["p"]["off"]["work"], 200 * c["p"]["C"]
+            same = bits_equal(got[o], c["bufs"][o][0])
+            res[o] = Verdict(bool(same[:at].all() and same[at + n:].all()), 0.0, "written outside its 200 * C floats")
+        elif c["op"] == "bn_bwd" and o == "dbias" and not c["exact"]:
+            # += the column sums of dpre AS STORED BY THIS CALL (held to the reference on its own), in an unknown order
+            p = c["p"]
+            sl, at = _bn_bwd_slots(c)[o], p["off"]["dpre"]
+            d = got["dpre"][at:at + p["rows"] * p["C"]].astype(np.float64).reshape(p["rows"], p["C"])
+            val, err = c["bufs"][o][0].astype(np.float64), np.zeros(c["bufs"][o][0].shape)
+            n = int(row_valid(p["rows"], p["row_mask"]).sum()) + 1                       # the prefill is a term
+            with np.errstate(invalid="ignore", over="ignore"):                           # (a wrong kernel's infinities)
+                err[sl] = sum_expect(None, np.abs(d).sum(0) + np.abs(val[sl]), n, False)
+                val[sl] += d.sum(0)
+            res[o] = accepts(got[o], val, err, dt, factor)
         else:
             val, err = exp[o]
             res[o] = accepts(got[o], val, err, dt, factor)

@@ -1,6 +1,8 @@
 """BatchNorm backward with the column sums out of the PRODUCING product (ns_gemm stat_z -> ns_bn_bwd sum_dy / sum_dyxh,
 modules.py:198 backward) against a float64 restatement, on every kernel family that forms a dy in the training step;
-the stand-alone reduction fallback; bitwise repeatability (no float atomics); the vector form of ns_cast2d."""
+the stand-alone reduction fallback; bitwise repeatability (no float atomics); the vector form of ns_cast2d.
+The tolerances here are whole-tensor ones; the per-element contract of ns_bn_bwd - every kernel form, activation, dtype
+pair and option - lives in tests/pointwise_ref.py and tests/test_pointwise_contract_gpu.py."""
 import numpy as np
 import pytest
 import torch

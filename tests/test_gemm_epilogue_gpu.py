@@ -322,6 +322,46 @@ def test_gemm_epilogue(dev, monkeypatch, form, opt):
         assert int(counters.abs().max().item()) == 0
 
 
+# ------------------------------------------------------------------ the BatchNorm finaliser folded into the statistics' second stage
+# ns_gemm_params.bn: gemm_stats_finalize_kernel goes on from a column's sums to mean / 1/std and the moving statistics.
+# 64-row slots: 2200 rows are 35 (more than the 32 slot lanes: the strided slot loop), 130 rows 3; N = 36 leaves a ragged
+# second block of 32 columns.  The four outputs are held to pointwise_ref.bn_finalize applied to the col_sum / col_sumsq
+# that the SAME call returned (which test_gemm_epilogue holds to float64 sums), at the bound of the bn_fwd contract.
+@pytest.mark.parametrize("rows,N,dtype", [(2200, 128, f32), (130, 512, bf), (2200, 36, f32)],
+                         ids=["35-slots", "3-slots", "N36"])
+def test_bn_fold_against_the_bn_fwd_contract(dev, rows, N, dtype):
+    import numpy as np
+    import pointwise_ref as P
+    from nspeech_amd import ops
+    K, mask = 64, (110, 3, 104, 0)
+    g = _gen(rows + N)
+    A = (torch.randn(rows, K, generator=g) * 0.3).to(dtype).to(dev)
+    B = (torch.randn(N, K, generator=g) * 0.3).to(dtype).to(dev)
+    bias = (torch.randn(N, generator=g) * 0.1).to(dev)
+    mm0, mv0 = 0.1 * torch.randn(N, generator=g), 1.0 + 0.2 * torch.rand(N, generator=g)
+    count = float(R.valid_rows(rows, mask).sum())
+    z = torch.full((rows, N), float("nan"), dtype=dtype, device=dev)
+    st = torch.full((4 * N + 8,), float("nan"), device=dev)
+    st[4 * N:] = SENTINEL
+    mm, mv = mm0.to(dev), mv0.to(dev)
+    ops.gemm(A, B, z, rows, N, K, K, K, N, bias=bias, act=R.ACT_RELU, row_mask=mask, col_sum=st, col_sumsq=st[N:], f32_passes=0,
+             bn=dict(count=count, training=True, moving_mean=mm, moving_var=mv, mean_out=st[2 * N:], istd_out=st[3 * N:]))
+    torch.cuda.synchronize()
+    got = st.cpu().numpy()
+    assert (got[4 * N:] == SENTINEL).all()
+    fr = lambda x: (P.framed(np.asarray(x, np.float32)), "f32")
+    c = dict(p=dict(C=N, training=1, count=count, momentum=0.99, eps=1e-3),
+             bufs=dict(col_sum=fr(got[:N]), col_sumsq=fr(got[N:2 * N]), moving_mean=fr(mm0.numpy()), moving_var=fr(mv0.numpy())))
+    want = P.bn_finalize(P.RunErr(), c)
+    have = (got[2 * N:3 * N], got[3 * N:4 * N], mm.cpu().numpy(), mv.cpu().numpy())
+    for name, w, h in zip(("mean_out", "istd_out", "moving_mean", "moving_var"), want, have):
+        val, err = P.RunErr().out(w)
+        v = P.accepts(h, val, err, "f32", 2.0)
+        print("BN FOLD %s %-12s error / bound %.3f" % ((rows, N), name, v.worst))
+        assert v.ok, (name, v.why)
+    assert not np.array_equal(mm.cpu().numpy(), mm0.numpy())
+
+
 # ------------------------------------------------------------------ refusals: an argument error, and nothing launched
 def _refused(dev, M=64, N=128, K=64, dtype=bf, c_dtype=f32, presplit=False, **kw):
     from nspeech_amd import ops

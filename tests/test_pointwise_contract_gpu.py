@@ -1,6 +1,7 @@
-"""Every kernel body of csrc/elementwise.hip, and ns_zero / ns_zero_many of core.hip, against the float64 contract of
-tests/pointwise_ref.py (itself proven by tests/test_pointwise_ref_cpu.py), through nspeech_amd.ops - and through the
-parameter block directly where a form has no wrapper argument (ns_colsum without `work`).
+"""Every kernel body of csrc/elementwise.hip - but ns_dropout_rows, which tests/test_prenet_dropout_contract_gpu.py holds
+to its own contract - and ns_zero / ns_zero_many of core.hip, against the float64 contract of tests/pointwise_ref.py
+(itself proven by tests/test_pointwise_ref_cpu.py), through nspeech_amd.ops - and through the parameter block directly
+where a form has no wrapper argument (ns_colsum without `work`).
 
 For every case: every buffer the call sees sits between MARGIN sentinels, and the expectation covers the WHOLE buffer, so
 the margins, the padding behind a row, the columns a leading dimension leaves out and the pad rows of a padded layout are
@@ -25,6 +26,22 @@ Worst error / bound on the MI355X (every test prints its own, `pytest -s`; the b
                             4 / 1 048 202; every other value of every bf16 buffer is bf16(reference)
 0.50 is a kernel whose single worst element sits at the first-order bound (one half-ulp rounding of an expression with
 one operation: gru mode 0, highway dx); nothing exceeds it.
+
+BatchNorm backward (ns_bn_bwd, ns_bn_bwd_finalize and their use of ns_stats_finalize; 51 cases and 27 one-hot probes, each
+launched twice, the second time on the work area the first launch left; 80 tests in 2.1 s on the MI355X, the slowest
+0.16 s).  `work` is 200 * C NaNs followed by a guard tail of sentinels, the gradients are prefilled, masked rows of dy and z
+hold 1e30 and the columns of a wide dy outside the block NaN.  Worst error / bound per form:
+                 dpre fp32   dpre bf16 (neighbours / computed)   dgamma   dbeta   dbias (against the call's own dpre)
+  scalar           0.23          0 / 1 043                        0.35     0.36     0.32
+  vector (sums)    0.46          0 / 89 955                       exact    exact    0.44
+  fallback         0.06          1 / 24 523                       0.24     0.10     0.42
+  and 0 of every element differs in the nine exact-by-construction cases and the probes, dbias included.
+Found: no kernel computes a wrong value.  The scalar form's dbias met in one float atomicAdd per row block, against the
+header's "every output is bitwise repeatable": on the parent commit 20 launches of the 32-block case gave 20 different bit
+patterns of dbias (all within the bound; dpre, dgamma, dbeta repeated).  The row blocks park their partial sums in `work`
+now and a third launch adds them in block order; test_bn_bwd_scalar_32_blocks_three_times guards that, and the proof is
+that ns_bn_bwd reaches no float atomic.  A dpre_dtype outside the documented pair was ignored; it is refused now
+(tests/test_bn_bwd_abi_cpu.py).
 """
 import ctypes
 import functools
@@ -208,6 +225,31 @@ def _act_bwd(c, d):
     _ops().act_bwd(d["dy"][M:], d["y"][M:], d["dpre"][M:], p["rows"], p["C"], p["act"], row_mask=p["row_mask"])
 
 
+_BN_WORK = {}                          # case name -> the work area its first launch left behind
+
+
+def _bn_bwd(c, d):
+    """ops.bn_bwd (every NULL gradient and dpre_dtype are expressible through it).  The second launch of a case runs on
+    the work area that the first one used, as it was left.  no_finalize: the three gradients are bit-identical after the
+    first call; ops.bn_bwd_finalize on the returned block then adds them."""
+    p, ops = c["p"], _ops()
+    off = p["off"]
+    d["work"] = _BN_WORK.setdefault(c["name"], d["work"])
+    inner = lambda k: d[k][off[k]:] if k in d else None
+    form = R.bn_bwd_form(c, lambda k: (d[k].data_ptr() + off[k] * d[k].element_size()) % 16)
+    assert form == c["name"].split("-")[0] == R.bn_bwd_form(c), (c["name"], form)
+    blk = ops.bn_bwd(d["dy"], inner("z"), inner("dpre"), p["rows"], p["C"], inner("mean"), inner("istd"), d["gamma"], d.get("dgamma"),
+                     d.get("dbeta"), d.get("dbias"), inner("work"), p["count"], p["act"], row_mask=p["row_mask"],
+                     gamma_off=off["gamma"], dgamma_off=off.get("dgamma", 0), dbeta_off=off.get("dbeta", 0),
+                     dbias_off=off.get("dbias", 0), sums=(inner("sum_dy"), inner("sum_dyxh")) if p["sums"] else None,
+                     dy_off=off["dy"], ld_dy=p["ld_dy"], no_finalize=p["no_finalize"])
+    if p["no_finalize"]:
+        torch.cuda.synchronize()
+        for k in ("dgamma", "dbeta", "dbias"):
+            assert R.bits_equal(d[k].cpu().numpy(), c["bufs"][k][0]).all(), (c["name"], k, "written before the finaliser ran")
+        ops.bn_bwd_finalize(blk)
+
+
 def _zero(c, d):
     ops, p, buf = _ops(), c["p"], d["buf"]
     if not p["many"]:
@@ -222,7 +264,7 @@ def _zero(c, d):
 
 CALL = dict(copy3d=_copy3d, embedding_fwd=_embedding_fwd, embedding_bwd=_embedding_bwd, bn_fwd=_bn_fwd, colsum=_colsum,
             l1_loss=_l1_loss, sumsq=_sumsq, segment_stats=_segment_stats, adam=_adam, cast2d=_cast2d, split_hi_lo=_split,
-            gru_pointwise=_gru_pointwise, highway=_highway, act_bwd=_act_bwd, zero=_zero)
+            gru_pointwise=_gru_pointwise, highway=_highway, act_bwd=_act_bwd, zero=_zero, bn_bwd=_bn_bwd)
 
 
 # ------------------------------------------------------------------------------------------------------ the cases
@@ -274,6 +316,29 @@ def test_bn_fwd_on_column_sums_from_colsum(dev):
     c["bufs"].update(z=(R.framed(z), "f32"), col_sum=(R.framed(s.cpu().numpy()), "f32"),
                      col_sumsq=(R.framed((z64 * z64).sum(0)), "f32"))
     run(c, dev)
+
+
+# ns_bn_bwd / ns_bn_bwd_finalize: which of bn_bwd_reduce_kernel + bn_bwd_apply_kernel + bn_bwd_bias_kernel ("scalar-"),
+# bn_bwd_apply4_kernel + bn_bwd_finalize_kernel ("vector-": the sums are given) and bn_bwd_reduce4_kernel +
+# ns_stats_finalize in front of those two ("fallback-") a case takes is restated in pointwise_ref.bn_bwd_form beside the
+# table of cases (its docstring has the row-block arithmetic) and asserted in _bn_bwd on the device addresses of the
+# operands against the name's prefix.  Each case runs twice, the second time on the work area the first one left.
+@cases_of(R.bn_bwd_cases, R.bn_bwd_probes)
+def test_bn_bwd(dev, fn, name):
+    run(get(fn, name), dev, twice=True)
+
+
+def test_bn_bwd_scalar_32_blocks_three_times(dev):
+    """The scalar form's dbias used to meet in one float atomicAdd per row block; the blocks' partial sums are parked in
+    `work` now and added in block order.  Three launches of the 32-block case give the same bits in every output.  (A race
+    cannot be made to show: this guards; the proof is that ns_bn_bwd reaches no float atomic.)"""
+    c = [k for k in R.bn_bwd_cases() if k["name"] == "scalar-C6-rows2049-none-mask"][0]
+    assert R.bn_bwd_row_blocks(c) == (32, 65)
+    _BN_WORK.pop(c["name"], None)
+    first = run(c, dev, twice=True)
+    third = run(c, dev)
+    for o in c["outs"]:
+        assert R.bits_equal(third[o], first[o]).all(), o
 
 
 # ns_colsum: colsum4_kernel when round_up(C, 4) <= ld, ld % 4 == 0 and x is aligned to four elements ("vector": grid

@@ -66,6 +66,8 @@ def emulate(c, A=None, mut=None):
         return R.flat_emulate(c, R.compute_highway(c, A, mut), p["n"], A)
     if op == "act_bwd":
         return R.flat_emulate(c, R.compute_act_bwd(c, A, mut), p["rows"] * p["C"], A)
+    if op == "bn_bwd":
+        return R.emulate_bn_bwd(c, A, mut)
     exp = R.EXPECT[op](c, mut) if mut else R.expect(c)
     return {o: R.store(v.astype(np.float32), c["bufs"][o][1]) for o, (v, e) in exp.items() if o in c["outs"]}
 
@@ -298,6 +300,76 @@ def test_highway_and_act_bwd_against_autograd():
         assert np.allclose(R.expect(c)["dpre"][0][MARGIN:-MARGIN], pre.grad.numpy(), rtol=1e-8, atol=1e-12), c["name"]
 
 
+def test_bn_bwd_against_autograd():
+    """y = gamma * (act(pre) - mean) * istd + beta with the batch statistics of the valid rows INSIDE the graph (eps as in
+    bn_fwd_cases): dpre, dgamma, dbeta of every activation under a mask, and dbias as the column sum of dpre."""
+    eps = 1e-3
+    for act in range(5):
+        c = R._bn_bwd_case("fallback-C8-rows70-autograd-act%d" % act, 70, 8, act, mask=(10, 2, 9), seed=300 + act)
+        p, b, off = c["p"], c["bufs"], c["p"]["off"]
+        rows, C = p["rows"], p["C"]
+        valid = R.row_valid(rows, p["row_mask"])
+        z32 = logical(c, "z").reshape(rows, C).copy()
+        lo, hi = {R.ACT_TANH: (-0.99, 0.99), R.ACT_SOFTSIGN: (-0.99, 0.99), R.ACT_SIGMOID: (0.01, 0.99)}.get(act, (-9, 9))
+        z32[valid] = np.clip(z32[valid], lo, hi)             # the inverse activation must exist (the GPU cases keep |z| = 1)
+        z = T(z32[valid])
+        pre = {R.ACT_RELU: torch.where(z > 0, z, torch.full_like(z, -1.0)), R.ACT_TANH: torch.atanh(z),
+               R.ACT_SIGMOID: torch.log(z / (1 - z)), R.ACT_SOFTSIGN: z / (1 - z.abs())}.get(act, z).clone().requires_grad_(True)
+        a = {R.ACT_RELU: torch.relu, R.ACT_TANH: torch.tanh, R.ACT_SIGMOID: torch.sigmoid,
+             R.ACT_SOFTSIGN: torch.nn.functional.softsign}.get(act, lambda v: v)(pre)
+        gamma, beta = T(logical(c, "gamma")).requires_grad_(True), torch.zeros(C, dtype=torch.float64, requires_grad=True)
+        mean = a.mean(0)
+        istd = (((a - mean) ** 2).mean(0) + eps).rsqrt()
+        dy = T(logical(c, "dy").reshape(rows, C)[valid])
+        ((gamma * (a - mean) * istd + beta) * dy).sum().backward()
+        c["bufs"] = dict(b, z=(R.framed(z32), "f32"), mean=(R.framed(mean.detach().numpy()), "f32"),
+                         istd=(R.framed(istd.detach().numpy()), "f32"))
+        exp = R.expect(c)
+        dpre = exp["dpre"][0][MARGIN:-MARGIN].reshape(rows, C)
+        assert (dpre[~valid] == 0).all() and not np.signbit(dpre[~valid]).any(), "masked rows are +0"
+        assert np.allclose(dpre[valid], pre.grad.numpy(), rtol=1e-4, atol=1e-6), act
+        for k, g in (("dgamma", gamma.grad), ("dbeta", beta.grad)):
+            assert np.allclose(exp[k][0][MARGIN:-MARGIN] - logical(c, k), g.numpy(), rtol=1e-4, atol=1e-5), (act, k)
+        got = emulate(c)
+        assert not R.rejected(c, got, factor=1.0)
+        assert np.allclose(got["dbias"][MARGIN:-MARGIN] - logical(c, "dbias"), pre.grad.sum(0).numpy(), rtol=1e-4, atol=1e-4), act
+
+
+def test_bn_bwd_cases_hold_what_the_contract_asks():
+    """Every form under its name, the inputs that make mistakes visible, and the exact bf16 case's point."""
+    cases = R.bn_bwd_cases()
+    forms = {}
+    for c in cases:
+        forms.setdefault(R.bn_bwd_form(c), []).append(c)
+        assert c["name"].startswith(R.bn_bwd_form(c) + "-")
+        p = c["p"]
+        valid = R.row_valid(p["rows"], p["row_mask"])
+        z = logical(c, "z", p["rows"] * p["C"], p["off"]["z"]).reshape(p["rows"], p["C"])
+        assert (z[~valid] > 1e29).all() and np.isnan(c["bufs"]["work"][0][p["off"]["work"]:-MARGIN]).all()
+        if not c["exact"]:
+            want = {R.ACT_RELU: [0, 2.0 ** -126], R.ACT_TANH: [1, -1, 0], R.ACT_SIGMOID: [0, 1], R.ACT_SOFTSIGN: [1, -1]}.get(p["act"], [])
+            assert all((z[valid] == v).any() for v in want), c["name"]
+        if p["ld_dy"]:
+            assert np.isnan(logical(c, "dy")).sum() == p["rows"] * (p["ld_dy"] - p["C"])
+    for form in ("scalar", "vector", "fallback"):
+        got = forms[form]
+        assert {c["p"]["act"] for c in got} == set(range(5)), form
+        assert {(c["p"]["dtype"], c["bufs"]["dpre"][1]) for c in got} == {("f32", "f32"), ("bf16", "bf16"), ("f32", "bf16")}, form
+        assert any(c["exact"] for c in got) and any(c["p"]["count"] != c["p"]["rows"] for c in got)
+        assert all(any(k not in c["bufs"] for c in got) for k in ("dgamma", "dbeta", "dbias"))
+    assert R.bn_bwd_row_blocks(find(cases, "scalar-C6-rows65-relu")) == (2, 33)
+    assert R.bn_bwd_row_blocks(find(cases, "scalar-C6-rows2049-none-mask")) == (32, 65)
+    assert R.bn_bwd_row_blocks(find(cases, "vector-C132-rows129-sigmoid-mask")) == (2, 65)
+    assert R.bn_bwd_row_blocks(find(cases, "fallback-C8-rows8193-relu-mask")) == (64, 129)
+    for name, rpb in (("scalar-C6-rows2049-none-mask", 65), ("vector-C8-rows8193-relu-mask", 129)):      # a whole block invalid
+        c = find(cases, name)
+        valid = R.row_valid(c["p"]["rows"], c["p"]["row_mask"])
+        assert any(not valid[k:k + rpb].any() for k in range(0, c["p"]["rows"], rpb)), name
+    c = find(cases, "vector-exact-C8-rows160-bf16dpre-none")
+    v = R.expect(c)["dpre"][0]
+    assert (R.rne_bf16(v.astype(np.float32)) != v).sum() > 10, "fp32-exact values that bf16 rounds"
+
+
 def test_gru_pointwise_against_the_cell():
     """Modes 0 - 3 chained through the candidate product reproduce one step of the cell of tests/test_gru_seq_gpu.py
     (ru = sigmoid(xg + h Wg), c = tanh(xc + (r h) Wc), h' = u h + (1 - u) c, masked past the length) and its autograd."""
@@ -352,7 +424,7 @@ def test_gru_pointwise_against_the_cell():
 
 # ------------------------------------------------------------------------------------------------------ the bounds
 BOUNDED = dict(bn_fwd=R.bn_fwd_cases, adam=R.adam_cases, highway=R.highway_cases, act_bwd=R.act_bwd_cases,
-               gru_pointwise=R.gru_pointwise_cases)
+               gru_pointwise=R.gru_pointwise_cases, bn_bwd=R.bn_bwd_cases)
 
 
 @pytest.mark.parametrize("op", sorted(BOUNDED))
@@ -424,12 +496,18 @@ def test_exact_by_construction_sums_are_order_free():
     rng = np.random.RandomState(4)
     n = 0
     for c in (R.colsum_cases() + R.sumsq_cases() + R.segment_stats_cases()[:1] + R.l1_loss_cases() + R.embedding_bwd_cases() +
-              R.colsum_probes()[:3] + R.sumsq_probes()[:3] + R.l1_loss_probes()[:3] + R.embedding_bwd_probes()[:3]):
+              R.colsum_probes()[:3] + R.sumsq_probes()[:3] + R.l1_loss_probes()[:3] + R.embedding_bwd_probes()[:3] +
+              R.bn_bwd_cases() + R.bn_bwd_probes()):
         if not c["exact"]:
             continue
         exp = R.expect(c)                                   # runs the assertions
         assert all(e is None for o, (v, e) in exp.items()), c["name"]
         n += 1
+        if c["op"] == "bn_bwd":                             # every summation order and product association, fused or not
+            assert set(exp) == set(c["outs"])
+            for A in ARITHMETICS:
+                got = emulate(c, A)
+                assert all(R.bits_equal(got[o], R.store(exp[o][0].astype(np.float32), c["bufs"][o][1])).all() for o in c["outs"]), c["name"]
         if c["op"] == "sumsq":
             x = logical(c, "x")
             o = c["p"]["out_off"]
@@ -441,7 +519,9 @@ def test_exact_by_construction_sums_are_order_free():
             k = p["C"] - 1
             sums = _f32_sums(np.concatenate([[c["bufs"]["out"][0][p["out_off"] + k]], x[:, k]]), rng)
             assert len(set(float(s) for s in sums)) == 1 and float(sums[0]) == exp["out"][0][p["out_off"] + k], c["name"]
-    assert n > 60
+    assert n > 60 + 8 + 27
+    with pytest.raises(AssertionError):                     # an intermediate that fp32 would round
+        R.Exact().mul(R.Exact().lift(np.float32(1 + 2.0 ** -20)), R.Exact().lift(np.float32(1 + 2.0 ** -20)))
     with pytest.raises(AssertionError):
         R.assert_exact_sum(2.0 ** 24 * R.UNIT, R.UNIT)
     bad = find(R.sumsq_cases(), "n4200003-work")
@@ -480,7 +560,7 @@ def _cases_of(op):
     return dict(colsum=lambda: R.colsum_cases() + R.colsum_probes(), l1_loss=R.l1_loss_cases, adam=R.adam_cases, bn_fwd=R.bn_fwd_cases,
                 gru_pointwise=R.gru_pointwise_cases, embedding_fwd=R.embedding_fwd_cases, embedding_bwd=R.embedding_bwd_cases,
                 cast2d=R.cast2d_cases, split_hi_lo=R.split_cases, copy3d=R.copy3d_cases, sumsq=R.sumsq_cases,
-                highway=R.highway_cases, act_bwd=R.act_bwd_cases)[op]()
+                highway=R.highway_cases, act_bwd=R.act_bwd_cases, bn_bwd=R.bn_bwd_cases)[op]()
 
 
 # wrong kernel -> (op, mutation, a case of the GPU module that must reject it; None: some case of the op must)
@@ -516,6 +596,21 @@ MUTANTS = {
     "h_init taken at t == 0 in the reverse direction": ("gru_pointwise", "init_at_zero", "N3-H128-f32-mode1-init-rev"),
     "an id outside [0, V) not clamped (forward)": ("embedding_fwd", "no_clamp", "ragged-bf16"),
     "an id outside [0, V) not clamped (backward)": ("embedding_bwd", "no_clamp", "ragged-exact"),
+    "xhat without istd in the sum of dy * xhat": ("bn_bwd", "s2_no_istd", "fallback-C132-rows129-sigmoid-mask"),
+    "count replaced by rows": ("bn_bwd", "count_rows", "scalar-C6-rows70-tanh-mask"),
+    "masked rows included in the sums": ("bn_bwd", "sums_unmasked", "scalar-C6-rows70-tanh-mask"),
+    "masked rows of dpre not zeroed": ("bn_bwd", "dpre_mask_ignored", "vector-C68-rows128-tanh-mask"),
+    "the ReLU passes at z = 0 (bn_bwd)": ("bn_bwd", "relu_at_zero", "scalar-C6-rows65-relu"),
+    "tanh factor 1 - z": ("bn_bwd", "tanh_linear", "vector-C68-rows128-tanh-mask"),
+    "sigmoid factor z (1 + z)": ("bn_bwd", "sigmoid_plus", "vector-C132-rows129-sigmoid-mask"),
+    "softsign factor unsquared": ("bn_bwd", "softsign_unsquared", "fallback-C68-rows300-bf16-softsign-mask"),
+    "istd dropped from gamma * istd": ("bn_bwd", "no_istd_scale", "fallback-C68-rows128-tanh-mask"),
+    "dgamma and dbeta swapped": ("bn_bwd", "swapped", "scalar-C6-rows70-tanh-mask"),
+    "= in place of += (bn_bwd)": ("bn_bwd", "overwrite", "vector-C68-rows128-tanh-mask"),
+    "ld_dy ignored": ("bn_bwd", "ld_ignored", "vector-C68-rows300-bf16dpre-relu-ld80-col8"),
+    "the last row block dropped from the sums": ("bn_bwd", "drop_last_block", "fallback-C132-rows129-sigmoid-mask"),
+    "given sums ignored for recomputed ones": ("bn_bwd", "recompute_sums", "vector-C68-rows300-sums-not-the-column-sums"),
+    "dbias summed on unrounded values": ("bn_bwd", "dbias_unrounded", "vector-exact-C8-rows160-bf16dpre-none"),
 }
 
 
@@ -540,3 +635,13 @@ def test_every_probe_rejects_a_moved_element():
         moved = dict(good)
         moved[o] = c["bufs"][o][0] + (np.roll(delta, 1) if delta.any() else np.eye(1, len(delta), MARGIN, dtype=np.float32)[0])
         assert R.rejected(c, moved), c["name"]
+    for c in R.bn_bwd_probes():          # the column's sum of dy (dbeta) moved to the next column, its dpre to the next element
+        good = emulate(c)
+        assert not R.rejected(c, good)
+        for o in ("dbeta", "dpre"):
+            delta = good[o] - c["bufs"][o][0]
+            moved = dict(good)
+            moved[o] = c["bufs"][o][0] + (np.roll(delta, 1) if "masked" not in c["name"] else np.eye(1, len(delta), MARGIN, dtype=np.float32)[0])
+            assert R.rejected(c, moved), (c["name"], o)
+        s1 = (good["dbeta"] - c["bufs"]["dbeta"][0]).sum()
+        assert s1 == (0.0 if "masked" in c["name"] else 1.0), c["name"]
