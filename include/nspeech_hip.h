@@ -333,6 +333,33 @@ typedef struct {
 } ns_l1_loss_params;
 int ns_l1_loss(const ns_l1_loss_params* p, ns_stream_t stream);
 
+/* The same L1 sums and gradient over each utterance's real frames only (the mask_padding / mask_decoder switch of other
+ * Tacotron-2 code bases).  Not in the reference: hparam mask_padding, false = off.
+ * pred, target, dpred (fp32 or bf16, nullable: the sums only), n_prio, w_all, w_prio as for ns_l1_loss.
+ * T_n = lengths[n] clamped into [1, T] (device int32 [N]; NULL: T for every row).
+ *   acc[0] = sum |pred - target| over t < T_n, all bins;  acc[1] = the same over bins < n_prio
+ *            (raw sums, the caller normalises; written, not accumulated)
+ *   dpred[n,padl+t,f] = sign(pred-target) * (w_all + (f<n_prio ? w_prio : 0))     t < T_n;  sign(0) = 0
+ *   dpred[n,padl+t,f] = 0                                                         T_n <= t < T  (written: a caller that
+ *            reuses its gradient buffer from call to call finds no earlier gradient there)
+ * The rows of dpred outside [padl, padl+T) and its columns F..ldd keep their bits; pred and target are not loaded at
+ * t >= T_n.  work: ns_l1_loss_masked_work_floats(N, T, F) floats, no need to clear.  Every sum has a fixed order (a
+ * thread's terms in loop order, the wave tree, a workgroup's waves in index order, the workgroups' partials in index
+ * order through a second one-workgroup launch); the grid depends on (N, T, F) only: two calls on the same inputs give the
+ * same bits, and there is no float atomic.  The caller owns all memory. */
+typedef struct {
+  const float* pred; int64_t ldp;
+  const float* target;
+  void* dpred; int dpred_dtype; int64_t ldd;
+  int N, T, P, padl, F;
+  int n_prio; float w_all, w_prio;
+  const int* lengths;
+  float* acc;
+  float* work;
+} ns_l1_loss_masked_params;
+int ns_l1_loss_masked(const ns_l1_loss_masked_params* p, ns_stream_t stream);
+size_t ns_l1_loss_masked_work_floats(int N, int T, int F);
+
 /* Guided attention loss (Tachibana et al. 2017) and the alignment scores of a batch, with the loss' gradient with
  * respect to the alignments in the same pass.  Not in the reference: hparam guided_attention_weight, 0 = off.
  * align fp32 [N, S+1, Tia], step s in slot s+1 (the layout every attention kernel writes).  For row n, with

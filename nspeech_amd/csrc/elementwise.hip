@@ -802,6 +802,209 @@ extern "C" int ns_l1_loss(const ns_l1_loss_params* p, ns_stream_t s) {
   return NS_OK;
 }
 
+// ------------------------------------------------------------------ masked L1 loss + gradient (hparam mask_padding)
+// ns_l1_loss with a frame count per batch row: frames t >= T_n add nothing, are not loaded, and their gradient rows are
+// written as zero.  The loops are those of l1_loss_kernel (a wave per wide row, quads of narrow rows, the scalar
+// fall-backs); the two float atomics are gone: a workgroup parks its two sums in work[2 b], work[2 b + 1] and a one-block
+// kernel behind it adds the partials in index order, so the grid and every order of adds depend on the shape and the
+// operands' alignment only.  Without the atomics' queue the grid can be wider than ns_l1_loss': 1024 / 512 workgroups.
+#define L1M_WIDE_BLOCKS 1024
+#define L1M_NARROW_BLOCKS 512
+static inline int l1m_grid(long N, long T, long F) {
+  const long rows = N * T;
+  if (F >= 256) return (int)min((long)L1M_WIDE_BLOCKS, (rows + 3) / 4);
+  return (int)min((long)L1M_NARROW_BLOCKS, ((rows * F + 3) / 4 + 255) / 256);
+}
+extern "C" size_t ns_l1_loss_masked_work_floats(int N, int T, int F) {
+  if (N < 1 || T < 1 || F < 1) return 0;
+  return (size_t)2 * l1m_grid(N, T, F);
+}
+
+__device__ __forceinline__ int l1m_frames(const ns_l1_loss_masked_params& p, long n) {
+  return p.lengths ? min(max(p.lengths[n], 1), p.T) : p.T;
+}
+__device__ __forceinline__ float l1m_grad(const ns_l1_loss_masked_params& p, float d, bool pr) {
+  return (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (p.w_all + (pr ? p.w_prio : 0.f));
+}
+__device__ __forceinline__ void l1m_point(const ns_l1_loss_masked_params& p, float pv, float tv, long prow, int f,
+                                          float& s_all, float& s_pr) {
+  const float d = pv - tv;
+  const float ab = fabsf(d);
+  s_all += ab;
+  const bool pr = f < p.n_prio;
+  if (pr) s_pr += ab;
+  if (p.dpred) st_dyn(p.dpred, p.dpred_dtype, prow * p.ldd + f, l1m_grad(p, d, pr));
+}
+// four gradient columns from column f on (16-byte aligned by the launcher's choice of VEC)
+__device__ __forceinline__ void l1m_store4(const ns_l1_loss_masked_params& p, long prow, int f, const float (&g)[4]) {
+  if (p.dpred_dtype == NS_BF16) {
+    bf16x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (bf16_t)g[i];
+    *(bf16x4*)((bf16_t*)p.dpred + prow * p.ldd + f) = o;
+  } else {
+    *(float4*)((float*)p.dpred + prow * p.ldd + f) = make_float4(g[0], g[1], g[2], g[3]);
+  }
+}
+template <bool WIDE, bool VEC>
+__global__ __launch_bounds__(256) void l1_loss_masked_kernel(ns_l1_loss_masked_params p) {
+  __shared__ float red[32];
+  float s_all = 0.f, s_pr = 0.f;
+  const float zero4[4] = {0.f, 0.f, 0.f, 0.f};
+  if (WIDE) {
+    // target rows are only 4-byte aligned (F = 1025 floats): their quads come through 4-byte-aligned 16-byte loads
+    struct __attribute__((packed, aligned(4))) f4u { float v[4]; };
+    const int lane = threadIdx.x & 63;
+    const long rows = (long)p.N * p.T;
+    const int nq = VEC ? p.F >> 2 : 0;             // whole quads; the tail columns (all of them without VEC) go one per lane
+    for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (long)gridDim.x * 4) {
+      const int t = (int)(row % p.T);
+      const long n = row / p.T;
+      const long prow = n * p.P + p.padl + t;
+      if (t >= l1m_frames(p, n)) {                 // a padded frame: nothing is loaded, its gradient row becomes zero
+        if (!p.dpred) continue;
+        for (int q = lane; q < nq; q += 64) l1m_store4(p, prow, 4 * q, zero4);
+        for (int f = 4 * nq + lane; f < p.F; f += 64) st_dyn(p.dpred, p.dpred_dtype, prow * p.ldd + f, 0.f);
+        continue;
+      }
+      const float* pr_ = p.pred + prow * p.ldp;
+      const float* tg_ = p.target + row * p.F;
+      for (int q0 = lane; q0 < nq; q0 += 64 * 4) {
+        float4 a[4];
+        f4u b[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int q = q0 + 64 * j;
+          if (q < nq) { a[j] = *(const float4*)(pr_ + 4 * q); b[j] = *(const f4u*)(tg_ + 4 * q); }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int q = q0 + 64 * j;
+          if (q >= nq) continue;
+          const float av[4] = {a[j].x, a[j].y, a[j].z, a[j].w};
+          float g[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float d = av[i] - b[j].v[i], ab = fabsf(d);
+            s_all += ab;
+            const bool pr = 4 * q + i < p.n_prio;
+            if (pr) s_pr += ab;
+            g[i] = l1m_grad(p, d, pr);
+          }
+          if (p.dpred) l1m_store4(p, prow, 4 * q, g);
+        }
+      }
+      for (int f0 = 4 * nq + lane; f0 < p.F; f0 += 64 * 8) {
+        float a[8], b[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int f = f0 + 64 * j;
+          a[j] = f < p.F ? pr_[f] : 0.f;
+          b[j] = f < p.F ? tg_[f] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int f = f0 + 64 * j;
+          if (f < p.F) l1m_point(p, a[j], b[j], prow, f, s_all, s_pr);
+        }
+      }
+    }
+  } else if (VEC) {
+    // narrow rows, four columns per thread (F % 4 == 0, 16-byte aligned rows, fp32 gradient), 32-bit index arithmetic
+    const int q4 = p.F >> 2;
+    const unsigned total4 = (unsigned)p.N * (unsigned)p.T * (unsigned)q4;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += gridDim.x * blockDim.x) {
+      const unsigned nt = i / (unsigned)q4, f = (i - nt * (unsigned)q4) * 4u;
+      const unsigned n = nt / (unsigned)p.T, t = nt - n * (unsigned)p.T;
+      const long prow = (long)n * p.P + p.padl + t;
+      if ((int)t >= l1m_frames(p, n)) {
+        if (p.dpred) l1m_store4(p, prow, (int)f, zero4);
+        continue;
+      }
+      const float4 a = *(const float4*)(p.pred + prow * p.ldp + f);
+      const float4 b = *(const float4*)(p.target + (long)nt * p.F + f);
+      const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+      float g[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d = av[j] - bv[j], ab = fabsf(d);
+        s_all += ab;
+        const bool pr = (int)f + j < p.n_prio;
+        if (pr) s_pr += ab;
+        g[j] = l1m_grad(p, d, pr);
+      }
+      if (p.dpred) l1m_store4(p, prow, (int)f, g);
+    }
+  } else {
+    const long total = (long)p.N * p.T * p.F;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+      const int f = idx % p.F;
+      const long nt = idx / p.F;
+      const int t = nt % p.T;
+      const long n = nt / p.T;
+      const long prow = n * p.P + p.padl + t;
+      if (t >= l1m_frames(p, n)) {
+        if (p.dpred) st_dyn(p.dpred, p.dpred_dtype, prow * p.ldd + f, 0.f);
+        continue;
+      }
+      l1m_point(p, p.pred[prow * p.ldp + f], p.target[idx], prow, f, s_all, s_pr);
+    }
+  }
+  s_all = block_sum(s_all, red);       // fixed tree: the wave's butterfly, then the four waves in index order
+  s_pr = block_sum(s_pr, red);
+  if (threadIdx.x == 0) {
+    p.work[2 * blockIdx.x] = s_all;
+    p.work[2 * blockIdx.x + 1] = s_pr;
+  }
+}
+// one workgroup: thread i adds the partials i, i + 256, .. in that order, block_sum's tree adds the threads
+__global__ __launch_bounds__(256) void l1_loss_masked_finish_kernel(const float* __restrict__ work, int G,
+                                                                    float* __restrict__ acc) {
+  __shared__ float red[32];
+  float s_all = 0.f, s_pr = 0.f;
+  for (int g = threadIdx.x; g < G; g += 256) { s_all += work[2 * g]; s_pr += work[2 * g + 1]; }
+  s_all = block_sum(s_all, red);
+  s_pr = block_sum(s_pr, red);
+  if (threadIdx.x == 0) { acc[0] = s_all; acc[1] = s_pr; }
+}
+extern "C" int ns_l1_loss_masked(const ns_l1_loss_masked_params* p, ns_stream_t s) {
+  NS_CHECK_ARG(p, "ns_l1_loss_masked: null parameter block");
+  NS_CHECK_ARG(p->pred, "ns_l1_loss_masked: pred is null");
+  NS_CHECK_ARG(p->target, "ns_l1_loss_masked: target is null");
+  NS_CHECK_ARG(p->acc, "ns_l1_loss_masked: acc is null");
+  NS_CHECK_ARG(p->work, "ns_l1_loss_masked: work is null (ns_l1_loss_masked_work_floats(N, T, F) floats)");
+  NS_CHECK_ARG(p->N >= 1 && p->T >= 1 && p->F >= 1, "ns_l1_loss_masked: N, T and F must be at least 1 (got %d, %d, %d)",
+               p->N, p->T, p->F);
+  NS_CHECK_ARG(p->padl >= 0 && p->P >= p->padl + p->T, "ns_l1_loss_masked: P must hold padl + T rows (got P %d, padl %d, T %d)",
+               p->P, p->padl, p->T);
+  NS_CHECK_ARG(p->ldp >= p->F, "ns_l1_loss_masked: ldp is smaller than F (%lld < %d)", (long long)p->ldp, p->F);
+  NS_CHECK_ARG(p->n_prio >= 0, "ns_l1_loss_masked: n_prio must not be negative (got %d)", p->n_prio);
+  if (p->dpred) {
+    NS_CHECK_ARG(p->dpred_dtype == NS_F32 || p->dpred_dtype == NS_BF16,
+                 "ns_l1_loss_masked: dpred_dtype must be fp32 or bf16 (got %d)", p->dpred_dtype);
+    NS_CHECK_ARG(p->ldd >= p->F, "ns_l1_loss_masked: ldd is smaller than F (%lld < %d)", (long long)p->ldd, p->F);
+  }
+  const long total = (long)p->N * p->T * p->F;
+  const dim3 grid(l1m_grid(p->N, p->T, p->F)), block(256);
+  hipStream_t st = (hipStream_t)s;
+  auto al = [](const void* x, int b) { return (((uintptr_t)x) % b) == 0; };
+  if (p->F >= 256) {
+    const bool vec = p->ldp % 4 == 0 && al(p->pred, 16) && al(p->target, 4) &&
+                     (!p->dpred || (p->ldd % 4 == 0 && al(p->dpred, p->dpred_dtype == NS_BF16 ? 8 : 16)));
+    if (vec) hipLaunchKernelGGL((l1_loss_masked_kernel<true, true>), grid, block, 0, st, *p);
+    else hipLaunchKernelGGL((l1_loss_masked_kernel<true, false>), grid, block, 0, st, *p);
+  } else {
+    const bool vec = p->F % 4 == 0 && p->ldp % 4 == 0 && al(p->pred, 16) && al(p->target, 16) && total / 4 < 0x7fffffffL &&
+                     (!p->dpred || (p->dpred_dtype == NS_F32 && p->ldd % 4 == 0 && al(p->dpred, 16)));
+    if (vec) hipLaunchKernelGGL((l1_loss_masked_kernel<false, true>), grid, block, 0, st, *p);
+    else hipLaunchKernelGGL((l1_loss_masked_kernel<false, false>), grid, block, 0, st, *p);
+  }
+  NS_CHECK_LAUNCH("l1_loss_masked");
+  hipLaunchKernelGGL(l1_loss_masked_finish_kernel, dim3(1), block, 0, st, (const float*)p->work, (int)grid.x, p->acc);
+  NS_CHECK_LAUNCH("l1_loss_masked_finish");
+  return NS_OK;
+}
+
 // ------------------------------------------------------------------ sum of squares / Adam
 __global__ void sumsq_kernel(ns_sumsq_params p) {
   __shared__ float red[32];

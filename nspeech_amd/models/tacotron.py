@@ -1021,11 +1021,17 @@ class Tacotron(Tacotron2):
         self._n_prio = n_prio
         decA, melp, post, lin = st["decA"], st["melp"], st["post"], st["lin"]
         dlin = self._buf("d_lin", N * Po * Fp, T_)
-        ops.l1_loss(lin, Fp, self.linear_targets, dlin, Fp, N, To, Po, self.padl, F, n_prio, 0.5 / (N * To * F),
-                    0.5 / (N * To * n_prio), self.scal, acc_off=2)
         # mel loss gradient lands directly in the decoder-output gradient ([N, S1*r, M] row view)
-        ops.l1_loss(decA.buf, M, self.mel_targets, decA.grad, M, N, To, S1 * r, r, M, 0, 1.0 / (N * To * M), 0.0,
-                    self.scal, acc_off=0)
+        if self.mask_padding:       # over each utterance's real frames (Tacotron2._masked_l1)
+            self._masked_l1(lin, Fp, self.linear_targets, dlin, Fp, Po, self.padl, F, n_prio, 2)
+            self._masked_l1(decA.buf, M, self.mel_targets, decA.grad, M, S1 * r, r, M, 0, 0)
+            self._loss_frames = self._masked_frames()[1]
+        else:
+            ops.l1_loss(lin, Fp, self.linear_targets, dlin, Fp, N, To, Po, self.padl, F, n_prio, 0.5 / (N * To * F),
+                        0.5 / (N * To * n_prio), self.scal, acc_off=2)
+            ops.l1_loss(decA.buf, M, self.mel_targets, decA.grad, M, N, To, S1 * r, r, M, 0, 1.0 / (N * To * M), 0.0,
+                        self.scal, acc_off=0)
+            self._loss_frames = N * To
         # linear head
         dwl = self._buf("d_wl_pad", 256 * Fp, torch.float32)
         ops.zero(dwl)

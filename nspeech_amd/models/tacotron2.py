@@ -163,6 +163,11 @@ class Tacotron2(object):
         if self.guided_weight < 0.0 or not self.guided_sigma > 0.0:
             raise ValueError("guided_attention_weight must be >= 0 and guided_attention_sigma > 0 (got %g, %g)"
                              % (self.guided_weight, self.guided_sigma))
+        # L1 losses over each utterance's real frames only (hparam mask_padding; the reference takes the mean over every
+        # frame of the padded batch, so the shipped switch is false and then no launch and no bit differs).  true: the two
+        # loss launches of backward() go through ns_l1_loss_masked with T_n = min(target_lengths[n], T_out): the frames
+        # behind T_n add nothing and get a zero gradient, and the means divide by C = sum_n T_n.
+        self.mask_padding = bool(getattr(hparams, "mask_padding", False))
         self.zoneout_base_seed = (int(seed) * 2654435761 + 97) & 0xFFFFFFFF
         # Prenet dropout (hparams prenet_dropout / drop_rate).  The reference's tf.layers.dropout call never gets
         # training=True (modules.py:21-27), so it is the identity and the shipped switch is false: nothing below changes a
@@ -192,6 +197,8 @@ class Tacotron2(object):
         self.stop_logits = self.stop_steps = self.decoder_h2 = None      # synthesis (stop_token): see output_lengths()
         self.target_lengths = None      # frames per utterance before padding (None: every row spans all S steps)
         self._out_steps = None
+        self._frames = None             # mask_padding: (T_n as a device int32 [N] or None, C = sum_n T_n) of this batch
+        self._loss_frames = None        # the frame count the last backward pass' L1 means divide by (N * T_out, or C)
         self.gradients = self.flat_g
         self.optimize = None
         self.stats = None
@@ -616,6 +623,7 @@ class Tacotron2(object):
         """Frames per utterance before padding (the feeder's .target_lengths), kept on the host: the guided attention loss
         turns them into decoder steps when it runs.  None: every row spans all S steps (synthetic batches)."""
         self._out_steps = None
+        self._frames = None
         if target_lengths is not None:
             tl = target_lengths.cpu().numpy() if torch.is_tensor(target_lengths) else np.asarray(target_lengths)
             target_lengths = tl.reshape(-1).astype(np.int64)
@@ -632,6 +640,29 @@ class Tacotron2(object):
             steps = np.clip(-(-self.target_lengths // r), 1, self.dims["S"]).astype(np.int32)
             self._out_steps = torch.from_numpy(steps).to(self.device)
         return self._out_steps
+
+    def _masked_frames(self):
+        """mask_padding: (T_n = min(T_out, max(1, target_lengths[n])) as a device int32 [N], or None for T_n = T_out;
+        C = sum_n T_n on the host).  Uploaded once per batch."""
+        if self._frames is None:
+            N, To = self.dims["N"], self.dims["To"]
+            if self.target_lengths is None:
+                self._frames = (None, N * To)
+            else:
+                fr = np.clip(self.target_lengths, 1, To).astype(np.int32)
+                self._frames = (torch.from_numpy(fr).to(self.device), int(fr.sum()))
+        return self._frames
+
+    def _masked_l1(self, pred, ldp, target, dpred, ldd, P, padl, F, n_prio, acc_off):
+        """One L1 term of the step over the real frames (ns_l1_loss_masked): its raw sums are written into
+        scal[acc_off : acc_off + 2], its gradient - mean over C frames; with n_prio the reference's half / half of all
+        bins and the priority band - into dpred, zero at the padded frames."""
+        N, To = self.dims["N"], self.dims["To"]
+        frames, C = self._masked_frames()
+        half = 0.5 if n_prio else 1.0
+        work = self._buf("l1m_work", ops.l1_loss_masked_work_floats(N, To, F), torch.float32)
+        ops.l1_loss_masked(pred, ldp, target, dpred, ldd, N, To, P, padl, F, n_prio, half / (C * F),
+                           0.5 / (C * n_prio) if n_prio else 0.0, frames, self.scal, work, acc_off=acc_off)
 
     def _guided_attention(self, da0, acc, acc_off=0):
         """One ns_guided_attention launch on the forward pass' alignments: L_att and the focus score into acc[acc_off:
@@ -1470,10 +1501,16 @@ class Tacotron2(object):
         n_prio = int(2000 / (hp.sample_rate * 0.5) * F)
         dmel = self._buf("d_mel", N * Po * M, torch.float32)
         dlin = self._buf("d_lin", N * Po * Fp, Tx)
-        ops.l1_loss(B["mel_out"], M, self.mel_targets, dmel, M, N, To, Po, self.padl, M, 0, 1.0 / (N * To * M), 0.0,
-                    self.scal, acc_off=0)
-        ops.l1_loss(B["lin_out"], Fp, self.linear_targets, dlin, Fp, N, To, Po, self.padl, F, n_prio,
-                    0.5 / (N * To * F), 0.5 / (N * To * n_prio), self.scal, acc_off=2)
+        if self.mask_padding:
+            self._masked_l1(B["mel_out"], M, self.mel_targets, dmel, M, Po, self.padl, M, 0, 0)
+            self._masked_l1(B["lin_out"], Fp, self.linear_targets, dlin, Fp, Po, self.padl, F, n_prio, 2)
+            self._loss_frames = self._masked_frames()[1]
+        else:
+            ops.l1_loss(B["mel_out"], M, self.mel_targets, dmel, M, N, To, Po, self.padl, M, 0, 1.0 / (N * To * M), 0.0,
+                        self.scal, acc_off=0)
+            ops.l1_loss(B["lin_out"], Fp, self.linear_targets, dlin, Fp, N, To, Po, self.padl, F, n_prio,
+                        0.5 / (N * To * F), 0.5 / (N * To * n_prio), self.scal, acc_off=2)
+            self._loss_frames = N * To
         self._n_prio = n_prio
         self._tick("loss")
 
@@ -1777,9 +1814,9 @@ class Tacotron2(object):
         if s[9] != 0:
             self.global_step -= 1         # nothing was applied (on any rank: the skip is collective)
             raise RuntimeError("the optimiser step was skipped: a persistent recurrence reported a timeout")
-        N, To = d["N"], d["To"]
-        self.mel_loss = float(s[0]) / (N * To * hp.num_mels)
-        self.linear_loss = 0.5 * float(s[2]) / (N * To * hp.num_freq) + 0.5 * float(s[3]) / (N * To * self._n_prio)
+        C = self._loss_frames             # N * T_out, or with mask_padding the batch's real frames
+        self.mel_loss = float(s[0]) / (C * hp.num_mels)
+        self.linear_loss = 0.5 * float(s[2]) / (C * hp.num_freq) + 0.5 * float(s[3]) / (C * self._n_prio)
         self.loss = self.mel_loss + self.linear_loss
         if self.guided_weight > 0.0:
             self.attention_loss, self.attention_focus = float(s[4]), float(s[5])
@@ -1807,7 +1844,8 @@ class Tacotron2(object):
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         d = self.dims
-        return dict(host=host, event=ev, N=d["N"], To=d["To"], n_prio=self._n_prio, step=self.global_step,
+        return dict(host=host, event=ev, N=d["N"], To=d["To"], frames=self._loss_frames, n_prio=self._n_prio,
+                    step=self.global_step,
                     lr=self.learning_rate, guided_weight=self.guided_weight,
                     stop_weight=self.stop_weight if self.stop_token else None)
 
@@ -1821,9 +1859,9 @@ class Tacotron2(object):
         s = handle["host"].numpy()
         if s[9] != 0:
             raise RuntimeError("the optimiser step %d was skipped: a persistent recurrence reported a timeout" % handle["step"])
-        N, To = handle["N"], handle["To"]
-        mel_loss = float(s[0]) / (N * To * hp.num_mels)
-        lin_loss = 0.5 * float(s[2]) / (N * To * hp.num_freq) + 0.5 * float(s[3]) / (N * To * handle["n_prio"])
+        C = handle["frames"]              # the frames that step's means divide by: N * T_out, or its real frames
+        mel_loss = float(s[0]) / (C * hp.num_mels)
+        lin_loss = 0.5 * float(s[2]) / (C * hp.num_freq) + 0.5 * float(s[3]) / (C * handle["n_prio"])
         loss = mel_loss + lin_loss
         handle["attention_loss"] = handle["attention_focus"] = None
         if handle["guided_weight"] > 0.0:

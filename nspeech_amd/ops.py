@@ -370,6 +370,24 @@ def l1_loss(pred, ldp, target, dpred, ldd, N, T, P, padl, F, n_prio, w_all, w_pr
     L.call("ns_l1_loss", p, stream())
 
 
+def l1_loss_masked_work_floats(N, T, F):
+    fn = L.lib().ns_l1_loss_masked_work_floats
+    fn.restype = C.c_size_t
+    return int(fn(int(N), int(T), int(F)))
+
+
+def l1_loss_masked(pred, ldp, target, dpred, ldd, N, T, P, padl, F, n_prio, w_all, w_prio, lengths, acc, work, acc_off=0):
+    """l1_loss over the frames t < lengths[n] of each row (ns_l1_loss_masked): acc[acc_off], acc[acc_off + 1] are WRITTEN
+    with the two raw sums, the gradient rows of the frames behind a row's length are written as zero.  lengths: device
+    int32 [N] or None (T for every row); work: at least l1_loss_masked_work_floats(N, T, F) fp32, no need to clear."""
+    p = L.struct("ns_l1_loss_masked_params")
+    _fill(p, pred=ptr(pred), ldp=ldp, target=ptr(target), dpred=ptr(dpred),
+          dpred_dtype=dt(dpred) if dpred is not None else 0, ldd=ldd, N=N, T=T, P=P, padl=padl, F=F,
+          n_prio=n_prio, w_all=w_all, w_prio=w_prio, lengths=ptr(lengths), acc=ptr(acc, acc_off), work=ptr(work))
+    assert work.dtype == torch.float32 and work.numel() >= l1_loss_masked_work_floats(N, T, F)
+    L.call("ns_l1_loss_masked", p, stream())
+
+
 def guided_attention(N, S, Tia, in_lengths, out_steps, sigma, align, da0, grad_scale, row_out, acc=None, acc_off=0):
     """Guided attention loss and focus of align fp32 [N, S+1, Tia] (ns_guided_attention): row_out[2n] = G_n,
     row_out[2n+1] = F_n, acc[acc_off], acc[acc_off + 1] = their batch means; with da0 the loss' gradient times grad_scale

@@ -157,6 +157,9 @@ def train(log_dir, args):
     hp.num_speakers = len(feeder.speaker2id)        # train.py:45
     log("Loaded %d different speaker(s)" % hp.num_speakers, logf)
     model = create_model(args.model, hp, device="cuda:%d" % local, dtype=args.precision, world_size=world)
+    if model.mask_padding and not model.stop_token:
+        log("Warning: mask_padding=true without stop_token=true: nothing teaches the model where an utterance ends, and "
+            "find_endpoint has no trained silence to find", logf)
     step0 = 0
     if args.restore_step:
         path = "%s-%d" % (os.path.join(log_dir, "model.ckpt"), args.restore_step)
